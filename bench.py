@@ -176,6 +176,28 @@ def note(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, model, d, per_tensor=4096, seed=1234):
+    """--dump-outputs: what the timed path computed in its LAST step, as float32 DIR/<name>.npy - the arrays train_step returns
+    (top, bott, final, loss_parts, asr_cls[, trans_cls]) and, for every parameter tensor in slot order, the same fixed seeded sample
+    of min(numel, per_tensor) elements of the fp32 master weights the step updated (params_sample) and of the gradients it left in
+    the arena (grads_sample).  Called right after the timed region, before anything else runs a step."""
+    os.makedirs(d, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in out.items() if v is not None}
+    rng = np.random.default_rng(seed)
+    idx = np.concatenate([s.offset + np.sort(rng.choice(s.numel, min(s.numel, per_tensor), replace=False)) for s in model.arena.slots])
+    idx = torch.from_numpy(idx).to(model.arena.p.device)
+    host["params_sample"] = model.arena.p[idx].cpu().numpy()
+    host["grads_sample"] = model.arena.g[idx].cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes exceeds the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    for k, v in host.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    note("dumped %s (%.1f MB) to %s" % (", ".join(sorted(host)), total / 1e6, d))
+
+
 def real_data_throughput(model, optim, labels, batch_size, n_best, epochs=2, min_utts=16384):
     """VERDICT r3 item 8 / SURVEY 8f-1: the REAL-data loop - the shipped `valid` split (tests/golden/valid_512.txt: 512 lines of
     the reference's dstc2 valid file) tiled to >= 16 k utterances, through trainer.EncodedSplit (tokenised once) + Prefetcher
@@ -238,7 +260,12 @@ def main():
     ap.add_argument("--real", action="store_true", help="after the synthetic measurement: the real-data loop (shipped valid split tiled to 16 k utterances "
                     "through EncodedSplit + Prefetcher + train_epoch, decode and F1 included) as a second JSON key `real_data` (N = 1 only)")
     ap.add_argument("--epochs", type=int, default=2, help="--real: epochs over the tiled split (the last one is reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last timed step computed (its outputs, a fixed sample of the updated "
+                         "weights and of the gradients) as float32 DIR/<name>.npy (rank 0; not with the sharded optimizer)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     from nbest_amd import trainer as _trainer
     _trainer.limit_host_threads()            # the container's CPU quota, not the machine's core count (trainer.limit_host_threads)
 
@@ -283,6 +310,8 @@ def main():
     # overlappable with anything) cost about what the 0.57 ms replicated update does, so the plain all-reduce path stays
     n_params = sum(s.numel for s in model.arena.slots)
     shard = distributed and (a.shard_optimizer == "on" or (a.shard_optimizer == "auto" and n_params > 200e6))
+    if shard and a.dump_outputs:
+        sys.exit("--dump-outputs: the sharded optimizer leaves rank 0 with part of the weights and gradients only")
     optim = HipBertAdam(model, lr=3e-5, bert_lr=3e-5, warmup=0.1, t_total=t_total, shard=shard)
     reducer = GradReducer(model.arena, owner_ranges=optim.owner_ranges) if distributed else None
 
@@ -315,6 +344,8 @@ def main():
         dt = tt.item()
     loss = float(out["loss_parts"].sum().item())
     assert np.isfinite(loss), "non-finite loss in the timed region"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, model, a.dump_outputs)
     if distributed:
         # every rank leaves the process group together, right after the timed region: rank 0's extra measurements
         # below (dominant-kernel timing) must not keep its peers waiting inside a communicator tear-down
