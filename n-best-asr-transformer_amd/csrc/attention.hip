@@ -18,7 +18,6 @@
 //             of the 32x32x16 operand AND for the 4-row transposed reads.
 // fp32 path (parity/debug): one thread per query row, plain VALU math, any S <= 512.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -417,165 +416,6 @@ __global__ __launch_bounds__(256, (NKB <= 4 ? (DROP ? 3 : 4) : 1)) void attn_fwd
     if (lane == 0) amax_update(a_new, amax8);
   }
 }
-
-#ifdef NBEST_EXPERIMENTS   // first-generation backward: kept for A/B measurements only
-// backward, Sp = 32*NKB <= 128.  LDS: Qt | Kt | Vt | dOt ([Sp][64] bf16 each) | dSb [Sp][128] bf16 | lse | delta | madd
-template <int NKB>
-__global__ __launch_bounds__(256) void attn_bwd_bf16_kernel(const bf16* __restrict__ qkv, const uint8_t* __restrict__ mask,
-                                                            const bf16* __restrict__ ctx, const bf16* __restrict__ dctx,
-                                                            const float* __restrict__ lse, bf16* __restrict__ dqkv,
-                                                            float* __restrict__ colpart, int S, int heads, int H,
-                                                            float scale, DropCfg drop) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  constexpr int Sp = NKB * 32;
-  char* Qt = lds;
-  char* Kt = Qt + Sp * 128;
-  char* Vt = Kt + Sp * 128;
-  char* dOt = Vt + Sp * 128;
-  char* dSb = dOt + Sp * 128;                    // [Sp][256 B], chunk ^= row & 15
-  float* lse_s = (float*)(dSb + Sp * 256);
-  float* del_s = lse_s + Sp;
-  float* madd = del_s + Sp;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
-  const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
-  const int ld = 3 * H;
-  const bf16* base = qkv + (int64_t)b * S * ld;
-  const bf16* dobase = dctx + (int64_t)b * S * H;
-  const bf16* obase = ctx + (int64_t)b * S * H;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (uint32_t)(S * ld * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)dobase, 0, (uint32_t)(S * H * 2), 0x00020000);
-  stage_rows(rs, Qt, Sp, h * 64, ld, tid);
-  stage_rows(rs, Kt, Sp, H + h * 64, ld, tid);
-  stage_rows(rs, Vt, Sp, 2 * H + h * 64, ld, tid);
-  stage_rows(rsd, dOt, Sp, h * 64, H, tid);
-  for (int k = tid; k < Sp; k += 256) {
-    madd[k] = (k < S && mask[b * S + k]) ? 0.f : -INFINITY;
-    lse_s[k] = (k < S) ? lse[(int64_t)bh * S + k] : INFINITY;
-  }
-  {  // delta[q] = sum_d dO[q][d] * O[q][d]; two threads per row (Sp <= 128 -> 256 threads cover it)
-    const int r = tid >> 1, half = tid & 1;
-    float s = 0.f;
-    if (r < S) {
-      const bf16* dp = dobase + (int64_t)r * H + h * 64 + 32 * half;
-      const bf16* op = obase + (int64_t)r * H + h * 64 + 32 * half;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float a[8], o[8];
-        Vec8<bf16>::load(dp + 8 * c, a);
-        Vec8<bf16>::load(op + 8 * c, o);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s = fmaf(a[j], o[j], s);
-      }
-    }
-    s += __shfl_xor(s, 1, 64);
-    if (half == 0 && r < Sp) del_s[r] = s;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  f32x16 dk0, dk1, dv0, dv1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dk0[r] = dk1[r] = dv0[r] = dv1[r] = 0.f;
-  if (wave < NKB) {
-    const int key = 32 * wave + (lane & 31);
-    const float mk = madd[key];
-    bf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      kf[ks] = row_frag(Kt, 32 * wave, ks, lane);
-      vf[ks] = row_frag(Vt, 32 * wave, ks, lane);
-    }
-#pragma unroll 1
-    for (int qb = 0; qb < NKB; ++qb) {
-      f32x16 sa, da;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sa[r] = da[r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qt, 32 * qb, ks, lane), kf[ks], sa, 0, 0, 0);
-        da = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(dOt, 32 * qb, ks, lane), vf[ks], da, 0, 0, 0);
-      }
-      // sa/da: lane holds [q = 32qb + crow(r,hh)][key]
-#pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) {
-        const f32x4 l4 = *(const f32x4*)(lse_s + 32 * qb + 8 * r4 + 4 * hh);
-        const f32x4 d4 = *(const f32x4*)(del_s + 32 * qb + 8 * r4 + 4 * hh);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * r4 + e;
-          const int q = 32 * qb + 8 * r4 + 4 * hh + e;
-          const float p = __expf(sa[r] * scale + mk - l4[e]);
-          float pt = p, dp = da[r];
-          if (drop.thr16) {
-            const bool keep = nb_keep(drop, (uint32_t)((bh * S + q) * S + key));
-            pt = keep ? p * drop.scale : 0.f;
-            dp = keep ? dp * drop.scale : 0.f;
-          }
-          const float ds = p * (dp - d4[e]) * scale;
-          sa[r] = pt;   // P~  (-> dV)
-          da[r] = ds;   // dS' (-> dK, dQ)
-          *(bf16*)(dSb + q * 256 + ((((key >> 3) ^ (q & 15))) << 4) + (key & 7) * 2) = (bf16)ds;
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const bf16x8 pa = acc_to_frag(sa, s), dsa = acc_to_frag(da, s);
-        const bf16x8 do0 = tr_frag<true>(dOt, 32 * qb + 16 * s, 0, lane), do1 = tr_frag<true>(dOt, 32 * qb + 16 * s, 32, lane);
-        const bf16x8 q0f = tr_frag<true>(Qt, 32 * qb + 16 * s, 0, lane), q1f = tr_frag<true>(Qt, 32 * qb + 16 * s, 32, lane);
-        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, do0, dv0, 0, 0, 0);
-        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, do1, dv1, 0, 0, 0);
-        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa, q0f, dk0, 0, 0, 0);
-        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa, q1f, dk1, 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();  // dSb complete
-  f32x16 dq0, dq1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dq0[r] = dq1[r] = 0.f;
-  if (wave < NKB) {
-#pragma unroll
-    for (int ks = 0; ks < 2 * NKB; ++ks) {
-      const int row = 32 * wave + (lane & 31);
-      const int c = 2 * ks + hh;
-      const bf16x8 dsf = *(const bf16x8*)(dSb + row * 256 + ((c ^ (row & 15)) << 4));
-      dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsf, tr_frag<false>(Kt, 16 * ks, 0, lane), dq0, 0, 0, 0);
-      dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsf, tr_frag<false>(Kt, 16 * ks, 32, lane), dq1, 0, 0, 0);
-    }
-  }
-  __syncthreads();  // everyone is done reading Qt / Kt / Vt / dSb: reuse them as output images / scratch
-  if (colpart) {
-    // fused Q|K|V bias gradient: column sums of this (sample, head)'s dQ, dK, dV -> colpart[b][3H]
-    float* cs = (float*)dSb;   // [4 waves][3][64]
-    const f32x16* tiles[6] = {&dq0, &dq1, &dk0, &dk1, &dv0, &dv1};
-#pragma unroll
-    for (int t6 = 0; t6 < 6; ++t6) {
-      float x = 0.f;
-      if (wave < NKB) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x += (*tiles[t6])[r];
-      }
-      x += __shfl_xor(x, 32, 64);
-      if (lane < 32) cs[(wave * 3 + (t6 >> 1)) * 64 + (t6 & 1) * 32 + lane] = x;
-    }
-    __syncthreads();
-    if (tid < 192) {
-      const int which = tid >> 6, dcol = tid & 63;
-      const float x = (cs[(0 * 3 + which) * 64 + dcol] + cs[(1 * 3 + which) * 64 + dcol]) +
-                      (cs[(2 * 3 + which) * 64 + dcol] + cs[(3 * 3 + which) * 64 + dcol]);
-      colpart[(int64_t)b * 3 * H + which * H + h * 64 + dcol] = x;
-    }
-  }
-  if (wave < NKB) {
-    const int r0 = 32 * wave;
-    bf16* g = dqkv + ((int64_t)b * S + r0) * ld + h * 64;
-    store_tile(Qt, r0, dq0, dq1, lane, g, ld, S - r0);
-    store_tile(Kt, r0, dk0, dk1, lane, g + H, ld, S - r0);
-    store_tile(Vt, r0, dv0, dv1, lane, g + 2 * H, ld, S - r0);
-  }
-}
-
-#endif  // NBEST_EXPERIMENTS
 
 // ---- backward, second structure: S <= 256, small LDS footprint -----------------------------------------
 // One wave per 32-key block (4 waves for S <= 128, 8 for S <= 256).  LDS: Qt | Kt | dOt ([Sp][64] bf16), the dS image of TWO query
@@ -1373,9 +1213,6 @@ static size_t fwd_lds_bytes(int nkb) {
   const size_t kv = (size_t)nkb * 32 * 256, madd = (size_t)nkb * 32 * 4;
   return (nkb <= 4) ? kv + madd : kv + madd + 4 * 4096;
 }
-#ifdef NBEST_EXPERIMENTS
-static size_t bwd_lds_bytes(int nkb) { return (size_t)nkb * 32 * (4 * 128 + 256) + (size_t)nkb * 32 * 12; }
-#endif
 
 template <int NKB>
 static void launch_fwd(const bf16* qkv, const uint8_t* mask, bf16* ctx, float* lse, int B, int S, int heads, int H, float scale,
@@ -1389,15 +1226,6 @@ static void launch_fwd(const bf16* qkv, const uint8_t* mask, bf16* ctx, float* l
     attn_fwd_bf16_kernel<NKB, false><<<B * heads, 256, sm, st>>>(qkv, mask, ctx, lse, S, heads, H, scale, d, ctx8, keep, a_prev, a_new);
   }
 }
-#ifdef NBEST_EXPERIMENTS
-template <int NKB>
-static void launch_bwd(const bf16* qkv, const uint8_t* mask, const bf16* ctx, const bf16* dctx, const float* lse, bf16* dqkv,
-                       float* colpart, int B, int S, int heads, int H, float scale, DropCfg d, hipStream_t st) {
-  const size_t sm = bwd_lds_bytes(NKB);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_bf16_kernel<NKB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  attn_bwd_bf16_kernel<NKB><<<B * heads, 256, sm, st>>>(qkv, mask, ctx, dctx, lse, dqkv, colpart, S, heads, H, scale, d);
-}
-#endif
 
 static int check_common(const char* who, int B, int S, int heads, int d, int dtype) {
   NB_CHECK(B > 0 && S > 0 && heads > 0, NBEST_ERR_SHAPE, "%s: bad shape", who);
@@ -1496,49 +1324,23 @@ int nbest_internal_attention_bwd8(const void* qkv, const uint8_t* key_mask, cons
     if (dbias) return nbest_internal_partial_rows_sum(colpart, B, 3 * H, dbias, accumulate, st);
     return NBEST_OK;
   }
-#ifdef NBEST_EXPERIMENTS
-  // experiment builds (`make diag`): NBEST_ATTN_BWD=1 selects the first structure (everything in LDS, S <= 128) for A/B runs
-  static const int old_structure = [] { const char* e = getenv("NBEST_ATTN_BWD"); return (e && e[0] == '1') ? 1 : 0; }();
-  if (old_structure && nkb <= 4) {
-#define F(N) case N: launch_bwd<N>((const bf16*)qkv, key_mask, (const bf16*)ctx, (const bf16*)dctx, lse, (bf16*)dqkv, colpart, B, S, heads, H, scale, dc, st); break;
-    switch (nkb) { F(1) F(2) F(3) F(4) }
-#undef F
-    NB_LAUNCH_CHECK();
-    if (dbias) return nbest_internal_partial_rows_sum(colpart, B, 3 * H, dbias, accumulate, st);
-    return NBEST_OK;
-  }
-#endif
-  // 96 < S <= 128: 16-key waves (attn_bwd3_bf16_kernel).  The 16-wave form for 224 < S <= 256 is correct (tests) but measured 0.7 - 0.9 % SLOWER on the
-  // S = 256 steps than the second structure (one workgroup per CU either way, 25 spilled registers): experiment builds only (NBEST_ATTN_BWD=3).
-  bool third = (nkb == 4);
-#ifdef NBEST_EXPERIMENTS
-  {
-    static const int forced = [] { const char* e = getenv("NBEST_ATTN_BWD"); return (e && (e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 0; }();
-    if (forced == 2) third = false;
-    if (forced == 3 && nkb == 8) third = true;
-  }
-#endif
-  if (third) {
-    const size_t sm = bwd2_lds_bytes(nkb);
-    const bool kb = keep && dc.thr16;
-#define G(N, K_)                                                                                                                        \
+  // 96 < S <= 128: 16-key waves (attn_bwd3_bf16_kernel).  The 16-wave form for 224 < S <= 256 measured 0.7 - 0.9 % SLOWER on the S = 256
+  // steps than the second structure (one workgroup per CU either way, 25 spilled registers).
+  if (nkb == 4) {
+    const size_t sm = bwd2_lds_bytes(4);
+#define G(K_)                                                                                                                           \
     do {                                                                                                                                \
-      (void)hipFuncSetAttribute((const void*)attn_bwd3_bf16_kernel<N, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);        \
-      attn_bwd3_bf16_kernel<N, K_><<<B * heads, N * 128, sm, st>>>((const bf16*)qkv, key_mask, (const bf16*)ctx, (const bf16*)dctx, lse, \
+      (void)hipFuncSetAttribute((const void*)attn_bwd3_bf16_kernel<4, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);        \
+      attn_bwd3_bf16_kernel<4, K_><<<B * heads, 4 * 128, sm, st>>>((const bf16*)qkv, key_mask, (const bf16*)ctx, (const bf16*)dctx, lse, \
                                                                    (bf16*)dqkv, colpart, S, heads, H, scale, dc, f8, K_ ? keep : nullptr); \
     } while (0)
-    if (nkb == 4) { if (kb) G(4, true); else G(4, false); }
-#ifdef NBEST_EXPERIMENTS
-    else { if (kb) G(8, true); else G(8, false); }
-#endif
+    if (keep && dc.thr16) G(true); else G(false);
 #undef G
-    NB_LAUNCH_CHECK();
-    if (dbias) return nbest_internal_partial_rows_sum(colpart, B, 3 * H, dbias, accumulate, st);
-    return NBEST_OK;
-  }
+  } else {
 #define F(N) case N: launch_bwd2<N>((const bf16*)qkv, key_mask, (const bf16*)ctx, (const bf16*)dctx, lse, (bf16*)dqkv, colpart, B, S, heads, H, scale, dc, st, f8, keep); break;
-  switch (nkb) { F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) }
+    switch (nkb) { F(1) F(2) F(3) F(5) F(6) F(7) F(8) }
 #undef F
+  }
   NB_LAUNCH_CHECK();
   if (dbias) return nbest_internal_partial_rows_sum(colpart, B, 3 * H, dbias, accumulate, st);
   return NBEST_OK;

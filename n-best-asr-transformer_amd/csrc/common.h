@@ -96,15 +96,6 @@ template <> struct Vec8<bf16> {
   }
 };
 
-// cache-policy bits of the LDS-DMA operand loads (aux of raw_ptr_buffer_load_lds: 1 = sc0, 2 = nt, 16 = sc1); experiments only
-#ifndef NBEST_DIAG
-#define NB_AUX_A 0
-#define NB_AUX_B 0
-#else
-#define NB_AUX_A ((NBEST_DIAG & 8192) ? 2 : 0)
-#define NB_AUX_B ((NBEST_DIAG & 16384) ? 2 : 0)
-#endif
-
 // Tile id -> (tile_m, tile_n) with the tile columns blocked in groups of `gn`: every tile row of one column group is visited
 // before the next group, so the group's slice of the WEIGHT operand ([gn * BN][K]) stays in the 4 MiB L2 of the XCD while the
 // activation panel streams past it.  Row-major order (gn = tiles_n) re-reads the whole weight matrix once per tile row, and
@@ -122,28 +113,20 @@ inline int nb_group_cols(int64_t tiles_n, int64_t slice_bytes_per_tile, int64_t 
   int best = 1;
   for (int d = 1; d <= tiles_n; ++d)
     if (tiles_n % d == 0 && d * slice_bytes_per_tile <= limit_kb * 1024) best = d;
-#ifdef NBEST_EXPERIMENTS
-  if (const char* e = getenv("NBEST_GN")) { const int v = atoi(e); if (v > 0 && tiles_n % v == 0) best = v; else if (v == 0) best = (int)tiles_n; }
-#endif
   return best;
 }
 
 // Streaming (nontemporal) store: for GEMM / attention outputs of tens to hundreds of MB, which otherwise wash the operands
-// other tiles still read out of the 4 MiB L2 of every XCD.  The shipped library streams EVERY GEMM output (nb_stream_output), so
+// other tiles still read out of the 4 MiB L2 of every XCD.  The library streams EVERY GEMM output (GemmP*::stream_out = 1), so
 // the hint is unconditional there: `__builtin_nontemporal_store` (global_store ... nt), which the compiler schedules and whose
 // data registers it tracks.  (Round 2 selected it at run time through an inline-asm store inside an if / else: every store became
 // its own basic block with an `s_waitcnt vmcnt(0)` at the join - harmless behind an LDS restage that serialised the epilogue
-// anyway, 50 us per launch once the epilogue became one block of independent work.)  Experiment builds keep the run-time switch.
+// anyway, 50 us per launch once the epilogue became one block of independent work.)  `nt` is the kernel argument that used to
+// select it; it is always set.
 template <typename V> __device__ __forceinline__ void st_stream(V* p, V v, bool nt) {
   static_assert(sizeof(V) == 8 || sizeof(V) == 16, "st_stream: 8- or 16-byte vectors");
-#ifdef NBEST_EXPERIMENTS
-  if (!nt) { *p = v; return; }
-  if constexpr (sizeof(V) == 16) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-  else asm volatile("global_store_dwordx2 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
-#else
   (void)nt;
   __builtin_nontemporal_store(v, p);
-#endif
 }
 __device__ __forceinline__ void st_stream_bf16x8(bf16* p, const float* v, bool nt) {
   bf16x8 o;
@@ -157,24 +140,14 @@ __device__ __forceinline__ void st_stream_bf16x8(bf16* p, const float* v, bool n
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-template <int AUX = 2 /* nt */>
 __device__ __forceinline__ void nb_bstore_bf16x8(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, const float* v) {
   bf16x8 o;
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = (bf16)v[i];
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs, byte_off, 0, AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs, byte_off, 0, 2 /* nt */);
 }
 __device__ __forceinline__ void nb_bstore8(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, uint32_t lo, uint32_t hi) {
   __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo, hi}, rs, byte_off, 0, 2 /* nt */);
-}
-
-// host side: which GEMM outputs are streamed (bytes of the bf16 output)
-inline bool nb_stream_output(int64_t out_bytes) {
-  int64_t min_mb = 0;
-#ifdef NBEST_EXPERIMENTS
-  if (const char* e = getenv("NBEST_NT_MIN_MB")) min_mb = atoll(e);
-#endif
-  return out_bytes >= (min_mb << 20);
 }
 
 // ---- 64x64 tile transpose of a row-major matrix with 1- or 2-byte elements (transposed weight copies) ----------------------

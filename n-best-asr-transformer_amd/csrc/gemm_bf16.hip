@@ -41,7 +41,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // ---- staging: one operand tile, 4 LDS-DMA instructions per thread -------------------------------
-template <bool TR, int AUX = 0>
+template <bool TR>
 __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rs, char* lds_tile, int64_t row0, int64_t k0, int64_t ld,
                                            int tid) {
   const int wave = tid >> 6;
@@ -59,7 +59,7 @@ __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rs, char* lds_
       voff = (uint32_t)(((k0 + krow) * ld + row0 + mc * 8) * 2);
     }
     char* dst = lds_tile + (i * 256 + wave * 64) * 16;  // wave-uniform; the DMA adds lane*16
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, 0);
   }
 }
 
@@ -140,8 +140,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
   }
 
   if (nk > 0) {
-    stage_tile<TA, NB_AUX_A>(rsA, lds, m0, kbeg, p.lda, tid);
-    stage_tile<TB, NB_AUX_B>(rsB, lds + kTileBytes, n0, kbeg, p.ldb, tid);
+    stage_tile<TA>(rsA, lds, m0, kbeg, p.lda, tid);
+    stage_tile<TB>(rsB, lds + kTileBytes, n0, kbeg, p.ldb, tid);
   }
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
       if (kt + 1 < nk) {
         char* nxt = lds + ((kt + 1) & 1) * kStageBytes;
         const int64_t k0 = kbeg + (int64_t)(kt + 1) * BK;
-        stage_tile<TA, NB_AUX_A>(rsA, nxt, m0, k0, p.lda, tid);
-        stage_tile<TB, NB_AUX_B>(rsB, nxt + kTileBytes, n0, k0, p.ldb, tid);
+        stage_tile<TA>(rsA, nxt, m0, k0, p.lda, tid);
+        stage_tile<TB>(rsB, nxt + kTileBytes, n0, k0, p.ldb, tid);
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -178,8 +178,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
       if (kt + 1 < nk) {
         char* nxt = lds + ((kt + 1) & 1) * kStageBytes;
         const int64_t k0 = kbeg + (int64_t)(kt + 1) * BK;
-        stage_tile<TA, NB_AUX_A>(rsA, nxt, m0, k0, p.lda, tid);
-        stage_tile<TB, NB_AUX_B>(rsB, nxt + kTileBytes, n0, k0, p.ldb, tid);
+        stage_tile<TA>(rsA, nxt, m0, k0, p.lda, tid);
+        stage_tile<TB>(rsB, nxt + kTileBytes, n0, k0, p.ldb, tid);
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -384,7 +384,7 @@ int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   NB_CHECK(ab < ((int64_t)1 << 32) && bb < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm(bf16): operand larger than 4 GiB");
   p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
-  p.stream_out = nb_stream_output(a->M * a->N * 2) ? 1 : 0;
+  p.stream_out = 1;   // every output is streamed (common.h st_stream)
   p.gn = (int)(a->N / BN);      // row-major tile order (column groups measured neutral to negative on the N = 768 shapes this kernel serves)
   NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm(bf16): dropout counter overflow");
   const int epi = a->epilogue;

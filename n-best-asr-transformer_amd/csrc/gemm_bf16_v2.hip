@@ -11,9 +11,9 @@
 //                (fragment reads + DMA issue + counted wait) and an MFMA slot (32 MFMAs), one slot out of
 //                phase.  QKV / FFN-up forward, FFN-down dgrad, and - with both operands read transposed -
 //                the QKV / FFN weight gradients (split-K).
-//       256x128 / 128x128, 4 waves, 2 workgroups/CU  plain ring / ring with double-buffered fragments
-//                (kept for the fp32-master fallback layouts and for experiments; v1 wins on N = 768).
-//       gemm2p_kernel  persistent ping-pong: experiment builds only (`make diag`, -DNBEST_EXPERIMENTS), see there.
+//       256x192, 128x384, 128x512 (8 waves)  the same ping-pong for the k-contiguous forward / dgrad GEMMs of narrower N.
+//       256x128, 4 waves, 2 workgroups/CU  plain ring (the fp32-master fallback layouts); 128-row tiles narrower than
+//                384 columns run on v1 (nbest_gemm_bf16_v2_wins).
 //   * LDS images (LDS-DMA is lane-linear, so the swizzle lives in the SOURCE address and the read
 //     address): k-contiguous operand [rows][32 k], 64-B rows: chunk ^= (-(row>>2))&3 (conflict-free
 //     for the 16-lane groups of ds_read_b128 even though a group mixes two k-chunks);
@@ -23,20 +23,12 @@
 //   * epilogue as v1 (fp32 restage through wave-private LDS into a row-contiguous layout, 16-byte
 //     whole-line I/O, fast erf) but in 32-row chunks, with the residual / pre-activation rows of the
 //     next chunk prefetched while the current one is processed.
-//   * -DNBEST_DIAG=<mask> (`make diag DIAG=<mask>`) builds are timing-only ablations / cycle-stamp builds (tools/,
-//     profiles/README.md); the shipped library is built with NBEST_DIAG = 0 and without NBEST_EXPERIMENTS.
 #include "common.h"
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace {
 
 constexpr int BK = 32;
-#ifndef NBEST_DIAG
-#define NBEST_DIAG 0
-#endif
-constexpr int DIAG = NBEST_DIAG;   // timing-only ablation builds of the ping-pong loop: 1 no in-loop DMA, 2 no fragment reads, 4 no MFMA
 
 struct GemmP2 {
   const bf16* A; const bf16* B; void* C; const float* bias; const bf16* R; bf16* U; float* slab; float* colpart;
@@ -72,7 +64,7 @@ __device__ __forceinline__ int xcd_remap2(int bid, int nwg) {
 // is issued by EVERY wave so that all waves count the same number of LDS-DMA operations per stage (the counted s_waitcnt vmcnt of
 // the ring assume it); the waves with no chunk left read past the end of the buffer (range check: zero fill, no memory traffic)
 // into their own 1-KiB slot of `dump`.
-template <bool TR, int ROWS, int NT, int AUX = 0, int PW = 0>
+template <bool TR, int ROWS, int NT, int PW = 0>
 __device__ __forceinline__ void stage_tile2(__amdgpu_buffer_rsrc_t rs, char* tile, int64_t row0, int64_t k0, int64_t ld, int tid,
                                             char* dump = nullptr) {
   const int wave = tid >> 6;
@@ -101,13 +93,13 @@ __device__ __forceinline__ void stage_tile2(__amdgpu_buffer_rsrc_t rs, char* til
         dst = dump + (wave % (NT / 64)) * 1024;
       }
     }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, 0);
   }
 }
 
 // the same tile from a PRE-PACKED operand: the LDS image of every (tile, stage) stored contiguously, so the LDS-DMA is a linear copy
 // (1 KiB contiguous per wave-instruction instead of sixteen 64-byte row segments)
-template <int ROWS, int NT, int AUX = 0>
+template <int ROWS, int NT>
 __device__ __forceinline__ void stage_tile_packed(__amdgpu_buffer_rsrc_t rs, char* tile, uint32_t stage_byte0, int tid, char* dump = nullptr) {
   const int wave = tid >> 6;
   constexpr int NI = (ROWS * 4 + NT - 1) / NT;
@@ -121,34 +113,10 @@ __device__ __forceinline__ void stage_tile_packed(__amdgpu_buffer_rsrc_t rs, cha
         dst = dump + (wave % (NT / 64)) * 1024;
       }
     }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(dst), 16, voff, 0, 0, 0);
   }
 }
 
-// A operand of the k-contiguous ping-pong kernels, staged in PAIRS of K stages: one LDS-DMA wave-instruction fetches 8 rows x 128
-// contiguous bytes (two stages' worth of a row) instead of 16 rows x 64 - LDS-DMA delivers 33 B/clk/CU on 128-byte segments against 22
-// on 64-byte ones (tools/micro/dma_rate.hip), and the operand delivery is co-critical with the MFMA issue in these kernels.  Pair image:
-// [ROWS][128 B], 16-byte chunk c = 4 * (stage & 1) + kc of a row stored at chunk slot c ^ ((row >> 1) & 7): conflict-free for the
-// fragment reads of either stage (a 16-lane group of ds_read_b128 holds 16 distinct rows, 8 with kc and 8 with kc ^ 1).
-// I0 .. I1: the wave-instructions issued by this call (a pair is issued in two halves, one per slot of the ping-pong loop)
-template <int ROWS, int NT, int AUX, int I0, int I1>
-__device__ __forceinline__ void stage_a_pair(__amdgpu_buffer_rsrc_t rs, char* pair, int64_t row0, int64_t k0, int64_t ld, int tid) {
-  const int wave = tid >> 6;
-  static_assert((ROWS * 8) % NT == 0 && I1 <= (ROWS * 8) / NT, "stage_a_pair: whole instructions only");
-#pragma unroll
-  for (int i = I0; i < I1; ++i) {
-    const int p = i * NT + tid;
-    const int row = p >> 3, slot = p & 7;
-    const int c = slot ^ ((row >> 1) & 7);
-    const uint32_t voff = (uint32_t)(((row0 + row) * ld + k0 + c * 8) * 2);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(pair + (i * NT + wave * 64) * 16), 16, voff, 0, 0, AUX);
-  }
-}
-__device__ __forceinline__ bf16x8 read_frag_pair(const char* pair, int half, int row_base, int lane) {
-  const int row = row_base + (lane & 15);
-  const int c = 4 * half + (lane >> 4);
-  return *(const bf16x8*)(pair + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-}
 // s_waitcnt vmcnt(n) for a wave-uniform even n <= 12
 __device__ __forceinline__ void wait_vm_even(int n) {
   switch (n) {
@@ -219,13 +187,13 @@ __device__ __forceinline__ void pp_issue(__amdgpu_buffer_rsrc_t rsA, __amdgpu_bu
                                          const uint32_t* voB, int wv, bool dumpB, char* dump, uint32_t sA, uint32_t sB) {
 #pragma unroll
   for (int i = 0; i < NIA; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(lds + NB_ * STAGE + (i * NT + wv * 64) * 16), 16, voA[i], sA, 0, NB_AUX_A);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(lds + NB_ * STAGE + (i * NT + wv * 64) * 16), 16, voA[i], sA, 0, 0);
 #pragma unroll
   for (int i = 0; i < NIB; ++i) {
     char* dst = lds + NB_ * STAGE + A_BYTES + (i * NT + wv * 64) * 16;
     const bool d = ((BN * 4) % NT != 0) && i == NIB - 1 && dumpB;      // wave-uniform
     if (d) dst = dump;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(dst), 16, voB[i], d ? 0u : sB, 0, NB_AUX_B);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(dst), 16, voB[i], d ? 0u : sB, 0, 0);
   }
 }
 template <int B_, int STAGE, int A_BYTES, int BM, int BN, int TMt, int TNt>
@@ -279,10 +247,10 @@ __device__ __forceinline__ void tt_issue(__amdgpu_buffer_rsrc_t rsA, __amdgpu_bu
                                          const uint32_t* voB, int wv) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(ldsA + ((i * 8 + wv) * STAGES + NB_) * 1024), 16, voA[i], 0, 0, NB_AUX_A);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(ldsA + ((i * 8 + wv) * STAGES + NB_) * 1024), 16, voA[i], 0, 0, 0);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(ldsB + ((i * 8 + wv) * STAGES + NB_) * 1024), 16, voB[i], 0, 0, NB_AUX_B);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(ldsB + ((i * 8 + wv) * STAGES + NB_) * 1024), 16, voB[i], 0, 0, 0);
 }
 // end of a LOAD slot: the (asm) fragment reads have landed; every fragment is redefined AFTER the wait so that no MFMA can be scheduled above it
 template <int TMt, int TNt>
@@ -305,16 +273,10 @@ __device__ __forceinline__ void tt_mfma(const bf16x8* af, const bf16x8* bfr, f32
   __builtin_amdgcn_sched_barrier(0);
 }
 
-#define NB_STAMP(IDX)                                                                                          \
-  if ((DIAG & 32) && p.U && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == 700))                       \
-    ((uint64_t*)p.U)[16000 + (blockIdx.x ? 8 : 0) + (IDX)] = __builtin_readcyclecounter()
-
-template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, int EPI, bool SYM = false>
+template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, int EPI>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  NB_STAMP(0);
   constexpr int NT = WM * WN * 64;                   // 256 threads (2 x 2 waves) or 512 (2 x 4 waves)
-  constexpr bool PIPE = (BM == 128 && NT == 256);   // second fragment register set: fits only the 64x64 wave tile
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TMt = WTM / 16, TNt = WTN / 16;
   // k-contiguous operands with a bf16 output: un-swapped MFMA, permuted B rows, epilogue straight from the accumulators (see above)
@@ -348,7 +310,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
   }
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)opA, 0, a_bytes, 0x00020000);
-  const bool b_packed = kDirect && NT == 512 && p.Bp != nullptr && ((BN != 384 && BN != 512) || !(DIAG & 0x8000));      // workgroup-uniform
+  const bool b_packed = kDirect && NT == 512 && p.Bp != nullptr;      // workgroup-uniform
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(b_packed ? (void*)p.Bp : (void*)opB, 0, b_packed ? p.bp_bytes : b_bytes, 0x00020000);
   const int nkt = (int)(p.K / BK);
 
@@ -381,7 +343,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   const int dg = lane >> 4, dc = lane & 15;
   const int64_t dcol = n0 + wn * WTN + TNt * dc;
   const int64_t drow0 = m0 + wm * WTM + 4 * dg;
-  constexpr int NPRE0 = SYM ? 0 : 1;   // 16-row tiles whose residual / GELU' rows are fetched before the K loop (the rest right after it)
   float db[TNt];
   u32x4 dpre[TMt][4];        // TNt = 8: 16 bytes of residual (8 bf16) per (i, e); TNt = 6: 12 bytes; TNt = 4: 8 bytes; GELU': TNt bytes
   const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, p.c_bytes, 0x00020000);
@@ -413,11 +374,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
   };
   if constexpr (kDirect) {
-    if constexpr (!SYM) load_bias();
-    if (kHasR || kHasUin) {
-#pragma unroll
-      for (int i = 0; i < NPRE0; ++i) load_dpre(i);
-    }
+    load_bias();
+    if (kHasR || kHasUin) load_dpre(0);   // the residual / GELU' rows of the first 16-row tile; the others right after the K loop
   }
 
   f32x4 acc[TMt][TNt];
@@ -426,176 +384,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #pragma unroll
     for (int j = 0; j < TNt; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
 
-  if constexpr (SYM) {
-    // ---- symmetric software pipeline (experiment): every wave interleaves the fragment reads of stage kt+1 (second register set)
-    // with the MFMAs of stage kt; ONE workgroup barrier per stage (stage kt+1 landed for everyone / slot of stage kt-1 free).
-    static_assert(NT == 512 && kDirect && !TA && !TB, "SYM: k-contiguous 8-wave tiles only");
-    // The current stage lives in registers only: after the barrier of stage kt every wave has its fragments of stage kt (lgkmcnt(0)
-    // before the barrier), so slot kt % STAGES is refilled with stage kt + STAGES right away - three stages stay in flight.
-#pragma unroll
-    for (int s0 = 0; s0 < STAGES; ++s0) {
-      if (s0 < nk) {
-        stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + s0 * STAGE, m0a, kbeg + (int64_t)s0 * BK, lda_, tid);
-        stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + s0 * STAGE + A_BYTES, n0, kbeg + (int64_t)s0 * BK, ldb_, tid, lds + STAGES * STAGE);
-      }
-    }
-    {
-      const int younger = (nk - 1 < STAGES - 1) ? nk - 1 : STAGES - 1;
-      if (younger >= 3) wait_vm<3 * NDMA>();
-      else if (younger == 2) wait_vm<2 * NDMA>();
-      else if (younger == 1) wait_vm<NDMA>();
-      else wait_vm<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    bf16x8 aP[TMt], bP[TNt], aQ[TMt], bQ[TNt];
-#pragma unroll
-    for (int j = 0; j < TNt; ++j) bP[j] = read_frag2<false, BN>(lds + A_BYTES, wn * WTN + j * 16, lane);
-#pragma unroll
-    for (int i = 0; i < TMt; ++i) aP[i] = read_frag2<false, BM>(lds, wm * WTM + i * 16, lane);
-    int buf = 0;
-    // body of a stage that has a successor: wait for / publish stage kt+1, refill the ring, then ONE basic block of 32 MFMAs on the
-    // current fragments with the 12 reads of the next fragments spread between them
-    auto body = [&](int kt, bf16x8 (&aX)[TMt], bf16x8 (&bX)[TNt], bf16x8 (&aY)[TMt], bf16x8 (&bY)[TNt]) {
-      // issued so far: stages .. kt+3 (those below nk); stage kt+1 must have landed, this wave's fragments of stage kt too
-      if (kt + 3 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * NDMA) : "memory");
-      else if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NDMA) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (kt + STAGES < nk && !(DIAG & 256)) {
-        const int64_t k0 = kbeg + (int64_t)(kt + STAGES) * BK;
-        stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + buf * STAGE, m0a, k0, lda_, tid);
-        stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + buf * STAGE + A_BYTES, n0, k0, ldb_, tid, lds + STAGES * STAGE);
-      }
-      int nx = buf + 1;
-      if (nx >= STAGES) nx -= STAGES;
-      const char* nxt = lds + nx * STAGE;
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(DIAG & 128)) {
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) bY[j] = read_frag2<false, BN>(nxt + A_BYTES, wn * WTN + j * 16, lane);
-#pragma unroll
-        for (int i = 0; i < TMt; ++i) aY[i] = read_frag2<false, BM>(nxt, wm * WTM + i * 16, lane);
-      } else {
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) bY[j] = bX[j];
-#pragma unroll
-        for (int i = 0; i < TMt; ++i) aY[i] = aX[i];
-      }
-      if constexpr (!(DIAG & 64)) {
-#pragma unroll
-      for (int i = 0; i < TMt; ++i)
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aX[i], bX[j], acc[i][j], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < TMt; ++i) asm volatile("" :: "v"(aX[i]));
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) asm volatile("" :: "v"(bX[j]));
-      }
-      if constexpr (!(DIAG & (64 | 128 | 512))) {
-      constexpr int N3 = TMt * TNt - 2 * (TMt + TNt), N2 = TMt + TNt - N3;
-      static_assert(N3 >= 0 && N2 >= 0, "SYM: interleave pattern");
-#pragma unroll
-      for (int g = 0; g < N3; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-#pragma unroll
-      for (int g = 0; g < N2; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      buf = nx;
-    };
-    // (the body of the LAST stage runs the same code: its barrier is harmless and its fragment reads fetch a stale slot nobody uses -
-    // a separate tail would be a third copy of the body, and the register allocator spilled 300 dwords per thread around it)
-    for (int kt = 0; kt < nk; kt += 2) {
-      body(kt, aP, bP, aQ, bQ);
-      if (kt + 1 < nk) body(kt + 1, aQ, bQ, aP, bP);
-    }
-    load_bias();
-  } else if constexpr (NT == 512 && kDirect && BM == 256 && (DIAG & 2048)) {
-    // ---- EXPERIMENT (`make diag DIAG=2048`; measured 25 % SLOWER than per-stage staging - waves wait twice as long for the LDS-DMA,
-    // no LDS bank conflicts; cause not found - kept for the next attempt) ----
-    // ---- ping-pong as below, with the A operand staged in PAIRS of stages (128-byte row segments, stage_a_pair): LDS = 3 pair buffers
-    // of A (2 x A_BYTES each) | STAGES tiles of B | dump slots.  A LOAD slot is as long as an MFMA slot and most of it is LDS-DMA issue,
-    // so a pair is issued in two halves, one per slot: slot j issues half (j & 1) of A pair j/2 + 2 and then B stage j + 3 - four
-    // wave-instructions per slot, as with per-stage staging.  Per wave the issue order is  A0 A1 B0 B1 B2 | A2a B3 | A2b B4 | A3a B5 | ...
-    // and slot kt retires this wave's share of stage kt+1 = B(kt+1), the last instruction of slot kt-2 (A((kt+1)/2) is older): whatever
-    // slots kt-1 and kt issued may stay in flight.
-    constexpr int AP_BYTES = 2 * A_BYTES, NAP = 3;
-    constexpr int NDA = (BM * 8) / NT, NDB = (BN * 4 + NT - 1) / NT, NDH = NDA / 2;
-    static_assert(NDH % 2 == 0 && NDB % 2 == 0 && 2 * NDH + 2 * NDB <= 12, "wait_vm_even covers even counts up to 12");
-    static_assert(STAGES == 4, "pair path: B ring of 4");
-    char* const ldsB = lds + NAP * AP_BYTES;
-    char* const dumpB = ldsB + STAGES * B_BYTES;
-    const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
-    auto issue_b = [&](int st_) {
-      char* dst = ldsB + (st_ & (STAGES - 1)) * B_BYTES;
-      if (b_packed) stage_tile_packed<BN, NT, NB_AUX_B>(rsB, dst, (uint32_t)((tile_n * nkt + st_) * B_BYTES), tid, dumpB);
-      else stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, dst, n0, kbeg + (int64_t)st_ * BK, ldb_, tid, dumpB);
-    };
-    // slot j: half (j & 1) of the pair holding stages j' + 4, j' + 5 (j' = j rounded down to even); exists iff stage j' + 4 does
-    auto a_half_exists = [&](int j) { return (j & ~1) + 4 < nk; };
-    auto issue_a_half = [&](int j) {
-      const int q = (j >> 1) + 2;
-      char* dst = lds + (q % NAP) * AP_BYTES;
-      const int64_t k0 = kbeg + (int64_t)q * (2 * BK);
-      if (j & 1) stage_a_pair<BM, NT, NB_AUX_A, NDH, NDA>(rsA, dst, m0a, k0, lda_, tid);
-      else stage_a_pair<BM, NT, NB_AUX_A, 0, NDH>(rsA, dst, m0a, k0, lda_, tid);
-    };
-    if (0 < nk) stage_a_pair<BM, NT, NB_AUX_A, 0, NDA>(rsA, lds, m0a, kbeg, lda_, tid);
-    if (2 < nk) stage_a_pair<BM, NT, NB_AUX_A, 0, NDA>(rsA, lds + AP_BYTES, m0a, kbeg + 2 * BK, lda_, tid);
-#pragma unroll
-    for (int s0 = 0; s0 < STAGES - 1; ++s0)
-      if (s0 < nk) issue_b(s0);
-    {
-      const int younger = (nk - 1 < STAGES - 2) ? nk - 1 : STAGES - 2;   // B stages issued after B0
-      wait_vm_even(younger * NDB);
-    }
-    __builtin_amdgcn_s_barrier();                 // stage 0 landed for everyone
-    asm volatile("" ::: "memory");
-    if (grp == 1) __builtin_amdgcn_s_barrier();   // offset group 1 by one slot
-    bf16x8 af[TMt], bfr[TNt];
-    for (int kt = 0; kt < nk; ++kt) {
-      // ---------------- LOAD slot ----------------
-      const bool ah = a_half_exists(kt), bh = kt + STAGES - 1 < nk;
-      if (ah) issue_a_half(kt);
-      if (bh) issue_b(kt + STAGES - 1);
-      {
-        const char* curB = ldsB + (kt & (STAGES - 1)) * B_BYTES;
-        const char* curA = lds + ((kt >> 1) % NAP) * AP_BYTES;
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) bfr[j] = read_frag2<false, BN>(curB, wn * WTN + j * 16, lane);
-#pragma unroll
-        for (int i = 0; i < TMt; ++i) af[i] = read_frag_pair(curA, kt & 1, wm * WTM + i * 16, lane);
-      }
-      if (kt + 1 < nk) {   // retire this wave's share of stage kt+1
-        int cnt = (ah ? NDH : 0) + (bh ? NDB : 0);                                                    // this slot
-        if (kt == 0) cnt += (2 < nk ? NDB : 0);                                                      // B2 of the prologue follows B1
-        else cnt += (a_half_exists(kt - 1) ? NDH : 0) + (kt + 2 < nk ? NDB : 0);                      // slot kt-1
-        wait_vm_even(cnt);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---------------- MFMA slot ----------------
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i)
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();   // balance the barrier count
-  } else if constexpr (NT == 512 && kDirect && !(DIAG & 0x8000)) {
+  if constexpr (NT == 512 && kDirect) {
     // ---- ping-pong as in the generic branch below (two wave groups one slot out of phase, LOAD slot | barrier | MFMA slot | barrier),
     // with the LOAD slot stripped to its memory instructions (round 4).  The ISA of the generic branch spent, per slot: ~20 VALU
     // instructions on addresses (per-lane DMA source offsets re-derived from k0, LDS destinations computed in VGPRs and moved to M0
@@ -706,7 +495,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #undef PP_MFMA
 #undef PP_STEADY
 #undef PP_GENERIC
-  } else if constexpr (NT == 512 && TA && TB && BM == 256 && BN == 256 && STAGES == 4 && !(DIAG & 0x8000)) {
+  } else if constexpr (NT == 512 && TA && TB && BM == 256 && BN == 256 && STAGES == 4) {
     // ---- the weight-gradient kernel (both operands token-major), round 4.  Two changes against the generic ping-pong branch below:
     // (1) the LOAD slot is stripped to its memory instructions, as in the k-contiguous branch above.  The generic LOAD slot carried 41 vector
     //     and ~19 scalar instructions around its 4 LDS-DMA pieces and 24 transposed reads (per-lane DMA offsets re-derived from k0, LDS
@@ -716,7 +505,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     //     per-lane offset: the rows past the last token are zero-filled by the descriptor, and a scalar offset is not range-checked),
     //     fragment addresses = 12 per-lane registers set up once + immediates (tt_frags; ring image with the stage index below the
     //     k-row pair), steady state and tail separate.  165 -> 136 us per launch.
-    // (2) ONE workgroup barrier per stage instead of two per slot.  Stamps (tools/slot_trace_tt.py) showed LOAD slot 620 and MFMA slot 655
+    // (2) ONE workgroup barrier per stage instead of two per slot.  Cycle stamps showed LOAD slot 620 and MFMA slot 655
     //     cycles plus 80 - 120 cycles at EACH of the two barriers of a slot - 80 is what s_barrier costs the LAST wave to arrive.  The two
     //     groups need one rendezvous per stage, not four: group 0 runs [LOAD k | MFMA k], group 1 [MFMA k-1 | LOAD k] between two
     //     barriers - each group's LOAD overlaps the other's MFMA by construction, and the barrier at the end of the period is what orders
@@ -783,13 +572,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
       tt_frags_ready<TMt, TNt>(af, bfr);                                       \
     } while (0)
 #define TT_MFMA() tt_mfma<TMt, TNt>(af, bfr, acc)
-    // (DIAG & 32: s_memtime stamps of workgroup 0, one wave per group: period start, between its two halves, before and after the barrier -
-    // tools/slot_trace_tt.py)
-    uint64_t* const stamps = ((DIAG & 32) && p.U && blockIdx.x == 0 && lane == 0 && (wv & 3) == 0) ? (uint64_t*)p.U + (wv >> 2) * 8192 : nullptr;
-    int sp = 0;
-#define TT_ST(I) do { if ((DIAG & 32) && stamps) stamps[4 * sp + (I)] = __builtin_readcyclecounter(); } while (0)
-#define TT_MID() TT_ST(1)
-#define TT_BAR() do { __builtin_amdgcn_sched_barrier(0); TT_ST(2); __builtin_amdgcn_s_barrier(); TT_ST(3); ++sp; TT_ST(0); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TT_BAR() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
     if (0 < nk) TT_ISSUE(0);
     if (1 < nk) TT_ISSUE(1);
     if (2 < nk) TT_ISSUE(2);
@@ -801,22 +584,21 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
     __builtin_amdgcn_s_barrier();                 // stage 0 landed for everyone
     asm volatile("" ::: "memory");
-    TT_ST(0);
     const int n_steady = nk - (STAGES - 1);       // stages kt < n_steady still have a stage to issue in their LOAD slot
     if (grp == 0) {
       // period kt: LOAD kt | MFMA kt | barrier
       int kt = 0;
       for (; kt + STAGES <= n_steady; kt += STAGES) {
-        TT_LOAD_STEADY(0); TT_MID(); TT_MFMA(); TT_BAR();
-        TT_LOAD_STEADY(1); TT_MID(); TT_MFMA(); TT_BAR();
-        TT_LOAD_STEADY(2); TT_MID(); TT_MFMA(); TT_BAR();
-        TT_LOAD_STEADY(3); TT_MID(); TT_MFMA(); TT_BAR();
+        TT_LOAD_STEADY(0); TT_MFMA(); TT_BAR();
+        TT_LOAD_STEADY(1); TT_MFMA(); TT_BAR();
+        TT_LOAD_STEADY(2); TT_MFMA(); TT_BAR();
+        TT_LOAD_STEADY(3); TT_MFMA(); TT_BAR();
       }
       for (; kt < nk; kt += STAGES) {
-        TT_LOAD_GENERIC(kt, 0); TT_MID(); TT_MFMA(); TT_BAR();
-        if (kt + 1 < nk) { TT_LOAD_GENERIC(kt + 1, 1); TT_MID(); TT_MFMA(); TT_BAR(); }
-        if (kt + 2 < nk) { TT_LOAD_GENERIC(kt + 2, 2); TT_MID(); TT_MFMA(); TT_BAR(); }
-        if (kt + 3 < nk) { TT_LOAD_GENERIC(kt + 3, 3); TT_MID(); TT_MFMA(); TT_BAR(); }
+        TT_LOAD_GENERIC(kt, 0); TT_MFMA(); TT_BAR();
+        if (kt + 1 < nk) { TT_LOAD_GENERIC(kt + 1, 1); TT_MFMA(); TT_BAR(); }
+        if (kt + 2 < nk) { TT_LOAD_GENERIC(kt + 2, 2); TT_MFMA(); TT_BAR(); }
+        if (kt + 3 < nk) { TT_LOAD_GENERIC(kt + 3, 3); TT_MFMA(); TT_BAR(); }
       }
       TT_BAR();                                   // the period in which group 1 multiplies its last stage
     } else {
@@ -825,16 +607,16 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
       TT_BAR();
       int kt = 1;
       for (; kt + STAGES <= n_steady; kt += STAGES) {       // kt = 1 (mod 4): ring slots 1, 2, 3, 0
-        TT_MFMA(); TT_MID(); TT_LOAD_STEADY(1); TT_BAR();
-        TT_MFMA(); TT_MID(); TT_LOAD_STEADY(2); TT_BAR();
-        TT_MFMA(); TT_MID(); TT_LOAD_STEADY(3); TT_BAR();
-        TT_MFMA(); TT_MID(); TT_LOAD_STEADY(0); TT_BAR();
+        TT_MFMA(); TT_LOAD_STEADY(1); TT_BAR();
+        TT_MFMA(); TT_LOAD_STEADY(2); TT_BAR();
+        TT_MFMA(); TT_LOAD_STEADY(3); TT_BAR();
+        TT_MFMA(); TT_LOAD_STEADY(0); TT_BAR();
       }
       for (; kt < nk; kt += STAGES) {
-        TT_MFMA(); TT_MID(); TT_LOAD_GENERIC(kt, 1); TT_BAR();
-        if (kt + 1 < nk) { TT_MFMA(); TT_MID(); TT_LOAD_GENERIC(kt + 1, 2); TT_BAR(); }
-        if (kt + 2 < nk) { TT_MFMA(); TT_MID(); TT_LOAD_GENERIC(kt + 2, 3); TT_BAR(); }
-        if (kt + 3 < nk) { TT_MFMA(); TT_MID(); TT_LOAD_GENERIC(kt + 3, 0); TT_BAR(); }
+        TT_MFMA(); TT_LOAD_GENERIC(kt, 1); TT_BAR();
+        if (kt + 1 < nk) { TT_MFMA(); TT_LOAD_GENERIC(kt + 1, 2); TT_BAR(); }
+        if (kt + 2 < nk) { TT_MFMA(); TT_LOAD_GENERIC(kt + 2, 3); TT_BAR(); }
+        if (kt + 3 < nk) { TT_MFMA(); TT_LOAD_GENERIC(kt + 3, 0); TT_BAR(); }
       }
       if (0 < nk) TT_MFMA();
       TT_BAR();
@@ -845,8 +627,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #undef TT_LOAD_GENERIC
 #undef TT_MFMA
 #undef TT_BAR
-#undef TT_MID
-#undef TT_ST
   } else if constexpr (NT == 512) {
     // ---- ping-pong (8 waves = 2 groups of one wave per SIMD): a group alternates a LOAD slot (fragment
     // reads of stage j, LDS-DMA of stage j+STAGES-1, counted vmcnt) with an MFMA slot (stage j); group 1
@@ -856,10 +636,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #pragma unroll
     for (int s0 = 0; s0 < STAGES - 1; ++s0) {
       if (s0 < nk) {
-        stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + s0 * STAGE, m0a, kbeg + (int64_t)s0 * BK, lda_, tid);
-        if (b_packed) stage_tile_packed<BN, NT, NB_AUX_B>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTES), tid, lds + STAGES * STAGE);
+        stage_tile2<TA, BM, NT>(rsA, lds + s0 * STAGE, m0a, kbeg + (int64_t)s0 * BK, lda_, tid);
+        if (b_packed) stage_tile_packed<BN, NT>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTES), tid, lds + STAGES * STAGE);
         else
-        stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + s0 * STAGE + A_BYTES, n0, kbeg + (int64_t)s0 * BK, ldb_, tid, lds + STAGES * STAGE);
+        stage_tile2<TB, BN, NT, kPW>(rsB, lds + s0 * STAGE + A_BYTES, n0, kbeg + (int64_t)s0 * BK, ldb_, tid, lds + STAGES * STAGE);
       }
     }
     {
@@ -871,28 +651,25 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
     __builtin_amdgcn_s_barrier();                 // stage 0 landed for everyone
     asm volatile("" ::: "memory");
-    NB_STAMP(1);
     if (grp == 1) __builtin_amdgcn_s_barrier();   // offset group 1 by one slot
     int buf = 0;
     bf16x8 af[TMt], bfr[TNt];
     for (int kt = 0; kt < nk; ++kt) {
       // ---------------- LOAD slot ----------------
-      if (kt + STAGES - 1 < nk && !(DIAG & 1)) {
+      if (kt + STAGES - 1 < nk) {
         int nb = buf + STAGES - 1;
         if (nb >= STAGES) nb -= STAGES;
         const int64_t k0 = kbeg + (int64_t)(kt + STAGES - 1) * BK;
-        stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + nb * STAGE, m0a, k0, lda_, tid);
-        if (b_packed) stage_tile_packed<BN, NT, NB_AUX_B>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTES), tid, lds + STAGES * STAGE);
+        stage_tile2<TA, BM, NT>(rsA, lds + nb * STAGE, m0a, k0, lda_, tid);
+        if (b_packed) stage_tile_packed<BN, NT>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTES), tid, lds + STAGES * STAGE);
         else
-        stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, ldb_, tid, lds + STAGES * STAGE);
+        stage_tile2<TB, BN, NT, kPW>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, ldb_, tid, lds + STAGES * STAGE);
       }
       const char* cur = lds + buf * STAGE;
-      if ((DIAG & 2) == 0 || kt == 0) {
 #pragma unroll
-        for (int j = 0; j < TNt; ++j) bfr[j] = read_frag2<TB, BN, true>(cur + A_BYTES, wn * WTN + j * 16, lane);
+      for (int j = 0; j < TNt; ++j) bfr[j] = read_frag2<TB, BN, true>(cur + A_BYTES, wn * WTN + j * 16, lane);
 #pragma unroll
-        for (int i = 0; i < TMt; ++i) af[i] = read_frag2<TA, BM, true>(cur, wm * WTM + i * 16, lane);
-      }
+      for (int i = 0; i < TMt; ++i) af[i] = read_frag2<TA, BM, true>(cur, wm * WTM + i * 16, lane);
       {
         // retire this wave's share of stage kt+1 (read by group 0 two slots from now)
         const int c = (nk - 1 - kt < STAGES - 1) ? nk - 1 - kt : STAGES - 1;   // stages kt+1.. outstanding
@@ -902,9 +679,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
         else if (c == 1) wait_vm<0>();
       }
       __builtin_amdgcn_sched_barrier(0);
-      if ((DIAG & 32) && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0 && p.U) ((uint64_t*)p.U)[(wave >> 2) * 8192 + 4 * kt + 0] = __builtin_readcyclecounter();
       __builtin_amdgcn_s_barrier();
-      if ((DIAG & 32) && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0 && p.U) ((uint64_t*)p.U)[(wave >> 2) * 8192 + 4 * kt + 1] = __builtin_readcyclecounter();
       __builtin_amdgcn_sched_barrier(0);
       // ---------------- MFMA slot ----------------
       __builtin_amdgcn_s_setprio(1);
@@ -917,97 +692,25 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #pragma unroll
         for (int j = 0; j < TNt; ++j) asm volatile("" : "+v"(bfr[j]));
       }
-      if constexpr (!(DIAG & 4)) {
 #pragma unroll
-        for (int i = 0; i < TMt; ++i)
+      for (int i = 0; i < TMt; ++i)
 #pragma unroll
-          for (int j = 0; j < TNt; ++j) acc[i][j] = kDirect ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < TMt; ++i) asm volatile("" :: "v"(af[i]));
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) asm volatile("" :: "v"(bfr[j]));
-      }
+        for (int j = 0; j < TNt; ++j) acc[i][j] = kDirect ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0)
+                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if ((DIAG & 32) && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0 && p.U) ((uint64_t*)p.U)[(wave >> 2) * 8192 + 4 * kt + 2] = __builtin_readcyclecounter();
       __builtin_amdgcn_s_barrier();
-      if ((DIAG & 32) && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0 && p.U) ((uint64_t*)p.U)[(wave >> 2) * 8192 + 4 * kt + 3] = __builtin_readcyclecounter();
       __builtin_amdgcn_sched_barrier(0);
       buf = (buf + 1 == STAGES) ? 0 : buf + 1;
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();   // balance the barrier count
-    NB_STAMP(2);
-  } else if constexpr (PIPE) {
-  // ---- ring: buffers hold stages kt+1 .. kt+STAGES; fragments of stage kt+1 are read (into the other
-  // register set) while the MFMAs of stage kt run, so no LDS round trip is exposed at a stage boundary.
-#pragma unroll
-  for (int s = 0; s < STAGES; ++s) {
-    if (s < nk) {
-      stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + s * STAGE, m0a, kbeg + (int64_t)s * BK, lda_, tid);
-      stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + s * STAGE + A_BYTES, n0, kbeg + (int64_t)s * BK, ldb_, tid);
-    }
-  }
-  bf16x8 afA[TMt], bfA[TNt], afB[TMt], bfB[TNt];
-  {
-    const int inflight = (nk < STAGES ? nk : STAGES) - 1;   // stages that may stay in flight behind stage 0
-    if (inflight >= 3) wait_vm<3 * NDMA>();
-    else if (inflight == 2) wait_vm<2 * NDMA>();
-    else if (inflight == 1) wait_vm<NDMA>();
-    else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (nk > 0) {
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) bfA[j] = read_frag2<TB, BN>(lds + A_BYTES, wn * WTN + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i) afA[i] = read_frag2<TA, BM>(lds, wm * WTM + i * 16, lane);
-    }
-  }
-  int buf = 0;  // buffer of stage kt
-  // one pipeline step: top-of-iteration sync for stage kt+1, refill the buffer stage kt occupied,
-  // read fragments of stage kt+1 into (an, bn) while multiplying (ac, bc)
-#define NB_STEP(ac, bc, an, bn)                                                                              \
-  {                                                                                                          \
-    const int c = (nk - 1 - kt < STAGES - 1) ? nk - 1 - kt : STAGES - 1; /* stages kt+1.. still outstanding */ \
-    if (c >= 3) wait_vm<2 * NDMA>();                                                                         \
-    else if (c == 2) wait_vm<NDMA>();                                                                        \
-    else if (c == 1) wait_vm<0>();                                                                           \
-    __builtin_amdgcn_s_barrier();                                                                            \
-    asm volatile("" ::: "memory");                                                                           \
-    if (kt + STAGES < nk) {                                                                                  \
-      const int64_t k0 = kbeg + (int64_t)(kt + STAGES) * BK;                                                 \
-      stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + buf * STAGE, m0a, k0, lda_, tid);                                       \
-      stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + buf * STAGE + A_BYTES, n0, k0, ldb_, tid);                             \
-    }                                                                                                        \
-    const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;                                                      \
-    if (kt + 1 < nk) {                                                                                       \
-      const char* nx = lds + nbuf * STAGE;                                                                   \
-      _Pragma("unroll") for (int j = 0; j < TNt; ++j) bn[j] = read_frag2<TB, BN>(nx + A_BYTES, wn * WTN + j * 16, lane); \
-      _Pragma("unroll") for (int i = 0; i < TMt; ++i) an[i] = read_frag2<TA, BM>(nx, wm * WTM + i * 16, lane); \
-    }                                                                                                        \
-    _Pragma("unroll") for (int i = 0; i < TMt; ++i)                                                          \
-      _Pragma("unroll") for (int j = 0; j < TNt; ++j)                                                        \
-        acc[i][j] = kDirect ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(ac[i], bc[j], acc[i][j], 0, 0, 0)   \
-                            : __builtin_amdgcn_mfma_f32_16x16x32_bf16(bc[j], ac[i], acc[i][j], 0, 0, 0);  \
-    buf = nbuf;                                                                                              \
-    ++kt;                                                                                                    \
-  }
-  for (int kt = 0; kt < nk;) {
-    NB_STEP(afA, bfA, afB, bfB)
-    if (kt >= nk) break;
-    NB_STEP(afB, bfB, afA, bfA)
-  }
-#undef NB_STEP
-
   } else {
-  // ---- plain ring (256x128: no registers left for a second fragment set): STAGES-1 stages in flight ----
+  // ---- plain ring (256x128, 4 waves): STAGES-1 stages in flight ----
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s) {
     if (s < nk) {
-      stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + s * STAGE, m0a, kbeg + (int64_t)s * BK, lda_, tid);
-      stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + s * STAGE + A_BYTES, n0, kbeg + (int64_t)s * BK, ldb_, tid);
+      stage_tile2<TA, BM, NT>(rsA, lds + s * STAGE, m0a, kbeg + (int64_t)s * BK, lda_, tid);
+      stage_tile2<TB, BN, NT, kPW>(rsB, lds + s * STAGE + A_BYTES, n0, kbeg + (int64_t)s * BK, ldb_, tid);
     }
   }
   int buf = 0;
@@ -1023,8 +726,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
       int nb = buf + STAGES - 1;
       if (nb >= STAGES) nb -= STAGES;
       const int64_t k0 = kbeg + (int64_t)(kt + STAGES - 1) * BK;
-      stage_tile2<TA, BM, NT, NB_AUX_A>(rsA, lds + nb * STAGE, m0a, k0, lda_, tid);
-      stage_tile2<TB, BN, NT, NB_AUX_B, kPW>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, ldb_, tid, lds + STAGES * STAGE);
+      stage_tile2<TA, BM, NT>(rsA, lds + nb * STAGE, m0a, k0, lda_, tid);
+      stage_tile2<TB, BN, NT, kPW>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, ldb_, tid, lds + STAGES * STAGE);
     }
     const char* cur = lds + buf * STAGE;
     bf16x8 af[TMt], bfr[TNt];
@@ -1046,7 +749,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     // lane in one basic block, which the compiler is free to interleave (the GELU forms are ~25-instruction chains)
     if (kHasR || kHasUin) {
 #pragma unroll
-      for (int i = NPRE0; i < TMt; ++i) load_dpre(i);
+      for (int i = 1; i < TMt; ++i) load_dpre(i);
     }
     float colacc[TNt];
 #pragma unroll
@@ -1101,9 +804,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #pragma unroll
           for (int j = 0; j < TNt; ++j) v[j] *= gd[j];
         }
-        // (experiment DIAG & 4096: the QKV projection - the step's only plain-bias GEMM - written WITHOUT the streaming hint, for its
-        // immediate reader, the attention forward)
-        if constexpr (TNt == 8) nb_bstore_bf16x8<(EPI == NBEST_EPI_BIAS && (DIAG & 4096)) ? 0 : 2>(rsC, voC + rr * svC, v);
+        if constexpr (TNt == 8) nb_bstore_bf16x8(rsC, voC + rr * svC, v);
         else if constexpr (TNt == 6) {
           bf16x2 o0 = {(bf16)v[0], (bf16)v[1]}, o1 = {(bf16)v[2], (bf16)v[3]}, o2 = {(bf16)v[4], (bf16)v[5]};
           __builtin_amdgcn_raw_buffer_store_b96(u32x3{__builtin_bit_cast(uint32_t, o0), __builtin_bit_cast(uint32_t, o1), __builtin_bit_cast(uint32_t, o2)},
@@ -1222,8 +923,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
     asm volatile("" ::: "memory");
   }
-  if (DIAG & 32) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stamp after the stores are acknowledged
-  NB_STAMP(3);
   if (EPI != NBEST_EPI_F32_SPLITK && p.colpart) {   // fused bias gradient: per-wave column sums -> partial rows
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -1238,334 +937,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
     }
   }
 }
-
-#ifdef NBEST_EXPERIMENTS
-// LDS / global accesses that the wait-count pass must not see (it would drain the in-flight LDS-DMA ring, and every
-// store with it, in front of each of them); the caller orders them with explicit s_waitcnt.
-__device__ __forceinline__ void lds_write_b128_asm(const void* addr, f32x4 v) {
-  const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)addr;
-  asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(v) : "memory");
-}
-__device__ __forceinline__ f32x4 lds_read_b128_asm(const void* addr) {
-  f32x4 v;
-  const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)addr;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
-}
-__device__ __forceinline__ f32x4 global_load_f32x4_asm(const float* ptr) {
-  f32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
-  return v;
-}
-
-// ---- persistent ping-pong kernel -------------------------------------------------------------------------------
-// One workgroup per CU walks tiles b, b+G, b+2G, ...; the 4-stage LDS ring simply runs on into the next tile: the
-// last three LOAD slots of a tile issue stages 0..2 of the NEXT tile, so its prologue (≈10 % of a K = 768 tile,
-// the LDS-DMA latency of the first stage) is hidden behind the current tile's MFMAs and epilogue.  While those
-// three stages sit in three ring buffers the epilogue restages through the fourth (32 KiB: 4 KiB per wave, 16-row
-// chunks).  k-contiguous operands, epilogues without a residual / GELU' input (NONE, BIAS, BIAS_GELU), splits == 1,
-// nk >= 3.  vmcnt: the epilogue's stores (and the tile's bias loads) enter the per-wave stream between DMA stages;
-// completion is in order, so the counted waits of the first two LOAD slots of a tile allow for them explicitly
-// (full tiles issue a fixed number of stores; the ragged last row tile drains with vmcnt(0) instead).
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm2p_kernel(GemmP2 p) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  constexpr int BM = 256, BN = 256, WN = 4, NT = 512, STAGES = 4;
-  constexpr int WTM = 128, WTN = 64, TMt = 8, TNt = 4;
-  constexpr int A_BYTES = BM * BK * 2, STAGE = 2 * A_BYTES;
-  constexpr int NDMA = (BM + BN) * 4 / NT;   // 4
-  constexpr bool kDirect = false;            // LDS-restaged epilogue, swapped MFMA operands
-  constexpr int kPW = 0;
-  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU);
-  constexpr int NSTORE = (WTM / 8) * (EPI == NBEST_EPI_BIAS_GELU ? 2 : 1);   // store instructions per wave and (full) tile
-  constexpr int NBIAS = kHasBias ? 2 : 0;
-  static_assert(EPI == NBEST_EPI_NONE || EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU, "no residual / GELU' input");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int grp = __builtin_amdgcn_readfirstlane(wm);
-  const int G = gridDim.x, tiles = p.tiles_m * p.tiles_n;
-  const int nk = (int)(p.K / BK);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, p.b_bytes, 0x00020000);
-
-  auto tile_origin = [&](int t, int64_t& m0, int64_t& n0) {
-    const int id = xcd_remap2(t, tiles);
-    const int tile_m = id / p.tiles_n, tile_n = id - tile_m * p.tiles_n;
-    m0 = (int64_t)tile_m * BM; n0 = (int64_t)tile_n * BN;
-  };
-  auto issue = [&](int gstage, int64_t m0, int64_t n0, int s) {   // stage s of the tile at (m0, n0) -> ring buffer gstage & 3
-    char* dst = lds + (gstage & 3) * STAGE;
-    stage_tile2<false, BM, NT, NB_AUX_A>(rsA, dst, m0, (int64_t)s * BK, p.lda, tid);
-    stage_tile2<false, BN, NT, NB_AUX_B>(rsB, dst + A_BYTES, n0, (int64_t)s * BK, p.ldb, tid);
-  };
-
-  int t_cur = blockIdx.x;
-  int64_t m0, n0;
-  tile_origin(t_cur, m0, n0);
-  int gs = 0;   // ring position of stage 0 of the current tile
-#pragma unroll
-  for (int s = 0; s < 3; ++s) issue(gs + s, m0, n0, s);
-  int dbg_i = 0;
-#define NB_PSTAMP() if ((DIAG & 32) && EPI == NBEST_EPI_NONE && p.U && tid == 0 && blockIdx.x == 0 && dbg_i < 64) ((uint64_t*)p.U)[dbg_i++] = __builtin_readcyclecounter()
-  NB_PSTAMP();
-  if ((DIAG & 32) && EPI == NBEST_EPI_NONE && p.U && tid == 0) ((uint64_t*)p.U)[1000 + 2 * blockIdx.x] = __builtin_readcyclecounter();
-  int extra = 0;   // younger non-DMA operations (stores of the previous tile, bias loads) that may precede stage 3 in the stream
-
-  while (true) {
-    const int t_next = t_cur + G;
-    const bool has_next = t_next < tiles;
-    int64_t m0n = 0, n0n = 0;
-    if (has_next) tile_origin(t_next, m0n, n0n);
-    const int64_t en8 = n0 + wn * WTN + (lane & 7) * 8;
-    f32x4 pb0 = {0, 0, 0, 0}, pb1 = {0, 0, 0, 0};
-    if (kHasBias) { pb0 = global_load_f32x4_asm(p.bias + en8); pb1 = global_load_f32x4_asm(p.bias + en8 + 4); }
-    f32x4 acc[TMt][TNt];
-#pragma unroll
-    for (int i = 0; i < TMt; ++i)
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-
-    // stage 0 landed: stream tail is  s0 s1 s2 [stores of the previous tile] [bias loads]
-    if (extra < 0) wait_vm<0>();
-    else if (extra == 0) wait_vm<2 * NDMA + NBIAS>();   // first tile of this workgroup: no stores in the stream yet
-    else wait_vm<2 * NDMA + NSTORE + NBIAS>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    NB_PSTAMP();
-    if (grp == 1) __builtin_amdgcn_s_barrier();   // offset group 1 by one slot
-    bf16x8 af[TMt], bfr[TNt];
-    for (int kt = 0; kt < nk; ++kt) {
-      // ---------------- LOAD slot ----------------
-      const int si = kt + 3;
-      if (si < nk) issue(gs + si, m0, n0, si);
-      else if (has_next) issue(gs + si, m0n, n0n, si - nk);
-      const char* cur = lds + ((gs + kt) & 3) * STAGE;
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) bfr[j] = read_frag2<false, BN>(cur + A_BYTES, wn * WTN + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i) af[i] = read_frag2<false, BM>(cur, wm * WTM + i * 16, lane);
-      {
-        // stage kt+1 must have landed; younger: the stages issued after it (+ at kt = 0, 1 the non-DMA operations
-        // that sit between stage 2 and stage 3 of this tile in the stream)
-        const int c = has_next ? 3 : ((nk - 1 - kt < 3) ? nk - 1 - kt : 3);   // stages kt+1 .. outstanding
-        if (c >= 3) {
-          if (kt >= 2) wait_vm<2 * NDMA>();
-          else if (extra < 0) wait_vm<0>();
-          else if (extra == 0) wait_vm<2 * NDMA + NBIAS>();
-          else wait_vm<2 * NDMA + NSTORE + NBIAS>();
-        } else if (c == 2) wait_vm<NDMA>();   // (with nk < 5 this over-waits for the mixed operations at kt < 2: safe)
-        else wait_vm<0>();
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---------------- MFMA slot ----------------
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i)
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) acc[i][j] = kDirect ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();   // balance the barrier count: both groups are in step again
-    NB_PSTAMP();
-
-    // ---- epilogue: 16-row chunks through the one ring buffer the next tile's first three stages do not occupy ----
-    float* ep = (float*)(lds + ((gs + nk + 3) & 3) * STAGE) + wave * 1024;
-    const bool full = (m0 + BM <= p.M);
-    // the bias loads of this tile are older than its stage 3, and stage nk-1 has landed (in-order completion)
-    if (kHasBias) asm volatile("" : "+v"(pb0), "+v"(pb1));
-#pragma unroll
-    for (int c = 0; c < TMt; ++c) {
-      const int wrow = lane & 15;
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) {
-        const int cidx = j * 4 + (lane >> 4);
-        lds_write_b128_asm(ep + wrow * 64 + ((cidx ^ wrow) << 2), acc[c][j]);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      f32x4 rv[2][2];
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int pidx = it * 64 + lane, row = pidx >> 3, c8 = pidx & 7;
-        rv[it][0] = lds_read_b128_asm(ep + row * 64 + (((2 * c8) ^ row) << 2));
-        rv[it][1] = lds_read_b128_asm(ep + row * 64 + (((2 * c8 + 1) ^ row) << 2));
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      asm volatile("" : "+v"(rv[0][0]), "+v"(rv[0][1]), "+v"(rv[1][0]), "+v"(rv[1][1]));
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int pidx = it * 64 + lane, row = pidx >> 3;
-        const int64_t m = m0 + wm * WTM + c * 16 + row;
-        const f32x4 v0 = rv[it][0], v1 = rv[it][1];
-        if (m >= p.M) continue;
-        float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        if (kHasBias) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] += pb0[e]; v[4 + e] += pb1[e]; }
-        }
-        if (EPI == NBEST_EPI_BIAS_GELU) {
-          float gp[8];
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) {
-            f32x2 h2, g2;   // gelu(u), and gelu'(u) kept for the backward
-            gelu_pair_fast(f32x2{v[e], v[e + 1]}, h2, g2);
-            gp[e] = g2[0]; gp[e + 1] = g2[1]; v[e] = h2[0]; v[e + 1] = h2[1];
-          }
-          st_stream((i32x2*)((uint8_t*)p.U + m * p.ldu + en8), i32x2{(int)gd_pack4(gp), (int)gd_pack4(gp + 4)}, p.stream_out);
-        }
-        st_stream_bf16x8((bf16*)p.C + m * p.ldc + en8, v, p.stream_out);
-      }
-      asm volatile("" ::: "memory");
-    }
-    NB_PSTAMP();
-    if ((DIAG & 32) && EPI == NBEST_EPI_NONE && p.U && tid == 0 && !has_next) ((uint64_t*)p.U)[1001 + 2 * blockIdx.x] = __builtin_readcyclecounter();
-    if (!has_next) break;
-    __builtin_amdgcn_s_barrier();   // every wave is done with the restage buffer: stage 3 of the next tile may overwrite it
-    asm volatile("" ::: "memory");
-    extra = full ? NSTORE : -1;      // ragged tile: unknown store count -> the next tile drains with vmcnt(0)
-    gs += nk;
-    t_cur = t_next; m0 = m0n; n0 = n0n;
-  }
-}
-
-
-// ---- persistent ping-pong kernel with the REGISTER epilogue (experiment, NBEST_PERSISTENT=2): one workgroup per CU walks tiles
-// t = blockIdx, blockIdx + G, ...; the LDS ring runs on into the next tile (its first three stages are issued during the last three
-// LOAD slots of the current one), so neither the LDS-DMA latency of a tile's prologue nor the workgroup launch is exposed, and the
-// epilogue - registers and buffer stores only, no LDS - overlaps the landing of those stages.  k-contiguous operands, 256 x 256 tiles,
-// 4 x 2 waves of 64 x 128, epilogues NONE / BIAS / BIAS_GELU.  vmcnt bookkeeping: per tile and wave the stream is
-//   S0 S1 S2 (issued inside the previous tile) | NST epilogue stores of the previous tile | 2 bias loads | S3 S4 ...
-// and operations complete in order, so "stage kt+1 landed" allows 2 stages + NST + 2 in flight at kt < 2 and 2 stages afterwards.
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm2d_kernel(GemmP2 p) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  constexpr int BM = 256, BN = 256, WN = 2, NT = 512, STAGES = 4;
-  constexpr int WTM = 64, WTN = 128, TMt = 4, TNt = 8;
-  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
-  constexpr int NDMA = 4;
-  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU);
-  constexpr int NST = TMt * 4 * (EPI == NBEST_EPI_BIAS_GELU ? 2 : 1);   // store wave-instructions per tile and wave (ragged tiles too: range-checked)
-  constexpr int NBIAS = kHasBias ? 2 : 0;
-  static_assert(EPI == NBEST_EPI_NONE || EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU, "no residual / GELU' input");
-  static_assert(2 * NDMA + NST + NBIAS <= 63, "vmcnt is a 6-bit counter");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
-  const int G = gridDim.x, tiles = p.tiles_m * p.tiles_n;
-  const int nk = (int)(p.K / BK);
-  const bool b_packed = p.Bp != nullptr;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(b_packed ? (void*)p.Bp : (void*)p.B, 0, b_packed ? p.bp_bytes : p.b_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, p.c_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc((void*)p.U, 0, p.u_bytes, 0x00020000);
-  auto tile_coords = [&](int t, int& tm, int& tn) {
-    const int id = xcd_remap2(t, tiles);
-    nb_tile_coords(id, p.tiles_m, p.gn, tm, tn);
-  };
-  auto issue = [&](int gstage, int tm, int tn, int s) {   // stage s of tile (tm, tn) -> ring buffer gstage & 3
-    char* dst = lds + (gstage & 3) * STAGE;
-    stage_tile2<false, BM, NT, NB_AUX_A>(rsA, dst, (int64_t)tm * BM, (int64_t)s * BK, p.lda, tid);
-    if (b_packed) stage_tile_packed<BN, NT, NB_AUX_B>(rsB, dst + A_BYTES, (uint32_t)((tn * nk + s) * B_BYTES), tid);
-    else stage_tile2<false, BN, NT, NB_AUX_B, WTN>(rsB, dst + A_BYTES, (int64_t)tn * BN, (int64_t)s * BK, p.ldb, tid);
-  };
-  const int dg = lane >> 4, dc = lane & 15;
-  int t_cur = blockIdx.x, tm, tn;
-  tile_coords(t_cur, tm, tn);
-  int gs = 0;   // ring position of stage 0 of the current tile
-#pragma unroll
-  for (int s = 0; s < 3; ++s) issue(gs + s, tm, tn, s);
-  bool first = true;
-  while (true) {
-    const int t_next = t_cur + G;
-    const bool has_next = t_next < tiles;
-    int tmn = 0, tnn = 0;
-    if (has_next) tile_coords(t_next, tmn, tnn);
-    const int64_t dcol = (int64_t)tn * BN + wn * WTN + TNt * dc;
-    const int64_t drow0 = (int64_t)tm * BM + wm * WTM + 4 * dg;
-    f32x4 b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0};
-    if (kHasBias) { b0 = global_load_f32x4_asm(p.bias + dcol); b1 = global_load_f32x4_asm(p.bias + dcol + 4); }
-    f32x4 acc[TMt][TNt];
-#pragma unroll
-    for (int i = 0; i < TMt; ++i)
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
-    if (first) wait_vm<2 * NDMA + NBIAS>();
-    else wait_vm<2 * NDMA + NST + NBIAS>();
-    __builtin_amdgcn_s_barrier();                 // stage 0 of this tile landed for everyone
-    asm volatile("" ::: "memory");
-    if (grp == 1) __builtin_amdgcn_s_barrier();   // offset group 1 by one slot
-    bf16x8 af[TMt], bfr[TNt];
-    for (int kt = 0; kt < nk; ++kt) {
-      // ---------------- LOAD slot ----------------
-      const int si = kt + 3;
-      if (si < nk) issue(gs + si, tm, tn, si);
-      else if (has_next) issue(gs + si, tmn, tnn, si - nk);
-      const char* cur = lds + ((gs + kt) & 3) * STAGE;
-#pragma unroll
-      for (int j = 0; j < TNt; ++j) bfr[j] = read_frag2<false, BN>(cur + A_BYTES, wn * WTN + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i) af[i] = read_frag2<false, BM>(cur, wm * WTM + i * 16, lane);
-      {
-        const int c = has_next ? 3 : ((nk - 1 - kt < 3) ? nk - 1 - kt : 3);   // stages kt+1 .. outstanding
-        if (c >= 3) {
-          if (kt >= 2) wait_vm<2 * NDMA>();
-          else if (first) wait_vm<2 * NDMA + NBIAS>();
-          else wait_vm<2 * NDMA + NST + NBIAS>();
-        } else if (c == 2) wait_vm<NDMA>();    // (tail of the last tile; over-waits at kt < 2 when nk < 5: safe)
-        else wait_vm<0>();
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---------------- MFMA slot ----------------
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < TMt; ++i)
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();   // balance the barrier count: both groups are in step again
-    // ---- register epilogue (gemm2_kernel's, reduced to these epilogues): bias loads are older than stage 3, which has landed ----
-    if (kHasBias) asm volatile("" : "+v"(b0), "+v"(b1));
-    const float db[TNt] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-    const uint32_t voC = (uint32_t)((drow0 * p.ldc + dcol) * 2), svC = (uint32_t)(2 * p.ldc);
-    const uint32_t voU = (uint32_t)(drow0 * p.ldu + dcol), svU = (uint32_t)p.ldu;
-#pragma unroll
-    for (int i = 0; i < TMt; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t rr = (uint32_t)(16 * i + e);
-        float v[TNt];
-#pragma unroll
-        for (int j = 0; j < TNt; ++j) v[j] = acc[i][j][e] + (kHasBias ? db[j] : 0.f);
-        if (EPI == NBEST_EPI_BIAS_GELU) {
-          float gp[TNt];
-#pragma unroll
-          for (int j = 0; j < TNt; j += 2) {
-            f32x2 h2, g2;
-            gelu_pair_fast(f32x2{v[j], v[j + 1]}, h2, g2);
-            gp[j] = g2[0]; gp[j + 1] = g2[1]; v[j] = h2[0]; v[j + 1] = h2[1];
-          }
-          nb_bstore8(rsU, voU + rr * svU, gd_pack4(gp), gd_pack4(gp + 4));
-        }
-        nb_bstore_bf16x8(rsC, voC + rr * svC, v);
-      }
-    }
-    if (!has_next) break;
-    t_cur = t_next; tm = tmn; tn = tnn; gs += nk; first = false;
-  }
-}
-
-#endif  // NBEST_EXPERIMENTS
 
 // rows >= m_split of the slabs' [M][N] image belong to the second output of a weight-gradient pair (C2, ldc2); m_split = M: none
 __global__ __launch_bounds__(256) void splitk_reduce2_kernel(const float* __restrict__ slab, float* __restrict__ C, int64_t MN,
@@ -1611,70 +982,21 @@ struct Plan {
   int64_t kps;
 };
 
-// The shipped library has ONE code path per shape and reads no environment.  `make diag` (-DNBEST_EXPERIMENTS) builds
-// csrc/diag/libnbest_diag.so, in which NBEST_PERSISTENT=1 selects the persistent kernel and NBEST_TILE=256x256 | 256x128 |
-// 128x256 | 128x128 forces a tile (tools/ load it through NBEST_LIB).
-#ifdef NBEST_EXPERIMENTS
-static bool persistent_enabled() {
-  static const bool v = [] { const char* e = getenv("NBEST_PERSISTENT"); return e && *e == '1'; }();
-  return v;
-}
-static bool persistent_direct_enabled() {
-  static const bool v = [] { const char* e = getenv("NBEST_PERSISTENT"); return e && *e == '2'; }();
-  return v;
-}
-static bool stages5_enabled() {
-  static const bool v = [] { const char* e = getenv("NBEST_STAGES"); return e && *e == '5'; }();
-  return v;
-}
-static bool sym_enabled() {
-  static const bool v = [] { const char* e = getenv("NBEST_SYM"); return e && *e == '1'; }();
-  return v;
-}
-static int forced_tile() {
-  static const int v = [] {
-    const char* e = getenv("NBEST_TILE");
-    if (!e) return 0;
-    if (!strcmp(e, "256x256")) return 3;
-    if (!strcmp(e, "256x192")) return 5;
-    if (!strcmp(e, "128x256")) return 4;
-    if (!strcmp(e, "256x128")) return 2;
-    if (!strcmp(e, "128x128")) return 1;
-    if (!strcmp(e, "128x384")) return 6;
-    if (!strcmp(e, "128x512")) return 7;
-    return 0;
-  }();
-  return v;
-}
-#else
-static constexpr bool persistent_enabled() { return false; }
-static constexpr bool sym_enabled() { return false; }
-static constexpr bool stages5_enabled() { return false; }
-static constexpr int forced_tile() { return 0; }
-#endif
-
 static Plan make_plan(const nbest_gemm_args* a) {
   Plan pl;
   pl.bn = 128;
   // 256x128 where it fills the chip (two workgroups per CU -> 512 slots) and is not a weight gradient
   const int64_t t256 = ((a->M + 255) / 256) * (a->N / 128);
   pl.bm = (!a->trans_a && t256 >= 1024) ? 256 : 128;
-  const int ft6 = forced_tile();
-  const int ft = (ft6 == 6 || ft6 == 7) ? 0 : ft6;      // 128x384 is an ADDITIONAL choice for the N = 768 shapes: every other shape plans as usual
   const bool ok256 = (a->N % 256 == 0) && (!a->trans_a || a->M % 256 == 0);
-  if (ft == 3 && ok256) { pl.bm = 256; pl.bn = 256; }
-  else if (ft == 4 && ok256) { pl.bm = 128; pl.bn = 256; }
-  else if (ft == 2 && !a->trans_a) { pl.bm = 256; pl.bn = 128; }
-  else if (ft == 1) { pl.bm = 128; pl.bn = 128; }
-  else if (ft == 0 && !a->trans_a && !a->trans_b && a->N % 256 == 0 &&
-           [&] {   // >= 4 rounds of tiles on the 256 CUs, or at least one round with the last one >= 85 % full
-             const int64_t t = ((a->M + 255) / 256) * (a->N / 256);
-             return t >= 1024 || (t >= 256 && (double)t / (double)(((t + 255) / 256) * 256) >= 0.85);
-           }()) {
+  if (!a->trans_a && !a->trans_b && a->N % 256 == 0 &&
+      [&] {   // >= 4 rounds of tiles on the 256 CUs, or at least one round with the last one >= 85 % full
+        const int64_t t = ((a->M + 255) / 256) * (a->N / 256);
+        return t >= 1024 || (t >= 256 && (double)t / (double)(((t + 255) / 256) * 256) >= 0.85);
+      }()) {
     pl.bm = 256; pl.bn = 256;   // ping-pong schedule: best for k-contiguous operands on the wide GEMMs (QKV, FFN-up forward); round 3: also
                                 // for 1 - 3 full rounds (xlm-roberta-large, M = 16 384: 1 478 -> 1 562 utt/s with every N % 256 == 0 GEMM on it)
-  } else if (ft == 0 && a->trans_a && a->trans_b && a->epilogue == NBEST_EPI_F32_SPLITK && ok256 &&
-             (a->M / 256) * (a->N / 256) >= 18) {
+  } else if (a->trans_a && a->trans_b && a->epilogue == NBEST_EPI_F32_SPLITK && ok256 && (a->M / 256) * (a->N / 256) >= 18) {
     pl.bm = 256; pl.bn = 256;   // weight gradients with >= 18 output tiles (QKV, FFN): 1.0-1.05 PFLOP/s vs 0.85-0.94 for v1;
                                 // the 768x768 attention-output gradient (9 tiles, 28 splits) stays on v1 (0.90 vs 0.79)
   }
@@ -1688,35 +1010,21 @@ static Plan make_plan(const nbest_gemm_args* a) {
   {
     const bool epi192 = a->epilogue == NBEST_EPI_NONE || a->epilogue == NBEST_EPI_BIAS || a->epilogue == NBEST_EPI_BIAS_DROP_RES ||
                         a->epilogue == NBEST_EPI_RES;
-    if (!a->trans_a && !a->trans_b && a->N % 192 == 0 && epi192 && (ft == 0 || ft == 5)) {
+    if (!a->trans_a && !a->trans_b && a->N % 192 == 0 && epi192) {
       const int64_t rows = (a->M + 255) / 256, t192 = rows * (a->N / 192);
       auto eff = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); };
       const double e256 = (a->N % 256 == 0) ? eff(rows * (a->N / 256)) : 0.0;
-      const double ecur = (pl.bm == 256 && pl.bn == 256) ? e256 : (a->N % 256 == 0 ? e256 : 0.0);
-      int64_t t192_min = 256;   // one full round of tiles is enough (was two): M = 16 384 rows - configs[3] +2.6 %, a 128-utterance batch +4.8 %
-#ifdef NBEST_EXPERIMENTS
-      if (const char* e = getenv("NBEST_T192MIN")) t192_min = atoll(e);
-#endif
-      double handicap = 0.85;
-#ifdef NBEST_EXPERIMENTS
-      if (const char* e = getenv("NBEST_T192H")) handicap = atof(e);
-#endif
-      if (ft == 5 || (t192 >= t192_min && handicap * eff(t192) > ecur)) { pl.bm = 256; pl.bn = 192; }
+      // one full round of tiles is enough (was two): M = 16 384 rows - configs[3] +2.6 %, a 128-utterance batch +4.8 %
+      if (t192 >= 256 && 0.85 * eff(t192) > e256) { pl.bm = 256; pl.bn = 192; }
     }
     // 128 x 384 tiles (2 x 4 waves of 64 x 96; round 4): the same MFMA work per stage as 256 x 192 with HALF the bytes of the A operand - the
     // activation panel, which in the training step comes cold from HBM - and twice those of the weight panel, which the L2
     // holds (and which arrives packed: two adjacent 192-column blocks).  Takes over wherever 256 x 192 was chosen and N is a multiple of
     // 384.  Same call, alternating: the five N = 768 GEMMs of a layer 620 -> 586 us cold / 541 -> 510 warm; the step 21.15 / 21.22 -> 20.85 / 20.88 ms.
-    if (pl.bm == 256 && pl.bn == 192 && a->N % 384 == 0 && a->K % BK == 0 && ft != 5) { pl.bm = 128; pl.bn = 384; }
+    if (pl.bm == 256 && pl.bn == 192 && a->N % 384 == 0 && a->K % BK == 0) { pl.bm = 128; pl.bn = 384; }
     // 128 x 512 (2 x 4 waves of 64 x 128, 40 KB stages: all 160 KB of LDS): the same turn for the N = 1024 shapes of xlm-roberta-large, which plan
-    // 256 x 256 (4 tile columns): xlm-roberta-large S = 256, 64 utterances 1 585 -> 1 622 utt/s (same call, twice).  NBEST_TILE=256x256 keeps the old plan.
-    if (ft6 != 3 && pl.bm == 256 && pl.bn == 256 && !a->trans_a && !a->trans_b && epi192 && a->N % 512 == 0 && a->N <= 2048 && a->K % BK == 0) { pl.bm = 128; pl.bn = 512; }
-#ifdef NBEST_EXPERIMENTS
-    {   // NBEST_T512ALL=1: every 256 x 256 plan with N % 512 == 0, GELU epilogues included
-      static const int all = [] { const char* e = getenv("NBEST_T512ALL"); return (e && e[0] == '1') ? 1 : 0; }();
-      if (all && pl.bm == 256 && pl.bn == 256 && !a->trans_a && !a->trans_b && a->epilogue != NBEST_EPI_F32_SPLITK && a->N % 512 == 0 && a->K % BK == 0) { pl.bm = 128; pl.bn = 512; }
-    }
-#endif
+    // 256 x 256 (4 tile columns): xlm-roberta-large S = 256, 64 utterances 1 585 -> 1 622 utt/s (same call, twice).
+    if (pl.bm == 256 && pl.bn == 256 && !a->trans_a && !a->trans_b && epi192 && a->N % 512 == 0 && a->N <= 2048 && a->K % BK == 0) { pl.bm = 128; pl.bn = 512; }
   }
   const int64_t tiles = ((a->M + pl.bm - 1) / pl.bm) * (a->N / pl.bn);
   const int64_t slots = (pl.bn >= 192) ? 256 : 512;   // workgroups resident at once
@@ -1738,16 +1046,14 @@ static Plan make_plan(const nbest_gemm_args* a) {
   return pl;
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, bool SYM = false>
+template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB>
 static int launch2(const GemmP2& p, int epi, int grid, hipStream_t st) {
   constexpr int NT = WM * WN * 64;
-  constexpr int lds_ring = STAGES * (BM + BN) * BK * 2;
-  constexpr int lds_pairs = (!TA && !TB && NT == 512 && BM == 256 && (DIAG & 2048)) ? (3 * 2 * BM + STAGES * BN) * BK * 2 : 0;   // A staged in pairs of stages (3 pair buffers)
-  constexpr int lds_bytes = (lds_pairs > lds_ring ? lds_pairs : lds_ring) + (((BN * 4) % NT) ? (NT / 64) * 1024 : 0);   // + the zero-fill dump slots
+  constexpr int lds_bytes = STAGES * (BM + BN) * BK * 2 + (((BN * 4) % NT) ? (NT / 64) * 1024 : 0);   // ring + the zero-fill dump slots
 #define L(E)                                                                                                        \
   case E:                                                                                                           \
-    (void)hipFuncSetAttribute((const void*)gemm2_kernel<BM, BN, WM, WN, STAGES, TA, TB, E, SYM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-    gemm2_kernel<BM, BN, WM, WN, STAGES, TA, TB, E, SYM><<<grid, NT, lds_bytes, st>>>(p);                            \
+    (void)hipFuncSetAttribute((const void*)gemm2_kernel<BM, BN, WM, WN, STAGES, TA, TB, E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
+    gemm2_kernel<BM, BN, WM, WN, STAGES, TA, TB, E><<<grid, NT, lds_bytes, st>>>(p);                                 \
     break;
   if constexpr (BN / WN == 64) {   // the fp32 split-K output goes through the LDS-restaged epilogue (64-column wave tiles)
     if (epi == NBEST_EPI_F32_SPLITK) {
@@ -1785,7 +1091,7 @@ bool nbest_gemm_bf16_v2_wins(const nbest_gemm_args* a) {
   // column sums fused into an epilogue other than x GELU': the generation-1 kernel carries them for every epilogue (no caller in the training step)
   if (a->colsum_out && a->epilogue != NBEST_EPI_DGELU && a->epilogue != NBEST_EPI_F32_SPLITK && !a->trans_a && !a->trans_b) return false;
   const Plan pl = make_plan(a);
-  return pl.bm == 256 || (pl.bm == 128 && pl.bn >= 384) || (forced_tile() != 0 && forced_tile() < 6);
+  return pl.bm == 256 || (pl.bm == 128 && pl.bn >= 384);
 }   // 256x128 ring or 256x256 ping-pong
 
 int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
@@ -1858,7 +1164,7 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
     p.u_bytes = a->U ? (uint32_t)(a->M * a->ldu) : 0;
   }
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
-  p.stream_out = nb_stream_output(a->M * a->N * 2) ? 1 : 0;
+  p.stream_out = 1;   // every output is streamed (common.h st_stream)
   // B is a weight matrix (k-contiguous [N][K]) in the forward / dgrad GEMMs; the weight gradients have no small operand
   // B is a weight matrix (k-contiguous [N][K]) in the forward / dgrad GEMMs; the weight gradients have no small operand.
   // (Column groups re-read the ACTIVATION panel once per group: 490 MB of HBM-side traffic per launch for 277 MB of operands on the
@@ -1871,9 +1177,6 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
   // in step and only a few stages of them are live at a time.  Same call: the five N = 768 GEMMs of a layer 587 / 600 -> 570 / 576 us cold,
   // the step 21.02 / 21.01 -> 20.86 / 20.85 ms.
   if (pl.bm == 128 && pl.bn >= 384 && (a->N / pl.bn) % 2 == 0) p.gn = 2;
-#ifdef NBEST_EXPERIMENTS
-  if (pl.bn == 384) { if (const char* e = getenv("NBEST_GN384")) { const int v = atoi(e); if (v > 0 && (a->N / pl.bn) % v == 0) p.gn = v; } }
-#endif
   NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm(bf16): dropout counter overflow");
   const int epi = a->epilogue;
   if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
@@ -1891,73 +1194,32 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
   if (pl.bm == 128 && pl.bn == 512) {
     rc = launch2<128, 512, 2, 4, 4, false, false>(p, epi, grid, st);
   } else if (pl.bm == 128 && pl.bn == 384) {
-    if (a->K >= 2048 || stages5_enabled()) rc = launch2<128, 384, 2, 4, 5, false, false>(p, epi, grid, st);
+    if (a->K >= 2048) rc = launch2<128, 384, 2, 4, 5, false, false>(p, epi, grid, st);
     else rc = launch2<128, 384, 2, 4, 4, false, false>(p, epi, grid, st);
   } else if (pl.bm == 256 && pl.bn == 192) {
     // ring depth: the operand delivery of these kernels is bound by bytes in flight against the LDS-DMA latency (3 stages of 28-32 KB
     // against ~2 us); a fifth stage (all 160 KB of LDS at 256 x 256) pays at long K - FFN-down forward 162 -> 155 us, FFN-up dgrad 157 ->
     // 154, QKV dgrad 122 -> 120 - and costs 1-2 % at K = 768, where the longer prologue of each tile weighs more (same-call A/B, twice)
-    if (a->K >= 2048 || stages5_enabled()) rc = launch2<256, 192, 4, 2, 5, false, false>(p, epi, grid, st);
+    if (a->K >= 2048) rc = launch2<256, 192, 4, 2, 5, false, false>(p, epi, grid, st);
     else rc = launch2<256, 192, 4, 2, 4, false, false>(p, epi, grid, st);
     wave_rows = 4;
-  } else if (pl.bm == 128 && pl.bn == 256) {
-    if (!a->trans_a && !a->trans_b) rc = launch2<128, 256, 2, 4, 4, false, false>(p, epi, grid, st);
-    else if (!a->trans_a && a->trans_b) rc = launch2<128, 256, 2, 4, 4, false, true>(p, epi, grid, st);
-    else rc = launch2<128, 256, 2, 4, 4, true, true>(p, epi, grid, st);
-#ifdef NBEST_EXPERIMENTS
-  } else if (pl.bm == 256 && pl.bn == 256 && !a->trans_a && !a->trans_b && pl.splits == 1 && !p.colpart && a->K % BK == 0 &&
-             a->K >= 3 * BK && grid > 256 && (epi == NBEST_EPI_NONE || epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU) &&
-             persistent_enabled()) {
-    constexpr int lds_bytes = 4 * 2 * 256 * BK * 2;
-    const int pgrid = 256;
-#define LP(E)                                                                                              \
-  case E:                                                                                                  \
-    (void)hipFuncSetAttribute((const void*)gemm2p_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-    gemm2p_kernel<E><<<pgrid, 512, lds_bytes, st>>>(p);                                                    \
-    break;
-    switch (epi) { LP(NBEST_EPI_NONE) LP(NBEST_EPI_BIAS) LP(NBEST_EPI_BIAS_GELU) default: break; }
-#undef LP
-    NB_LAUNCH_CHECK();
-    rc = NBEST_OK;
-#endif
-#ifdef NBEST_EXPERIMENTS
-  } else if (pl.bm == 256 && pl.bn == 256 && !a->trans_a && !a->trans_b && pl.splits == 1 && !p.colpart && a->K % BK == 0 &&
-             a->K >= 5 * BK && grid > 256 && (epi == NBEST_EPI_NONE || epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU) &&
-             persistent_direct_enabled()) {
-    constexpr int lds_bytes = 4 * 2 * 256 * BK * 2;
-#define LD(E)                                                                                              \
-  case E:                                                                                                  \
-    (void)hipFuncSetAttribute((const void*)gemm2d_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-    gemm2d_kernel<E><<<256, 512, lds_bytes, st>>>(p);                                                      \
-    break;
-    switch (epi) { LD(NBEST_EPI_NONE) LD(NBEST_EPI_BIAS) LD(NBEST_EPI_BIAS_GELU) default: break; }
-#undef LD
-    NB_LAUNCH_CHECK();
-    rc = NBEST_OK; wave_rows = 4;
-#endif
   } else if (pl.bm == 256 && pl.bn == 256) {
     // k-contiguous operands: 4 x 2 waves with 64 x 128 wave tiles (register epilogue: 16-byte stores, whole 128-byte lines)
     if (!a->trans_a && !a->trans_b && epi != NBEST_EPI_F32_SPLITK) {
-#ifdef NBEST_EXPERIMENTS
-      if (sym_enabled()) rc = launch2<256, 256, 4, 2, 4, false, false, true>(p, epi, grid, st);
-      else
-#endif
-      if (a->K >= 2048 || stages5_enabled()) rc = launch2<256, 256, 4, 2, 5, false, false>(p, epi, grid, st);
+      if (a->K >= 2048) rc = launch2<256, 256, 4, 2, 5, false, false>(p, epi, grid, st);
       else rc = launch2<256, 256, 4, 2, 4, false, false>(p, epi, grid, st);
       wave_rows = 4;
     }
     else if (!a->trans_a && !a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, false>(p, epi, grid, st);
     else if (!a->trans_a && a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, true>(p, epi, grid, st);
-    else if (stages5_enabled()) rc = launch2<256, 256, 2, 4, 5, true, true>(p, epi, grid, st);
     else rc = launch2<256, 256, 2, 4, 4, true, true>(p, epi, grid, st);
   } else if (pl.bm == 256) {
     if (!a->trans_b && epi != NBEST_EPI_F32_SPLITK) { rc = launch2<256, 128, 4, 1, 3, false, false>(p, epi, grid, st); wave_rows = 4; }
     else if (!a->trans_b) rc = launch2<256, 128, 2, 2, 3, false, false>(p, epi, grid, st);
     else rc = launch2<256, 128, 2, 2, 3, false, true>(p, epi, grid, st);
-  } else {
-    if (!a->trans_a && !a->trans_b) rc = launch2<128, 128, 2, 2, 4, false, false>(p, epi, grid, st);
-    else if (!a->trans_a && a->trans_b) rc = launch2<128, 128, 2, 2, 4, false, true>(p, epi, grid, st);
-    else rc = launch2<128, 128, 2, 2, 4, true, true>(p, epi, grid, st);
+  } else {   // 128-row tiles narrower than 384 columns run on generation 1 (nbest_gemm_bf16_v2_wins)
+    nbest_set_error("gemm(bf16, generation 2): no kernel for the %d x %d plan", pl.bm, pl.bn);
+    return NBEST_ERR_SHAPE;
   }
   if (rc) return rc;
   if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * wave_rows, (int)a->N, a->colsum_out, a->colsum_accumulate, st);

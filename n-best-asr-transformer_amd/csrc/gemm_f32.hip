@@ -3,7 +3,6 @@
 // bf16 MFMA kernel.  It exists so the hand-written backward formulas and the host orchestration can
 // be checked against the oracle at 1e-4 without bf16 rounding in the way; it is not a fast path.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -124,22 +123,7 @@ size_t nbest_gemm_bf16_ws_bytes(const nbest_gemm_args* a);
 int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st);
 size_t nbest_gemm_bf16_v2_ws_bytes(const nbest_gemm_args* a);
 int nbest_gemm_bf16_v2(const nbest_gemm_args* a, hipStream_t st);
-bool nbest_gemm_bf16_v2_wins(const nbest_gemm_args* a);
-
-// per-shape choice of the kernel generation; experiment builds (`make diag`, -DNBEST_EXPERIMENTS) can force one with
-// NBEST_GEMM=v1 / v2 for A/B measurements - the shipped library reads no environment
-#ifdef NBEST_EXPERIMENTS
-static int forced_gen() {
-  static const int v = [] { const char* e = getenv("NBEST_GEMM"); return (e && e[0] == 'v' && (e[1] == '1' || e[1] == '2')) ? e[1] - '0' : 0; }();
-  return v;
-}
-#else
-static constexpr int forced_gen() { return 0; }
-#endif
-static bool use_v2(const nbest_gemm_args* a) {
-  const int f = forced_gen();
-  return f == 2 || (f == 0 && nbest_gemm_bf16_v2_wins(a));
-}
+bool nbest_gemm_bf16_v2_wins(const nbest_gemm_args* a);   // per-shape choice of the kernel generation
 
 extern "C" size_t nbest_gemm_ws_bytes(const nbest_gemm_args* a) {
   if (!a) return 0;
@@ -162,7 +146,7 @@ extern "C" int nbest_gemm(const nbest_gemm_args* a, nbest_stream_t stream) {
     }
     return NBEST_OK;
   }
-  if (a->dtype == NBEST_BF16) return use_v2(a) ? nbest_gemm_bf16_v2(a, (hipStream_t)stream) : nbest_gemm_bf16(a, (hipStream_t)stream);
+  if (a->dtype == NBEST_BF16) return nbest_gemm_bf16_v2_wins(a) ? nbest_gemm_bf16_v2(a, (hipStream_t)stream) : nbest_gemm_bf16(a, (hipStream_t)stream);
   nbest_set_error("gemm: bad dtype %d", a->dtype);
   return NBEST_ERR_DTYPE;
 }

@@ -24,13 +24,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 constexpr int BK8 = 64;
-#ifndef NBEST_DIAG
-#define NBEST_DIAG 0
-#endif
-// timing-only ablations of the epilogue (`make diag DIAG=<mask>`, results are wrong): 256 no GELU math, 512 no 8-bit stores,
-// 1024 no bf16 store, 2048 no main loop; of the ping-pong main loop: 1 no in-loop DMA, 2 no fragment
-// reads, 4 no MFMA
-constexpr int DIAG8 = NBEST_DIAG;
 // Epilogue stores are streaming (nontemporal, common.h st_stream): the outputs (50 - 400 MB per GEMM) otherwise wash the
 // weights and the activation panel out of the 4 MiB L2 of every XCD while other tiles still read them (FFN-up 175 -> 163 us).
 
@@ -51,17 +44,13 @@ struct GemmP8 {
   uint32_t bp_bytes;
 };
 
-#ifdef NBEST_EXPERIMENTS
-__device__ unsigned long long* g_trace8;   // per workgroup: key | late << 16, t_start, t_main_end, t_end (100 MHz clock)
-#endif
-
 __device__ __forceinline__ int xcd_remap8(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
 // one operand tile: ROWS rows x 64 bytes = 4 ROWS 16-byte chunks, NT threads -> 4 ROWS / NT LDS-DMA instructions per thread
-template <int ROWS = 256, int NT = 512, int AUX = 0>
+template <int ROWS = 256, int NT = 512>
 __device__ __forceinline__ void stage_tile8(__amdgpu_buffer_rsrc_t rs, char* tile, int64_t row0, int64_t k0, int64_t ld, int tid) {
   const int wave = tid >> 6;
 #pragma unroll
@@ -70,17 +59,17 @@ __device__ __forceinline__ void stage_tile8(__amdgpu_buffer_rsrc_t rs, char* til
     const int row = p >> 2, slot = p & 3;
     const int kc = slot ^ ((row >> 2) & 3);
     const uint32_t voff = (uint32_t)((row0 + row) * ld + k0 + kc * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(tile + (i * NT + wave * 64) * 16), 16, voff, 0, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(tile + (i * NT + wave * 64) * 16), 16, voff, 0, 0, 0);
   }
 }
 
 // the same B tile from a PRE-PACKED operand (pack_b8_kernel): a linear copy, 1 KiB contiguous per wave-instruction
-template <int ROWS, int NT, int AUX = 0>
+template <int ROWS, int NT>
 __device__ __forceinline__ void stage_tile8_packed(__amdgpu_buffer_rsrc_t rs, char* tile, uint32_t stage_byte0, int tid) {
   const int wave = tid >> 6;
 #pragma unroll
   for (int i = 0; i < ROWS * 4 / NT; ++i)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(tile + (i * NT + wave * 64) * 16), 16, stage_byte0 + (uint32_t)(i * NT + tid) * 16u, 0, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(tile + (i * NT + wave * 64) * 16), 16, stage_byte0 + (uint32_t)(i * NT + tid) * 16u, 0, 0, 0);
 }
 
 __device__ __forceinline__ i32x8 read_frag8(const char* tile, int row_base, int lane) {
@@ -109,7 +98,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
   int tile_m, tile_n;
   nb_tile_coords(id, p.tiles_m, p.gn, tile_m, tile_n);
   const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-  const int nk = (DIAG8 & 2048) ? 1 : (int)(p.K / BK8);
+  const int nk = (int)(p.K / BK8);
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.a_bytes, 0x00020000);
   const bool b_packed = p.Bp != nullptr;                        // workgroup-uniform
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(b_packed ? (void*)p.Bp : (void*)p.B, 0, b_packed ? p.bp_bytes : p.b_bytes, 0x00020000);
@@ -158,9 +147,9 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
   #pragma unroll
     for (int s0 = 0; s0 < STAGES - 1; ++s0) {
       if (s0 < nk) {
-        stage_tile8<BM, NT, NB_AUX_A>(rsA, lds + s0 * STAGE, m0, (int64_t)s0 * BK8, p.lda, tid);
-        if (b_packed) stage_tile8_packed<BN, NT, NB_AUX_B>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTESc), tid);
-        else stage_tile8<BN, NT, NB_AUX_B>(rsB, lds + s0 * STAGE + A_BYTES, n0, (int64_t)s0 * BK8, p.ldb, tid);
+        stage_tile8<BM, NT>(rsA, lds + s0 * STAGE, m0, (int64_t)s0 * BK8, p.lda, tid);
+        if (b_packed) stage_tile8_packed<BN, NT>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTESc), tid);
+        else stage_tile8<BN, NT>(rsB, lds + s0 * STAGE + A_BYTES, n0, (int64_t)s0 * BK8, p.ldb, tid);
       }
     }
     {
@@ -175,19 +164,19 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
     int buf = 0;
     for (int kt = 0; kt < nk; ++kt) {
       // ---------------- LOAD slot ----------------
-      if (!(DIAG8 & 1) && kt + STAGES - 1 < nk) {
+      if (kt + STAGES - 1 < nk) {
         int nb = buf + STAGES - 1;
         if (nb >= STAGES) nb -= STAGES;
         const int64_t k0 = (int64_t)(kt + STAGES - 1) * BK8;
-        stage_tile8<BM, NT, NB_AUX_A>(rsA, lds + nb * STAGE, m0, k0, p.lda, tid);
-        if (b_packed) stage_tile8_packed<BN, NT, NB_AUX_B>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTESc), tid);
-        else stage_tile8<BN, NT, NB_AUX_B>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, p.ldb, tid);
+        stage_tile8<BM, NT>(rsA, lds + nb * STAGE, m0, k0, p.lda, tid);
+        if (b_packed) stage_tile8_packed<BN, NT>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTESc), tid);
+        else stage_tile8<BN, NT>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, p.ldb, tid);
       }
       const char* cur = lds + buf * STAGE;
   #pragma unroll
-      for (int j = 0; j < TNb; ++j) if (!(DIAG8 & 2) || kt == 0) bfr[j] = read_frag8(cur + A_BYTES, wn * WTN + j * 32, lane);
+      for (int j = 0; j < TNb; ++j) bfr[j] = read_frag8(cur + A_BYTES, wn * WTN + j * 32, lane);
   #pragma unroll
-      for (int i = 0; i < TMb; ++i) if (!(DIAG8 & 2) || kt == 0) af[i] = read_frag8(cur, wm * WTM + i * 32, lane);
+      for (int i = 0; i < TMb; ++i) af[i] = read_frag8(cur, wm * WTM + i * 32, lane);
       {
         const int c = (nk - 1 - kt < STAGES - 1) ? nk - 1 - kt : STAGES - 1;   // stages kt+1.. outstanding
         if (c >= 3) wait_vm8<2 * NDMA>();
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
       for (int i = 0; i < TMb; ++i)
   #pragma unroll
         for (int j = 0; j < TNb; ++j)
-          if (!(DIAG8 & 4) || kt == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[j], af[i], acc[i][j], 0, 0, 0, 127, 0, 127);
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[j], af[i], acc[i][j], 0, 0, 0, 127, 0, 127);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
@@ -213,24 +202,15 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
     if (grp == 0) __builtin_amdgcn_s_barrier();
   } else {
     // ---- two independent workgroups per CU: plain 3-stage ring, one barrier per k-step ----
-    // (The two workgroups of a CU drift out of phase by themselves - tools/gemm8_trace.py - so the epilogue of one does
-    // overlap the main loop of the other; what it cannot buy back is that a main loop running alone has only its own two
+    // (The two workgroups of a CU drift out of phase by themselves - per-workgroup timestamps showed it - so the epilogue of one
+    // does overlap the main loop of the other; what it cannot buy back is that a main loop running alone has only its own two
     // stages in flight.)
-#ifdef NBEST_EXPERIMENTS
-    if (g_trace8 && tid == 0) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_trace8[blockIdx.x * 4 + 0] = ((unsigned long long)xcc << 32) | hw;
-      g_trace8[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 #pragma unroll
     for (int s0 = 0; s0 < STAGES - 1; ++s0) {
       if (s0 < nk) {
-        stage_tile8<BM, NT, NB_AUX_A>(rsA, lds + s0 * STAGE, m0, (int64_t)s0 * BK8, p.lda, tid);
-        if (b_packed) stage_tile8_packed<BN, NT, NB_AUX_B>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTESc), tid);
-        else stage_tile8<BN, NT, NB_AUX_B>(rsB, lds + s0 * STAGE + A_BYTES, n0, (int64_t)s0 * BK8, p.ldb, tid);
+        stage_tile8<BM, NT>(rsA, lds + s0 * STAGE, m0, (int64_t)s0 * BK8, p.lda, tid);
+        if (b_packed) stage_tile8_packed<BN, NT>(rsB, lds + s0 * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + s0) * B_BYTESc), tid);
+        else stage_tile8<BN, NT>(rsB, lds + s0 * STAGE + A_BYTES, n0, (int64_t)s0 * BK8, p.ldb, tid);
       }
     }
     int buf = 0;
@@ -243,9 +223,9 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
         int nb = buf + STAGES - 1;
         if (nb >= STAGES) nb -= STAGES;
         const int64_t k0 = (int64_t)(kt + STAGES - 1) * BK8;
-        stage_tile8<BM, NT, NB_AUX_A>(rsA, lds + nb * STAGE, m0, k0, p.lda, tid);
-        if (b_packed) stage_tile8_packed<BN, NT, NB_AUX_B>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTESc), tid);
-        else stage_tile8<BN, NT, NB_AUX_B>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, p.ldb, tid);
+        stage_tile8<BM, NT>(rsA, lds + nb * STAGE, m0, k0, p.lda, tid);
+        if (b_packed) stage_tile8_packed<BN, NT>(rsB, lds + nb * STAGE + A_BYTES, (uint32_t)((tile_n * nkt + kt + STAGES - 1) * B_BYTESc), tid);
+        else stage_tile8<BN, NT>(rsB, lds + nb * STAGE + A_BYTES, n0, k0, p.ldb, tid);
       }
       const char* cur = lds + buf * STAGE;
 #pragma unroll
@@ -261,9 +241,6 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
       __builtin_amdgcn_s_setprio(0);
       buf = (buf + 1 == STAGES) ? 0 : buf + 1;
     }
-#ifdef NBEST_EXPERIMENTS
-    if (g_trace8 && tid == 0) g_trace8[blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
   }
 
   // ---- epilogue: 32-row blocks restaged through wave-private LDS ([32][64] fp32, chunk16 ^= row & 15) ----
@@ -309,19 +286,16 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
         float gp[8];
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
-          if (DIAG8 & 256) { gp[e] = v[e]; gp[e + 1] = v[e + 1]; continue; }
           f32x2 h2, g2;
           gelu_pair_fast(f32x2{v[e], v[e + 1]}, h2, g2);
           gp[e] = g2[0]; gp[e + 1] = g2[1]; v[e] = h2[0]; v[e + 1] = h2[1];
         }
-        if (!(DIAG8 & 512)) {
-          st_stream((i32x2*)(p.U + oU), i32x2{(int)gd_pack4(gp), (int)gd_pack4(gp + 4)}, p.stream_out);
-          // e4m3 copy of gelu(u) for the FFN-down GEMM, times the tensor's delayed scale (c8s = 1 without a history); this pass's amax
-          float q[8];
+        st_stream((i32x2*)(p.U + oU), i32x2{(int)gd_pack4(gp), (int)gd_pack4(gp + 4)}, p.stream_out);
+        // e4m3 copy of gelu(u) for the FFN-down GEMM, times the tensor's delayed scale (c8s = 1 without a history); this pass's amax
+        float q[8];
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { q[e] = v[e] * c8s; amax8 = fmaxf(amax8, fabsf(v[e])); }
-          st_stream((i32x2*)(p.C8 + oC8), i32x2{(int)fp8_pack4(q), (int)fp8_pack4(q + 4)}, p.stream_out);
-        } else if (gp[0] + gp[3] + gp[5] == 123.f) p.U[0] = 1;
+        for (int e = 0; e < 8; ++e) { q[e] = v[e] * c8s; amax8 = fmaxf(amax8, fabsf(v[e])); }
+        st_stream((i32x2*)(p.C8 + oC8), i32x2{(int)fp8_pack4(q), (int)fp8_pack4(q + 4)}, p.stream_out);
       }
       if (EPI == NBEST_EPI_BIAS_DROP_RES && p.drop.thr16) {
         const uint32_t k = nb_keep4(p.drop, dbase) | (nb_keep4(p.drop, dbase + 4) << 4);
@@ -351,12 +325,12 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
         }
       }
       if ((EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_DGELU) && !p.C) {   // only the e4m3 copy is wanted
-      } else if (!(DIAG8 & 1024)) {
+      } else {
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
         st_stream((bf16x8*)(p.C + oC), o, p.stream_out);
-      } else if (v[0] + v[1] + v[2] + v[3] + v[4] + v[5] + v[6] + v[7] == 123.f) p.C[0] = (bf16)1.f;
+      }
       }
       oC += sC; oU += sU; oC8 += sC8; dbase += sD;
     }
@@ -379,9 +353,6 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
     amax8 = wave_max(amax8);
     if (lane == 0) amax_update(p.c8g.amax_new, amax8);
   }
-#ifdef NBEST_EXPERIMENTS
-  if (WN == 2 && g_trace8 && tid == 0) g_trace8[blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // bf16 [n] -> e4m3 (unit scale): the A operands of the fp8 forward GEMMs that no producer kernel writes directly
@@ -976,12 +947,6 @@ extern "C" int nbest_quantize_weights_fp8(const float* master, void* w8, void* w
 
 int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
 
-#ifdef NBEST_EXPERIMENTS
-extern "C" int nbest_experiment_trace8(void* buf) {   // nullptr: off
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_trace8), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" size_t nbest_gemm_fp8_ws_bytes(const nbest_gemm_fp8_args* a) {
   return (a && a->colsum_out) ? (size_t)((a->M + 255) / 256) * 2 * a->N * sizeof(float) : 0;
 }
@@ -1016,10 +981,7 @@ extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t strea
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldu = a->ldu; p.ldc8 = a->ldc8;
   // 256x128 tiles, two workgroups per CU, where 256x256 tiles leave the last round half empty and the main loop is short
   // (N = K = 768: 384 big tiles on 256 CUs; 47 -> 41 us); the big ping-pong tile elsewhere (the two tie on the other shapes)
-  int wn = (a->N * (int64_t)((a->M + 255) / 256) <= 3 * 128 * 256 && a->K <= 1024) ? 2 : 4;
-#ifdef NBEST_EXPERIMENTS
-  if (const char* e = getenv("NBEST_GEMM8_WN")) if (e[0] == '2' || e[0] == '4') wn = e[0] - '0';
-#endif
+  const int wn = (a->N * (int64_t)((a->M + 255) / 256) <= 3 * 128 * 256 && a->K <= 1024) ? 2 : 4;
   p.tiles_m = (int)((a->M + 255) / 256);
   p.tiles_n = (int)(a->N / (64 * wn));
   p.Bp = nullptr; p.bp_bytes = 0;
@@ -1037,7 +999,7 @@ extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t strea
   p.c8g = Fp8Grad{epi == NBEST_EPI_DGELU ? (uint8_t*)a->C8 : nullptr, a->c8_amax_prev, a->c8_amax_new};
   p.colpart = (epi == NBEST_EPI_DGELU && a->colsum_out) ? (float*)a->ws : nullptr;
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
-  p.stream_out = nb_stream_output(a->M * a->N * 2) ? 1 : 0;
+  p.stream_out = 1;   // every output is streamed (common.h st_stream)
   p.gn = nb_group_cols(p.tiles_n, (int64_t)64 * wn * a->K, 1600);
   NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm_fp8: dropout counter overflow");
 

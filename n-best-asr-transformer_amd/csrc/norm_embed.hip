@@ -7,11 +7,6 @@
 // Column reductions (dgamma, dbeta, bias gradients) are deterministic: per-block partial rows in a
 // workspace + a finalize kernel (no float atomics on the gradient of a parameter).
 #include "common.h"
-#include <stdlib.h>
-
-#ifndef NBEST_EMB_TPC
-#define NBEST_EMB_TPC 16
-#endif
 
 namespace {
 
@@ -997,7 +992,7 @@ extern "C" size_t nbest_rowred_ws_bytes(int64_t M, int64_t N) {
   if (b > kMaxLnBwdBlocks) b = kMaxLnBwdBlocks;
   return (size_t)3 * b * N * sizeof(float);
 }
-constexpr int kEmbTpc = NBEST_EMB_TPC;   // sorted tokens per wave of embed_bwd_word_kernel
+constexpr int kEmbTpc = 16;   // sorted tokens per wave of embed_bwd_word_kernel
 extern "C" size_t nbest_embed_bwd_ws_bytes(int64_t M, int64_t H) {
   // partial rows of embed_bwd_pos_kernel (<= kMaxLnBwdBlocks blocks x 5 quantities) | two partial rows per chunk of embed_bwd_word_kernel
   // | the fix-up work list (a counter + one chunk id per entry)
@@ -1052,10 +1047,7 @@ int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* st
   if (nblk > 512) nblk = 512;   // isolated, 256 and 512 blocks tie (32 us for 200 MB); inside the step 512 is faster (35 vs 44 us)
   int rpb = (int)((M + nblk - 1) / nblk);
   nblk = (int)((M + rpb - 1) / rpb);
-#ifndef NBEST_LN_WAVES
-#define NBEST_LN_WAVES 4
-#endif
-  constexpr int waves = NBEST_LN_WAVES;   // 8: measured in the step, see profiles/README.md
+  constexpr int waves = 4;   // 8: measured in the step, see profiles/README.md
   float* part = (float*)ws;
   const size_t smem = (size_t)3 * H * sizeof(float);
   const int wb = dbias ? 1 : 0;

@@ -10,7 +10,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("NBEST_LIB") or os.path.join(_HERE, "csrc", "libnbest_hip.so")   # NBEST_LIB: diagnostic builds only
+LIB_PATH = os.environ.get("NBEST_LIB") or os.path.join(_HERE, "csrc", "libnbest_hip.so")   # NBEST_LIB: another build of the library - how one GPU run times the parent commit's library against this one, alternating
 
 F32, BF16 = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F32_SPLITK = range(7)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The deterministic embedding backward at the bench shape (bert-base, B=256, S=128, synthetic n-best ids): all four kernels
 back to back, as the step issues them (tables zeroed by a memset, touched rows overwritten).  Run under
-`rocprofv3 --kernel-trace --stats` for per-kernel times; NBEST_LIB=<variant .so> for -DNBEST_EMB_TPC builds.
+`rocprofv3 --kernel-trace --stats` for per-kernel times.
     python tools/embed_bench.py [B] [S]"""
 import ctypes as C
 import os

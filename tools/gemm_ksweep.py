@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """K sweep of one k-contiguous GEMM shape (M x N fixed): separates the per-tile fixed cost from the per-stage cost.
-    NBEST_LIB=... [NBEST_SYM=1] python tools/gemm_ksweep.py [N]"""
+    python tools/gemm_ksweep.py [N]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

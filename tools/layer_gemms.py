@@ -2,8 +2,7 @@
 """The sixteen GEMM launches of one encoder layer (forward, dgrad, weight gradient) exactly as the training step issues them
 (operand layouts, epilogues, fused column sums), timed with HIP events through the C-ABI: per launch µs / TFLOP/s, rounds
 interleaved over the whole list so that every shape sees the same clock state.  BASELINE configs[1] shapes by default.
-    python tools/layer_gemms.py [--M 32768] [--rounds 12] [--tag name]
-With a `make diag` build (NBEST_LIB=.../libnbest_diag.so) NBEST_TILE / NBEST_GEMM force a tile / kernel generation."""
+    python tools/layer_gemms.py [--M 32768] [--rounds 12] [--tag name]"""
 import argparse
 import os
 import sys
@@ -95,8 +94,7 @@ def main():
             times[k].append((e0, e1))
     torch.cuda.synchronize()
     tot = 0.0
-    print("# %s  prep=%s inner=%d  M=%d  lib=%s  NBEST_TILE=%s NBEST_GEMM=%s" % (a.tag, a.prep, a.inner, M, os.path.basename(hb.LIB_PATH), os.environ.get("NBEST_TILE", "-"),
-                                                             os.environ.get("NBEST_GEMM", "-")))
+    print("# %s  prep=%s inner=%d  M=%d  lib=%s" % (a.tag, a.prep, a.inner, M, os.path.basename(hb.LIB_PATH)))
     for (name, fl, _), ts in zip(jobs, times):
         v = sorted(e0.elapsed_time(e1) / a.inner * 1e3 for e0, e1 in ts)
         med, mn = v[len(v) // 2], v[0]
