@@ -58,10 +58,14 @@ int nbest_embed_ln_fwd(const int64_t* ids, const int64_t* seg, const int64_t* po
  *   perm [B*S] int32 (REQUIRED): token indices sorted by ids, ties in ascending token index (any STABLE argsort of ids; the
  *        data loader builds it next to ids - nbest_amd/trainer.py EncodedSplit.host_batch, bench.py).
  * Rows word_pad_id of dword and pos_pad_id of dptab receive nothing (nn.Embedding padding_idx; pass -1 for "no padding row").
- * tables_accumulate == 0: the table rows the batch touches are OVERWRITTEN (the caller has zeroed the rest of dword / dptab /
- * dtype_tab); != 0: they are added to.  dgamma / dbeta are overwritten unless accumulate.  Deterministic for inputs whose
- * position ids are the same in every sequence up to padding rows and whose token types are 0 / 1 (BERT, the RoBERTa family);
- * other rows fall back to float atomics on dptab / dtype_tab.  M = B*S < 2^31.  ws: >= nbest_embed_bwd_ws_bytes(M, H) bytes. */
+ * tables_accumulate == 0: every row of dword / dptab / dtype_tab that a token of the batch reaches (word_pad_id / pos_pad_id
+ * rows excepted), and dtype_tab rows 0 and 1 (row 1 when n_types > 1), is OVERWRITTEN with the gradient; every other row is left as
+ * it is.  != 0: the gradient is added to those rows.  dgamma / dbeta are overwritten unless accumulate.
+ * Bit-reproducible when, in every sequence position j, all non-padding rows carry the same position key, no two positions share
+ * a key, and token types are 0 / 1: BERT's arange positions and right-padded RoBERTa-family positions (cumsum of non-padding
+ * tokens), in ANY row order.  Any other in-range layout (left padding, a padding id inside a row, arbitrary or repeated keys,
+ * token types >= 2) is summed correctly, partly with float atomics on dptab / dtype_tab (not reproducible in the last bit).
+ * Tables are fp32, 16-byte aligned.  M = B*S < 2^31.  ws: >= nbest_embed_bwd_ws_bytes(M, H) bytes. */
 int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
                        const void* type, const void* ptab, const float* gamma, const float* stats,
                        const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,

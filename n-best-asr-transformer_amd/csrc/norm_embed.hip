@@ -473,13 +473,16 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 }
 
 // Embedding backward, deterministic (round 4; rounds 1-3 summed the word table with fp32 atomics: 150 us at the atomic rate and
-// a step that was not bit-reproducible).  LayerNorm backward per token gives de = o (fp32, registers only); three kernels:
-//   embed_bwd_pos_kernel   block (j, y) owns sequence position j for the samples b = y, y + Y, ...: every row it sees has the same
-//                          position key (pos[b * S + j] == pos[j]: BERT's arange; for the RoBERTa family the same except padding rows,
-//                          whose key is the padding row and carries no gradient), so the position / token-type 0, 1 / LayerNorm-parameter
-//                          sums stay in registers and leave as ONE partial row per block and quantity (summed by embed_bwd_finalize_kernel
-//                          in a fixed order).  Rows with another position key / token type >= 2 fall back to row atomics (no family of
-//                          the path produces them).
+// a step that was not bit-reproducible).  LayerNorm backward per token gives de = o (fp32, registers only); five kernels:
+//   embed_bwd_colkey_kernel  one block per sequence position j: the column's key colkey[j] = the position key of its first
+//                          non-padding row, and whether another non-padding row of the column has a different key (`mixed`).
+//   embed_bwd_pos_kernel   block (j, y) owns sequence position j for the samples b = y, y + Y, ...: the rows whose key is colkey[j]
+//                          (every non-padding row of the column for BERT's arange and for right-padded RoBERTa-family positions, in any
+//                          row order) keep the position / token-type 0, 1 / LayerNorm-parameter sums in registers and leave them as ONE
+//                          partial row per block and quantity (summed by embed_bwd_finalize_kernel in a fixed order).  Rows with another
+//                          non-padding key (left padding, a padding id inside a row, arbitrary positions) and token types >= 2 fall back
+//                          to float row atomics - correct, not reproducible.  Block (j, 0) also records whether position row colkey[j]
+//                          can receive anything besides column j's sum (`shared`: a fallback anywhere, or another column with that key).
 //   embed_bwd_word_kernel  the word table as a SEGMENTED REDUCE over the tokens sorted by word id (`perm`: a stable argsort of ids,
 //                          built by the data loader next to ids): wave c owns `tpc` consecutive sorted tokens, recomputes o for each
 //                          and adds runs of equal id in registers, in sorted order.  A run that begins and ends inside the chunk is
@@ -489,7 +492,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 //   embed_bwd_wordfix_kernel  one block per chunk; the chunk in which a boundary-crossing run BEGINS sums that run's partial rows in
 //                          chunk order (fixed tree: wave w takes every 4th row, the four wave sums are added in wave order) and stores
 //                          the table row.  Frequent ids ([SEP]: (n_best + 1) x B tokens) span up to M / tpc chunks.
-// Same additions in the same order on every run: the gradient is bit-reproducible.  Both token kernels recompute o (two reads of
+// Same additions in the same order on every run: for the layouts without fallback rows (every column's non-padding keys equal,
+// column keys distinct, token types 0 / 1) the gradient is bit-reproducible.  Both token kernels recompute o (two reads of
 // dout and of the gathered table rows, 2 x 100 MB at B = 256, S = 128 - mostly out of the Infinity Cache the second time) instead of
 // writing it (100 MB fp32 out, 100 MB back in).
 template <typename T, int VPL>
@@ -549,6 +553,41 @@ __device__ __forceinline__ void emb_tok_grad(const EmbTok<T, VPL>& r, int64_t ro
 }
 constexpr int kEmbGroupWord = 4, kEmbGroupPos = 2;   // tokens whose rows a wave has in flight at once (the position kernel carries five accumulator rows)
 
+// grid S, block 256: colkey[j] = key of the first non-padding row of column j (pos_pad_id if there is none), mixed[j] = some
+// non-padding row of the column has another key.  tables_accumulate == 0: zero every row something will be ADDED to - row colkey[j]
+// (finalize adds into it when the row is shared), the rows of the column's fallback tokens and dtype_tab rows >= 2 - so that a touched
+// row is overwritten whichever path reaches it (zeros only: blocks that zero the same row do not conflict).
+__global__ __launch_bounds__(256) void embed_bwd_colkey_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ pos, int B, int S,
+                                                               int H, int64_t pos_pad_id, int tables_accumulate, int64_t* __restrict__ colkey,
+                                                               int* __restrict__ mixed, float* __restrict__ dptab, float* __restrict__ dtype_tab) {
+  __shared__ int first[4];
+  const int j = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bmin = B;
+  for (int b = threadIdx.x; b < B; b += blockDim.x)
+    if (pos[(int64_t)b * S + j] != pos_pad_id) { bmin = b; break; }
+  for (int o = 32; o > 0; o >>= 1) bmin = min(bmin, __shfl_xor(bmin, o, 64));
+  if (lane == 0) first[wave] = bmin;
+  __syncthreads();
+  bmin = min(min(first[0], first[1]), min(first[2], first[3]));
+  const int64_t key = bmin < B ? pos[(int64_t)bmin * S + j] : pos_pad_id;
+  const f32x4 zero = {0, 0, 0, 0};
+  bool mix = false;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const int64_t m = (int64_t)b * S + j, k = pos[m], sv = seg ? seg[m] : 0;
+    const bool off = k != key && k != pos_pad_id, tx = sv != 0 && sv != 1;
+    mix |= off;
+    if (!tables_accumulate && (off || tx))
+      for (int c = 0; c < H; c += 4) {
+        if (off) *(f32x4*)(dptab + k * H + c) = zero;
+        if (tx) *(f32x4*)(dtype_tab + sv * H + c) = zero;
+      }
+  }
+  mix = __syncthreads_or(mix);
+  if (!tables_accumulate && key != pos_pad_id)
+    for (int c = 4 * threadIdx.x; c < H; c += 4 * blockDim.x) *(f32x4*)(dptab + key * H + c) = zero;
+  if (threadIdx.x == 0) { colkey[j] = key; mixed[j] = mix; }
+}
+
 template <typename T, int VPL, bool FULL>
 __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seg,
                                                             const int64_t* __restrict__ pos, const T* __restrict__ word,
@@ -556,7 +595,8 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
                                                             const float* __restrict__ gamma, const float* __restrict__ stats,
                                                             const T* __restrict__ dout, float* __restrict__ dtype_tab,
                                                             float* __restrict__ dptab, float* __restrict__ part, int* __restrict__ fixlist,
-                                                            int B, int S, int H, int64_t pos_pad_id, DropCfg drop) {
+                                                            const int64_t* __restrict__ colkey, const int* __restrict__ mixed,
+                                                            int* __restrict__ shared, int B, int S, int H, int64_t pos_pad_id, DropCfg drop) {
   extern __shared__ __attribute__((aligned(16))) float acc[];  // [5][H] column sums (dgamma, dbeta, position, type 0, type 1)
   // (readfirstlane: the wave index is uniform, but only this tells the compiler - otherwise every token index below is a
   // "divergent" value and each readlane becomes a waterfall loop)
@@ -573,7 +613,13 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
     gm[i] = (c < nvec) ? *(const f32x4*)(gamma + 4 * c) : f32x4{0, 0, 0, 0};
   }
   const int j = blockIdx.x;
-  const int64_t key0 = pos[j];
+  const int64_t key0 = colkey[j];
+  if (blockIdx.y == 0) {   // can row key0 receive anything besides this column's sum? (block-uniform branch)
+    bool hit = false;
+    for (int jj = threadIdx.x; jj < S; jj += blockDim.x) hit |= mixed[jj] || (jj != j && colkey[jj] == key0);
+    hit = __syncthreads_or(hit);
+    if (threadIdx.x == 0) shared[j] = hit;
+  }
   const int bstep = gridDim.y * wpb, b0 = blockIdx.y + gridDim.y * wave;
   // this wave's tokens b0, b0 + bstep, ...: indices of up to 64 of them at a time, one per lane (no dependent scalar load per token)
   for (int base = b0; base < B; base += 64 * bstep) {
@@ -610,7 +656,7 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
           if (t_is0) t0[i] += o[i];
           if (t_is1) t1[i] += o[i];
         }
-        if ((!own_key && key != pos_pad_id) || (!t_is0 && !t_is1)) {   // not reached by BERT / RoBERTa-family inputs (see above)
+        if ((!own_key && key != pos_pad_id) || (!t_is0 && !t_is1)) {   // the fallback: not reached by BERT / right-padded RoBERTa positions
 #pragma unroll
           for (int i = 0; i < VPL; ++i) {
             const int c = lane + 64 * i;
@@ -649,9 +695,11 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
 
 // sums of the partial rows of embed_bwd_pos_kernel, fixed order.  grid (ceil(H / 32), 4 + ceil(S / 32)), block (32, 32):
 //   y = 0, 1, 2, 3: dgamma, dbeta, token-type rows 0 / 1 = sum over all S * Y blocks (32 row lanes + an LDS tree);
-//   y = 4 + g: thread row r owns position j = 32 g + r: position row pos[j] = sum over the Y blocks (j, 0), (j, 1), ...
-// `accum_ln` / `accum_tab`: add to what the outputs hold.
-__global__ __launch_bounds__(1024) void embed_bwd_finalize_kernel(const float* __restrict__ part, const int64_t* __restrict__ pos, int S, int Y,
+//   y = 4 + g: thread row r owns position j = 32 g + r: position row colkey[j] = sum over the Y blocks (j, 0), (j, 1), ..., stored
+//   (or added, `accum_tab`) when column j is the row's only contributor; a float atomic add otherwise (embed_bwd_colkey_kernel zeroed
+//   the row when !accum_tab).  `accum_ln` / `accum_tab`: add to what the outputs hold.
+__global__ __launch_bounds__(1024) void embed_bwd_finalize_kernel(const float* __restrict__ part, const int64_t* __restrict__ colkey,
+                                                                  const int* __restrict__ shared, int S, int Y,
                                                                   int H, int n_types, int64_t pos_pad_id, float* __restrict__ dgamma,
                                                                   float* __restrict__ dbeta, float* __restrict__ dtype_tab,
                                                                   float* __restrict__ dptab, int accum_ln, int accum_tab) {
@@ -660,13 +708,14 @@ __global__ __launch_bounds__(1024) void embed_bwd_finalize_kernel(const float* _
   if (y >= 4) {
     const int j = (y - 4) * 32 + threadIdx.y;
     if (j >= S || col >= H) return;
-    const int64_t key = pos[j];
+    const int64_t key = colkey[j];
     if (key == pos_pad_id) return;
     const float* p = part + ((int64_t)2 * nblk + j) * H + col;      // blocks (j, 0), (j, 1), ...: bid = yy * S + j
     float s = 0.f;
     for (int yy = 0; yy < Y; ++yy) s += p[(int64_t)yy * S * H];
     float* o = dptab + key * H + col;
-    *o = accum_tab ? *o + s : s;
+    if (shared[j]) atomicAdd(o, s);
+    else *o = accum_tab ? *o + s : s;
     return;
   }
   float* outp = y == 0 ? dgamma : (y == 1 ? dbeta : (y == 2 ? dtype_tab : (n_types > 1 ? dtype_tab + H : nullptr)));
@@ -994,10 +1043,12 @@ extern "C" size_t nbest_rowred_ws_bytes(int64_t M, int64_t N) {
 }
 constexpr int kEmbTpc = 16;   // sorted tokens per wave of embed_bwd_word_kernel
 extern "C" size_t nbest_embed_bwd_ws_bytes(int64_t M, int64_t H) {
-  // partial rows of embed_bwd_pos_kernel (<= kMaxLnBwdBlocks blocks x 5 quantities) | two partial rows per chunk of embed_bwd_word_kernel
-  // | the fix-up work list (a counter + one chunk id per entry)
+  // partial rows of embed_bwd_pos_kernel (<= kMaxLnBwdBlocks blocks x 5 quantities) | column keys (int64) and the mixed / shared flags
+  // (int, int) of the <= kMaxLnBwdBlocks positions | two partial rows per chunk of embed_bwd_word_kernel | the fix-up work list (a
+  // counter + one chunk id per entry)
   const int64_t chunks = (M + kEmbTpc - 1) / kEmbTpc;
-  return (size_t)5 * kMaxLnBwdBlocks * H * sizeof(float) + (size_t)chunks * 2 * H * sizeof(float) + (size_t)(chunks + 4) * sizeof(int);
+  return (size_t)5 * kMaxLnBwdBlocks * H * sizeof(float) + (size_t)kMaxLnBwdBlocks * (sizeof(int64_t) + 2 * sizeof(int)) +
+         (size_t)chunks * 2 * H * sizeof(float) + (size_t)(chunks + 4) * sizeof(int);
 }
 
 // y8 != NULL (bf16, H % 256 == 0, H <= 1024 only): also write the e4m3 copy of y that the next fp8 forward GEMM reads
@@ -1154,7 +1205,10 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
   if (Y < 1) Y = 1;
   NB_CHECK((int64_t)S * Y <= kMaxLnBwdBlocks, NBEST_ERR_SHAPE, "embed_ln_bwd: S = %d exceeds %d", S, kMaxLnBwdBlocks);
   float* part = (float*)ws;
-  float* wpart = part + (size_t)5 * kMaxLnBwdBlocks * H;
+  int64_t* colkey = (int64_t*)(part + (size_t)5 * kMaxLnBwdBlocks * H);
+  int* mixed = (int*)(colkey + kMaxLnBwdBlocks);
+  int* shared = mixed + kMaxLnBwdBlocks;
+  float* wpart = (float*)(shared + kMaxLnBwdBlocks);              // 16-byte aligned: every region before it is a multiple of 16 bytes
   const size_t smem = (size_t)5 * H * sizeof(float);
   const dim3 grid(S, Y);
   const int64_t chunks = (M + kEmbTpc - 1) / kEmbTpc;
@@ -1163,7 +1217,8 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
 #define NB_EMB_BWD2(TT, FULL)                                                                                                   \
   DISPATCH_VPL(H, ((void)hipFuncSetAttribute((const void*)embed_bwd_pos_kernel<TT, VPL, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), \
                    embed_bwd_pos_kernel<TT, VPL, FULL><<<grid, 256, smem, st>>>(ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, gamma, \
-                                                                                 stats, (const TT*)dout, dtype_tab, dptab, part, fixlist, B, S, H, pos_pad_id, d), \
+                                                                                 stats, (const TT*)dout, dtype_tab, dptab, part, fixlist, colkey, mixed, \
+                                                                                 shared, B, S, H, pos_pad_id, d), \
                    embed_bwd_word_kernel<TT, VPL, FULL><<<wgrid, 256, 0, st>>>(perm, ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, \
                                                                                 gamma, stats, (const TT*)dout, dword, wpart, fixlist, M, H,  \
                                                                                 kEmbTpc, word_pad_id, tables_accumulate, d)))
@@ -1172,6 +1227,7 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
     if (H % 256 == 0 && H <= 1024) NB_EMB_BWD2(TT, true); \
     else NB_EMB_BWD2(TT, false);                         \
   } while (0)
+  embed_bwd_colkey_kernel<<<S, 256, 0, st>>>(seg, pos, B, S, H, pos_pad_id, tables_accumulate, colkey, mixed, dptab, dtype_tab);
   if (dtype == NBEST_F32) NB_EMB_BWD(float);
   else if (dtype == NBEST_BF16) NB_EMB_BWD(bf16);
   else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_ln_bwd: bad dtype %d", dtype);
@@ -1180,7 +1236,7 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
   NB_LAUNCH_CHECK();
   embed_bwd_wordfix_kernel<<<(unsigned)(chunks < 2048 ? chunks : 2048), 256, (size_t)4 * H * sizeof(float), st>>>(perm, ids, wpart, fixlist, dword, M, H,
                                                                                                                     kEmbTpc, tables_accumulate);
-  embed_bwd_finalize_kernel<<<dim3((H + 31) / 32, 4 + (S + 31) / 32), dim3(32, 32), 0, st>>>(part, pos, S, Y, H, n_types, pos_pad_id, dgamma, dbeta,
+  embed_bwd_finalize_kernel<<<dim3((H + 31) / 32, 4 + (S + 31) / 32), dim3(32, 32), 0, st>>>(part, colkey, shared, S, Y, H, n_types, pos_pad_id, dgamma, dbeta,
                                                                                              dtype_tab, dptab, accumulate, tables_accumulate);
   NB_LAUNCH_CHECK();
   return NBEST_OK;

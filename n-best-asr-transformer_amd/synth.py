@@ -82,9 +82,12 @@ def pretrained_like(sd, cfg, seed=999, n_dims=6, ln_gain=10.0, col_gain=20.0):
     return dims
 
 
-def nbest_batch(cfg, labels, B, S, n_best=5, seed=999, ragged=False, trans_len=None):
+def nbest_batch(cfg, labels, B, S, n_best=5, seed=999, ragged=False, trans_len=None, row0_shortest=False):
     """Synthetic padded hypothesis batch.  Returns dict of int64/float32 ndarrays:
-    ids[B,S], seg[B,S], labels[B,n_bottom] (+ tids/tseg [B,trans_len] when trans_len)."""
+    ids[B,S], seg[B,S], labels[B,n_bottom] (+ tids/tseg [B,trans_len] when trans_len).
+    ragged: row 0 has the full length, the others random lengths.  row0_shortest: then swap a shortest row (of ids, and separately
+    of tids) into row 0, the order of real-data batches that puts RoBERTa-family position keys of a column in rows other than 0;
+    the random stream is the same, so the batch is a row permutation of the default one."""
     g = _rng(seed, "batch/%d/%d/%d" % (B, S, n_best))
     pad, cls, sep = cfg.pad_token_id, cfg.cls_token_id, cfg.sep_token_id
     lo = 1000 if cfg.family == "bert" else 4
@@ -121,6 +124,13 @@ def nbest_batch(cfg, labels, B, S, n_best=5, seed=999, ragged=False, trans_len=N
         for t in tops:
             bs = labels.top2bottom[int(t)]
             y[b, bs[int(g.integers(0, len(bs)))]] = 1.0
+    def shortest_first(*arrs):
+        k = int(np.argmin((arrs[0] != pad).sum(1)))
+        for a in arrs:
+            a[[0, k]] = a[[k, 0]]
+
+    if row0_shortest:
+        shortest_first(ids, seg, y)
     out = dict(ids=ids, seg=seg, labels=y)
     if trans_len:
         tids = np.full((B, trans_len), pad, np.int64)
@@ -128,5 +138,7 @@ def nbest_batch(cfg, labels, B, S, n_best=5, seed=999, ragged=False, trans_len=N
         for b in range(B):
             length = trans_len if (not ragged or b == 0) else int(g.integers(trans_len // 2, trans_len + 1))
             fill(tids[b], tseg[b], length, 1)
+        if row0_shortest:
+            shortest_first(tids, tseg)
         out.update(tids=tids, tseg=tseg)
     return out

@@ -125,6 +125,45 @@ def test_synthetic_batch_layout(labels):
     assert all(np.array_equal(b[k], b2[k]) for k in b)                           # deterministic
 
 
+# sha256 (first 16 hex digits) of synth.nbest_batch's default output (16 x 64, n_best 5, trans_len 24): every synthetic test and
+# bench.py measure on these batches, so an option added to the generator must leave them byte-identical
+SYNTH_DIGESTS = {("bert", False, 3): "a273410aeff673de", ("bert", False, 11): "26cf705e6ffaae09",
+                 ("bert", True, 3): "db6f4ddb0364fb9b", ("bert", True, 11): "96a35782eceb2c07",
+                 ("xlmr", False, 3): "6af35886c16f4978", ("xlmr", False, 11): "84dccb3f1dfbd77e",
+                 ("xlmr", True, 3): "4314f40abbdde7e6", ("xlmr", True, 11): "d649fe782c61e2f2"}
+
+
+def _batch_digest(b):
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(b):
+        h.update(k.encode()); h.update(str(b[k].dtype).encode()); h.update(str(b[k].shape).encode())
+        h.update(np.ascontiguousarray(b[k]).tobytes())
+    return h.hexdigest()[:16]
+
+
+@pytest.mark.parametrize("family", ["bert", "xlmr"])
+def test_synthetic_batch_digest_and_row0_shortest(labels, family):
+    cfg = ncfg.bert_base() if family == "bert" else ncfg.xlmr_base(num_hidden_layers=2, vocab_size=3000)
+    pad = cfg.pad_token_id
+    for (fam, ragged, seed), want in SYNTH_DIGESTS.items():
+        if fam != family:
+            continue
+        b = synth.nbest_batch(cfg, labels, 16, 64, n_best=5, seed=seed, ragged=ragged, trans_len=24)
+        assert _batch_digest(b) == want, "default synthetic batch changed (%s, ragged=%s, seed=%d)" % (family, ragged, seed)
+        s = synth.nbest_batch(cfg, labels, 16, 64, n_best=5, seed=seed, ragged=ragged, trans_len=24, row0_shortest=True)
+        for x, t, lab in (("ids", "seg", "labels"), ("tids", "tseg", None)):
+            n = (s[x] != pad).sum(1)
+            assert n[0] == n.min(), "%s: row 0 (%d tokens) is not the shortest (%d)" % (x, n[0], n.min())
+            if ragged:
+                assert n[0] < n.max()
+            k = int(np.argmin((b[x] != pad).sum(1)))
+            perm = np.arange(16)
+            perm[[0, k]] = perm[[k, 0]]
+            for key in (x, t) + ((lab,) if lab else ()):
+                assert np.array_equal(s[key], b[key][perm]), key      # a row permutation of the default batch
+
+
 def test_arena_layout(labels):
     """layout only (no device allocation): contiguity of the fused QKV / head matrices, alignment, HF names"""
     from nbest_amd import arena as ar

@@ -326,6 +326,168 @@ def test_embed_bwd_segmented_reduce(dtype, H, roberta):
         assert torch.equal(x, y), n
 
 
+# Position / token-type layouts of the embedding backward.  embed_bwd_pos_kernel keys a sequence column on the key its non-padding
+# rows share; every other non-padding key (and token types >= 2) takes the float-atomic fallback, and finalize must then neither
+# overwrite what the fallback added nor race with another column of the same key.  Each case: (ids, seg, pos, n_types, word pad id,
+# position pad id, position-table rows, deterministic) - deterministic = the layouts include/nbest_hip.h documents as bit-reproducible.
+EMB_LAYOUTS = ["roberta_row0_shortest", "roberta_row0_shortest_big", "roberta_tail_all_pad", "bert_no_seg", "left_padded", "interior_pad",
+               "arbitrary_positions_nopad", "arbitrary_positions_pad", "three_token_types"]
+
+
+def _emb_layout(case, V=400):
+    g = torch.Generator().manual_seed(sum(map(ord, case)))
+    B, S = (256, 128) if case.endswith("_big") else (24, 40)
+    if case == "roberta_tail_all_pad":
+        S = 48
+    ids = torch.randint(4, V, (B, S), generator=g)
+    ids[:, 0] = 0                                                    # <s>
+    pad = 1
+    seg, n_types, word_pad, pos_pad, det = torch.zeros(B, S, dtype=torch.long), 1, pad, pad, True
+
+    def lengths(lo, hi):
+        n = torch.randint(lo, hi + 1, (B,), generator=g)
+        n[0] = 3                                                     # row 0 strictly the shortest
+        if hi == S:
+            n[1 + int(torch.randint(0, B - 1, (1,), generator=g))] = S   # one full row
+        return n
+
+    def roberta_pos(ids):                                            # model.position_ids_for
+        nonpad = ids.ne(pad).long()
+        return torch.cumsum(nonpad, dim=1) * nonpad + pad
+
+    if case.startswith("roberta"):
+        n = lengths(4, S if case != "roberta_tail_all_pad" else 40)  # tail: columns 40 .. 47 are padding in every row
+        for b in range(B):
+            ids[b, n[b]:] = pad
+        pos = roberta_pos(ids)
+    elif case == "left_padded":
+        n = lengths(4, S)
+        for b in range(B):
+            ids[b, :S - n[b]] = pad
+        pos, det = roberta_pos(ids), False
+    elif case == "interior_pad":                                    # row 0 full here: its keys are the ones the other rows shift onto
+        n = lengths(8, S)
+        n[0] = S
+        for b in range(B):
+            ids[b, n[b]:] = pad
+            if b % 3 == 0 and n[b] > 4:
+                ids[b, 1 + b % (int(n[b]) - 2)] = pad                # a padding id inside the row: the keys after it shift by one
+        pos, det = roberta_pos(ids), False
+    elif case.startswith("arbitrary_positions"):
+        n_pos = 2 * S
+        pos = torch.randint(0, n_pos, (B, S), generator=g)
+        pos[0, 5] = pos[0, 2]                                        # repeats inside row 0 (two columns own one key) ...
+        pos[0, 9] = pos[0, 2]
+        pos[3, 7] = pos[0, 2]                                        # ... and across columns
+        if case.endswith("_pad"):
+            pos[:, 30:] = pad                                        # columns that are padding in every row ...
+            pos[0, 11] = pad                                         # ... and one whose row 0 is padding
+            pos[5, 2] = pad
+            word_pad = -1
+        else:
+            pos_pad = word_pad = -1
+        det = False
+    else:                                                            # bert_no_seg / three_token_types: arange positions, BERT padding
+        word_pad, pos_pad = 0, -1
+        ids[:, 0] = 2
+        n = lengths(4, S)
+        for b in range(B):
+            ids[b, n[b]:] = 0
+        pos = torch.arange(S)[None, :].expand(B, S).contiguous()
+        if case == "bert_no_seg":
+            seg, n_types = None, 2
+        else:
+            seg = (torch.arange(S)[None, :] > 12).long().expand(B, S).contiguous().clone()
+            seg[::4, 20:] = 2                                        # token type 2: the dtype_tab fallback
+            n_types, det = 3, False
+    n_pos = max(int(pos.max()) + 1, 2)
+    to = lambda t: None if t is None else t.contiguous().to(DEV)
+    return to(ids), to(seg), to(pos), n_types, word_pad, pos_pad, n_pos, det
+
+
+def _emb_problem(case, dtype, H):
+    ids, seg, pos, n_types, word_pad, pos_pad, n_pos, det = _emb_layout(case)
+    B, S = ids.shape
+    V = 400
+    word, tt, pt = rnd(V, H, dtype=dtype, s=0.5, seed=71), rnd(n_types, H, dtype=dtype, s=0.5, seed=72), rnd(n_pos, H, dtype=dtype, s=0.5, seed=73)
+    gam, bet = 1 + 0.1 * rnd(H, seed=74), 0.1 * rnd(H, seed=75)
+    wr, tr, pr = (t.float().clone().requires_grad_(True) for t in (word, tt, pt))
+    gr, br = gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
+    F = torch.nn.functional
+    e = (F.embedding(ids, wr, padding_idx=word_pad if word_pad >= 0 else None) + (tr[seg] if seg is not None else tr[0])
+         + F.embedding(pos, pr, padding_idx=pos_pad if pos_pad >= 0 else None))
+    ref = F.layer_norm(e, (H,), gr, br, 1e-5).reshape(B * S, H)
+    dout = rnd(B * S, H, dtype=dtype, seed=76)
+    ref.backward(dout.float())
+    return dict(ids=ids, seg=seg, pos=pos, word=word, tt=tt, pt=pt, gam=gam, bet=bet, dout=dout, B=B, S=S, word_pad=word_pad,
+                pos_pad=pos_pad, det=det, ref=ref.detach(), grads=(wr.grad, tr.grad, pr.grad, gr.grad, br.grad))
+
+
+EMB_NAMES = ("dword", "dtype", "dpos", "dgamma", "dbeta")
+
+
+@pytest.mark.parametrize("H", [768, 1024, 320])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("case", EMB_LAYOUTS)
+def test_embed_bwd_position_layouts(case, dtype, H):
+    """Forward and all five backward outputs against fp32 autograd for every layout, in both table modes (fresh tables, and
+    tables_accumulate into a known non-zero gradient); the documented-deterministic layouts also give the same bits on three runs,
+    and accumulating into the single-pass result gives exactly twice it."""
+    P = _emb_problem(case, dtype, H)
+    tol = tol_of(dtype)
+    out, stats = hb.embed_ln_fwd(P["ids"], P["seg"], P["pos"], P["word"], P["tt"], P["pt"], P["gam"], P["bet"], 1e-5)
+    close("embed_fwd[%s] out" % case, out, P["ref"], tol)
+    run = lambda acc=None: hb.embed_ln_bwd(P["ids"], P["seg"], P["pos"], P["word"], P["tt"], P["pt"], P["gam"], stats, P["dout"], P["B"],
+                                           P["S"], word_pad_id=P["word_pad"], pos_pad_id=P["pos_pad"], accumulate_into=acc)
+    one = run()
+    for n, x, want in zip(EMB_NAMES, one, P["grads"]):
+        close("embed_bwd[%s] %s" % (case, n), x, want, 5 * tol)
+    prior = tuple(rnd(*x.shape, seed=80 + i) * w.abs().max() for i, (x, w) in enumerate(zip(one, P["grads"])))   # the gradient's scale
+    acc = run(tuple(t.clone() for t in prior))
+    for n, x, p0, want in zip(EMB_NAMES, acc, prior, P["grads"]):
+        close("embed_bwd[%s] accumulate %s" % (case, n), x, p0 + want, 5 * tol)
+    if P["det"]:
+        for _ in range(2):
+            again = run()
+            for n, x, y in zip(EMB_NAMES, one, again):
+                assert torch.equal(x, y), "embed_bwd[%s] %s is not bit-reproducible" % (case, n)
+        two = run(tuple(t.clone() for t in one))
+        for n, x, y in zip(EMB_NAMES, two, one):
+            assert torch.equal(x, y + y), "embed_bwd[%s] accumulate: %s != 2 x the single pass" % (case, n)
+
+
+@pytest.mark.parametrize("case", EMB_LAYOUTS)
+def test_embed_bwd_overwrite_contract(case):
+    """nbest_embed_ln_bwd with tables_accumulate == accumulate == 0, called through the C ABI on tables full of NaN: every row the
+    batch touches (and dtype_tab rows 0 and 1, dgamma, dbeta) holds the gradient afterwards, every other row is left as it was."""
+    H, dtype = 768, torch.float32
+    P = _emb_problem(case, dtype, H)
+    _, stats = hb.embed_ln_fwd(P["ids"], P["seg"], P["pos"], P["word"], P["tt"], P["pt"], P["gam"], P["bet"], 1e-5)
+    outs = [torch.full(t.shape, float("nan"), dtype=torch.float32, device=DEV) for t in (P["word"], P["tt"], P["pt"])]
+    outs += [torch.full((H,), float("nan"), device=DEV), torch.full((H,), float("nan"), device=DEV)]
+    B, S = P["B"], P["S"]
+    ws = torch.empty(hb.lib().nbest_embed_bwd_ws_bytes(B * S, H), dtype=torch.uint8, device=DEV)
+    p = hb.ptr
+    hb.check(hb.lib().nbest_embed_ln_bwd(p(P["ids"]), p(P["seg"]), p(P["pos"]), p(hb.word_perm(P["ids"])), p(P["word"]), p(P["tt"]), p(P["pt"]),
+                                         p(P["gam"]), p(stats), p(P["dout"]), *map(p, outs), B, S, H, P["tt"].shape[0],
+                                         hb.dtype_code(dtype), P["word_pad"], P["pos_pad"], 0, 0, 0.0, 0, 0, p(ws), ws.numel(), hb.stream_ptr()),
+             "embed_ln_bwd")
+    torch.cuda.synchronize()
+    ids, pos = P["ids"].reshape(-1), P["pos"].reshape(-1)
+    seg = P["seg"].reshape(-1) if P["seg"] is not None else torch.zeros_like(ids)
+    touched = [torch.zeros(t.shape[0], dtype=torch.bool, device=DEV) for t in outs[:3]]
+    touched[0][ids[ids != P["word_pad"]]] = True
+    touched[1][seg] = True
+    touched[1][:2] = True                                            # rows 0 and 1 (n_types > 1) are always written
+    touched[2][pos[pos != P["pos_pad"]]] = True
+    for n, x, want, t in zip(EMB_NAMES, outs[:3], P["grads"][:3], touched):
+        assert not torch.isnan(x[t]).any(), "embed_bwd[%s] %s: a touched row was not written" % (case, n)
+        close("embed_bwd[%s] overwrite %s" % (case, n), x[t], want[t], 5e-4)
+        assert torch.isnan(x[~t]).all(), "embed_bwd[%s] %s: an untouched row was written" % (case, n)
+    for n, x, want in zip(EMB_NAMES[3:], outs[3:], P["grads"][3:]):
+        close("embed_bwd[%s] overwrite %s" % (case, n), x, want, 5e-4)
+
+
 # ------------------------------------------------------------------------------------------------
 def _attn_ref(qkv, mask, B, S, heads):
     H = heads * 64
