@@ -366,6 +366,31 @@ int nbest_bertadam_norms(const float* g, const nbest_tensor_desc* descs, int n_t
 int nbest_bertadam_update(float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                           int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* partial, float* coef,
                           float lr_mult, float b1, float b2, float eps, float max_grad_norm, nbest_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
+ * K9b  torch Adam / HF AdamW over the same arenas and descriptors, under ONE global-norm clip
+ * (the reference's n_best_asr_bert.py:266-277,551-569, --optim_choice adam | adamw):
+ *   clip: total = sqrt(sum over every tensor of ||g_t||^2), c = min(1, max_grad_norm / (total + 1e-6)) (1 if max_grad_norm <= 0)
+ *         = torch.nn.utils.clip_grad_norm_;
+ *   NBEST_ADAM_L2 (torch.optim.Adam, weight_decay = l2): g = c g + wd p; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
+ *         p -= (lr lr_mult / bc1) m / (sqrt(v) / bc2_sqrt + eps), bc1 = 1 - b1^t, bc2_sqrt = sqrt(1 - b2^t);
+ *   NBEST_ADAMW (HF AdamW, correct_bias=False; pass bc1 = bc2_sqrt = 1): g = c g; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
+ *         p -= lr lr_mult m / (sqrt(v) + eps); then, if wd > 0, p -= lr lr_mult wd p (on the updated p).
+ * lr and wd are the descriptor's (torch Adam: the same lr and wd = l2 in every descriptor).  b1 and b2 are doubles: the kernels
+ * use (float)b and (float)(1 - b), the values torch's kernels receive from its Python-float hyper-parameters.  Inactive tensors are
+ * skipped and contribute nothing to the norm.
+ * Range form: nbest_bertadam_norms writes the block sums of squares of each descriptor table; the caller lays the partials of
+ * all tables back to back in one vector of n_partial floats (zeroed and SUM-all-reduced over the ranks when the optimizer is
+ * sharded).  nbest_adam_clip_coef reduces it in a fixed order (fp64) into clip[0] = c, clip[1] = total norm (device memory:
+ * no host synchronisation); nbest_adam_update then updates blocks [blk_lo, blk_hi) of one table, reading clip[0].
+ * nbest_adam_step = norms + clip coefficient + update of one table; ws: >= (n_blocks + 2) floats.                       */
+enum { NBEST_ADAM_L2 = 0, NBEST_ADAMW = 1 };
+int nbest_adam_clip_coef(const float* partial, int n_partial, float max_grad_norm, float* clip, nbest_stream_t stream);
+int nbest_adam_update(int mode, float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                      int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* clip, float lr_mult, float bc1,
+                      float bc2_sqrt, double b1, double b2, float eps, nbest_stream_t stream);
+int nbest_adam_step(int mode, float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                    int n_tensors, int n_blocks, float lr_mult, float bc1, float bc2_sqrt, double b1, double b2, float eps,
+                    float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* Transposed bf16 copy of the weight matrices (same element offsets in `dst` as in `src`): matrix t is
  * [rows][cols] in src and [cols][rows] in dst.  The backward's dgrad GEMMs read this copy so that both of
  * their operands are k-contiguous (no transposed LDS reads).  descs: DEVICE array ordered by tile_start,

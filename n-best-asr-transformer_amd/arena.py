@@ -286,10 +286,11 @@ class ParamArena:
         return [s for s in self.slots if (select is None or select(s.name)) and "pooler" not in s.name and
                 (s.name.startswith("clf.") or s.name.endswith("bias") or "LayerNorm" in s.name)]
 
-    def build_descs(self, lr, bert_lr, active=None, select=None):
+    def build_descs(self, lr, bert_lr, active=None, select=None, wd=None):
         """device array of nbest_tensor_desc, one per tensor (grouping of n_best_asr_bert.py:540-550);
         ``select(name)`` restricts the set to some tensors (the optimizer is split so the embedding tables can be
-        updated after their own, last, gradient exchange)."""
+        updated after their own, last, gradient exchange).  ``wd`` overrides the decay of EVERY tensor (torch Adam's one
+        group: weight_decay = --l2 on biases and LayerNorm too; pass bert_lr = lr for its one learning rate)."""
         chunk = hb.lib().nbest_bertadam_chunk()
         slots = [s for s in self.slots if select is None or select(s.name)]
         n = len(slots)
@@ -300,6 +301,8 @@ class ParamArena:
             d.offset, d.numel = s.offset, s.numel
             d.lr = bert_lr if "bert_encoder" in s.name else lr
             d.wd = 0.0 if any(nd in s.name for nd in NO_DECAY) else 0.01
+            if wd is not None:
+                d.wd = wd
             d.active = 0 if "pooler" in s.name else 1            # never receives a gradient
             if active is not None:
                 d.active = int(bool(active(s.name)))

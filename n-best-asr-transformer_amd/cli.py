@@ -29,7 +29,7 @@ import torch
 from . import config as ncfg, observe, synth, trainer
 from .inputs import SentencePieceTokenizer, WordPieceTokenizer
 from .model import NBestSTCModel
-from .optim import HipBertAdam
+from .optim import HipAdam, HipBertAdam
 
 
 def parse_arguments(argv=None):
@@ -74,8 +74,11 @@ def parse_arguments(argv=None):
     g.add_argument("--max_epoch", type=int, default=50)
     g.add_argument("--experiment", default="exp")
     g.add_argument("--optim_choice", default="bertadam", choices=["adam", "adamw", "bertadam"],
-                   help="only bertadam (the shipped script's choice) is built as a fused HIP optimizer; adam / adamw "
-                        "(n_best_asr_bert.py:552-569: torch Adam, HF AdamW + linear schedule, global-norm clip) are refused")
+                   help="fused HIP optimizers, as n_best_asr_bert.py:266-277,551-569: bertadam (the shipped script's choice; "
+                        "each tensor clipped to norm 1, warmup-linear schedule) | adam (torch Adam: one lr for every tensor, "
+                        "--bert_lr ignored, L2 decay --l2, bias correction) | adamw (HF AdamW, correct_bias=False: BertAdam's "
+                        "groups, decoupled decay 0.01, linear warm-up / decay schedule; needs --restated_adamw).  adam and adamw "
+                        "clip the global gradient norm to --max_norm")
     g.add_argument("--lr", type=float, default=5e-4)
     g.add_argument("--bert_lr", type=float, default=1e-5)
     g.add_argument("--warmup_proportion", type=float, default=0.1)
@@ -98,16 +101,22 @@ def parse_arguments(argv=None):
                    help="LOCAL HF-format encoder checkpoint (directory or model.safetensors / pytorch_model.bin); its vocab.txt is "
                         "used when --vocab is not given.  Stands in for from_pretrained(name), which needs the network")
     g.add_argument("--stop_after_epoch", type=int, default=None, help="leave after this epoch (preemption drills; use with --resume)")
-    g.add_argument("--resume", action="store_true", help="continue from <exp_dir>/last.pt (model + BertAdam state + epoch)")
+    g.add_argument("--resume", action="store_true", help="continue from <exp_dir>/last.pt (model + optimizer state + epoch)")
     g.add_argument("--vocab", default=None, help="WordPiece vocabulary: vocab.txt (one token per line) or a JSON list")
     g.add_argument("--label_space", default=None, help="JSON with top2bottom / idx2label instead of memory.pt")
     g.add_argument("--encoder_layers", type=int, default=None, help="override the number of encoder layers (smoke runs)")
     g.add_argument("--shard_optimizer", default="off", choices=["on", "off"],
-                   help="data parallel only: BertAdam sharded over the ranks (reduce-to-owner + owner broadcasts, DESIGN 6) instead of "
-                        "replicated behind the all-reduce.  Opt-in: the path has not run over RCCL on more than one GPU yet")
+                   help="data parallel only: the optimizer (bertadam, adam or adamw) sharded over the ranks (reduce-to-owner + owner "
+                        "broadcasts, DESIGN 6) instead of replicated behind the all-reduce.  Opt-in: the path has not run over RCCL on "
+                        "more than one GPU yet")
+    g.add_argument("--restated_adamw", action="store_true",
+                   help="run --optim_choice adamw.  The reference's AdamW (transformers.optimization.AdamW, correct_bias=False) is "
+                        "not in current transformers releases, so its branch cannot run there; this build restates the update rule "
+                        "(DESIGN.md, kernel K9b) and checks it against that restatement, not against the reference's own code")
     opt = ap.parse_args(argv)
-    if opt.optim_choice != "bertadam":
-        ap.error("only --optim_choice bertadam is built (the shipped script's choice)")
+    if opt.optim_choice == "adamw" and not opt.restated_adamw:
+        ap.error("--optim_choice adamw: the reference's AdamW is not in current transformers releases, so the reference cannot run "
+                 "it; this build's restatement of its update rule runs when --restated_adamw is passed too")
     if opt.deviceId < 0:
         ap.error("--deviceId -1 (CPU) is not available: the path is HIP-only")
     if opt.pre_trained_model == "roberta":
@@ -238,8 +247,13 @@ def main(argv=None):
     if train is None:
         raise SystemExit("no training split at %s" % os.path.join(opt.dataroot, opt.train_file))
     t_total = (len(train) // opt.batchSize + 1) * opt.max_epoch            # n_best_asr_bert.py:556
-    opt.optimizer = HipBertAdam(model, lr=opt.lr, bert_lr=opt.bert_lr, warmup=opt.warmup_proportion, t_total=t_total,
-                                shard=opt.shard_optimizer == "on")
+    if opt.optim_choice == "bertadam":
+        opt.optimizer = HipBertAdam(model, lr=opt.lr, bert_lr=opt.bert_lr, warmup=opt.warmup_proportion, t_total=t_total,
+                                    shard=opt.shard_optimizer == "on")
+    else:                                                                   # n_best_asr_bert.py:551-569
+        opt.optimizer = HipAdam(model, kind=opt.optim_choice, lr=opt.lr, bert_lr=opt.bert_lr, l2=opt.l2, warmup=opt.warmup_proportion,
+                                t_total=t_total, max_grad_norm=opt.max_norm, shard=opt.shard_optimizer == "on")
+    opt.scheduler = getattr(opt.optimizer, "scheduler", None)
     log = _Log(os.path.join(opt.exp_dir, "log.train"), rank, append=opt.resume and os.path.exists(os.path.join(opt.exp_dir, "last.pt")))
     t_start = time.time()
     log.info("Training starts at %s" % time.asctime(time.localtime(t_start)))
@@ -248,7 +262,10 @@ def main(argv=None):
     if opt.resume and os.path.exists(last):
         ck = torch.load(last, map_location="cpu", weights_only=True)           # written by this program: tensors + numbers
         model.load_reference_state(ck["model"])
-        opt.optimizer.load_state_dict(ck["optimizer"])
+        try:
+            opt.optimizer.load_state_dict(ck["optimizer"])
+        except ValueError as e:
+            raise SystemExit("--resume from %s: %s" % (last, e))
         best, first_epoch = ck["best"], ck["epoch"] + 1
         model.step_counter = int(ck["dropout_step"])                           # dropout streams continue where they stopped
         log.info("Resumed after epoch %02d (optimizer step %d)" % (ck["epoch"], opt.optimizer.step_count))

@@ -5,6 +5,7 @@
 // HBM-bound: phase 1 reads g (4 B/param) for the per-tensor norms, phase 3 reads p,g,m,v and writes
 // p,m,v (+2 B bf16 copy) = 30 B/param.  All tensors are processed by ONE launch per phase: the block
 // -> (tensor, chunk) map is a binary search over desc.block_start (tensors ordered by offset).
+// torch Adam / HF AdamW (--optim_choice adam | adamw) reuse phase 1 and the block map under one global-norm clip (below).
 #include "common.h"
 
 namespace {
@@ -114,6 +115,96 @@ __global__ __launch_bounds__(256) void bertadam_kernel(float* __restrict__ p, co
   }
 }
 
+// ---- torch Adam (L2, bias-corrected) / HF AdamW (decoupled decay, no bias correction) under ONE global-norm clip ----------
+// c = min(1, max_norm / (sqrt(sum of all partials) + 1e-6)): one workgroup adds the block sums of squares of every descriptor
+// table (the caller lays the tables' partials back to back) in a fixed order, in fp64, so the coefficient is the same bits on
+// every run and every rank.  out[0] = c, out[1] = the total norm.
+__global__ __launch_bounds__(256) void global_clip_kernel(const float* __restrict__ partial, int n, float max_norm,
+                                                          float* __restrict__ out) {
+  __shared__ double sm[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
+  sm[threadIdx.x] = s;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float total = (float)sqrt(sm[0]);
+    float c = 1.f;
+    if (max_norm > 0.f) c = fminf(max_norm / (total + 1e-6f), 1.0f);
+    out[0] = c;
+    out[1] = total;
+  }
+}
+
+// ADAM_L2 (torch.optim.Adam): g = c g + wd p; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
+//                             p -= (lr / bc1) * m / (sqrt(v) / bc2s + eps)
+// ADAMW (HF AdamW, correct_bias=False): g = c g; m = b1 m + (1-b1) g; v = ...; p -= lr * m / (sqrt(v) + eps); p -= lr wd p
+// ob1 / ob2 = 1 - b1 / 1 - b2 rounded from double, as torch passes them (1 - 0.999f would be 1.3e-5 off)
+template <int MODE>
+__device__ __forceinline__ void adam_mode1(float& p, float g, float& m, float& v, float c, float b1, float b2, float ob1, float ob2,
+                                           float eps, float lr, float wd, float bc2s) {
+  g *= c;
+  if (MODE == NBEST_ADAM_L2) {
+    if (wd != 0.f) g += wd * p;
+    m += ob1 * (g - m);
+    v = v * b2 + ob2 * g * g;
+    p += -lr * (m / (sqrtf(v) / bc2s + eps));
+  } else {
+    m = m * b1 + ob1 * g;
+    v = v * b2 + ob2 * g * g;
+    p += -lr * (m / (sqrtf(v) + eps));
+    if (wd > 0.f) p += (-lr * wd) * p;
+  }
+}
+
+// the block -> (tensor, chunk) map, float4 path and bf16 compute-copy write of bertadam_kernel; the clip coefficient is read
+// from device memory (written by global_clip_kernel in stream order: no host round trip).  lr = d.lr * lr_mult / bc1.
+template <int MODE>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, bf16* __restrict__ plow,
+                                                   const nbest_tensor_desc* __restrict__ descs, int n_tensors,
+                                                   const float* __restrict__ clip, float lr_mult, float bc1, float bc2s, float b1,
+                                                   float b2, float ob1, float ob2, float eps, int blk_off) {
+  const int blk = blockIdx.x + blk_off;
+  const int t = find_tensor(descs, n_tensors, blk);
+  const nbest_tensor_desc d = descs[t];
+  if (!d.active) return;
+  const float cf = clip[0];
+  const float lr = d.lr * lr_mult / bc1;
+  const int64_t c0 = (int64_t)(blk - d.block_start) * kChunk;
+  const int64_t c1 = (c0 + kChunk < d.numel) ? c0 + kChunk : d.numel;
+  const int64_t base = d.offset;
+  const bool vec = ((base & 3) == 0);
+  int64_t v1 = c0;
+  if (vec) {
+    v1 = c0 + ((c1 - c0) & ~(int64_t)3);
+    for (int64_t i = c0 + 4 * threadIdx.x; i < v1; i += 1024) {
+      f32x4 pp = *(f32x4*)(p + base + i), gg = *(const f32x4*)(g + base + i);
+      f32x4 mm = *(f32x4*)(m + base + i), vv = *(f32x4*)(v + base + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float p1 = pp[e], m1 = mm[e], v1e = vv[e];
+        adam_mode1<MODE>(p1, gg[e], m1, v1e, cf, b1, b2, ob1, ob2, eps, lr, d.wd, bc2s);
+        pp[e] = p1; mm[e] = m1; vv[e] = v1e;
+      }
+      *(f32x4*)(p + base + i) = pp;
+      *(f32x4*)(m + base + i) = mm;
+      *(f32x4*)(v + base + i) = vv;
+      if (plow) Vec4<bf16>::store(plow + base + i, pp);
+    }
+  }
+  for (int64_t i = v1 + threadIdx.x; i < c1; i += 256) {
+    float pp = p[base + i], mm = m[base + i], vv = v[base + i];
+    adam_mode1<MODE>(pp, g[base + i], mm, vv, cf, b1, b2, ob1, ob2, eps, lr, d.wd, bc2s);
+    p[base + i] = pp; m[base + i] = mm; v[base + i] = vv;
+    if (plow) plow[base + i] = (bf16)pp;
+  }
+}
+
 // bf16 [rows][cols] -> [cols][rows] for a table of matrices living at the same element offsets in two
 // arenas (the k-contiguous weight copy the dgrad GEMMs read).  One launch: block -> (matrix, 64x64 tile).
 __global__ __launch_bounds__(256) void transpose_multi_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
@@ -197,4 +288,43 @@ extern "C" int nbest_bertadam_step(float* p, float* g, float* m, float* v, void*
   if (int rc = nbest_bertadam_norms(g, descs, n_tensors, n_blocks, 0, n_blocks, partial, stream)) return rc;
   return nbest_bertadam_update(p, g, m, v, p_lowp, descs, n_tensors, n_blocks, 0, n_blocks, partial, coef, lr_mult, b1, b2, eps,
                                max_grad_norm, stream);
+}
+
+// ---- Adam / AdamW under a global-norm clip: the partials of every table -> one coefficient -> the updates --------------------
+extern "C" int nbest_adam_clip_coef(const float* partial, int n_partial, float max_grad_norm, float* clip, nbest_stream_t stream) {
+  NB_CHECK(partial && clip && n_partial > 0, NBEST_ERR_ARG, "adam_clip_coef: bad arguments");
+  global_clip_kernel<<<1, 256, 0, (hipStream_t)stream>>>(partial, n_partial, max_grad_norm, clip);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_adam_update(int mode, float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                                 int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* clip, float lr_mult, float bc1,
+                                 float bc2_sqrt, double b1, double b2, float eps, nbest_stream_t stream) {
+  NB_CHECK(p && g && m && v && descs && clip && n_tensors > 0 && 0 <= blk_lo && blk_lo <= blk_hi && blk_hi <= n_blocks &&
+           (mode == NBEST_ADAM_L2 || mode == NBEST_ADAMW) && bc1 > 0.f && bc2_sqrt > 0.f, NBEST_ERR_ARG, "adam_update: bad arguments");
+  if (blk_hi == blk_lo) return NBEST_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const float fb1 = (float)b1, fb2 = (float)b2, ob1 = (float)(1.0 - b1), ob2 = (float)(1.0 - b2);
+  if (mode == NBEST_ADAM_L2)
+    adam_kernel<NBEST_ADAM_L2><<<blk_hi - blk_lo, 256, 0, st>>>(p, g, m, v, (bf16*)p_lowp, descs, n_tensors, clip, lr_mult, bc1,
+                                                                bc2_sqrt, fb1, fb2, ob1, ob2, eps, blk_lo);
+  else
+    adam_kernel<NBEST_ADAMW><<<blk_hi - blk_lo, 256, 0, st>>>(p, g, m, v, (bf16*)p_lowp, descs, n_tensors, clip, lr_mult, bc1,
+                                                              bc2_sqrt, fb1, fb2, ob1, ob2, eps, blk_lo);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_adam_step(int mode, float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                               int n_tensors, int n_blocks, float lr_mult, float bc1, float bc2_sqrt, double b1, double b2, float eps,
+                               float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  NB_CHECK(p && g && m && v && descs && ws && n_tensors > 0 && n_blocks > 0, NBEST_ERR_ARG, "adam_step: null pointer");
+  NB_CHECK(ws_bytes >= ((size_t)n_blocks + 2) * sizeof(float), NBEST_ERR_WORKSPACE, "adam_step: workspace too small");
+  float* partial = (float*)ws;
+  float* clip = partial + n_blocks;
+  if (int rc = nbest_bertadam_norms(g, descs, n_tensors, n_blocks, 0, n_blocks, partial, stream)) return rc;
+  if (int rc = nbest_adam_clip_coef(partial, n_blocks, max_grad_norm, clip, stream)) return rc;
+  return nbest_adam_update(mode, p, g, m, v, p_lowp, descs, n_tensors, n_blocks, 0, n_blocks, clip, lr_mult, bc1, bc2_sqrt, b1, b2, eps,
+                           stream);
 }

@@ -1,4 +1,4 @@
-"""BertAdam over the flat parameter arena, one multi-tensor HIP launch set per step.
+"""BertAdam (and torch Adam / HF AdamW: ``HipAdam``) over the flat parameter arena, one multi-tensor HIP launch set per step.
 
 Interface and semantics of /root/reference/models/optimization.py:183-302 as driven by
 /root/reference/n_best_asr_bert.py:540-561: each parameter tensor is its own group (lr = bert_lr for
@@ -57,7 +57,7 @@ class HipBertAdam:
         self.parts = []
         self._selects = (lambda n: not is_emb(n), is_emb)
         for sel in self._selects:
-            descs, n_t, n_b = a.build_descs(self.lr, self.bert_lr, select=sel)
+            descs, n_t, n_b = self._build_descs(sel)
             ws = torch.empty((n_b + n_t + 16) * 4, dtype=torch.uint8, device=a.device)
             self.parts.append((descs, n_t, n_b, ws))
         self.rank, self.world = 0, 1
@@ -102,6 +102,9 @@ class HipBertAdam:
         self.owner_ranges = [[self.elem_ranges[p_][r] for p_ in range(len(self.parts)) if self.elem_ranges[p_][r][1] > self.elem_ranges[p_][r][0]]
                              for r in range(W)]
 
+    def _build_descs(self, select):
+        return self.arena.build_descs(self.lr, self.bert_lr, select=select)
+
     def get_lr_mult(self):
         return warmup_linear(self.step_count, self.t_total, self.warmup)
 
@@ -131,7 +134,11 @@ class HipBertAdam:
         hb.check(hb.lib().nbest_bertadam_update(hb.ptr(a.p), hb.ptr(a.g), hb.ptr(a.m), hb.ptr(a.v), hb.ptr(a.w16), hb.ptr(descs), n_t, n_b,
                                                 lo, hi, hb.ptr(partial), hb.ptr(coef), self.get_lr_mult(), self.b1, self.b2, self.e,
                                                 self.max_grad_norm, hb.stream_ptr()), "bertadam_update")
-        # the owners hand out what the next step reads
+        self._broadcast_owned(part)
+
+    def _broadcast_owned(self, part):
+        """sharded mode: the owners hand out what the next step reads"""
+        a = self.arena
         for r, (elo, ehi) in enumerate(self.elem_ranges[part]):
             if ehi <= elo:
                 continue
@@ -186,9 +193,151 @@ class HipBertAdam:
                                         next_v=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots})
 
     def load_state_dict(self, sd):
+        if sd.get("kind", "bertadam") != "bertadam":
+            raise ValueError("optimizer state of kind %r cannot be loaded into BertAdam (--optim_choice must match the run that "
+                             "wrote it)" % sd["kind"])
         a = self.arena
         self.step_count = int(sd["step"])
         for s in a.slots:
             st = sd["state"][s.name]
             a.view(a.m, s.name).copy_(st["next_m"])
             a.view(a.v, s.name).copy_(st["next_v"])
+
+
+def linear_schedule_with_warmup(k, warmup_steps, t_total):
+    """learning-rate multiplier after k scheduler steps: transformers.get_linear_schedule_with_warmup's lambda
+    (the reference's n_best_asr_bert.py:564-568)"""
+    if k < warmup_steps:
+        return float(k) / float(max(1, warmup_steps))
+    return max(0.0, float(t_total - k) / float(max(1, t_total - warmup_steps)))
+
+
+class LinearScheduleWithWarmup:
+    """``opt.scheduler`` of --optim_choice adamw: a position k (``last_epoch``, as torch's LambdaLR) that ``step()`` advances and
+    the optimizer reads as its learning-rate multiplier.  It is not advanced by the optimizer step itself, so the reference's
+    loop body ``optimizer.step(); scheduler.step()`` runs verbatim (trainer.train_epoch calls ``step()`` the same way)."""
+
+    def __init__(self, warmup_steps, t_total):
+        self.warmup_steps, self.t_total, self.last_epoch = int(warmup_steps), int(t_total), 0
+
+    def get_lr_mult(self):
+        return linear_schedule_with_warmup(self.last_epoch, self.warmup_steps, self.t_total)
+
+    def step(self):
+        self.last_epoch += 1
+
+
+class HipAdam(HipBertAdam):
+    """--optim_choice adam | adamw (the reference's n_best_asr_bert.py:266-277,551-569) over the arena, through nbest_adam_*:
+
+      * both: ONE gradient-norm clip over every trainable tensor (clip_grad_norm_(params, max_grad_norm); skipped when
+        max_grad_norm <= 0, e.g. when the caller clips itself); the pooler never has a gradient and is left out, as torch
+        skips ``p.grad is None``;
+      * ``adam``: torch.optim.Adam(params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=l2) - ONE group: lr for every tensor
+        (bert_lr is ignored, as there), coupled L2 decay on every tensor, bias correction, no schedule (``scheduler`` is None);
+      * ``adamw``: HF AdamW(groups, lr, correct_bias=False) - BertAdam's groups (bert_lr for the encoder, decay 0.01 except
+        bias / LayerNorm), eps 1e-6, decoupled decay on the updated parameters, no bias correction - with
+        ``scheduler`` = get_linear_schedule_with_warmup(W = int(warmup * t_total), t_total).
+
+    Because the clip is global, nothing may be updated before the LAST gradients (the embedding tables') are in: under data
+    parallelism ``step_main`` only computes the block norms of the encoder / head tensors, ``step_embeddings`` adds the
+    embedding tables' norms, the coefficient and every update.  Sharded mode: each rank writes its own blocks' norms into a
+    zeroed vector that is SUM-all-reduced (x + 0 is exact: every rank computes the replicated coefficient); update, broadcasts
+    and ``gather_master`` are BertAdam's."""
+
+    KINDS = {"adam": hb.ADAM_L2, "adamw": hb.ADAMW}
+
+    def __init__(self, model, kind="adamw", lr=5e-4, bert_lr=None, l2=0.0, warmup=0.0, t_total=-1, max_grad_norm=5.0, shard=False,
+                 b1=0.9, b2=0.999):
+        if kind not in self.KINDS:
+            raise ValueError("HipAdam: kind must be 'adam' or 'adamw', not %r" % (kind,))
+        self.kind, self.mode, self.l2 = kind, self.KINDS[kind], float(l2)
+        if kind == "adam":
+            bert_lr = lr
+        super().__init__(model, lr, bert_lr=bert_lr, warmup=warmup, t_total=t_total, b1=b1, b2=b2,
+                         e=1e-8 if kind == "adam" else 1e-6, max_grad_norm=max_grad_norm, shard=shard)
+        self.scheduler = None
+        if kind == "adamw":
+            self.scheduler = LinearScheduleWithWarmup(int(self.warmup * t_total), t_total)
+        # the block sums of squares of both descriptor tables back to back: ONE vector, ONE coefficient
+        self.blk_base = [0, self.parts[0][2]]
+        self.partial = torch.zeros(max(self.parts[0][2] + self.parts[1][2], 1), dtype=torch.float32, device=self.arena.device)
+        self.clip = torch.ones(2, dtype=torch.float32, device=self.arena.device)       # [c, total norm]
+
+    def _build_descs(self, select):
+        if self.kind == "adam":
+            return self.arena.build_descs(self.lr, self.lr, select=select, wd=self.l2)
+        return self.arena.build_descs(self.lr, self.bert_lr, select=select)
+
+    def get_lr_mult(self):
+        return 1.0 if self.scheduler is None else self.scheduler.get_lr_mult()
+
+    def _range(self, part):
+        return self.blk_bounds[part][self.rank] if self.sharded else (0, self.parts[part][2])
+
+    def _norms(self, part):
+        a = self.arena
+        descs, n_t, n_b, _ = self.parts[part]
+        if n_t == 0 or self.max_grad_norm <= 0:
+            return
+        lo, hi = self._range(part)
+        hb.check(hb.lib().nbest_bertadam_norms(hb.ptr(a.g), hb.ptr(descs), n_t, n_b, lo, hi, hb.ptr(self.partial[self.blk_base[part]:]),
+                                               hb.stream_ptr()), "bertadam_norms")
+
+    def step_main(self):
+        """the block norms of every tensor but the embedding tables: nothing is updated before their gradients are in"""
+        if self.sharded and self.max_grad_norm > 0:
+            self.partial.zero_()
+        self._norms(0)
+
+    def step_embeddings(self):
+        a = self.arena
+        self._norms(1)
+        if self.max_grad_norm > 0:
+            if self.sharded:
+                dist.all_reduce(self.partial, op=dist.ReduceOp.SUM)
+            hb.check(hb.lib().nbest_adam_clip_coef(hb.ptr(self.partial), self.partial.numel(), self.max_grad_norm, hb.ptr(self.clip),
+                                                   hb.stream_ptr()), "adam_clip_coef")
+        else:
+            self.clip.fill_(1.0)
+        t = self.step_count + 1
+        bc1, bc2s = (1.0 - self.b1 ** t, (1.0 - self.b2 ** t) ** 0.5) if self.kind == "adam" else (1.0, 1.0)
+        lr_mult = self.get_lr_mult()
+        for part in range(len(self.parts)):
+            descs, n_t, n_b, _ = self.parts[part]
+            if n_t == 0:
+                continue
+            lo, hi = self._range(part)
+            hb.check(hb.lib().nbest_adam_update(self.mode, hb.ptr(a.p), hb.ptr(a.g), hb.ptr(a.m), hb.ptr(a.v), hb.ptr(a.w16), hb.ptr(descs),
+                                                n_t, n_b, lo, hi, hb.ptr(self.clip), lr_mult, bc1, bc2s, self.b1, self.b2, self.e,
+                                                hb.stream_ptr()), "adam_update")
+        if self.sharded:
+            for part in range(len(self.parts)):
+                self._broadcast_owned(part)
+        a.refresh_transposed()
+        self.step_count += 1
+
+    def state_dict(self, gather=True):
+        """torch's per-parameter ``exp_avg`` / ``exp_avg_sq`` keyed by parameter name, the step count and the scheduler position
+        (collective in sharded mode: see HipBertAdam.state_dict)"""
+        if gather:
+            self.gather_master()
+        a = self.arena
+        return dict(kind=self.kind, step=self.step_count, sched_step=None if self.scheduler is None else self.scheduler.last_epoch,
+                    t_total=self.t_total, warmup=self.warmup,
+                    state={s.name: dict(exp_avg=a.view(a.m, s.name).detach().cpu().clone(),
+                                        exp_avg_sq=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots})
+
+    def load_state_dict(self, sd):
+        kind = sd.get("kind", "bertadam")
+        if kind != self.kind:
+            raise ValueError("optimizer state of kind %r cannot be loaded into HipAdam(kind=%r) (--optim_choice must match the run "
+                             "that wrote it)" % (kind, self.kind))
+        a = self.arena
+        self.step_count = int(sd["step"])
+        if self.scheduler is not None:
+            self.scheduler.last_epoch = int(sd["sched_step"])
+        for s in a.slots:
+            st = sd["state"][s.name]
+            a.view(a.m, s.name).copy_(st["exp_avg"])
+            a.view(a.v, s.name).copy_(st["exp_avg_sq"])

@@ -629,6 +629,9 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
     lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)), shuffle=shuffle, seed=getattr(opt, "random_seed", 999) + epoch)
     group_rows = []                                                  # word-table rows touched by the running accumulation group
+    # --optim_choice adamw: the loop advances the learning-rate schedule after every optimizer step, as the reference's does
+    # (n_best_asr_bert.py:273-275); BertAdam and Adam have none
+    sched = getattr(opt.optimizer, "scheduler", None)
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -641,11 +644,15 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                     reducer.set_step_tokens(*group_rows)
                     reducer.reduce_all()
                 opt.optimizer.step()                                 # keeps replicas and schedule positions identical
+                if sched is not None:
+                    sched.step()
             model.step_counter += 1
             continue
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
                              global_batch=len(lists[bi]))
+            if sched is not None:
+                sched.step()
         else:
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
@@ -657,6 +664,8 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                     reducer.set_step_tokens(*group_rows)
                     reducer.reduce_all()
                 opt.optimizer.step()
+                if sched is not None:
+                    sched.step()
         losses.append((out["loss_parts"], len(mine), len(lists[bi])))
         pipe.push(out, [split.labels[j] for j in mine])
     counts, _ = pipe.finish()
