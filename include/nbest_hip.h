@@ -99,7 +99,7 @@ int nbest_rows_add(float* table, const int64_t* ids, const float* vals, int64_t 
 enum {
   NBEST_EPI_NONE = 0,          /* C = acc                                                    */
   NBEST_EPI_BIAS = 1,          /* C = acc + bias[n]                                          */
-  NBEST_EPI_BIAS_GELU = 2,     /* u = acc + bias[n]; C = gelu_erf(u); U = gelu'(u) (both stored) */
+  NBEST_EPI_BIAS_GELU = 2,     /* u = acc + bias[n]; C = gelu_erf(u); U = gelu'(u) (both stored; U = NULL: C only) */
   NBEST_EPI_BIAS_DROP_RES = 3, /* C = drop(acc + bias[n]) + R[m,n]                           */
   NBEST_EPI_DGELU = 4,         /* C = acc * U[m,n]   (U = gelu'(u) saved by BIAS_GELU, see U) */
   NBEST_EPI_RES = 5,           /* C = acc + R[m,n]                                           */
@@ -233,6 +233,13 @@ int nbest_cast_bf16_to_fp8(const void* src, void* dst, int64_t n, nbest_stream_t
 int nbest_attention_fwd(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int B, int S,
                         int heads, int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
                         nbest_stream_t stream);
+/* CLS-query forward (inference): for every (utterance b, head h) ONE query row, q[b * ldq + h d ..], against the S keys and values
+ * of the utterance, kv[(b S + j) * ldkv + h d ..] (K) and kv[(b S + j) * ldkv + H + h d ..] (V); writes ctx[b * ldctx + h d ..].
+ * The semantics of row 0 of nbest_attention_fwd (same scale and key_mask rule), no dropout, no LSE.  d = 64, 1 <= S <= 512, fp32
+ * or bf16; ldq, ldkv multiples of 16 bytes, q and kv 16-byte aligned.  (nbest_attention_fwd's row 0: q = qkv, ldq = 3 H S,
+ * kv = qkv + H, ldkv = 3 H.)                                                                                                   */
+int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
+                            int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 /* dqkv [M][3H] receives dQ | dK | dV (overwritten, no accumulation).  dbias != NULL: dbias[3H] (+)= column
  * sums of dqkv (the Q|K|V bias gradient), fused into the kernel; ws >= nbest_attention_bwd_ws_bytes().   */
 size_t nbest_attention_bwd_ws_bytes(int B, int S, int heads);
@@ -521,6 +528,14 @@ int nbest_encoder_backward(const nbest_encoder_desc* d, const void* wts, const v
                            const int64_t* ids, const int64_t* seg, const int64_t* pos, const uint8_t* key_mask,
                            void* act, size_t act_bytes, void* dhidden, void* ws, size_t ws_bytes, int accumulate,
                            int layer_begin, int layer_end, int with_embeddings, nbest_stream_t stream);
+
+/* Inference: the encoder forward without an activation stash, for the final hidden state of the B CLS rows only.  Same descriptor,
+ * arenas and inputs as nbest_encoder_forward; cls_out [B][H] in the compute dtype.  Layers 0 .. L-2 are nbest_encoder_forward's
+ * kernels (FFN-up without the GELU' rows); the last layer projects K|V on all B S rows and runs everything else on the B CLS rows.
+ * ws >= nbest_encoder_infer_ws_bytes(d) (independent of L).  Refuses (NBEST_ERR_ARG) non-zero dropout and the fp8 forward (w8).   */
+size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d);
+int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                        const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, nbest_stream_t stream);
 
 #ifdef __cplusplus
 }

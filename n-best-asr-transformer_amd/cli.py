@@ -61,6 +61,10 @@ def parse_arguments(argv=None):
     g.add_argument("--tod_pre_trained_model", help="ToD-BERT style checkpoint: keeps [SYS]/[USR] markers")
     g = ap.add_argument_group("training / testing")
     g.add_argument("--testing", action="store_true")
+    g.add_argument("--predict", default=None, metavar="FILE",
+                   help="label an n-best file with <exp_dir>/model.pt (loaded as --testing does): one 'ASR \\t<=>\\t labels' line per "
+                        "input line, in input order.  Input lines need only the ASR field.  One GPU")
+    g.add_argument("--predict_output", default=None, metavar="PATH", help="--predict output (default: <exp_dir>/<basename of FILE>.pred)")
     g.add_argument("--deviceId", type=int, default=-1,
                    help="as the reference (n_best_asr_bert.py:116-126): 0 = pick a GPU automatically (here: the first visible one; "
                         "the reference asks gpustat / NVML for the least loaded), k > 0 = GPU k-1, -1 = CPU (refused: the path is "
@@ -125,6 +129,11 @@ def parse_arguments(argv=None):
                  "with an IndexError; use bert or xlm-roberta")
     if opt.pre_trained_model and opt.pre_trained_model not in ncfg.NAMED:
         ap.error("--pre_trained_model %s: known shapes are %s" % (opt.pre_trained_model, ", ".join(sorted(ncfg.NAMED))))
+    if opt.predict is not None:
+        if not os.path.isfile(opt.predict):
+            ap.error("--predict %s: no such file" % opt.predict)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--predict runs on one GPU: start it without torchrun (world size %s)" % os.environ["WORLD_SIZE"])
     opt.gpu_index = 0 if opt.deviceId == 0 else opt.deviceId - 1            # n_best_asr_bert.py:116-126 (0: auto -> first GPU)
     # gradient accumulation exactly as the reference derives it (n_best_asr_bert.py:522): 4 micro-batches of batchSize / 4
     # per optimizer step when --n_layers 12 is passed (the shipped script never passes it -> 1)
@@ -141,6 +150,11 @@ def exp_dir(opt):
              "me_%s" % opt.max_epoch, "seed_%s" % opt.random_seed, "score_%s" % opt.score_util, "repr_%s" % opt.sent_repr,
              "cls_%s" % opt.cls_type]
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
+
+
+def predict_output_path(opt):
+    """where --predict writes: --predict_output, or <exp_dir>/<basename of FILE>.pred"""
+    return opt.predict_output or os.path.join(exp_dir(opt), os.path.basename(opt.predict) + ".pred")
 
 
 def load_memory(opt):
@@ -228,6 +242,17 @@ def main(argv=None):
         if not os.path.exists(fn):
             return None
         return trainer.EncodedSplit(trainer.read_wcn_data(fn, coverage), opt, memory)       # tokenised once per run
+
+    if opt.predict is not None:
+        model.load_model(os.path.join(opt.exp_dir, "model.pt"))
+        out_path = predict_output_path(opt)
+        t0 = time.time()
+        cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory)
+        with open(out_path, "w") as fp:
+            for raw, pc in cases:
+                fp.write("%s\t<=>\t%s\n" % (" ".join(raw), ";".join(pc)))
+        print("predicted %d utterances in %.2f s -> %s" % (len(cases), time.time() - t0, out_path), flush=True)
+        return 0
 
     valid, test = load(opt.valid_file), load(opt.test_file)
     if opt.testing:

@@ -1227,6 +1227,108 @@ static void launch_fwd(const bf16* qkv, const uint8_t* mask, bf16* ctx, float* l
   }
 }
 
+// =================================================================================================
+// CLS-query forward (inference): one query row per (utterance, head) - the row 0 that the STC heads read - against the S keys and
+// values of its utterance.  No dropout, no LSE.  The work is reading K and V (2 x S x 128 bytes per head in bf16): one workgroup per
+// (utterance, head), scores through LDS, then P.V with LPK lanes per value row (one 16-byte load each) and a fixed-order sum of the
+// key groups' partial rows.  One kernel for every S <= 512.
+// The arithmetic follows the full-attention kernels where it decides the rounding: fp32 - each score is one lane's sequential fma
+// chain over d (attn_fwd_f32_kernel), p = exp(s - lse); bf16 - the probabilities are rounded to bf16 before P.V, in log2 units for
+// S <= 256 (attn_fwd_bf16_kernel) and natural units above (attn_fwd_long_bf16_kernel).
+// Fully masked row (S = 1 under XLM-R, quirk Q1): fp32 writes 0 and bf16 writes NaN, as those kernels do.
+// =================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kv, int64_t ldkv,
+                                                           const uint8_t* __restrict__ mask, T* __restrict__ ctx, int64_t ldctx, int S,
+                                                           int heads, int H, float scale) {
+  constexpr bool kF32 = sizeof(T) == 4;
+  constexpr int VEC = 16 / (int)sizeof(T);   // elements per 16-byte load
+  constexpr int LPK = 64 / VEC;              // lanes per 64-wide head row: 8 (bf16) / 16 (fp32)
+  constexpr int KPP = 256 / LPK;             // key rows per pass of the workgroup: 32 / 16
+  __shared__ float sc[512];
+  __shared__ float qs[64];
+  __shared__ float part[KPP][65];
+  __shared__ float red[8];
+  const int tid = threadIdx.x, sub = tid % LPK, kg = tid / LPK, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+  auto load = [](const T* p, float* v) {
+    if constexpr (kF32) {
+      const f32x4 x = *(const f32x4*)p;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = x[e];
+    } else {
+      const bf16x8 x = __builtin_bit_cast(bf16x8, *(const i32x4*)p);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
+    }
+  };
+  if (tid < 64) qs[tid] = (float)q[(int64_t)b * ldq + h * 64 + tid];
+  __syncthreads();
+  const T* kbase = kv + (int64_t)b * S * ldkv + h * 64;
+  const T* vbase = kbase + H;
+  const uint8_t* mk = mask + (int64_t)b * S;
+  const bool log2u = !kF32 && S <= 256;                     // the bf16 kernel for S <= 256 scores in units of log2
+  const float sf = log2u ? scale * 1.4426950408889634f : scale;
+  // ---- scores: one lane per key, sequential over d (-inf on masked keys), and their max ----
+  float mloc = -INFINITY;
+  for (int j = tid; j < S; j += 256) {
+    const T* kp = kbase + (int64_t)j * ldkv;
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < 64; c += VEC) {
+      float kr[VEC];
+      load(kp + c, kr);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) d = fmaf(qs[c + e], kr[e], d);
+    }
+    const float sv = mk[j] ? d * sf : -INFINITY;
+    sc[j] = sv;
+    mloc = fmaxf(mloc, sv);
+  }
+  mloc = wave_max(mloc);
+  if (lane == 0) red[wave] = mloc;
+  __syncthreads();
+  const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float mxs = (mx == -INFINITY) ? 0.f : mx;
+  auto ex = [&](float v) { return log2u ? __builtin_amdgcn_exp2f(v - mxs) : (kF32 ? expf(v - mxs) : __expf(v - mxs)); };
+  float sum = 0.f;
+  for (int j = tid; j < S; j += 256) sum += ex(sc[j]);
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  // ---- probabilities: fp32 exp(s - lse) (masked keys 0); bf16 rounded to bf16 after normalising ----
+  const float lse = mxs + logf(sum), inv = 1.0f / sum;
+  for (int j = tid; j < S; j += 256) {
+    const float v = sc[j];
+    sc[j] = kF32 ? (v == -INFINITY ? 0.f : expf(v - lse)) : (float)(bf16)(ex(v) * inv);
+  }
+  __syncthreads();
+  // ---- P.V: partial rows per key group, then a fixed-order sum over the groups ----
+  float o[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) o[e] = 0.f;
+#pragma unroll 4
+  for (int j = kg; j < S; j += KPP) {
+    float vr[VEC];
+    load(vbase + (int64_t)j * ldkv + sub * VEC, vr);
+    const float pv = sc[j];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) o[e] = fmaf(pv, vr[e], o[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) part[kg][sub * VEC + e] = o[e];
+  __syncthreads();
+  if (tid < 64) {
+    float acc = 0.f;
+#pragma unroll
+    for (int g = 0; g < KPP; ++g) acc += part[g][tid];
+    T* op = ctx + (int64_t)b * ldctx + h * 64 + tid;
+    if constexpr (kF32) *op = acc;
+    else *op = (bf16)acc;
+  }
+}
+
 static int check_common(const char* who, int B, int S, int heads, int d, int dtype) {
   NB_CHECK(B > 0 && S > 0 && heads > 0, NBEST_ERR_SHAPE, "%s: bad shape", who);
   NB_CHECK(d == 64, NBEST_ERR_SHAPE, "%s: head dimension %d not supported (64 only)", who, d);
@@ -1278,6 +1380,33 @@ int nbest_internal_attention_fwd8(const void* qkv, const uint8_t* key_mask, void
 extern "C" int nbest_attention_fwd(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int B, int S, int heads,
                                    int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, nbest_stream_t stream) {
   return nbest_internal_attention_fwd8(qkv, key_mask, ctx, nullptr, lse, B, S, heads, d, dtype, drop_p, seed, drop_stream, stream, nullptr, nullptr, nullptr);
+}
+
+int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
+                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
+  NB_CHECK(q && kv && key_mask && ctx, NBEST_ERR_ARG, "attention_cls_fwd: null pointer");
+  NB_CHECK(B > 0 && S > 0 && heads > 0, NBEST_ERR_SHAPE, "attention_cls_fwd: bad shape");
+  NB_CHECK(d == 64, NBEST_ERR_SHAPE, "attention_cls_fwd: head dimension %d not supported (64 only)", d);
+  NB_CHECK(dtype == NBEST_F32 || dtype == NBEST_BF16, NBEST_ERR_DTYPE, "attention_cls_fwd: bad dtype %d", dtype);
+  NB_CHECK(S <= 512, NBEST_ERR_SHAPE, "attention_cls_fwd: S=%d > 512", S);
+  const int H = heads * d;
+  const int vec = dtype == NBEST_BF16 ? 8 : 4;   // 16-byte row loads
+  NB_CHECK(ldq >= H && ldkv >= 2 * H && ldctx >= H && ldq % vec == 0 && ldkv % vec == 0, NBEST_ERR_ALIGN,
+           "attention_cls_fwd: leading dimensions must cover the heads and be multiples of %d elements", vec);
+  NB_CHECK(((uintptr_t)q & 15) == 0 && ((uintptr_t)kv & 15) == 0, NBEST_ERR_ALIGN, "attention_cls_fwd: q and kv must be 16-byte aligned");
+  const float scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == NBEST_F32)
+    attn_cls_fwd_kernel<float><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, (float*)ctx, ldctx, S, heads, H, scale);
+  else
+    attn_cls_fwd_kernel<bf16><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, (bf16*)ctx, ldctx, S, heads, H, scale);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
+                                       int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
+  return nbest_attention_cls_fwd_internal(q, ldq, kv, ldkv, key_mask, ctx, ldctx, B, S, heads, d, dtype, stream);
 }
 
 int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);

@@ -39,6 +39,12 @@ void nbest_set_error(const char* fmt, ...);
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// Kernel-template variant of NBEST_EPI_BIAS_GELU for a null U (the inference forward): C = gelu(acc + bias[n]) only, with no
+// GELU' arithmetic, packing or stores.  Never part of the C ABI: the dispatchers map (BIAS_GELU, U == nullptr) onto it after the
+// plan is chosen, so both forms run the same plan and C is bit-identical.
+constexpr int kEpiBiasGeluNoU = 0x102;
+static inline int nb_kernel_epilogue(int epi, const void* U) { return (epi == NBEST_EPI_BIAS_GELU && !U) ? kEpiBiasGeluNoU : epi; }
+
 // ---- scalar conversions ----------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ float to_f(T v);
 template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }

@@ -466,3 +466,104 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                          d->hidden_drop, d->seed, sb, W + w.emb, w.emb_bytes, stream));
   return NBEST_OK;
 }
+
+// ---- inference: forward only, final hidden state of the B CLS rows ---------------------------------------------------------------
+// Layers 0 .. L-2 run the kernels of nbest_encoder_forward (dropout 0) on buffers reused from layer to layer; FFN-up leaves out the
+// GELU' rows (BIAS_GELU with U == NULL).  Layer L-1: K|V over all M rows, then Q, attention, attention-out, LayerNorm, FFN and
+// LayerNorm on the B CLS rows only (row 0 of each utterance: the one row the STC heads read).
+//   X[2] [M][H] T (ping-pong) | emb_stats [M][2] f32 | qkv [M][3H] T (last layer: K|V [M][2H]) | ctx | r1 | x1 | r2 [M][H] T |
+//   hact [M][F] T | lse [B heads S] f32 | st1 | st2 [M][2] f32.   Last layer: Q -> ctx, context -> r1, x1 -> x1, gelu -> hact,
+//   attention-out and FFN-down sums -> r2.  Independent of L.
+namespace {
+struct InferLayout {
+  size_t X0, X1, emb_stats, qkv, ctx, r1, x1, r2, hact, lse, st1, st2, total;
+};
+static InferLayout infer_layout(const nbest_encoder_desc* d) {
+  InferLayout w;
+  const size_t esz = d->dtype == NBEST_BF16 ? 2 : 4;
+  const int64_t M = (int64_t)d->B * d->S;
+  const size_t MH = al((size_t)M * d->H * esz), st = al((size_t)M * 2 * sizeof(float));
+  size_t o = 0;
+  w.X0 = o; o += MH;
+  w.X1 = o; o += MH;
+  w.emb_stats = o; o += st;
+  w.qkv = o; o += al((size_t)M * 3 * d->H * esz);
+  w.ctx = o; o += MH;
+  w.r1 = o; o += MH;
+  w.x1 = o; o += MH;
+  w.r2 = o; o += MH;
+  w.hact = o; o += al((size_t)M * d->F * esz);
+  w.lse = o; o += al((size_t)d->B * d->heads * d->S * sizeof(float));
+  w.st1 = o; o += st;
+  w.st2 = o; o += st;
+  w.total = o;
+  return w;
+}
+}  // namespace
+
+int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
+                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
+
+extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(d).total : 0; }
+
+extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                   const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                   nbest_stream_t stream) {
+  RUN(check_desc(d));
+  NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
+           "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
+  NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");
+  NB_CHECK(wts && prm && ids && pos && key_mask && ws && cls_out, NBEST_ERR_ARG, "encoder_infer: null pointer");
+  const InferLayout w = infer_layout(d);
+  NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes, w.total);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t esz = d->dtype == NBEST_BF16 ? 2 : 4;
+  const Ptrs P{(const char*)wts, prm, esz};
+  char* W = (char*)ws;
+  const int64_t M = (int64_t)d->B * d->S, B = d->B, SH = (int64_t)d->S * d->H;
+  const int H = d->H, F = d->F, dt = d->dtype;
+  auto PK = [&](int64_t off) -> const void* { return (d->wpk && dt == NBEST_BF16) ? (const void*)((const char*)d->wpk + off * 2) : nullptr; };
+  void* X[2] = {W + w.X0, W + w.X1};
+  void* qkv = W + w.qkv; void* ctx = W + w.ctx; void* r1 = W + w.r1; void* x1 = W + w.x1; void* r2 = W + w.r2; void* hact = W + w.hact;
+  float* lse = (float*)(W + w.lse); float* st1 = (float*)(W + w.st1); float* st2 = (float*)(W + w.st2);
+  const uint32_t sb = d->drop_stream_base;
+
+  RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
+                         P.P(d->off_emb_ln_b), X[0], (float*)(W + w.emb_stats), M, H, d->ln_eps, dt, d->hidden_drop, d->seed, sb, st));
+  for (int l = 0; l + 1 < d->L; ++l) {   // as nbest_encoder_forward (dropout 0), FFN-up without GELU'
+    const nbest_layer_offsets& o = d->layers_host[l];
+    void* xin = X[l & 1]; void* xout = X[(l + 1) & 1];
+    const uint32_t s0 = sb + 1 + 4 * l;
+    RUN(gemm(dt, xin, P.W(o.wqkv), qkv, M, 3 * H, H, H, H, 3 * H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv), nullptr, 0, nullptr, 0,
+             nullptr, 0, 0, 0.f, 0, 0, st, nullptr, PK(o.wqkv)));
+    RUN(nbest_internal_attention_fwd8(qkv, key_mask, ctx, nullptr, lse, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream,
+                                      nullptr, nullptr, nullptr));
+    RUN(gemm(dt, ctx, P.W(o.wo), r1, M, H, H, H, H, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo), xin, H, nullptr, 0, nullptr, 0, 0,
+             d->hidden_drop, d->seed, s0 + 1, st, nullptr, PK(o.wo)));
+    RUN(nbest_internal_layernorm_fwd8(r1, P.P(o.ln1_g), P.P(o.ln1_b), x1, nullptr, st1, M, H, d->ln_eps, dt, stream, nullptr, nullptr));
+    RUN(gemm(dt, x1, P.W(o.w1), hact, M, F, H, H, H, F, 0, 0, NBEST_EPI_BIAS_GELU, P.P(o.b1), nullptr, 0, nullptr, F, nullptr, 0, 0, 0.f,
+             0, 0, st, nullptr, PK(o.w1)));
+    RUN(gemm(dt, hact, P.W(o.w2), r2, M, H, F, F, F, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.b2), x1, H, nullptr, 0, nullptr, 0, 0,
+             d->hidden_drop, d->seed, s0 + 2, st, nullptr, PK(o.w2)));
+    RUN(nbest_internal_layernorm_fwd8(r2, P.P(o.ln2_g), P.P(o.ln2_b), xout, nullptr, st2, M, H, d->ln_eps, dt, stream, nullptr, nullptr));
+  }
+  // last layer, CLS rows only (weights read unpacked: the packed images are laid out for the full-width GEMMs)
+  const int l = d->L - 1;
+  const nbest_layer_offsets& o = d->layers_host[l];
+  const void* xin = X[l & 1];
+  void* kv = qkv; void* q = ctx; void* cctx = r1; void* cx1 = x1; void* ch = hact; void* cr = r2;
+  RUN(gemm(dt, xin, P.W(o.wqkv + (int64_t)H * H), kv, M, 2 * H, H, H, H, 2 * H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv + H), nullptr, 0,
+           nullptr, 0, nullptr, 0, 0, 0.f, 0, 0, st));                                                    // K | V, all rows
+  RUN(gemm(dt, xin, P.W(o.wqkv), q, B, H, H, SH, H, H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv), nullptr, 0, nullptr, 0, nullptr, 0, 0, 0.f,
+           0, 0, st));                                                                                    // Q, CLS rows (lda = S H)
+  RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream));
+  RUN(gemm(dt, cctx, P.W(o.wo), cr, B, H, H, H, H, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo), xin, SH, nullptr, 0, nullptr, 0, 0, 0.f,
+           0, 0, st));                                                                                    // residual: the CLS rows
+  RUN(nbest_internal_layernorm_fwd8(cr, P.P(o.ln1_g), P.P(o.ln1_b), cx1, nullptr, st1, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
+  RUN(gemm(dt, cx1, P.W(o.w1), ch, B, F, H, H, H, F, 0, 0, NBEST_EPI_BIAS_GELU, P.P(o.b1), nullptr, 0, nullptr, F, nullptr, 0, 0, 0.f,
+           0, 0, st));
+  RUN(gemm(dt, ch, P.W(o.w2), cr, B, H, F, F, F, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.b2), cx1, H, nullptr, 0, nullptr, 0, 0, 0.f,
+           0, 0, st));
+  RUN(nbest_internal_layernorm_fwd8(cr, P.P(o.ln2_g), P.P(o.ln2_b), cls_out, nullptr, st2, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
+  return NBEST_OK;
+}

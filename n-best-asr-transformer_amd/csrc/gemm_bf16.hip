@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
 
   // epilogue operands are independent of the K loop: fetch them now so their latency hides under it
   // (the row-contiguous epilogue layout: iteration `it` -> row it*8 + lane/8, 8 columns at (lane&7)*8)
-  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES);
+  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == kEpiBiasGeluNoU || EPI == NBEST_EPI_BIAS_DROP_RES);
   constexpr bool kHasR = (EPI == NBEST_EPI_BIAS_DROP_RES || EPI == NBEST_EPI_RES);
   constexpr bool kHasUin = (EPI == NBEST_EPI_DGELU);
   const int64_t en8 = n0 + wn * 64 + (lane & 7) * 8;
@@ -239,9 +239,17 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
       continue;
     }
     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-    if (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES) {
+    if (kHasBias) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v[e] += pb0[e]; v[4 + e] += pb1[e]; }
+    }
+    if (EPI == kEpiBiasGeluNoU) {
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        f32x2 h2, g2;   // gelu(u) only: g2 has no reader and is not computed
+        gelu_pair_fast(f32x2{v[e], v[e + 1]}, h2, g2);
+        v[e] = h2[0]; v[e + 1] = h2[1];
+      }
     }
     if (EPI == NBEST_EPI_BIAS_GELU) {
       float gp[8];
@@ -336,7 +344,7 @@ static int launch_epi(const GemmP& p, int epi, int grid, hipStream_t st) {
     break;
   switch (epi) {
     L(NBEST_EPI_NONE) L(NBEST_EPI_BIAS) L(NBEST_EPI_BIAS_GELU) L(NBEST_EPI_BIAS_DROP_RES) L(NBEST_EPI_DGELU)
-    L(NBEST_EPI_RES) L(NBEST_EPI_F32_SPLITK)
+    L(NBEST_EPI_RES) L(NBEST_EPI_F32_SPLITK) L(kEpiBiasGeluNoU)
     default:
       nbest_set_error("gemm: bad epilogue %d", epi);
       return NBEST_ERR_ARG;
@@ -391,15 +399,17 @@ int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
     NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm: epilogue %d needs bias", epi);
   if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES) NB_CHECK(a->R && a->ldr % 8 == 0 && ((uintptr_t)a->R & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs R", epi);
-  if (epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_DGELU) NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
+  // BIAS_GELU with a null U: C only (kEpiBiasGeluNoU)
+  if ((epi == NBEST_EPI_BIAS_GELU && a->U) || epi == NBEST_EPI_DGELU) NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
     NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
              "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
   const int grid = p.tiles_m * p.tiles_n * p.splits;
   int rc;
-  if (!a->trans_a && !a->trans_b) rc = launch_epi<false, false>(p, epi, grid, st);
-  else if (!a->trans_a && a->trans_b) rc = launch_epi<false, true>(p, epi, grid, st);
-  else rc = launch_epi<true, true>(p, epi, grid, st);
+  const int kepi = nb_kernel_epilogue(epi, a->U);
+  if (!a->trans_a && !a->trans_b) rc = launch_epi<false, false>(p, kepi, grid, st);
+  else if (!a->trans_a && a->trans_b) rc = launch_epi<false, true>(p, kepi, grid, st);
+  else rc = launch_epi<true, true>(p, kepi, grid, st);
   if (rc) return rc;
   if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * 2, (int)a->N, a->colsum_out, a->colsum_accumulate, st);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE)) {

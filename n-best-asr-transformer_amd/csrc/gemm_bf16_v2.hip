@@ -283,7 +283,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   constexpr bool kDirect = (!TA && !TB && EPI != NBEST_EPI_F32_SPLITK);
   constexpr int kPW = kDirect ? WTN : 0;
   static_assert(kDirect ? (WTN == 64 || WTN == 96 || WTN == 128) : WTN == 64, "LDS-restaged epilogue assumes 64-column wave tiles");
-  static_assert(TNt != 6 || (EPI != NBEST_EPI_BIAS_GELU && EPI != NBEST_EPI_DGELU), "96-column wave tiles: no GELU epilogues (8-bit rows)");
+  static_assert(TNt != 6 || (EPI != NBEST_EPI_BIAS_GELU && EPI != kEpiBiasGeluNoU && EPI != NBEST_EPI_DGELU), "96-column wave tiles: no GELU epilogues (8-bit rows)");
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
   constexpr int NDMA = (BM * 4 + NT - 1) / NT + (BN * 4 + NT - 1) / NT;   // LDS-DMA instructions per thread and stage
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   const int nkt = (int)(p.K / BK);
 
   // epilogue operands that do not depend on the K loop
-  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES);
+  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == kEpiBiasGeluNoU || EPI == NBEST_EPI_BIAS_DROP_RES);
   constexpr bool kHasR = (EPI == NBEST_EPI_BIAS_DROP_RES || EPI == NBEST_EPI_RES);
   constexpr bool kHasUin = (EPI == NBEST_EPI_DGELU);
   constexpr bool kPre = kHasR || kHasUin;
@@ -773,6 +773,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 #pragma unroll
           for (int j = 0; j < TNt; ++j) v[j] += db[j];
         }
+        if (EPI == kEpiBiasGeluNoU) {
+#pragma unroll
+          for (int j = 0; j < TNt; j += 2) {
+            f32x2 h2, g2;   // gelu(u) only: g2 has no reader and is not computed
+            gelu_pair_fast(f32x2{v[j], v[j + 1]}, h2, g2);
+            v[j] = h2[0]; v[j + 1] = h2[1];
+          }
+        }
         if (EPI == NBEST_EPI_BIAS_GELU) {
           float gp[TNt];
 #pragma unroll
@@ -884,6 +892,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
       if (kHasBias) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { v[e] += pb0[e]; v[4 + e] += pb1[e]; }
+      }
+      if (EPI == kEpiBiasGeluNoU) {
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+          f32x2 h2, g2;   // gelu(u) only
+          gelu_pair_fast(f32x2{v[e], v[e + 1]}, h2, g2);
+          v[e] = h2[0]; v[e + 1] = h2[1];
+        }
       }
       if (EPI == NBEST_EPI_BIAS_GELU) {
         float gp[8];
@@ -1072,7 +1088,7 @@ static int launch2(const GemmP2& p, int epi, int grid, hipStream_t st) {
   } else {
     switch (epi) {
       L(NBEST_EPI_NONE) L(NBEST_EPI_BIAS) L(NBEST_EPI_BIAS_GELU) L(NBEST_EPI_BIAS_DROP_RES) L(NBEST_EPI_DGELU)
-      L(NBEST_EPI_RES)
+      L(NBEST_EPI_RES) L(kEpiBiasGeluNoU)
       default:
         nbest_set_error("gemm: bad epilogue %d", epi);
         return NBEST_ERR_ARG;
@@ -1183,40 +1199,41 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
     NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm: epilogue %d needs bias", epi);
   if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES)
     NB_CHECK(a->R && a->ldr % 8 == 0 && ((uintptr_t)a->R & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs R", epi);
-  if (epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_DGELU)   // U: 8-bit GELU' rows (gd_pack4), ldu in bytes
+  if ((epi == NBEST_EPI_BIAS_GELU && a->U) || epi == NBEST_EPI_DGELU)   // U: 8-bit GELU' rows (gd_pack4), ldu in bytes; BIAS_GELU without U: C only
     NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
     NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
              "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
   const int grid = p.tiles_m * p.tiles_n * p.splits;
+  const int kepi = nb_kernel_epilogue(epi, a->U);   // the plan above was chosen on the public epilogue
   int rc, wave_rows = 2;   // wave rows per tile = partial rows of the fused column sums
   NB_CHECK(a->N % pl.bn == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld is not a multiple of the %d-column tile", (long long)a->N, pl.bn);
   if (pl.bm == 128 && pl.bn == 512) {
-    rc = launch2<128, 512, 2, 4, 4, false, false>(p, epi, grid, st);
+    rc = launch2<128, 512, 2, 4, 4, false, false>(p, kepi, grid, st);
   } else if (pl.bm == 128 && pl.bn == 384) {
-    if (a->K >= 2048) rc = launch2<128, 384, 2, 4, 5, false, false>(p, epi, grid, st);
-    else rc = launch2<128, 384, 2, 4, 4, false, false>(p, epi, grid, st);
+    if (a->K >= 2048) rc = launch2<128, 384, 2, 4, 5, false, false>(p, kepi, grid, st);
+    else rc = launch2<128, 384, 2, 4, 4, false, false>(p, kepi, grid, st);
   } else if (pl.bm == 256 && pl.bn == 192) {
     // ring depth: the operand delivery of these kernels is bound by bytes in flight against the LDS-DMA latency (3 stages of 28-32 KB
     // against ~2 us); a fifth stage (all 160 KB of LDS at 256 x 256) pays at long K - FFN-down forward 162 -> 155 us, FFN-up dgrad 157 ->
     // 154, QKV dgrad 122 -> 120 - and costs 1-2 % at K = 768, where the longer prologue of each tile weighs more (same-call A/B, twice)
-    if (a->K >= 2048) rc = launch2<256, 192, 4, 2, 5, false, false>(p, epi, grid, st);
-    else rc = launch2<256, 192, 4, 2, 4, false, false>(p, epi, grid, st);
+    if (a->K >= 2048) rc = launch2<256, 192, 4, 2, 5, false, false>(p, kepi, grid, st);
+    else rc = launch2<256, 192, 4, 2, 4, false, false>(p, kepi, grid, st);
     wave_rows = 4;
   } else if (pl.bm == 256 && pl.bn == 256) {
     // k-contiguous operands: 4 x 2 waves with 64 x 128 wave tiles (register epilogue: 16-byte stores, whole 128-byte lines)
     if (!a->trans_a && !a->trans_b && epi != NBEST_EPI_F32_SPLITK) {
-      if (a->K >= 2048) rc = launch2<256, 256, 4, 2, 5, false, false>(p, epi, grid, st);
-      else rc = launch2<256, 256, 4, 2, 4, false, false>(p, epi, grid, st);
+      if (a->K >= 2048) rc = launch2<256, 256, 4, 2, 5, false, false>(p, kepi, grid, st);
+      else rc = launch2<256, 256, 4, 2, 4, false, false>(p, kepi, grid, st);
       wave_rows = 4;
     }
-    else if (!a->trans_a && !a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, false>(p, epi, grid, st);
-    else if (!a->trans_a && a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, true>(p, epi, grid, st);
-    else rc = launch2<256, 256, 2, 4, 4, true, true>(p, epi, grid, st);
+    else if (!a->trans_a && !a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, false>(p, kepi, grid, st);
+    else if (!a->trans_a && a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, true>(p, kepi, grid, st);
+    else rc = launch2<256, 256, 2, 4, 4, true, true>(p, kepi, grid, st);
   } else if (pl.bm == 256) {
-    if (!a->trans_b && epi != NBEST_EPI_F32_SPLITK) { rc = launch2<256, 128, 4, 1, 3, false, false>(p, epi, grid, st); wave_rows = 4; }
-    else if (!a->trans_b) rc = launch2<256, 128, 2, 2, 3, false, false>(p, epi, grid, st);
-    else rc = launch2<256, 128, 2, 2, 3, false, true>(p, epi, grid, st);
+    if (!a->trans_b && epi != NBEST_EPI_F32_SPLITK) { rc = launch2<256, 128, 4, 1, 3, false, false>(p, kepi, grid, st); wave_rows = 4; }
+    else if (!a->trans_b) rc = launch2<256, 128, 2, 2, 3, false, false>(p, kepi, grid, st);
+    else rc = launch2<256, 128, 2, 2, 3, false, true>(p, kepi, grid, st);
   } else {   // 128-row tiles narrower than 384 columns run on generation 1 (nbest_gemm_bf16_v2_wins)
     nbest_set_error("gemm(bf16, generation 2): no kernel for the %d x %d plan", pl.bm, pl.bn);
     return NBEST_ERR_SHAPE;

@@ -69,8 +69,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmF p) {
         *c = p.accumulate ? *c + v : v;
         continue;
       }
-      if (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES) v += p.bias[n];
+      if (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == kEpiBiasGeluNoU || EPI == NBEST_EPI_BIAS_DROP_RES) v += p.bias[n];
       if (EPI == NBEST_EPI_BIAS_GELU) { p.U[m * p.ldu + n] = dgelu_f(v); v = gelu_f(v); }
+      if (EPI == kEpiBiasGeluNoU) v = gelu_f(v);
       if (EPI == NBEST_EPI_BIAS_DROP_RES) {
         if (p.drop.thr16) v = nb_keep(p.drop, (uint32_t)(m * p.N + n)) ? v * p.drop.scale : 0.f;
         v += p.R[m * p.ldr + n];
@@ -87,7 +88,7 @@ static int launch_epi(const GemmF& p, int epi, dim3 grid, hipStream_t st) {
 #define L(E) case E: gemm_f32_kernel<TA, TB, E><<<grid, 256, 0, st>>>(p); break;
   switch (epi) {
     L(NBEST_EPI_NONE) L(NBEST_EPI_BIAS) L(NBEST_EPI_BIAS_GELU) L(NBEST_EPI_BIAS_DROP_RES) L(NBEST_EPI_DGELU)
-    L(NBEST_EPI_RES) L(NBEST_EPI_F32_SPLITK)
+    L(NBEST_EPI_RES) L(NBEST_EPI_F32_SPLITK) L(kEpiBiasGeluNoU)
     default:
       nbest_set_error("gemm: bad epilogue %d", epi);
       return NBEST_ERR_ARG;
@@ -110,12 +111,13 @@ int nbest_gemm_f32(const nbest_gemm_args* a, hipStream_t st) {
   if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
     NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm: epilogue %d needs bias", epi);
   if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES) NB_CHECK(a->R, NBEST_ERR_ARG, "gemm: epilogue %d needs R", epi);
-  if (epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_DGELU) NB_CHECK(a->U, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
+  if (epi == NBEST_EPI_DGELU) NB_CHECK(a->U, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);   // BIAS_GELU with a null U: C only
   dim3 grid((unsigned)((a->N + TN - 1) / TN), (unsigned)((a->M + TM - 1) / TM));
-  if (!a->trans_a && !a->trans_b) return launch_epi<false, false>(p, epi, grid, st);
-  if (!a->trans_a && a->trans_b) return launch_epi<false, true>(p, epi, grid, st);
-  if (a->trans_a && a->trans_b) return launch_epi<true, true>(p, epi, grid, st);
-  return launch_epi<true, false>(p, epi, grid, st);
+  const int kepi = nb_kernel_epilogue(epi, a->U);
+  if (!a->trans_a && !a->trans_b) return launch_epi<false, false>(p, kepi, grid, st);
+  if (!a->trans_a && a->trans_b) return launch_epi<false, true>(p, kepi, grid, st);
+  if (a->trans_a && a->trans_b) return launch_epi<true, true>(p, kepi, grid, st);
+  return launch_epi<true, false>(p, kepi, grid, st);
 }
 
 // ---- public dispatcher ----------------------------------------------------------------------------

@@ -24,6 +24,7 @@ EXPORTS = [
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_forward",
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
+    "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
 ]
 
 
@@ -97,7 +98,7 @@ def lib():
                 raise RuntimeError("nbest_amd: %s does not export %s" % (LIB_PATH, name))
         for name in ("nbest_embed_bwd_ws_bytes", "nbest_gemm_ws_bytes", "nbest_wgrad_pair_ws_bytes", "nbest_rowred_ws_bytes", "nbest_heads_ws_bytes",
                      "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes",
-                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes"):
+                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.nbest_embed_bwd_ws_bytes.argtypes = [C.c_int64, C.c_int64]
         L.nbest_rows_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -140,6 +141,9 @@ def lib():
         L.nbest_adam_step.argtypes = [i32] + [vp] * 6 + [i32, i32, f32, f32, f32, f64, f64, f32, f32, vp, sz, vp]
         L.nbest_cast_f32_to_bf16.argtypes = [vp, vp, i64, vp]
         L.nbest_encoder_forward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, sz, C.POINTER(C.c_void_p), vp]
+        L.nbest_encoder_infer_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
+        L.nbest_encoder_infer.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp]
+        L.nbest_attention_cls_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
         L.nbest_encoder_backward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 9 + [sz, vp, vp, sz, i32, i32, i32, i32, vp]
         L.nbest_transpose_weights.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nbest_pack_bn.argtypes = [i64]
@@ -245,13 +249,14 @@ def pack_weight_fp8(W8):
 
 
 def gemm(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=None, R=None, U=None, out=None,
-         accumulate=False, drop_p=0.0, seed=0, drop_stream=0, colsum_out=None, defer_reduce=False, B_packed=None, b_pack_bn=0):
-    """C[M,N] = epi(op(A) . op(B)); returns C (and U for EPI_BIAS_GELU)."""
+         accumulate=False, drop_p=0.0, seed=0, drop_stream=0, colsum_out=None, defer_reduce=False, B_packed=None, b_pack_bn=0,
+         want_u=True):
+    """C[M,N] = epi(op(A) . op(B)); returns C (and U for EPI_BIAS_GELU; ``want_u=False``: C only, no GELU' rows written)."""
     dt = dtype_code(A.dtype)
     dev = A.device
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32 if epilogue == EPI_F32_SPLITK else A.dtype, device=dev)
-    if epilogue == EPI_BIAS_GELU and U is None:        # gelu'(u): float in the fp32 path, 8-bit fixed point in the bf16 path
+    if epilogue == EPI_BIAS_GELU and U is None and want_u:        # gelu'(u): float in the fp32 path, 8-bit fixed point in the bf16 path
         U = torch.empty(M, N, dtype=torch.float32 if A.dtype == torch.float32 else torch.uint8, device=dev)
     g = GemmArgs()
     g.A, g.B, g.C = A.data_ptr(), B.data_ptr(), out.data_ptr()
@@ -272,7 +277,7 @@ def gemm(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=No
     ws = _ws(nb, dev)
     g.ws, g.ws_bytes = ws.data_ptr(), ws.numel()
     check(lib().nbest_gemm(C.byref(g), stream_ptr()), "gemm")
-    return (out, U) if epilogue == EPI_BIAS_GELU else out
+    return (out, U) if epilogue == EPI_BIAS_GELU and want_u else out
 
 
 def wgrad_pair(dY1, X1, dY2, X2, out1=None, out2=None, accumulate=False):
@@ -425,6 +430,15 @@ def attention_fwd(qkv, key_mask, B, S, heads, drop_p=0.0, seed=0, drop_stream=0,
     check(lib().nbest_attention_fwd(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(lse), B, S, heads, 64, dtype_code(qkv.dtype),
                                     drop_p, seed, drop_stream, stream_ptr()), "attention_fwd")
     return ctx, lse
+
+
+def attention_cls_fwd(q, ldq, kv, ldkv, key_mask, B, S, heads, out=None):
+    """nbest_attention_cls_fwd: one query row per (utterance, head) -> ctx [B, heads * 64] (q, kv: element strides ldq / ldkv)"""
+    H = heads * 64
+    ctx = torch.empty(B, H, dtype=kv.dtype, device=kv.device) if out is None else out
+    check(lib().nbest_attention_cls_fwd(ptr(q), ldq, ptr(kv), ldkv, ptr(key_mask), ptr(ctx), ctx.stride(0), B, S, heads, 64,
+                                        dtype_code(kv.dtype), stream_ptr()), "attention_cls_fwd")
+    return ctx
 
 
 def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, dbias=None, keep=None):

@@ -183,6 +183,7 @@ class NBestSTCModel(nn.Module):
         self._ws = None
         self._ws_bytes = 0
         self._dh = None                    # grow-only scratch of the backward's input gradient
+        self._infer_ws = None              # grow-only workspace of predict() (nbest_encoder_infer)
         self._anchor = None                # autograd bridge: a leaf that makes the outputs of forward() require grad
 
     # ---- plumbing ------------------------------------------------------------------------------
@@ -250,16 +251,20 @@ class NBestSTCModel(nn.Module):
         self.arena.load_state(sd, strict=False)
         return missing
 
-    def _pass(self, B, S, slot):
-        """Real data pads every batch to its own longest row, so (B, S) changes almost every step: only the small
-        descriptor is per shape; the activation stash is one buffer per slot (ASR pass / transcript pass) that grows
-        to the largest shape seen and is then reused, like the workspace."""
+    def _desc(self, B, S, slot):
+        """the (cached) descriptor of a pass shape; allocates nothing"""
         key = (B, S, slot)
         if key not in self._passes:
             if len(self._passes) >= 4096:
                 self._passes.clear()
-            self._passes[key] = _Pass(self, B, S, stream_base=1000 * slot)
-        ps = self._passes[key]
+            self._passes[key] = _Pass(self, B, S, stream_base=1000 * slot if isinstance(slot, int) else 0)
+        return self._passes[key]
+
+    def _pass(self, B, S, slot):
+        """Real data pads every batch to its own longest row, so (B, S) changes almost every step: only the small
+        descriptor is per shape; the activation stash is one buffer per slot (ASR pass / transcript pass) that grows
+        to the largest shape seen and is then reused, like the workspace."""
+        ps = self._desc(B, S, slot)
         stash = self._stash.get(slot)
         if stash is None or stash.numel() < ps.act_bytes:
             self._stash[slot] = stash = None          # release before growing: never hold two generations
@@ -279,10 +284,8 @@ class NBestSTCModel(nn.Module):
             rank = torch.distributed.get_rank()
         return self.seed + 7919 * self.step_counter + 15485863 * rank
 
-    def _encode(self, ps, ids, seg, train, perm=None):
-        """one encoder pass through the C-ABI; returns hidden states [B*S, H] (a view into the stash).
-        ``perm``: the pass's tokens sorted by word id (hipabi.word_perm; host-built by the data loaders) - only the backward
-        reads it; None = sorted on the device when a backward pass asks for it."""
+    def _inputs(self, ids, seg):
+        """(ids, seg, pos, key mask) of one pass as the encoder entry points take them"""
         cfg = self.cfg
         ids = ids.contiguous()
         mask = (ids > 0).to(torch.uint8)               # quirk Q1: ids > 0 for EVERY family (models/model.py:43)
@@ -291,6 +294,14 @@ class NBestSTCModel(nn.Module):
             seg = None                                  # models/model.py:42-43: XLM-R never gets token types
         elif seg is not None:
             seg = seg.contiguous()
+        return ids, seg, pos, mask
+
+    def _encode(self, ps, ids, seg, train, perm=None):
+        """one encoder pass through the C-ABI; returns hidden states [B*S, H] (a view into the stash).
+        ``perm``: the pass's tokens sorted by word id (hipabi.word_perm; host-built by the data loaders) - only the backward
+        reads it; None = sorted on the device when a backward pass asks for it."""
+        cfg = self.cfg
+        ids, seg, pos, mask = self._inputs(ids, seg)
         d = ps.desc
         d.hidden_drop = cfg.hidden_dropout_prob if train else 0.0
         d.attn_drop = cfg.attention_probs_dropout_prob if train else 0.0
@@ -473,6 +484,41 @@ class NBestSTCModel(nn.Module):
         self.step_counter += 1
         return dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ha.view(B, S, H)[:, 0, :],
                     trans_cls=None if ht is None else ht.view(B, St, H)[:, 0, :])
+
+    # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
+    def predict(self, input_ids, seg_ids=None):
+        """Scores and decoded labels of one batch through nbest_encoder_infer: no activation stash, no dropout (in either
+        mode), the heads on the compact CLS rows.  Returns dict(top, bott, final, cls [B, H] compute dtype, pred int32 [B, n_top]).
+        Touches no training state: stashes, gradients, optimizer moments, step_counter and the fp8 amax histories stay as they
+        are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it)."""
+        cfg = self.cfg
+        B, S = input_ids.shape
+        H = cfg.hidden_size
+        first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
+        if S > 512 or S + first_pos > cfg.max_position_embeddings:     # refused before anything is enqueued (encoder.hip check_desc)
+            raise RuntimeError("nbest_amd predict: S=%d does not fit the position table (%d rows)" % (S, cfg.max_position_embeddings))
+        ps = self._desc(B, S, "infer")
+        d = ps.desc
+        ids, seg, pos, mask = self._inputs(input_ids, seg_ids)
+        d.hidden_drop = d.attn_drop = 0.0
+        d.seed = 0
+        d.w8 = d.w8_inv_scale = d.w8t = d.w8p = d.w8tp = None
+        d.aamax_prev = d.aamax_new = d.gamax_prev = d.gamax_new = None
+        d.fp8_act = d.fp8_bwd = 0
+        a = self.arena
+        d.wpk = a.wpk.data_ptr() if (getattr(a, "wpk", None) is not None and not a.w16t_stale) else None
+        need = hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d))
+        if self._infer_ws is None or self._infer_ws.numel() < need:
+            self._infer_ws = None
+            self._infer_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        cls = torch.empty(B, H, dtype=self.compute_dtype, device=self.device)
+        hb.check(hb.lib().nbest_encoder_infer(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos),
+                                              hb.ptr(mask), hb.ptr(self._infer_ws), self._infer_ws.numel(), hb.ptr(cls),
+                                              hb.stream_ptr()), "encoder_infer")
+        Wh, bh = a.heads_wb()
+        labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
+        top, bott, fin, _, _, _, _ = hb.stc_heads(cls, H, Wh, bh, self.dls, labels_f, B, H, need_grad=False, drop_p=0.0)
+        return dict(top=top, bott=bott, final=fin, cls=cls, pred=self.decode(top, bott))
 
     def decode(self, top, bott, out=None):
         """device decode of pred_one_sample -> int32 [B, n_top] bottom-label index or -1 (``out``: see hipabi.stc_decode)"""

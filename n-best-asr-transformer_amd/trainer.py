@@ -301,6 +301,23 @@ def read_wcn_data(fn, coverage=None):
     return asr, trans, labels
 
 
+def read_predict_data(fn):
+    """--predict input: the split format, but only the ASR field is required.  A line holds ``ASR`` alone or
+    ``ASR \t<=>\t TRANSCRIPT \t<=>\t labels`` (transcript and labels are read and not used).  Returns (asr, trans, labels)
+    like read_wcn_data, one entry per line in file order; a missing transcript is the ASR field, missing labels are []."""
+    asr, trans, labels = [], [], []
+    with open(fn) as fp:
+        for n, line in enumerate(fp, 1):
+            f = line.strip("\n\r").split("\t<=>\t")
+            if len(f) not in (1, 3):
+                raise ValueError("%s:%d: expected 1 or 3 fields separated by '\\t<=>\\t', got %d" % (fn, n, len(f)))
+            a = f[0].strip().split(" ")
+            asr.append(a)
+            trans.append(f[1].strip().split(" ") if len(f) == 3 else list(a))
+            labels.append(f[2].strip().split(";") if len(f) == 3 and f[2].strip() else [])
+    return asr, trans, labels
+
+
 def labels_to_multihot(label_lists, label2idx, device, unk=1):
     y = torch.zeros(len(label_lists), len(label2idx))
     for i, ls in enumerate(label_lists):
@@ -719,6 +736,27 @@ def eval_epoch(model, data, opt, memory, fp=None, efp=None):
         if efp is not None and set(pc) != set(gold):
             efp.write(line)
     return _finish(losses, counts, model.device, len(lists)) + (cases,)
+
+
+@torch.no_grad()
+def predict_split(model, data, opt, memory):
+    """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
+    [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
+    ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only."""
+    _, world = dist_info()
+    if world > 1:
+        raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
+    onto = getattr(opt, "ontology", None)
+    pipe = MetricsPipe(model, memory["idx2label"], onto)
+    split = encoded(data, opt, memory)
+    n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
+    lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
+    for bi, mine, b in Prefetcher(split, lists, model.device):
+        seg = b["seg"] if opt.add_segment_ids else None
+        out = model.predict(b["ids"], seg_ids=seg)
+        pipe.push(out, [split.labels[j] for j in mine], tag=mine)
+    _, tagged = pipe.finish()
+    return [(split.asr[j], pc) for mine, preds in tagged for j, pc in zip(mine, preds)]
 
 
 def _finish(losses, counts, device, n_batches=None):
