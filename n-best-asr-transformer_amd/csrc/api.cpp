@@ -3,7 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/nbest_hip.h"
+#include "internal.h"
 
 static thread_local char g_err[512] = "";
 

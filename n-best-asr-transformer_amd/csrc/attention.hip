@@ -1409,8 +1409,6 @@ extern "C" int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* k
   return nbest_attention_cls_fwd_internal(q, ldq, kv, ldkv, key_mask, ctx, ldctx, B, S, heads, d, dtype, stream);
 }
 
-int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
-
 extern "C" size_t nbest_attention_bwd_ws_bytes(int B, int S, int heads) {
   const size_t a = (size_t)B * 3 * heads * 64 * sizeof(float);
   const size_t b = nbest_rowred_ws_bytes((int64_t)B * S, (int64_t)3 * heads * 64);

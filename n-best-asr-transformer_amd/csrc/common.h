@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "../../include/nbest_hip.h"
+#include "internal.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
@@ -19,7 +20,6 @@ typedef __attribute__((ext_vector_type(2))) int i32x2;
 #define LDS_PTR(p) ((void __attribute__((address_space(3)))*)(p))
 
 // ---- error plumbing (host) -------------------------------------------------------------------
-void nbest_set_error(const char* fmt, ...);
 #define NB_CHECK(cond, code, ...)            \
   do {                                       \
     if (!(cond)) {                           \
@@ -111,6 +111,12 @@ __device__ __forceinline__ void nb_tile_coords(int t, int tiles_m, int gn, int& 
   const int g = t / per_group, r = t - g * per_group;
   tm = r / gn;
   tn = g * gn + (r - tm * gn);
+}
+// Workgroup id -> tile id such that consecutive tile ids run on one XCD (one L2): the dispatcher deals workgroups round-robin
+// over the 8 XCDs, and this bijection hands XCD x the x-th contiguous block of ids.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 // host: the largest divisor of tiles_n whose weight slice (cols_per_tile * K * elem_bytes each) stays under `limit_kb`.  Measured
 // on the step (same-box A/B): bf16 - halves of the 4.7 MB FFN matrices and thirds of the 3.5 MB QKV matrix pay (limit 2400),

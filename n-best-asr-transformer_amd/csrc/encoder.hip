@@ -12,26 +12,6 @@
 //              column-reduction partials, split-K slabs, embedding-backward buffer.
 #include "common.h"
 
-int nbest_internal_layernorm_fwd8(const void* x, const float* gamma, const float* beta, void* y, void* y8, float* stats,
-                                  int64_t M, int H, float eps, int dtype, nbest_stream_t stream, const uint32_t* a_prev, uint32_t* a_new);
-int nbest_internal_cast_bf16_to_fp8(const void* src, void* dst, int64_t n, const uint32_t* a_prev, uint32_t* a_new, hipStream_t st);
-int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
-                                  void* dx_drop, float* dgamma, float* dbeta, float* dbias, int64_t M, int H, int dtype,
-                                  int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream, void* ws,
-                                  size_t ws_bytes, nbest_stream_t stream, Fp8Grad f8);
-int nbest_internal_attention_bwd8(const void* qkv, const uint8_t* key_mask, const void* ctx, const void* dctx, const float* lse,
-                                  void* dqkv, float* dbias, int accumulate, void* ws, size_t ws_bytes, int B, int S, int heads,
-                                  int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, nbest_stream_t stream, Fp8Grad f8,
-                                  const uint32_t* keep);
-size_t nbest_internal_attention_keep_bytes(int B, int S, int heads);
-int nbest_internal_amax_bf16(const void* x, int64_t n, uint32_t* out, hipStream_t st);
-void nbest_internal_rowred_batch_begin();
-void nbest_internal_rowred_batch_abort();
-int nbest_internal_rowred_batch_flush(hipStream_t st);
-int nbest_internal_attention_fwd8(const void* qkv, const uint8_t* key_mask, void* ctx, void* ctx8, float* lse, int B, int S, int heads,
-                                  int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, nbest_stream_t stream, uint32_t* keep,
-                                  const uint32_t* a_prev, uint32_t* a_new);
-
 namespace {
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -500,9 +480,6 @@ static InferLayout infer_layout(const nbest_encoder_desc* d) {
   return w;
 }
 }  // namespace
-
-int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
-                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 
 extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(d).total : 0; }
 

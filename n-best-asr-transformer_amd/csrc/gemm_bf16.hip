@@ -35,11 +35,6 @@ struct GemmP {
   int gn;             // tile columns per L2 group (common.h nb_tile_coords)
 };
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 // ---- staging: one operand tile, 4 LDS-DMA instructions per thread -------------------------------
 template <bool TR>
 __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rs, char* lds_tile, int64_t row0, int64_t k0, int64_t ld,
@@ -301,38 +296,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmP p) {
   }
 }
 
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, float* __restrict__ C, int64_t MN,
-                                                            int64_t N, int64_t ldc, int splits, int accumulate) {
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < MN; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    f32x4 s = *(const f32x4*)(slab + i);
-    for (int z = 1; z < splits; ++z) s += *(const f32x4*)(slab + (int64_t)z * MN + i);
-    const int64_t m = i / N, n = i - m * N;
-    float* c = C + m * ldc + n;
-    if (accumulate) s += *(const f32x4*)c;
-    *(f32x4*)c = s;
-  }
-}
-
-static int choose_splits(const nbest_gemm_args* a, int64_t* kps) {
-  const int64_t tiles = ((a->M + BM - 1) / BM) * (a->N / BN);
-  int64_t splits = 1;
-  if (a->epilogue == NBEST_EPI_F32_SPLITK) {
-    // the chip runs 512 workgroups at a time (2 per CU): pick the smallest split count whose grid
-    // fills whole rounds (>= 93 %), so no round runs half empty; each split keeps K >= 512
-    const int64_t maxs = (a->K / 512 < 1) ? 1 : ((a->K / 512 > 32) ? 32 : a->K / 512);
-    double best = -1.0;
-    for (int64_t s = 1; s <= maxs; ++s) {
-      const int64_t blocks = tiles * s;
-      const double eff = (double)blocks / (double)(((blocks + 511) / 512) * 512);
-      if (eff > best + 1e-9) { best = eff; splits = s; }
-      if (blocks >= 400 && eff >= 0.93) { splits = s; break; }
-    }
-  }
-  int64_t k = (a->K + splits - 1) / splits;
-  k = (k + BK - 1) / BK * BK;
-  splits = (a->K + k - 1) / k;
-  *kps = k;
-  return (int)splits;
+// split-K plan: the chip runs 512 workgroups at a time (2 per CU); each split keeps K >= 512 (nb_splitk_plan)
+static void plan_splits(const nbest_gemm_args* a, int* splits, int64_t* kps) {
+  *splits = 1;
+  *kps = round_up(a->K, BK);
+  if (a->epilogue == NBEST_EPI_F32_SPLITK) nb_splitk_plan(((a->M + BM - 1) / BM) * (a->N / BN), a->K, 512, 400, splits, kps);
 }
 
 template <bool TA, bool TB>
@@ -356,29 +324,23 @@ static int launch_epi(const GemmP& p, int epi, int grid, hipStream_t st) {
 
 }  // namespace
 
-int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
-
 size_t nbest_gemm_bf16_ws_bytes(const nbest_gemm_args* a) {
   if (a->epilogue != NBEST_EPI_F32_SPLITK) return a->colsum_out ? (size_t)((a->M + BM - 1) / BM) * 2 * a->N * sizeof(float) : 0;
+  int splits;
   int64_t kps;
-  const int splits = choose_splits(a, &kps);
+  plan_splits(a, &splits, &kps);
   return splits > 1 ? (size_t)splits * a->M * a->N * sizeof(float) : 0;
 }
 
 int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   NB_CHECK(a->N % BN == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld must be a multiple of %d", (long long)a->N, BN);
   NB_CHECK(a->trans_a || a->K % BK == 0, NBEST_ERR_SHAPE, "gemm(bf16): K=%lld must be a multiple of %d", (long long)a->K, BK);
-  NB_CHECK(!(a->trans_a && !a->trans_b), NBEST_ERR_ARG, "gemm(bf16): trans_a without trans_b is not built");
-  NB_CHECK(!a->trans_a || a->M % BM == 0, NBEST_ERR_SHAPE, "gemm(bf16): trans_a needs M %% 128 == 0");
-  NB_CHECK(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 8 == 0, NBEST_ERR_ALIGN, "gemm(bf16): leading dimensions must be multiples of 8");
-  NB_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0, NBEST_ERR_ALIGN,
-           "gemm(bf16): pointers must be 16-byte aligned");
   GemmP p;
   p.A = (const bf16*)a->A; p.B = (const bf16*)a->B; p.C = a->C; p.bias = a->bias; p.R = (const bf16*)a->R; p.U = (bf16*)a->U;
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldu = a->ldu;
   p.tiles_m = (int)((a->M + BM - 1) / BM);
   p.tiles_n = (int)(a->N / BN);
-  p.splits = choose_splits(a, &p.k_per_split);
+  plan_splits(a, &p.splits, &p.k_per_split);
   p.accumulate = a->accumulate;
   p.slab = (float*)a->ws;
   p.colpart = nullptr;
@@ -389,18 +351,11 @@ int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   const int64_t a_rows = a->trans_a ? a->K : a->M, a_cols = a->trans_a ? a->M : a->K;
   const int64_t b_rows = a->trans_b ? a->K : a->N, b_cols = a->trans_b ? a->N : a->K;
   const int64_t ab = ((a_rows - 1) * a->lda + a_cols) * 2, bb = ((b_rows - 1) * a->ldb + b_cols) * 2;
-  NB_CHECK(ab < ((int64_t)1 << 32) && bb < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm(bf16): operand larger than 4 GiB");
   p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
   p.stream_out = 1;   // every output is streamed (common.h st_stream)
   p.gn = (int)(a->N / BN);      // row-major tile order (column groups measured neutral to negative on the N = 768 shapes this kernel serves)
-  NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm(bf16): dropout counter overflow");
   const int epi = a->epilogue;
-  if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
-    NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm: epilogue %d needs bias", epi);
-  if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES) NB_CHECK(a->R && a->ldr % 8 == 0 && ((uintptr_t)a->R & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs R", epi);
-  // BIAS_GELU with a null U: C only (kEpiBiasGeluNoU)
-  if ((epi == NBEST_EPI_BIAS_GELU && a->U) || epi == NBEST_EPI_DGELU) NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
     NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
              "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
@@ -412,12 +367,7 @@ int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   else rc = launch_epi<true, true>(p, kepi, grid, st);
   if (rc) return rc;
   if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * 2, (int)a->N, a->colsum_out, a->colsum_accumulate, st);
-  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE)) {
-    const int64_t MN = a->M * a->N;
-    int64_t g = (MN / 4 + 255) / 256;
-    if (g > 2048) g = 2048;
-    splitk_reduce_kernel<<<(int)g, 256, 0, st>>>(p.slab, (float*)a->C, MN, a->N, a->ldc, p.splits, a->accumulate);
-    NB_LAUNCH_CHECK();
-  }
+  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE))
+    return nbest_internal_splitk_reduce(p.slab, (float*)a->C, a->M, a->N, a->ldc, p.splits, a->accumulate, nullptr, a->M, 0, st);
   return NBEST_OK;
 }

@@ -52,11 +52,6 @@ struct GemmP2 {
   int bp_bn;          // tile width B was packed for (nbest_pack_bn): the kernel's BN, or BN / 2 (a 384-column tile reads two 192-column blocks)
 };
 
-__device__ __forceinline__ int xcd_remap2(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 // one operand tile: ROWS x 32 bf16 = ROWS*4 16-byte chunks, 256 threads -> ROWS/64 DMA instructions per thread
 // PW > 0 (k-contiguous B operand of the register-epilogue kernels): within every block of PW rows, LDS row 16 j + c is fetched
 // from operand row (PW / 16) * c + j.
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   const int wm = wave / WN, wn = wave % WN;
 
   const int nwg = gridDim.x;
-  const int id = xcd_remap2(blockIdx.x, nwg);
+  const int id = xcd_remap(blockIdx.x, nwg);
   const int tiles = p.tiles_m * p.tiles_n;
   const int z = id / tiles, t = id - z * tiles;
   int tile_m, tile_n;
@@ -954,20 +949,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   }
 }
 
-// rows >= m_split of the slabs' [M][N] image belong to the second output of a weight-gradient pair (C2, ldc2); m_split = M: none
-__global__ __launch_bounds__(256) void splitk_reduce2_kernel(const float* __restrict__ slab, float* __restrict__ C, int64_t MN,
-                                                             int64_t N, int64_t ldc, int splits, int accumulate,
-                                                             float* __restrict__ C2, int64_t m_split, int64_t ldc2) {
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < MN; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    f32x4 s = *(const f32x4*)(slab + i);
-    for (int z = 1; z < splits; ++z) s += *(const f32x4*)(slab + (int64_t)z * MN + i);
-    const int64_t m = i / N, n = i - m * N;
-    float* c = (m < m_split) ? C + m * ldc + n : C2 + (m - m_split) * ldc2 + n;
-    if (accumulate) s += *(const f32x4*)c;
-    *(f32x4*)c = s;
-  }
-}
-
 // B operand (a weight matrix [N][K], k-contiguous) -> the order the 256 x bn ping-pong kernel stages it: for every tile column and
 // K stage the bn x 32 LDS image (chunk swizzle and the register epilogue's row permutation applied), contiguous.  LDS-DMA with
 // 64-byte row segments delivers 22 B/clk/CU, contiguous 47 (tools/micro/dma_rate.hip); with MFMAs removed the k-contiguous GEMMs
@@ -1044,21 +1025,9 @@ static Plan make_plan(const nbest_gemm_args* a) {
   }
   const int64_t tiles = ((a->M + pl.bm - 1) / pl.bm) * (a->N / pl.bn);
   const int64_t slots = (pl.bn >= 192) ? 256 : 512;   // workgroups resident at once
-  int64_t splits = 1;
-  if (a->epilogue == NBEST_EPI_F32_SPLITK) {
-    const int64_t maxs = (a->K / 512 < 1) ? 1 : ((a->K / 512 > 32) ? 32 : a->K / 512);
-    double best = -1.0;
-    for (int64_t sp = 1; sp <= maxs; ++sp) {
-      const int64_t blocks = tiles * sp;
-      const double eff = (double)blocks / (double)(((blocks + slots - 1) / slots) * slots);
-      if (eff > best + 1e-9) { best = eff; splits = sp; }
-      if (blocks * 5 >= slots * 4 && eff >= 0.93) { splits = sp; break; }
-    }
-  }
-  int64_t k = (a->K + splits - 1) / splits;
-  k = (k + 63) / 64 * 64;
-  pl.splits = (int)((a->K + k - 1) / k);
-  pl.kps = k;
+  pl.splits = 1;
+  pl.kps = round_up(a->K, 64);
+  if (a->epilogue == NBEST_EPI_F32_SPLITK) nb_splitk_plan(tiles, a->K, slots, (4 * slots + 4) / 5, &pl.splits, &pl.kps);
   return pl;
 }
 
@@ -1110,8 +1079,6 @@ bool nbest_gemm_bf16_v2_wins(const nbest_gemm_args* a) {
   return pl.bm == 256 || (pl.bm == 128 && pl.bn >= 384);
 }   // 256x128 ring or 256x256 ping-pong
 
-int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
-
 size_t nbest_gemm_bf16_v2_ws_bytes(const nbest_gemm_args* a) {
   if (a->epilogue != NBEST_EPI_F32_SPLITK) {
     if (!a->colsum_out) return 0;
@@ -1127,11 +1094,6 @@ size_t nbest_gemm_bf16_v2_ws_bytes(const nbest_gemm_args* a) {
 static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int64_t m_split, hipStream_t st) {
   NB_CHECK(a->N % 64 == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld must be a multiple of 64", (long long)a->N);
   NB_CHECK(a->trans_a || a->K % BK == 0, NBEST_ERR_SHAPE, "gemm(bf16): K=%lld must be a multiple of %d", (long long)a->K, BK);
-  NB_CHECK(!(a->trans_a && !a->trans_b), NBEST_ERR_ARG, "gemm(bf16): trans_a without trans_b is not built");
-  NB_CHECK(!a->trans_a || a->M % 128 == 0, NBEST_ERR_SHAPE, "gemm(bf16): trans_a needs M %% 128 == 0");
-  NB_CHECK(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 8 == 0, NBEST_ERR_ALIGN, "gemm(bf16): leading dimensions must be multiples of 8");
-  NB_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0, NBEST_ERR_ALIGN,
-           "gemm(bf16): pointers must be 16-byte aligned");
   const Plan pl = make_plan(a);
   GemmP2 p;
   p.A = (const bf16*)a->A; p.B = (const bf16*)a->B; p.C = a->C; p.bias = a->bias; p.R = (const bf16*)a->R; p.U = (bf16*)a->U;
@@ -1161,11 +1123,9 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
   const int64_t a_rows = a->trans_a ? a->K : a->M, a_cols = a->trans_a ? (b2 ? m_split : a->M) : a->K;
   const int64_t b_rows = a->trans_b ? a->K : a->N, b_cols = a->trans_b ? a->N : a->K;
   const int64_t ab = ((a_rows - 1) * a->lda + a_cols) * 2, bb = ((b_rows - 1) * a->ldb + b_cols) * 2;
-  NB_CHECK(ab < ((int64_t)1 << 32) && bb < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm(bf16): operand larger than 4 GiB");
   p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
   if (b2) {
     const int64_t ab2 = ((a->K - 1) * b2->lda + b2->M) * 2, bb2 = ((a->K - 1) * b2->ldb + a->N) * 2;
-    NB_CHECK(ab2 < ((int64_t)1 << 32) && bb2 < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm(bf16): operand larger than 4 GiB");
     p.A2 = (const bf16*)b2->A; p.B2 = (const bf16*)b2->B; p.lda2 = b2->lda; p.ldb2 = b2->ldb; p.m_split = m_split;
     p.a2_bytes = (uint32_t)ab2; p.b2_bytes = (uint32_t)bb2;
     NB_CHECK(pl.bm == 256 && pl.bn == 256 && pl.splits > 1 && m_split % 256 == 0, NBEST_ERR_SHAPE, "wgrad pair: not a 256 x 256 split-K plan");
@@ -1193,14 +1153,7 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
   // in step and only a few stages of them are live at a time.  Same call: the five N = 768 GEMMs of a layer 587 / 600 -> 570 / 576 us cold,
   // the step 21.02 / 21.01 -> 20.86 / 20.85 ms.
   if (pl.bm == 128 && pl.bn >= 384 && (a->N / pl.bn) % 2 == 0) p.gn = 2;
-  NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm(bf16): dropout counter overflow");
   const int epi = a->epilogue;
-  if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
-    NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm: epilogue %d needs bias", epi);
-  if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES)
-    NB_CHECK(a->R && a->ldr % 8 == 0 && ((uintptr_t)a->R & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs R", epi);
-  if ((epi == NBEST_EPI_BIAS_GELU && a->U) || epi == NBEST_EPI_DGELU)   // U: 8-bit GELU' rows (gd_pack4), ldu in bytes; BIAS_GELU without U: C only
-    NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 15) == 0, NBEST_ERR_ARG, "gemm: epilogue %d needs U", epi);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
     NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
              "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
@@ -1240,14 +1193,9 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
   }
   if (rc) return rc;
   if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * wave_rows, (int)a->N, a->colsum_out, a->colsum_accumulate, st);
-  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE)) {
-    const int64_t MN = a->M * a->N;
-    int64_t g = (MN / 4 + 255) / 256;
-    if (g > 2048) g = 2048;
-    splitk_reduce2_kernel<<<(int)g, 256, 0, st>>>(p.slab, (float*)a->C, MN, a->N, a->ldc, p.splits, a->accumulate,
-                                                  b2 ? (float*)b2->C : nullptr, b2 ? m_split : a->M, b2 ? b2->ldc : 0);
-    NB_LAUNCH_CHECK();
-  }
+  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE))
+    return nbest_internal_splitk_reduce(p.slab, (float*)a->C, a->M, a->N, a->ldc, p.splits, a->accumulate, b2 ? (float*)b2->C : nullptr,
+                                        b2 ? m_split : a->M, b2 ? b2->ldc : 0, st);
   return NBEST_OK;
 }
 
@@ -1276,8 +1224,6 @@ size_t nbest_wgrad_pair_bf16_ws_bytes(const nbest_gemm_args* a, const nbest_gemm
 int nbest_wgrad_pair_bf16(const nbest_gemm_args* a, const nbest_gemm_args* b, hipStream_t st) {
   nbest_gemm_args v;
   NB_CHECK(pair_virtual(a, b, &v), NBEST_ERR_SHAPE, "wgrad pair: the two problems do not share one 256 x 256 split-K launch");
-  NB_CHECK(b->lda % 8 == 0 && b->ldb % 8 == 0 && b->ldc % 8 == 0 && ((uintptr_t)b->A & 15) == 0 && ((uintptr_t)b->B & 15) == 0 &&
-               ((uintptr_t)b->C & 15) == 0, NBEST_ERR_ALIGN, "wgrad pair: second problem misaligned");
   return gemm_v2_impl(&v, b, a->M, st);
 }
 

@@ -44,11 +44,6 @@ struct GemmP8 {
   uint32_t bp_bytes;
 };
 
-__device__ __forceinline__ int xcd_remap8(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 // one operand tile: ROWS rows x 64 bytes = 4 ROWS 16-byte chunks, NT threads -> 4 ROWS / NT LDS-DMA instructions per thread
 template <int ROWS = 256, int NT = 512>
 __device__ __forceinline__ void stage_tile8(__amdgpu_buffer_rsrc_t rs, char* tile, int64_t row0, int64_t k0, int64_t ld, int tid) {
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
   constexpr int NDMA = (BM + BN) * 4 / NT;                          // LDS-DMA instructions per thread and stage
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int id = xcd_remap8(blockIdx.x, gridDim.x);
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
   int tile_m, tile_n;
   nb_tile_coords(id, p.tiles_m, p.gn, tile_m, tile_n);
   const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
@@ -495,6 +490,8 @@ struct GemmP8T {
   const uint32_t* a_amax2;
   const uint32_t* b_amax2;
 };
+// split-K plan (nb_splitk_plan): one workgroup per CU, so 256 resident at once; stop at 4/5 of them
+constexpr int64_t kSlots8T = 256, kMinBlocks8T = (4 * kSlots8T + 4) / 5;
 
 __device__ __forceinline__ void stage_tile8t(__amdgpu_buffer_rsrc_t rs, char* tile, int64_t f0, int64_t k0, int64_t ld, int tid) {
   const int wave = tid >> 6;
@@ -558,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void gemm8tt_kernel(GemmP8T p) {
   constexpr int NDMA = 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int id = xcd_remap8(blockIdx.x, gridDim.x);
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int tiles = p.tiles_m * p.tiles_n;
   const int z = id / tiles, t = id - z * tiles;
   const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
@@ -750,36 +747,6 @@ __global__ __launch_bounds__(512, 2) void gemm8tt_kernel(GemmP8T p) {
   }
 }
 
-__global__ __launch_bounds__(256) void splitk_reduce8_kernel(const float* __restrict__ slab, float* __restrict__ C, int64_t MN,
-                                                             int64_t N, int64_t ldc, int splits, int accumulate,
-                                                             float* __restrict__ C2, int64_t m_split, int64_t ldc2) {
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < MN; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    f32x4 s = *(const f32x4*)(slab + i);
-    for (int z = 1; z < splits; ++z) s += *(const f32x4*)(slab + (int64_t)z * MN + i);
-    const int64_t m = i / N, n = i - m * N;
-    float* c = (m < m_split) ? C + m * ldc + n : C2 + (m - m_split) * ldc2 + n;   // rows >= m_split: the second output of a pair
-    if (accumulate) s += *(const f32x4*)c;
-    *(f32x4*)c = s;
-  }
-}
-
-static void plan8tt(int64_t M, int64_t N, int64_t K, int* splits, int64_t* kps) {
-  const int64_t tiles = (M / 256) * (N / 256);
-  const int64_t maxs = (K / 512 < 1) ? 1 : ((K / 512 > 32) ? 32 : K / 512);
-  int64_t best_s = 1;
-  double best = -1.0;
-  for (int64_t sp = 1; sp <= maxs; ++sp) {
-    const int64_t blocks = tiles * sp;
-    const double eff = (double)blocks / (double)(((blocks + 255) / 256) * 256);
-    if (eff > best + 1e-9) { best = eff; best_s = sp; }
-    if (blocks * 5 >= 256 * 4 && eff >= 0.93) { best_s = sp; break; }
-  }
-  int64_t k = (K + best_s - 1) / best_s;
-  k = (k + 63) / 64 * 64;
-  *splits = (int)((K + k - 1) / k);
-  *kps = k;
-}
-
 __global__ __launch_bounds__(256) void amax_bf16_kernel(const bf16* __restrict__ x, int64_t n, uint32_t* __restrict__ out) {
   float mx = 0.f;
   for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * 2048) {
@@ -826,7 +793,7 @@ extern "C" int nbest_fp8_amax_fold(void* slots, void* out, int32_t n_tensors, vo
 
 extern "C" size_t nbest_wgrad_fp8_ws_bytes(int64_t M, int64_t N, int64_t K) {
   int sp; int64_t kps;
-  plan8tt(M, N, K, &sp, &kps);
+  nb_splitk_plan((M / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &sp, &kps);
   return sp > 1 ? (size_t)sp * M * N * sizeof(float) : 0;
 }
 
@@ -840,7 +807,7 @@ static int wgrad_fp8_impl(const void* dY8, const void* X8, float* dW, int64_t M,
   GemmP8T p;
   p.A = (const uint8_t*)dY8; p.B = (const uint8_t*)X8; p.C = dW; p.slab = (float*)ws;
   p.M = Mv; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  plan8tt(Mv, N, K, &p.splits, &p.k_per_split);
+  nb_splitk_plan((Mv / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &p.splits, &p.k_per_split);
   p.tiles_m = (int)(Mv / 256); p.tiles_n = (int)(N / 256);
   p.accumulate = accumulate;
   const int64_t ab = (K - 1) * lda + M, bb = (K - 1) * ldb + N;
@@ -860,13 +827,7 @@ static int wgrad_fp8_impl(const void* dY8, const void* X8, float* dW, int64_t M,
   (void)hipFuncSetAttribute((const void*)gemm8tt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   gemm8tt_kernel<<<p.tiles_m * p.tiles_n * p.splits, 512, lds_bytes, st>>>(p);
   NB_LAUNCH_CHECK();
-  if (p.splits > 1) {
-    const int64_t MN = Mv * N;
-    int64_t g = (MN / 4 + 255) / 256;
-    if (g > 2048) g = 2048;
-    splitk_reduce8_kernel<<<(int)g, 256, 0, st>>>(p.slab, dW, MN, N, ldc, p.splits, accumulate, dWb, Mb > 0 ? M : Mv, ldcb);
-    NB_LAUNCH_CHECK();
-  }
+  if (p.splits > 1) return nbest_internal_splitk_reduce(p.slab, dW, Mv, N, ldc, p.splits, accumulate, dWb, Mb > 0 ? M : Mv, ldcb, st);
   return NBEST_OK;
 }
 
@@ -886,7 +847,7 @@ extern "C" int nbest_wgrad_fp8(const void* dY8, const void* X8, float* dW, int64
 extern "C" size_t nbest_wgrad_fp8_pair_ws_bytes(int64_t Ma, int64_t Mb, int64_t N, int64_t K) {
   if (Ma <= 0 || Mb <= 0 || Ma % 256 || Mb % 256 || N % 256) return 0;
   int sp; int64_t kps;
-  plan8tt(Ma + Mb, N, K, &sp, &kps);
+  nb_splitk_plan(((Ma + Mb) / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &sp, &kps);
   return sp > 1 ? (size_t)sp * (Ma + Mb) * N * sizeof(float) : 0;
 }
 extern "C" int nbest_wgrad_fp8_pair(const void* dY8a, const void* X8a, float* dWa, int64_t Ma, int64_t lda_a, int64_t ldb_a, int64_t ldc_a,
@@ -944,8 +905,6 @@ extern "C" int nbest_quantize_weights_fp8(const float* master, void* w8, void* w
   }
   return NBEST_OK;
 }
-
-int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
 
 extern "C" size_t nbest_gemm_fp8_ws_bytes(const nbest_gemm_fp8_args* a) {
   return (a && a->colsum_out) ? (size_t)((a->M + 255) / 256) * 2 * a->N * sizeof(float) : 0;

@@ -33,6 +33,27 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(hipabi.TensorDesc) == 32 and ctypes.sizeof(hipabi.LayerOffsets) == 96
 
 
+def test_split_k_plans_are_pinned():
+    """The weight-gradient workspace queries are host-only and size one fp32 slab per K-split: pin the split counts of the
+    bert-base / xlm-roberta-large shapes and of shapes near the planner's stops, for every GEMM family that splits K."""
+    L = hipabi.lib()
+
+    def wgrad(M, N, K):
+        a = hipabi.GemmArgs()
+        a.M, a.N, a.K, a.trans_a, a.trans_b, a.epilogue, a.dtype = M, N, K, 1, 1, hipabi.EPI_F32_SPLITK, hipabi.BF16
+        return a
+
+    f4 = 4   # bytes per slab element
+    for M, N, K, bf16_splits, fp8_splits in ((768, 768, 32768, 14, 27), (2304, 768, 32768, 9, 9), (3072, 768, 32768, 7, 7),
+                                             (768, 3072, 32768, 7, 7), (1024, 1024, 65536, 8, 15), (768, 768, 4096, 8, 8),
+                                             (1280, 1280, 32768, 10, 10), (2560, 2560, 16384, 5, 5), (768, 768, 16384, 14, 26)):
+        assert L.nbest_gemm_ws_bytes(ctypes.byref(wgrad(M, N, K))) == bf16_splits * M * N * f4, (M, N, K)
+        assert L.nbest_wgrad_fp8_ws_bytes(M, N, K) == fp8_splits * M * N * f4, (M, N, K)
+    for Ma, Mb, N, K, splits in ((2304, 768, 768, 32768, 7), (2304, 768, 768, 8192, 7), (3072, 1024, 1024, 65536, 4)):
+        assert L.nbest_wgrad_pair_ws_bytes(ctypes.byref(wgrad(Ma, N, K)), ctypes.byref(wgrad(Mb, N, K))) == splits * (Ma + Mb) * N * f4
+        assert L.nbest_wgrad_fp8_pair_ws_bytes(Ma, Mb, N, K) == splits * (Ma + Mb) * N * f4
+
+
 def test_no_cpu_fallback_in_product_package():
     """nothing under the product package may import the oracle"""
     pkg = os.path.join(ROOT, "n-best-asr-transformer_amd")

@@ -68,7 +68,7 @@ KERNELS = [
     ("bertadam_kernel", 373248, "BertAdam, embedding tables (23.8 M parameters)", None, 23.8e6 * 30 / 1e6),
     ("sumsq_kernel", 1374208, "per-tensor gradient norms (clip)", None, 85.6e6 * 4 / 1e6),
     ("splitk_reduce2_kernel", None, "split-K reduce of a weight gradient", None, None),
-    ("splitk_reduce_kernel", None, "split-K reduce (768x768)", None, None),
+    ("splitk_reduce_kernel", None, "split-K reduce of a weight gradient", None, None),
     ("pack_b_kernel", None, "weight matrices packed for the k-contiguous GEMMs (forward copy, dgrad copy)", None, 85e6 * 4 / 1e6),
     ("transpose_multi_kernel", None, "k-contiguous bf16 weight copy for the dgrads", None, 85e6 * 4 / 1e6),
     ("embed_bwd_tables_kernel", None, "embedding backward: position / type tables, LN parameters (folded into embed_bwd_kernel in round 3)", None, None),
