@@ -12,9 +12,9 @@ Training does not go through torch autograd: ``forward_backward`` enqueues the w
 (2 encoder passes when --add_l2_loss, heads + losses, backward) through the C-ABI and leaves the
 gradients in the flat arena ``arena.g`` (also visible as ``param.grad`` views).
 """
+import collections
 import ctypes as C
 import os
-import types
 
 import torch
 import torch.nn as nn
@@ -48,10 +48,12 @@ def _attach(root, dotted, param):
 
 
 class _Pass:
-    """descriptor of one encoder pass shape (B, S); the activation stash it writes belongs to the slot"""
+    """descriptor of one encoder pass shape (B, S); the activation stash it writes belongs to the slot.  Slots 0 / 1 are the
+    training path's ASR / transcript passes; a named slot ("infer") is a forward-only inference descriptor without fp8 fields."""
 
-    def __init__(self, model, B, S, stream_base):
+    def __init__(self, model, B, S, slot):
         a, cfg = model.arena, model.cfg
+        train = isinstance(slot, int)
         d = hb.EncoderDesc()
         d.dtype = hb.dtype_code(model.compute_dtype)
         d.B, d.S, d.H, d.L, d.heads, d.F = B, S, cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size
@@ -66,16 +68,22 @@ class _Pass:
         d.off_emb_ln_g = a.by_name[pre + "LayerNorm.weight"].offset
         d.off_emb_ln_b = a.by_name[pre + "LayerNorm.bias"].offset
         d.layers_host = C.cast(a.layer_offsets, C.POINTER(hb.LayerOffsets))
-        d.drop_stream_base = stream_base
-        if model.fp8_forward:          # set before the stash is sized: the fp8 mode keeps e4m3 copies of the GEMM inputs per layer
+        d.drop_stream_base = 1000 * slot if train else 0
+        if model.fp8_forward and train:    # set before the stash is sized: the fp8 mode keeps e4m3 copies of the GEMM inputs per layer
             d.w8, d.w8_inv_scale = a.w8.data_ptr(), a.w8_inv_scale.data_ptr()
         self.desc = d
         self.act_bytes = hb.lib().nbest_encoder_act_bytes(C.byref(d))
-        self.act = None                    # a view of the slot's grow-only stash, bound by NBestSTCModel._pass
         self.B, self.S = B, S
-        self.hidden = None
-        self.inputs = None
-        self.perm = None
+
+
+class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen")):
+    """one call's encoder pass: its _Pass, slot, (ids, seg, pos, mask), token permutation (None: sorted on the device when the
+    backward asks), hidden states [B*S, H] (a view into the slot's stash) and the generation of that stash it wrote"""
+    __slots__ = ()
+
+    @property
+    def cls(self):
+        return self.hidden.view(self.ps.B, self.ps.S, -1)[:, 0, :]
 
 
 class _STCBridge(torch.autograd.Function):
@@ -90,33 +98,19 @@ class _STCBridge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, input_ids, trans_input_ids, seg_ids, trans_seg_ids, feats_from_transcript):
         ctx.set_materialize_grads(False)
-        B, S = input_ids.shape
-        H = model.cfg.hidden_size
-        pa = model._pass(B, S, 0)
-        ha = model._encode(pa, input_ids, seg_ids, True)
-        pt = ht = None
-        St = 0
-        if trans_input_ids is not None:
-            St = trans_input_ids.shape[1]
-            pt = model._pass(B, St, 1)
-            ht = model._encode(pt, trans_input_ids, trans_seg_ids, True)
-        feats, Sf = (ht, St) if (feats_from_transcript and ht is not None) else (ha, S)
-        ws = hb.heads_ws(B, model.dls.n_rows, H, model.device)
-        seed = model._step_seed()
-        Wh, bh = model.arena.heads_wb()
-        labels_f = torch.zeros(B, model.labels.n_bottom, dtype=torch.float32, device=model.device)
-        top, bott, fin, _, _, _, _ = hb.stc_heads(feats, Sf * H, Wh, bh, model.dls, labels_f, B, H, need_grad=False, drop_p=model.dropout,
-                                                  seed=seed, drop_stream=900, ws=ws)
-        ctx.model, ctx.pa, ctx.pt, ctx.ws, ctx.seed = model, pa, pt, ws, seed
-        ctx.from_t = bool(feats_from_transcript and ht is not None)
+        from_t = bool(feats_from_transcript and trans_input_ids is not None)
+        ws = hb.heads_ws(input_ids.shape[0], model.dls.n_rows, model.cfg.hidden_size, model.device)
+        ra, rt, (top, bott, fin, _, _, _, _) = model._passes_and_heads(input_ids, seg_ids, trans_input_ids, trans_seg_ids, True,
+                                                                       from_transcript=from_t, ws=ws)
+        ctx.model, ctx.ra, ctx.rt, ctx.ws, ctx.seed, ctx.from_t = model, ra, rt, ws, model._step_seed(), from_t
         ctx.save_for_backward(top, bott)
-        asr_cls = ha.view(B, S, H)[:, 0, :].float()
-        trans_cls = ht.view(B, St, H)[:, 0, :].float() if ht is not None else torch.zeros(0, device=model.device)
-        return top, bott, fin, asr_cls, trans_cls
+        trans_cls = rt.cls.float() if rt is not None else torch.zeros(0, device=model.device)
+        return top, bott, fin, ra.cls.float(), trans_cls
 
     @staticmethod
     def backward(ctx, dtop, dbott, dfin, dasr, dtrans):
         m = ctx.model
+        m._check_stash(ctx.ra, ctx.rt)
         top, bott = ctx.saved_tensors
         B, H = top.shape[0], m.cfg.hidden_size
         z = lambda g, like: torch.zeros_like(like) if g is None else g.contiguous().float()
@@ -125,17 +119,16 @@ class _STCBridge(torch.autograd.Function):
         dcls = hb.stc_heads_vjp(m.arena.heads_wb()[0], m.dls, top, bott, z(dtop, top), z(dbott, bott), z(dfin, fin_like), B, H, dWh, dbh, ctx.ws,
                                 accumulate=True, drop_p=m.dropout, seed=ctx.seed, drop_stream=900)
         d_asr = dasr.contiguous().float() if dasr is not None else None
-        d_tr = dtrans.contiguous().float() if (dtrans is not None and ctx.pt is not None) else None
+        d_tr = dtrans.contiguous().float() if (dtrans is not None and ctx.rt is not None) else None
         if ctx.from_t:
             d_tr = dcls if d_tr is None else d_tr + dcls
         else:
             d_asr = dcls if d_asr is None else d_asr + dcls
-        if d_tr is not None and ctx.pt is not None:
-            m._backward_pass(ctx.pt, d_tr, accumulate=True)
+        if d_tr is not None and ctx.rt is not None:
+            m._backward_pass(ctx.rt, d_tr, accumulate=True)
         if d_asr is not None:
-            m._backward_pass(ctx.pa, d_asr, accumulate=True)
-        m._end_of_step_fp8(True)
-        m.step_counter += 1
+            m._backward_pass(ctx.ra, d_asr, accumulate=True)
+        m._end_of_step(True)
         return (None,) * 7
 
 
@@ -160,7 +153,6 @@ class NBestSTCModel(nn.Module):
         # 2^floor(log2(224 / amax of the same tensor in the previous step)); the first step after (re)loading weights is a
         # calibration step: bf16 GEMMs, amax recorded (round 3 cast activations at unit scale and saturated silently beyond 448)
         self._aamax_valid = False
-        self._step_fp8_fwd = False         # did the forward of the running step run in fp8 (its backward may then, too)
         if self.fp8_forward:
             if compute_dtype != torch.bfloat16:
                 raise RuntimeError("nbest_amd: fp8_forward rides on the bf16 path")
@@ -180,8 +172,8 @@ class NBestSTCModel(nn.Module):
         self.step_counter = 0
         self._passes = {}                  # (B, S, slot) -> _Pass: descriptors only (a few hundred bytes each)
         self._stash = {}                   # slot -> ONE grow-only activation stash, sized for the largest B*S seen
-        self._ws = None
-        self._ws_bytes = 0
+        self._stash_gen = collections.Counter()    # slot -> generation of its stash: moves on whenever a pass is handed the stash
+        self._ws = None                    # grow-only workspace of the encoder passes
         self._dh = None                    # grow-only scratch of the backward's input gradient
         self._infer_ws = None              # grow-only workspace of predict() (nbest_encoder_infer)
         self._anchor = None                # autograd bridge: a leaf that makes the outputs of forward() require grad
@@ -257,24 +249,36 @@ class NBestSTCModel(nn.Module):
         if key not in self._passes:
             if len(self._passes) >= 4096:
                 self._passes.clear()
-            self._passes[key] = _Pass(self, B, S, stream_base=1000 * slot if isinstance(slot, int) else 0)
+            self._passes[key] = _Pass(self, B, S, slot)
         return self._passes[key]
 
+    def _grow(self, table, key, n, dtype=torch.uint8):
+        """``table[key]``: a device buffer of at least n elements that only grows (``table``: ``self._stash`` keyed by slot, or
+        ``vars(self)`` for the workspace attributes).  Real data pads every batch to its own longest row, so sizes change almost every
+        step: one buffer sized for the largest seen is reused instead of a fresh tensor of a new size per step.  The old buffer is
+        released before the new one is allocated: two generations are never held at once."""
+        buf = table.get(key)
+        if buf is None or buf.numel() < n:
+            table[key] = buf = None
+            table[key] = buf = torch.empty(n, dtype=dtype, device=self.device)
+        return buf
+
     def _pass(self, B, S, slot):
-        """Real data pads every batch to its own longest row, so (B, S) changes almost every step: only the small
-        descriptor is per shape; the activation stash is one buffer per slot (ASR pass / transcript pass) that grows
-        to the largest shape seen and is then reused, like the workspace."""
+        """the descriptor of a training pass shape, with the slot's activation stash (ASR pass / transcript pass) and the
+        workspace grown to fit it.  Handing the stash to a pass moves its generation on: records of earlier passes are stale."""
         ps = self._desc(B, S, slot)
-        stash = self._stash.get(slot)
-        if stash is None or stash.numel() < ps.act_bytes:
-            self._stash[slot] = stash = None          # release before growing: never hold two generations
-            self._stash[slot] = stash = torch.empty(ps.act_bytes, dtype=torch.uint8, device=self.device)
-        ps.act = stash[:ps.act_bytes]
-        need = hb.lib().nbest_encoder_ws_bytes(C.byref(ps.desc))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
+        self._grow(self._stash, slot, ps.act_bytes)
+        self._grow(vars(self), "_ws", hb.lib().nbest_encoder_ws_bytes(C.byref(ps.desc)))
+        self._stash_gen[slot] += 1
         return ps
+
+    def _check_stash(self, *records):
+        """a backward reads the activations its forward left in the slot's stash: refuse, before anything is enqueued, if another
+        pass has written the stash since"""
+        for r in records:
+            if r is not None and r.gen != self._stash_gen[r.slot]:
+                raise RuntimeError("nbest_amd: another forward ran on this model between this forward() and its backward(): the "
+                                   "activations of its %s pass are overwritten" % ("ASR", "transcript")[r.slot])
 
     def _step_seed(self):
         """dropout counter base of this step: the element index a kernel hashes is the position inside THIS rank's
@@ -296,101 +300,97 @@ class NBestSTCModel(nn.Module):
             seg = seg.contiguous()
         return ids, seg, pos, mask
 
-    def _encode(self, ps, ids, seg, train, perm=None):
-        """one encoder pass through the C-ABI; returns hidden states [B*S, H] (a view into the stash).
+    def _encode(self, slot, ids, seg, train, perm=None):
+        """one encoder pass through the C-ABI into the slot's stash; returns its _PassRecord.
         ``perm``: the pass's tokens sorted by word id (hipabi.word_perm; host-built by the data loaders) - only the backward
         reads it; None = sorted on the device when a backward pass asks for it."""
-        cfg = self.cfg
-        ids, seg, pos, mask = self._inputs(ids, seg)
+        B, S = ids.shape
+        ps = self._pass(B, S, slot)
+        ids, seg, pos, mask = inputs = self._inputs(ids, seg)
         d = ps.desc
-        d.hidden_drop = cfg.hidden_dropout_prob if train else 0.0
-        d.attn_drop = cfg.attention_probs_dropout_prob if train else 0.0
+        d.hidden_drop = self.cfg.hidden_dropout_prob if train else 0.0
+        d.attn_drop = self.cfg.attention_probs_dropout_prob if train else 0.0
         d.seed = self._step_seed()
-        if self.fp8_forward:
-            d.w8, d.w8_inv_scale = self.arena.w8.data_ptr(), self.arena.w8_inv_scale.data_ptr()
-            self._set_fp8_forward(d)
-        self._set_packed(d)
-        self._set_fp8_backward(d)    # the forward leaves out the bf16 tensors an fp8 backward will not read
+        self._set_weights(d, "forward")
+        act, ws = self._stash[slot][:ps.act_bytes], self._ws
         out = C.c_void_p()
         hb.check(hb.lib().nbest_encoder_forward(C.byref(d), hb.ptr(self.arena.weights), hb.ptr(self.arena.p), hb.ptr(ids),
-                                                hb.ptr(seg), hb.ptr(pos), hb.ptr(mask), hb.ptr(ps.act), ps.act.numel(),
-                                                hb.ptr(self._ws), self._ws_bytes, C.byref(out), hb.stream_ptr()),
+                                                hb.ptr(seg), hb.ptr(pos), hb.ptr(mask), hb.ptr(act), act.numel(),
+                                                hb.ptr(ws), ws.numel(), C.byref(out), hb.stream_ptr()),
                  "encoder_forward")
-        ps.inputs = (ids, seg, pos, mask)
-        ps.perm = perm
-        off = out.value - ps.act.data_ptr()
-        M, H = ps.B * ps.S, cfg.hidden_size
+        off = out.value - act.data_ptr()
+        M, H = B * S, self.cfg.hidden_size
         esz = 2 if self.compute_dtype == torch.bfloat16 else 4
-        ps.hidden = ps.act[off:off + M * H * esz].view(self.compute_dtype).view(M, H)
-        return ps.hidden
+        hidden = act[off:off + M * H * esz].view(self.compute_dtype).view(M, H)
+        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot])
 
-    def _set_packed(self, d):
-        """packed weight copies (arena.wpk / wpkt, refreshed with the transposed copy after every optimizer step)"""
+    def _packed_bf16_ok(self):
+        """the packed bf16 weight copies (arena.wpk / wpkt) exist and are current: they are refreshed with the bf16 transposed
+        copy, which goes stale while the backward runs in fp8"""
+        return self.arena.wpk is not None and not self.arena.w16t_stale
+
+    def _set_weights(self, d, call):
+        """the weight-copy and fp8 fields of descriptor ``d`` for a "forward", "backward" or "infer" call.  The forward and the
+        backward of one step see the same values; an inference descriptor has no fp8 fields (_Pass) and reads the bf16 copy."""
         a = self.arena
-        ok = getattr(a, "wpk", None) is not None and not a.w16t_stale
+        fp8_bwd = self.fp8_backward and call != "infer" and self._gamax_valid and self._aamax_valid
+        if call == "backward" and a.w16t_stale and not fp8_bwd:
+            a.refresh_w16t()                      # a bf16 backward after fp8 steps (history dropped, mode switched)
+        ok = self._packed_bf16_ok()
         d.wpk = a.wpk.data_ptr() if ok else None
         d.wpkt = a.wpkt.data_ptr() if ok else None
-        ok8 = getattr(a, "w8p", None) is not None
+        if call == "infer":
+            return
+        ok8 = a.w8p is not None
         d.w8p = a.w8p.data_ptr() if ok8 else None
         d.w8tp = a.w8tp.data_ptr() if ok8 else None
+        if self.fp8_forward and call == "forward":
+            # activation amax history of the fp8 forward: the same two generations for every pass of a step (ASR + transcript pass
+            # record into the same words: the next step's scale covers both); the backward reads the fields its forward set
+            d.aamax_prev, d.aamax_new = a.aamax.data_ptr(), a.aamax_slots.data_ptr()
+            d.fp8_act = int(self._aamax_valid)
+        if self.fp8_backward:                     # the forward leaves out the bf16 tensors an fp8 backward will not read
+            d.w8t = a.w8t.data_ptr()
+            d.gamax_prev, d.gamax_new = a.gamax.data_ptr(), a.gamax_slots.data_ptr()
+            d.fp8_bwd = int(fp8_bwd)              # the fp8 weight gradients read the fp8 forward's activation copies
+            a.lazy_w16t = fp8_bwd                 # steady state: every dgrad reads w8t, nobody reads the bf16 transposed copy
 
-    def _set_fp8_forward(self, d):
-        """activation amax history of the fp8 forward: the same two generations for every pass of a step (ASR + transcript pass
-        record into the same words: the next step's scale covers both)"""
-        a = self.arena
-        d.aamax_prev, d.aamax_new = a.aamax.data_ptr(), a.aamax_slots.data_ptr()
-        d.fp8_act = int(self._aamax_valid)
-        self._step_fp8_fwd = self._aamax_valid
-
-    def _end_of_step_fp8(self, ran_backward):
+    def _end_of_step(self, ran_backward, advance=True):
         """this step's recorded amax (slots) becomes the history of the next one - after the backward, which reads the forward's
-        copies scaled by the old history"""
+        copies scaled by the old history; ``advance``: a training step moves the dropout streams on (an eval forward does not)"""
         if self.fp8_forward:
             hb.fp8_amax_fold(self.arena.aamax_slots, self.arena.aamax)
             self._aamax_valid = True
         if ran_backward and self.fp8_backward:
             hb.fp8_amax_fold(self.arena.gamax_slots, self.arena.gamax)
             self._gamax_valid = True
+        if advance:
+            self.step_counter += 1
 
-    def _set_fp8_backward(self, d):
-        """descriptor fields of the fp8 backward; the same values in the forward and the backward of one step"""
-        if self.fp8_backward:
-            a = self.arena
-            d.w8t = a.w8t.data_ptr()
-            d.gamax_prev, d.gamax_new = a.gamax.data_ptr(), a.gamax_slots.data_ptr()
-            on = self._gamax_valid and self._aamax_valid      # the fp8 weight gradients read the fp8 forward's activation copies
-            d.fp8_bwd = int(on)
-            a.lazy_w16t = on                      # steady state: every dgrad reads w8t, nobody reads the bf16 transposed copy
-
-    def _backward_pass(self, ps, dcls, accumulate, chunks=None, on_chunk_done=None):
-        cfg = self.cfg
-        self._set_fp8_backward(ps.desc)
-        if self.arena.w16t_stale and not (self.fp8_backward and self._gamax_valid and self._aamax_valid):
-            self.arena.refresh_w16t()             # a bf16 backward after fp8 steps (history dropped, mode switched)
-        self._set_packed(ps.desc)
-        # gradient w.r.t. the final hidden states [B*S, H] (zero except the CLS rows): ONE grow-only buffer, like the activation stash
-        # (real batches change shape every step: no fresh 40-50 MB tensor of a new size per step through the caching allocator)
-        n_dh = ps.B * ps.S * cfg.hidden_size
-        if self._dh is None or self._dh.numel() < n_dh:
-            self._dh = None
-            self._dh = torch.empty(n_dh, dtype=self.compute_dtype, device=self.device)
-        dh = hb.cls_grad_scatter(dcls, ps.B, ps.S, cfg.hidden_size, self.compute_dtype, out=self._dh[:n_dh].view(ps.B * ps.S, cfg.hidden_size))
-        ids, seg, pos, mask = ps.inputs
-        if ps.perm is None:
-            ps.perm = hb.word_perm(ids)
-        ps.desc.word_perm = ps.perm.data_ptr()
-        L = cfg.num_hidden_layers
-        bounds = chunks or [(0, L)]
+    def _backward_pass(self, rec, dcls, accumulate, chunks=None, on_chunk_done=None):
+        """the encoder backward of the pass ``rec`` recorded (its activations must still be in the slot's stash)"""
+        ps, d = rec.ps, rec.ps.desc
+        B, S, H = ps.B, ps.S, self.cfg.hidden_size
+        self._set_weights(d, "backward")
+        # gradient w.r.t. the final hidden states [B*S, H] (zero except the CLS rows), in a grow-only buffer like the stash
+        dh = self._grow(vars(self), "_dh", B * S * H, self.compute_dtype)[:B * S * H].view(B * S, H)
+        dh = hb.cls_grad_scatter(dcls, B, S, H, self.compute_dtype, out=dh)
+        ids, seg, pos, mask = rec.inputs
+        perm = rec.perm if rec.perm is not None else hb.word_perm(ids)
+        d.word_perm = perm.data_ptr()
+        act, ws = self._stash[rec.slot][:ps.act_bytes], self._ws
+        bounds = chunks or [(0, self.cfg.num_hidden_layers)]
         for (lo, hi) in sorted(bounds, reverse=True):
-            hb.check(hb.lib().nbest_encoder_backward(C.byref(ps.desc), hb.ptr(self.arena.weights), hb.ptr(self.arena.w16t),
+            hb.check(hb.lib().nbest_encoder_backward(C.byref(d), hb.ptr(self.arena.weights), hb.ptr(self.arena.w16t),
                                                      hb.ptr(self.arena.p),
                                                      hb.ptr(self.arena.g), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos), hb.ptr(mask),
-                                                     hb.ptr(ps.act), ps.act.numel(), hb.ptr(dh), hb.ptr(self._ws), self._ws_bytes,
+                                                     hb.ptr(act), act.numel(), hb.ptr(dh), hb.ptr(ws), ws.numel(),
                                                      int(accumulate), lo, hi, int(lo == 0), hb.stream_ptr()), "encoder_backward")
             if on_chunk_done is not None:
                 on_chunk_done(lo, hi)
 
-    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False):
+    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None):
+        """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch"""
         B, H = hidden.shape[0] // S, self.cfg.hidden_size
         Wh, bh = self.arena.heads_wb()
         dWh, dbh = self.arena.heads_grad_wb()
@@ -398,7 +398,16 @@ class NBestSTCModel(nn.Module):
             labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
         return hb.stc_heads(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), B, H, need_grad=need_grad,
                             accumulate=accumulate, drop_p=self.dropout if train else 0.0,
-                            seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh)
+                            seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
+
+    def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
+                          accumulate=False, perm=None, trans_perm=None, ws=None):
+        """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
+        ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs)."""
+        ra = self._encode(0, ids, seg, train, perm)
+        rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm)
+        r = rt if from_transcript else ra
+        return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws)
 
     def _bottoms_dict(self, bott):
         out, col = {}, 0
@@ -424,21 +433,10 @@ class NBestSTCModel(nn.Module):
             return self._forward_plain(input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type)
 
     def _forward_plain(self, input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type):
-        train = self.training
-        B, S = input_ids.shape
-        pa = self._pass(B, S, 0)
-        ha = self._encode(pa, input_ids, seg_ids, train)
-        asr_cls = ha.view(B, S, -1)[:, 0, :].float()
-        trans_cls, ht, St = None, None, None
-        if trans_input_ids is not None:
-            St = trans_input_ids.shape[1]
-            pt = self._pass(B, St, 1)
-            ht = self._encode(pt, trans_input_ids, trans_seg_ids, train)
-            trans_cls = ht.view(B, St, -1)[:, 0, :].float()
-        feats, Sf = (ht, St) if classifier_input_type == "transcript" else (ha, S)
-        top, bott, fin, _, _, _, _ = self._heads(feats, Sf, None, need_grad=False, train=train)
-        self._end_of_step_fp8(False)
-        return top, self._bottoms_dict(bott), fin, asr_cls, trans_cls
+        ra, rt, (top, bott, fin, _, _, _, _) = self._passes_and_heads(input_ids, seg_ids, trans_input_ids, trans_seg_ids, self.training,
+                                                                      from_transcript=classifier_input_type == "transcript")
+        self._end_of_step(False, advance=False)
+        return top, self._bottoms_dict(bott), fin, ra.cls.float(), None if rt is None else rt.cls.float()
 
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
@@ -452,38 +450,28 @@ class NBestSTCModel(nn.Module):
         make every gradient amax of the fp8 backward jump between two consecutive steps.
         ``tok_perm`` / ``trans_tok_perm``: int32 [B*S] token indices sorted (stably) by word id, for the deterministic embedding
         backward; the data loaders build them on the host next to the ids (None: sorted on the device)."""
-        train = self.training
-        B, S = input_ids.shape
-        H = self.cfg.hidden_size
-        pa = self._pass(B, S, 0)
-        ha = self._encode(pa, input_ids, seg_ids, train, tok_perm)
-        pt = ht = None
-        St = 0
-        if add_l2_loss and trans_input_ids is not None:
-            St = trans_input_ids.shape[1]
-            pt = self._pass(B, St, 1)
-            ht = self._encode(pt, trans_input_ids, trans_seg_ids, train, trans_tok_perm)
-        top, bott, fin, loss, dcls, _, _ = self._heads(ha, S, labels_f, need_grad=need_grad, train=train, accumulate=accumulate)
+        ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
+            input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
+            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm)
+        B, H = ra.ps.B, self.cfg.hidden_size
         dt = None
-        if pt is not None:
+        if rt is not None:
             dt = torch.empty(B, H, dtype=torch.float32, device=self.device) if need_grad else None
-            mse = hb.cls_mse(ha, S * H, ht, St * H, B, H, dcls, dt, grad_scale=mse_grad_scale)
+            mse = hb.cls_mse(ra.hidden, ra.ps.S * H, rt.hidden, rt.ps.S * H, B, H, dcls, dt, grad_scale=mse_grad_scale)
             loss[3:4].copy_(mse)
         if need_grad and encoder_grad_scale != 1.0:
             dcls.mul_(encoder_grad_scale)
             if dt is not None:
                 dt.mul_(encoder_grad_scale)
         if need_grad:
-            if pt is not None:
+            if rt is not None:
                 # transcript pass first (whole stack, no overlap hooks), then the ASR pass accumulates on top
-                self._backward_pass(pt, dt, accumulate=accumulate)
-                self._backward_pass(pa, dcls, accumulate=True, chunks=chunks, on_chunk_done=on_chunk_done)
+                self._backward_pass(rt, dt, accumulate=accumulate)
+                self._backward_pass(ra, dcls, accumulate=True, chunks=chunks, on_chunk_done=on_chunk_done)
             else:
-                self._backward_pass(pa, dcls, accumulate=accumulate, chunks=chunks, on_chunk_done=on_chunk_done)
-        self._end_of_step_fp8(need_grad)
-        self.step_counter += 1
-        return dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ha.view(B, S, H)[:, 0, :],
-                    trans_cls=None if ht is None else ht.view(B, St, H)[:, 0, :])
+                self._backward_pass(ra, dcls, accumulate=accumulate, chunks=chunks, on_chunk_done=on_chunk_done)
+        self._end_of_step(need_grad)
+        return dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
     def predict(self, input_ids, seg_ids=None):
@@ -497,24 +485,16 @@ class NBestSTCModel(nn.Module):
         first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
         if S > 512 or S + first_pos > cfg.max_position_embeddings:     # refused before anything is enqueued (encoder.hip check_desc)
             raise RuntimeError("nbest_amd predict: S=%d does not fit the position table (%d rows)" % (S, cfg.max_position_embeddings))
-        ps = self._desc(B, S, "infer")
-        d = ps.desc
+        d = self._desc(B, S, "infer").desc
         ids, seg, pos, mask = self._inputs(input_ids, seg_ids)
         d.hidden_drop = d.attn_drop = 0.0
         d.seed = 0
-        d.w8 = d.w8_inv_scale = d.w8t = d.w8p = d.w8tp = None
-        d.aamax_prev = d.aamax_new = d.gamax_prev = d.gamax_new = None
-        d.fp8_act = d.fp8_bwd = 0
+        self._set_weights(d, "infer")
+        ws = self._grow(vars(self), "_infer_ws", hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d)))
         a = self.arena
-        d.wpk = a.wpk.data_ptr() if (getattr(a, "wpk", None) is not None and not a.w16t_stale) else None
-        need = hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d))
-        if self._infer_ws is None or self._infer_ws.numel() < need:
-            self._infer_ws = None
-            self._infer_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         cls = torch.empty(B, H, dtype=self.compute_dtype, device=self.device)
         hb.check(hb.lib().nbest_encoder_infer(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos),
-                                              hb.ptr(mask), hb.ptr(self._infer_ws), self._infer_ws.numel(), hb.ptr(cls),
-                                              hb.stream_ptr()), "encoder_infer")
+                                              hb.ptr(mask), hb.ptr(ws), ws.numel(), hb.ptr(cls), hb.stream_ptr()), "encoder_infer")
         Wh, bh = a.heads_wb()
         labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
         top, bott, fin, _, _, _, _ = hb.stc_heads(cls, H, Wh, bh, self.dls, labels_f, B, H, need_grad=False, drop_p=0.0)

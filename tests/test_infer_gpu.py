@@ -148,6 +148,7 @@ def _state(m, opt=None):
             snap[k] = t.clone()
     snap["stash"] = {k: (v.data_ptr(), v.numel(), v.clone()) for k, v in m._stash.items()}
     snap["dh"] = None if m._dh is None else (m._dh.data_ptr(), m._dh.clone())
+    snap["stash_gen"] = dict(m._stash_gen)
     snap["valid"] = (m._aamax_valid, m._gamax_valid)
     return snap
 

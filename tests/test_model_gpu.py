@@ -998,3 +998,73 @@ def test_autograd_bridge_runs_the_reference_loop_body(add_l2, dropout, labels):
     mb.eval()
     t2 = mb(None, b["ids"], b["tids"], seg_ids=b["seg"], trans_seg_ids=b["tseg"])[0]
     assert not t2.requires_grad
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, "fp8w"])
+@pytest.mark.parametrize("with_trans", [False, True])
+@pytest.mark.parametrize("between", ["eval_forward", "eval_epoch_step", "other_shape"])
+def test_autograd_bridge_refuses_a_forward_between_forward_and_backward(between, with_trans, dtype, labels):
+    """The bridge's backward reads the activations its forward left in the per-slot stashes.  Another forward between the two
+    (an eval-mode model(...), forward_backward(need_grad=False) as eval_epoch runs it, a training model(...) of another (B, S))
+    overwrites them: backward() must raise before it enqueues anything - the gradients, step_counter and the fp8 amax histories
+    stay as they were - and the next forward + backward of the same model gives a clean model's gradients bit for bit
+    (dropout off: the eval_epoch step advances step_counter).  fp8w: the refusal only (the intervening call folds amax)."""
+    import nbest_amd  # noqa: F401
+    from nbest_amd import config as ncfg, synth
+    from nbest_amd.model import NBestSTCModel
+    fp8 = dtype == "fp8w"
+    cfg = ncfg.bert_base(num_hidden_layers=2, vocab_size=3000, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+    sd = synth.model_state(cfg, labels, seed=33)
+    cuda = lambda x: {k: torch.from_numpy(v).cuda() for k, v in x.items()}
+    b = cuda(synth.nbest_batch(cfg, labels, 5, 40, n_best=5, seed=9, ragged=True, trans_len=12))
+    o = cuda(synth.nbest_batch(cfg, labels, 3, 24, n_best=5, seed=10, ragged=True, trans_len=8))
+
+    def build():
+        m = NBestSTCModel(cfg, labels, device="cuda", compute_dtype=torch.bfloat16 if fp8 else dtype, dropout=0.0, seed=4, fp8_forward=fp8)
+        m.load_reference_state(sd)
+        m.train()
+        return m
+
+    def forward(m, x):
+        return m(None, x["ids"], x["tids"] if with_trans else None, seg_ids=x["seg"], trans_seg_ids=x["tseg"] if with_trans else None)
+
+    def loss(outs):
+        top, bottoms, final, asr_cls, trans_cls = outs
+        return final.sum() + 0.5 * top.sum() + 0.1 * asr_cls.sum() + (0.1 * trans_cls.sum() if with_trans else 0.0)
+
+    def state(m):
+        a = m.arena
+        return [m.step_counter, m._aamax_valid, m._gamax_valid] + [getattr(a, k).clone() for k in ("g", "aamax", "aamax_slots", "gamax",
+                                                                                                    "gamax_slots") if getattr(a, k) is not None]
+
+    m = build()
+    m.zero_grad()
+    outs = forward(m, b)
+    if between == "eval_forward":
+        m.eval()
+        forward(m, o)
+    elif between == "eval_epoch_step":
+        m.eval()
+        with torch.no_grad():
+            m.forward_backward(o["ids"], o["labels"], seg_ids=o["seg"], need_grad=False)
+    else:
+        forward(m, o)
+    m.train()
+    torch.cuda.synchronize()
+    before = state(m)
+    with pytest.raises(RuntimeError, match=r"another forward ran on this model between this forward\(\) and its backward\(\)"):
+        loss(outs).backward()
+    torch.cuda.synchronize()
+    after = state(m)
+    assert not m.arena.g.any()
+    for x, y in zip(before, after):
+        assert (torch.equal(x, y) if isinstance(x, torch.Tensor) else x == y), "state changed by the refused backward"
+    if fp8:
+        return
+
+    def grads(m):
+        m.zero_grad()
+        loss(forward(m, b)).backward()
+        torch.cuda.synchronize()
+        return m.arena.g.clone()
+    assert torch.equal(grads(m), grads(build())), "gradients after the refused backward differ from a clean model's"
