@@ -506,6 +506,17 @@ typedef struct nbest_encoder_desc {
   uint32_t* aamax_new;
   int32_t fp8_act;
   int32_t pad4;
+  /* optional frozen parameters (zero = everything trainable).  first_trainable = K in [0, L]: nothing of the embeddings or of layers
+   * [0, K) is trainable - nbest_encoder_forward runs those layers on scratch in `ws` (which it then needs: nbest_encoder_ws_bytes)
+   * with the same dropout streams, stashes nothing of them (nbest_encoder_act_bytes covers X[K..L] and layers K..L-1 only) and, in
+   * the fp8 mode, still records their activation amax; nbest_encoder_backward refuses layer_begin < K and with_embeddings unless
+   * K == 0.  no_input_grad != 0: the backward leaves out the gradient w.r.t. the input of layer K (its QKV dgrad GEMM and residual
+   * add; dhidden is not valid afterwards); refuses with_embeddings.  wgrad_skip_host: HOST memory [4 L] (NULL = none), non-zero =
+   * the weight-gradient GEMM of that matrix (QKV, attention-out, FFN-up, FFN-down per layer) is left out and its gradient is not
+   * written.  Bias and LayerNorm gradients are always written.                                                                 */
+  int32_t first_trainable;
+  int32_t no_input_grad;
+  const uint8_t* wgrad_skip_host;
 } nbest_encoder_desc;
 size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
 size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d);

@@ -267,15 +267,18 @@ class ParamArena:
         return missing
 
     # ---- optimizer descriptors -----------------------------------------------------------------
-    def block_table(self, select=None):
+    def block_table(self, select=None, active=None):
         """host view of the optimizer's block list for the tensors ``select`` picks (the order of build_descs): one
-        (arena offset, elements, active) triple per block of nbest_bertadam_chunk() elements of one tensor"""
+        (arena offset, elements, active) triple per block of nbest_bertadam_chunk() elements of one tensor (``active(name)``:
+        as in build_descs)"""
         chunk = hb.lib().nbest_bertadam_chunk()
         out = []
         for s in self.slots:
             if select is not None and not select(s.name):
                 continue
             act = 0 if "pooler" in s.name else 1
+            if active is not None:
+                act = int(bool(active(s.name)))
             for c0 in range(0, s.numel, chunk):
                 out.append((s.offset + c0, min(chunk, s.numel - c0), act))
         return out

@@ -55,7 +55,13 @@ def parse_arguments(argv=None):
     g.add_argument("--ontology_path", default=None, help="ontology JSON: evaluation keeps informative act-slot-value labels only")
     g = ap.add_argument_group("encoder")
     g.add_argument("--bert_model_name", default="bert-base-uncased")
-    g.add_argument("--fix_bert_model", action="store_true")
+    g.add_argument("--fix_bert_model", action="store_true",
+                   help="accepted and ignored, as by the reference (which parses it and never reads it); freeze with "
+                        "--freeze_embeddings / --freeze_layers")
+    g.add_argument("--freeze_embeddings", action="store_true",
+                   help="train with the word, position and token-type tables and the embedding LayerNorm frozen (requires_grad False)")
+    g.add_argument("--freeze_layers", type=int, default=0, metavar="K",
+                   help="train with encoder layers 0..K-1 frozen (0 <= K <= the number of layers)")
     g.add_argument("--pre_trained_model", help="bert | xlm-roberta (| xlm-roberta-large).  'roberta' is refused: the reference hands "
                    "segment ids to RoBERTa's one-row token-type table and dies with an IndexError (models/model.py:56)")
     g.add_argument("--tod_pre_trained_model", help="ToD-BERT style checkpoint: keeps [SYS]/[USR] markers")
@@ -123,6 +129,8 @@ def parse_arguments(argv=None):
                  "it; this build's restatement of its update rule runs when --restated_adamw is passed too")
     if opt.deviceId < 0:
         ap.error("--deviceId -1 (CPU) is not available: the path is HIP-only")
+    if opt.freeze_layers < 0:
+        ap.error("--freeze_layers %d: must be >= 0" % opt.freeze_layers)
     if opt.pre_trained_model == "roberta":
         ap.error("--pre_trained_model roberta: the reference passes segment ids (1 after the first separator) to RoBERTa's "
                  "one-row token-type table in both encoder passes (models/model.py:45,56; n_best_asr_bert.py:255) and fails "
@@ -149,7 +157,26 @@ def exp_dir(opt):
              "opt_%s_%s_%s_%s" % (opt.optim_choice, opt.warmup_proportion, opt.lr, opt.bert_lr), "mn_%s" % opt.max_norm,
              "me_%s" % opt.max_epoch, "seed_%s" % opt.random_seed, "score_%s" % opt.score_util, "repr_%s" % opt.sent_repr,
              "cls_%s" % opt.cls_type]
+    if getattr(opt, "freeze_embeddings", False) or getattr(opt, "freeze_layers", 0):     # only then: existing names stay as they are
+        parts.append("fz_%s_%s" % ("emb" if opt.freeze_embeddings else "none", opt.freeze_layers))
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
+
+
+def freeze_parameters(model, embeddings=False, layers=0):
+    """--freeze_embeddings / --freeze_layers K: requires_grad_(False) on the embedding tensors and on those of encoder layers
+    0..K-1, before the optimizer is built (everything else follows the parameters' flags, as for a user's own freezing code).
+    Returns the names frozen."""
+    L = model.cfg.num_hidden_layers
+    if not 0 <= layers <= L:
+        raise SystemExit("--freeze_layers %d: the encoder has %d layers" % (layers, L))
+    pre = ["bert_encoder.embeddings."] if embeddings else []
+    pre += ["bert_encoder.encoder.layer.%d." % l for l in range(layers)]
+    frozen = set()
+    for n, p in model.named_parameters():
+        if n.startswith(tuple(pre)):
+            p.requires_grad_(False)
+            frozen.add(n)
+    return frozen
 
 
 def predict_output_path(opt):
@@ -226,8 +253,9 @@ def main(argv=None):
         if opt.pretrained_path:
             model.load_pretrained_encoder(opt.pretrained_path)
     trainer.broadcast_parameters(model)
-    n_params = sum(s.numel for s in model.arena.slots)
-    n_bert = sum(s.numel for s in model.arena.slots if "bert_encoder" in s.name)
+    frozen = freeze_parameters(model, opt.freeze_embeddings, opt.freeze_layers)
+    n_params = sum(s.numel for s in model.arena.slots if s.name not in frozen)
+    n_bert = sum(s.numel for s in model.arena.slots if "bert_encoder" in s.name and s.name not in frozen)
     opt.exp_dir = exp_dir(opt)
     if rank == 0:
         os.makedirs(opt.exp_dir, exist_ok=True)

@@ -6,6 +6,8 @@
 // Activation stash `act` (written by forward, read by backward), T = dtype:
 //   X[0..L]   [M][H] T      X[0] = embedding output, X[l+1] = output of layer l
 //   emb_stats [M][2] f32
+// With desc.first_trainable = K > 0 only X[K..L] and the blocks of layers K..L-1 are stashed (no emb_stats): layers 0..K-1 run
+// on scratch in `ws` (region fz, plus the backward's layer-gradient buffers, which are idle during a forward).
 //   per layer: qkv [M][3H] T | ctx [M][H] T | lse [B*heads*S] f32 | r1 [M][H] T | st1 [M][2] f32 |
 //              x1 [M][H] T | u = gelu'(pre-activation) [M][F] (fp32, or 8-bit fixed point in the bf16 path) | hact [M][F] T | r2 [M][H] T | st2 [M][2] f32
 // Scratch `ws` (backward): dR | dRd | dB1 | dctx [M][H] T, dBig [M][F] T, dqkv [M][3H] T,
@@ -23,7 +25,10 @@ struct ActLayout {
   size_t o_keep, keep_bytes;          // bf16, S <= 256: attention-dropout keep words of the layer (forward -> backward)
   size_t total;
   int64_t M;
+  int K;                              // first stashed layer (desc.first_trainable)
 };
+
+static int first_trainable(const nbest_encoder_desc* d) { return d->first_trainable < 0 ? 0 : (d->first_trainable > d->L ? d->L : d->first_trainable); }
 
 static ActLayout act_layout(const nbest_encoder_desc* d) {
   ActLayout a;
@@ -31,9 +36,10 @@ static ActLayout act_layout(const nbest_encoder_desc* d) {
   a.M = (int64_t)d->B * d->S;
   const size_t MH = al((size_t)a.M * d->H * a.esz), MF = al((size_t)a.M * d->F * a.esz), M3H = al((size_t)a.M * 3 * d->H * a.esz);
   const size_t st = al((size_t)a.M * 2 * sizeof(float)), lse = al((size_t)d->B * d->heads * d->S * sizeof(float));
+  a.K = first_trainable(d);
   size_t o = 0;
-  a.X = o; o += (size_t)(d->L + 1) * MH;
-  a.emb_stats = o; o += st;
+  a.X = o; o += (size_t)(d->L + 1 - a.K) * MH;
+  a.emb_stats = o; o += a.K ? 0 : st;
   a.layer0 = o;
   size_t p = 0;
   a.o_qkv = p; p += M3H;
@@ -57,12 +63,13 @@ static ActLayout act_layout(const nbest_encoder_desc* d) {
     a.o_h8 = p; p += MF8;
   }
   a.layer_stride = p;
-  a.total = o + (size_t)d->L * p;
+  a.total = o + (size_t)(d->L - a.K) * p;
   return a;
 }
 
 struct WsLayout {
   size_t dR, dRd, dB1, dctx, dBig, dqkv, red, slab, slab_bytes, red_bytes, emb, emb_bytes, f8, f8_bytes, total;
+  size_t fz_x0, fz_x1, fz_emb_stats, fz_lse, fz_st1, fz_st2, fz_u;   // forward of the frozen layers 0..K-1 (first_trainable = K > 0)
 };
 
 static size_t max_splitk_bytes(const nbest_encoder_desc* d, int64_t M) {
@@ -131,6 +138,20 @@ static WsLayout ws_layout(const nbest_encoder_desc* d) {
   // (backward, fp8 dgrads: dQ|dK|dV copy over the first three blocks, FFN gradient copy over the fourth, a fifth [M][H] block)
   w.f8_bytes = (d->dtype == NBEST_BF16) ? 4 * al((size_t)M * d->H) + al((size_t)M * d->F) : 0;
   w.f8 = o; o += w.f8_bytes;
+  // frozen layers (first_trainable > 0): their forward runs without a stash, on the ping-pong layer inputs X0 | X1 and these
+  // small buffers; qkv, ctx, r1, x1, r2, gelu(u) and the e4m3 copies reuse dqkv, dctx, dR, dRd, dB1, dBig and f8 above.
+  // fp8 forward: the GELU' rows have no reader but the fp8 epilogue writes them (u, [M][F] bytes).
+  w.fz_x0 = w.fz_x1 = w.fz_emb_stats = w.fz_lse = w.fz_st1 = w.fz_st2 = w.fz_u = o;
+  if (first_trainable(d) > 0) {
+    const size_t st = al((size_t)M * 2 * sizeof(float));
+    w.fz_x0 = o; o += MH;
+    w.fz_x1 = o; o += MH;
+    w.fz_emb_stats = o; o += st;
+    w.fz_lse = o; o += al((size_t)d->B * d->heads * d->S * sizeof(float));
+    w.fz_st1 = o; o += st;
+    w.fz_st2 = o; o += st;
+    w.fz_u = o; o += d->w8 ? al((size_t)M * d->F) : 0;
+  }
   w.total = o;
   return w;
 }
@@ -160,6 +181,8 @@ static int check_desc(const nbest_encoder_desc* d) {
     NB_CHECK(d->H % 128 == 0 && d->F % 128 == 0, NBEST_ERR_SHAPE, "encoder(bf16): H and F must be multiples of 128");
   if (d->w8) NB_CHECK(d->dtype == NBEST_BF16 && d->w8_inv_scale && d->H % 256 == 0 && d->H <= 1024 && d->F % 256 == 0, NBEST_ERR_SHAPE,
                       "encoder(fp8 forward): needs the bf16 path, inverse scales and H, F multiples of 256");
+  NB_CHECK(0 <= d->first_trainable && d->first_trainable <= d->L, NBEST_ERR_ARG, "encoder: first_trainable %d outside [0, L=%d]",
+           d->first_trainable, d->L);
   return NBEST_OK;
 }
 
@@ -212,21 +235,31 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   auto AP = [&](int idx) -> const uint32_t* { return f8 ? d->aamax_prev + idx : nullptr; };
   auto AN = [&](int idx) -> uint32_t* { return arec ? d->aamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS : nullptr; };   // slot block of tensor idx
   const WsLayout wl = ws_layout(d);
-  if (f8) NB_CHECK(ws && ws_bytes >= wl.total, NBEST_ERR_WORKSPACE, "encoder_forward(fp8): workspace too small (%zu < %zu)", ws_bytes, wl.total);
+  const int FT = a.K;   // layers 0..FT-1 are frozen: run on scratch in ws, nothing of them stashed
+  if (f8 || FT > 0)
+    NB_CHECK(ws && ws_bytes >= wl.total, NBEST_ERR_WORKSPACE, "encoder_forward(%s): workspace too small (%zu < %zu)",
+             FT > 0 ? "first_trainable > 0" : "fp8", ws_bytes, wl.total);
   const Ptrs P{(const char*)wts, prm, a.esz};
   char* A = (char*)act;
+  char* W = (char*)ws;
   const int64_t M = a.M;
   const int H = d->H, F = d->F, dt = d->dtype;
-  const size_t MH = al((size_t)M * H * a.esz);
+  const size_t MH = al((size_t)M * H * a.esz), MH8 = al((size_t)M * H);
   auto PK = [&](int64_t off) -> const void* { return (d->wpk && dt == NBEST_BF16) ? (const void*)((const char*)d->wpk + off * 2) : nullptr; };
-  auto X = [&](int l) { return (void*)(A + a.X + (size_t)l * MH); };
+  auto X = [&](int l) { return l >= FT ? (void*)(A + a.X + (size_t)(l - FT) * MH) : (void*)(W + ((l & 1) ? wl.fz_x1 : wl.fz_x0)); };
   const uint32_t sb = d->drop_stream_base;
 
   RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
-                         P.P(d->off_emb_ln_b), X(0), (float*)(A + a.emb_stats), M, H, d->ln_eps, dt, d->hidden_drop, d->seed, sb, st));
+                         P.P(d->off_emb_ln_b), X(0), (float*)(FT > 0 ? W + wl.fz_emb_stats : A + a.emb_stats), M, H, d->ln_eps, dt,
+                         d->hidden_drop, d->seed, sb, st));
   // fp8 forward: the four GEMMs of a layer on the block-scaled fp8 MFMA; their A operands are e4m3 copies in `ws`
-  // (kept per layer in the activation stash: the fp8 weight gradients of the backward read them again)
-  auto L8 = [&](int l, size_t off) -> uint8_t* { return f8 ? (uint8_t*)(A + a.layer0 + (size_t)l * a.layer_stride + off) : nullptr; };
+  // (kept per layer in the activation stash: the fp8 weight gradients of the backward read them again; a frozen layer's in ws.f8)
+  auto L8 = [&](int l, size_t off) -> uint8_t* {
+    if (!f8) return nullptr;
+    if (l >= FT) return (uint8_t*)(A + a.layer0 + (size_t)(l - FT) * a.layer_stride + off);
+    const size_t i = off == a.o_x8 ? 0 : off == a.o_ctx8 ? 1 : off == a.o_x18 ? 2 : 3;
+    return (uint8_t*)(W + wl.f8 + i * MH8);
+  };
   auto gemm8 = [&](const uint8_t* A8, int64_t w_off, int mat, void* Cout, int64_t N, int64_t K, int epi, const float* bias, const void* R,
                    void* U, uint8_t* C8, float drop_p, uint32_t stream_id) -> int {
     nbest_gemm_fp8_args g = {};
@@ -242,10 +275,16 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   auto calib = [&](const void* t, int64_t n, int idx) -> int { return (arec && !f8) ? nbest_internal_amax_bf16(t, n, d->aamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS, st) : NBEST_OK; };
   for (int l = 0; l < d->L; ++l) {
     const nbest_layer_offsets& o = d->layers_host[l];
-    char* Lb = A + a.layer0 + (size_t)l * a.layer_stride;
-    void* qkv = Lb + a.o_qkv; void* ctx = Lb + a.o_ctx; float* lse = (float*)(Lb + a.o_lse);
-    void* r1 = Lb + a.o_r1; float* st1 = (float*)(Lb + a.o_st1); void* x1 = Lb + a.o_x1;
-    void* u = Lb + a.o_u; void* hact = Lb + a.o_hact; void* r2 = Lb + a.o_r2; float* st2 = (float*)(Lb + a.o_st2);
+    const bool frozen = l < FT;
+    char* Lb = frozen ? nullptr : A + a.layer0 + (size_t)(l - FT) * a.layer_stride;
+    void* qkv = frozen ? W + wl.dqkv : Lb + a.o_qkv; void* ctx = frozen ? W + wl.dctx : Lb + a.o_ctx;
+    float* lse = (float*)(frozen ? W + wl.fz_lse : Lb + a.o_lse);
+    void* r1 = frozen ? W + wl.dR : Lb + a.o_r1; float* st1 = (float*)(frozen ? W + wl.fz_st1 : Lb + a.o_st1);
+    void* x1 = frozen ? W + wl.dRd : Lb + a.o_x1;
+    // a frozen layer keeps no GELU' rows (BIAS_GELU without U, as nbest_encoder_infer), except in the fp8 epilogue, which writes them
+    void* u = frozen ? (f8 ? (void*)(W + wl.fz_u) : nullptr) : Lb + a.o_u;
+    void* hact = frozen ? W + wl.dBig : Lb + a.o_hact; void* r2 = frozen ? W + wl.dB1 : Lb + a.o_r2;
+    float* st2 = (float*)(frozen ? W + wl.fz_st2 : Lb + a.o_st2);
     const uint32_t s0 = sb + 1 + 4 * l;
     uint8_t* x8 = L8(l, a.o_x8); uint8_t* ctx8 = L8(l, a.o_ctx8); uint8_t* x18 = L8(l, a.o_x18); uint8_t* h8 = L8(l, a.o_h8);
     uint8_t* x8_next = (l + 1 < d->L) ? L8(l + 1, a.o_x8) : nullptr;   // the last LayerNorm's copy has no reader
@@ -256,7 +295,7 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
     } else
     RUN(gemm(dt, X(l), P.W(o.wqkv), qkv, M, 3 * H, H, H, H, 3 * H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv), nullptr, 0, nullptr, 0,
              nullptr, 0, 0, 0.f, 0, 0, st, nullptr, PK(o.wqkv)));
-    uint32_t* keepw = (a.keep_bytes && d->attn_drop > 0.f) ? (uint32_t*)(Lb + a.o_keep) : nullptr;
+    uint32_t* keepw = (a.keep_bytes && d->attn_drop > 0.f && !frozen) ? (uint32_t*)(Lb + a.o_keep) : nullptr;
     RUN(calib(X(l), M * H, 4 * l + 0));
     RUN(nbest_internal_attention_fwd8(qkv, key_mask, ctx, ctx8, lse, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, keepw,
                                       AP(4 * l + 1), f8 ? AN(4 * l + 1) : nullptr));
@@ -272,10 +311,11 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
     // FFN up + bias + GELU (GELU' of the pre-activation kept for the backward)
     if (f8) {
       // (bf16 gelu(u) has one reader, the bf16 FFN-down weight gradient: not written when the backward runs in fp8)
-      RUN(gemm8(x18, o.w1, 4 * l + 2, fp8_backward_active(d) ? nullptr : hact, F, H, NBEST_EPI_BIAS_GELU, P.P(o.b1), nullptr, u, h8, 0.f, 0));
+      RUN(gemm8(x18, o.w1, 4 * l + 2, (fp8_backward_active(d) || frozen) ? nullptr : hact, F, H, NBEST_EPI_BIAS_GELU, P.P(o.b1), nullptr, u, h8,
+                0.f, 0));
     } else
     RUN(gemm(dt, x1, P.W(o.w1), hact, M, F, H, H, H, F, 0, 0, NBEST_EPI_BIAS_GELU, P.P(o.b1), nullptr, 0, u, F, nullptr, 0, 0, 0.f,
-             0, 0, st, nullptr, PK(o.w1)));
+             0, 0, st, nullptr, PK(o.w1)));   // (U == NULL: BIAS_GELU without the GELU' rows)
     // FFN down + dropout + residual, then LayerNorm
     if (f8) {
       RUN(gemm8(h8, o.w2, 4 * l + 3, r2, H, F, NBEST_EPI_BIAS_DROP_RES, P.P(o.b2), x1, nullptr, nullptr, d->hidden_drop, s0 + 2));
@@ -298,6 +338,10 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   NB_CHECK(0 <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_backward: bad layer range");
   NB_CHECK(wts && prm && grad && ids && pos && key_mask && act && dhidden && ws, NBEST_ERR_ARG, "encoder_backward: null pointer");
   NB_CHECK(!with_embeddings || d->word_perm, NBEST_ERR_ARG, "encoder_backward: desc.word_perm (stable argsort of this pass's ids) is required");
+  NB_CHECK(layer_begin >= d->first_trainable, NBEST_ERR_ARG, "encoder_backward: layer_begin %d < first_trainable %d (those layers are not stashed)",
+           layer_begin, d->first_trainable);
+  NB_CHECK(!with_embeddings || (d->first_trainable == 0 && !d->no_input_grad), NBEST_ERR_ARG,
+           "encoder_backward: with_embeddings needs first_trainable == 0 and no_input_grad == 0");
   const ActLayout a = act_layout(d);
   const WsLayout w = ws_layout(d);
   NB_CHECK(act_bytes >= a.total, NBEST_ERR_WORKSPACE, "encoder_backward: activation stash too small");
@@ -314,8 +358,11 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   const int64_t M = a.M;
   const int H = d->H, F = d->F, dt = d->dtype;
   const size_t MH = al((size_t)M * H * a.esz);
-  auto X = [&](int l) { return (void*)(A + a.X + (size_t)l * MH); };
+  const int FT = a.K;
+  auto X = [&](int l) { return (void*)(A + a.X + (size_t)(l - FT) * MH); };
   auto G = [&](int64_t off) { return grad + off; };
+  // frozen matrices (desc.wgrad_skip_host[4 l + {0: QKV, 1: attention-out, 2: FFN-up, 3: FFN-down}]): no weight-gradient GEMM
+  auto skip = [&](int l, int j) -> bool { return d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]; };
   void* dA = dhidden;
   void* dR = W + w.dR;
   const bool hdrop = d->hidden_drop > 0.f;
@@ -358,7 +405,9 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   struct BatchGuard { ~BatchGuard() { nbest_internal_rowred_batch_abort(); } } batch_guard;   // an error return mid-layer must not leave it open
   for (int l = layer_end - 1; l >= layer_begin; --l) {
     const nbest_layer_offsets& o = d->layers_host[l];
-    char* Lb = A + a.layer0 + (size_t)l * a.layer_stride;
+    char* Lb = A + a.layer0 + (size_t)(l - FT) * a.layer_stride;
+    const bool input_grad = !(d->no_input_grad && l == FT);   // the gradient w.r.t. the input of layer FT has no reader
+    const bool pair_wo = paired && !skip(l, 1);              // the attention-out gradient rides with QKV's (or alone when QKV's is skipped)
     void* qkv = Lb + a.o_qkv; void* ctx = Lb + a.o_ctx; float* lse = (float*)(Lb + a.o_lse);
     void* r1 = Lb + a.o_r1; float* st1 = (float*)(Lb + a.o_st1); void* x1 = Lb + a.o_x1;
     void* u = Lb + a.o_u; void* hact = Lb + a.o_hact; void* r2 = Lb + a.o_r2; float* st2 = (float*)(Lb + a.o_st2);
@@ -380,7 +429,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       if (rec) RUN(nbest_internal_amax_bf16(dBig, M * F, d->gamax_new + (int64_t)(4 * l + 1) * NBEST_AMAX_TENSOR_WORDS, st));   // calibration pass: this producer is a bf16 kernel
     }
     stamp(0);
-    if (f8b) RUN(nbest_wgrad_fp8(dRd8, h8, G(o.w2), H, F, M, H, F, F, d->gamax_prev + 4 * l + 0, d->aamax_prev + 4 * l + 3, accumulate, slab, w.slab_bytes, stream));
+    if (skip(l, 3)) {
+    } else if (f8b) RUN(nbest_wgrad_fp8(dRd8, h8, G(o.w2), H, F, M, H, F, F, d->gamax_prev + 4 * l + 0, d->aamax_prev + 4 * l + 3, accumulate, slab, w.slab_bytes, stream));
     else RUN(gemm(dt, dRd, hact, G(o.w2), H, F, M, H, F, F, 1, 1, NBEST_EPI_F32_SPLITK, nullptr, nullptr, 0, nullptr, 0, slab, w.slab_bytes,
                   accumulate, 0.f, 0, 0, st));
     stamp(1);
@@ -388,7 +438,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     if (f8b) RUN(dgrad8(dBig8, 4 * l + 1, o.w1, 4 * l + 2, dB1, H, F, NBEST_EPI_RES, dR, nullptr, nullptr, -1, nullptr));
     else RUN(gemm(dt, dBig, PT.W(o.w1), dB1, M, H, F, F, wt ? F : H, H, 0, tbd, NBEST_EPI_RES, nullptr, dR, H, nullptr, 0, nullptr, 0, 0, 0.f, 0, 0, st, nullptr, PKT(o.w1)));
     stamp(0);
-    if (f8b) RUN(nbest_wgrad_fp8(dBig8, x18, G(o.w1), F, H, M, F, H, H, d->gamax_prev + 4 * l + 1, d->aamax_prev + 4 * l + 2, accumulate, slab, w.slab_bytes, stream));
+    if (skip(l, 2)) {
+    } else if (f8b) RUN(nbest_wgrad_fp8(dBig8, x18, G(o.w1), F, H, M, F, H, H, d->gamax_prev + 4 * l + 1, d->aamax_prev + 4 * l + 2, accumulate, slab, w.slab_bytes, stream));
     else RUN(gemm(dt, dBig, x1, G(o.w1), F, H, M, F, H, H, 1, 1, NBEST_EPI_F32_SPLITK, nullptr, nullptr, 0, nullptr, 0, slab, w.slab_bytes,
                   accumulate, 0.f, 0, 0, st));
     stamp(1);
@@ -401,7 +452,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     // (bf16: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
     if (!paired) {
       stamp(0);
-      if (f8b) RUN(nbest_wgrad_fp8(dRd8, ctx8, G(o.wo), H, H, M, H, H, H, d->gamax_prev + 4 * l + 2, d->aamax_prev + 4 * l + 1, accumulate, slab, w.slab_bytes, stream));
+      if (skip(l, 1)) {
+      } else if (f8b) RUN(nbest_wgrad_fp8(dRd8, ctx8, G(o.wo), H, H, M, H, H, H, d->gamax_prev + 4 * l + 2, d->aamax_prev + 4 * l + 1, accumulate, slab, w.slab_bytes, stream));
       else RUN(gemm(dt, dRd, ctx, G(o.wo), H, H, M, H, H, H, 1, 1, NBEST_EPI_F32_SPLITK, nullptr, nullptr, 0, nullptr, 0, slab, w.slab_bytes,
                     accumulate, 0.f, 0, 0, st));
       stamp(1);
@@ -411,15 +463,22 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                                       dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, 4 * l + 3),
                                       (a.keep_bytes && d->attn_drop > 0.f) ? (const uint32_t*)(Lb + a.o_keep) : nullptr));
     // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad
-    if (f8b) RUN(dgrad8(dqkv8, 4 * l + 3, o.wqkv, 4 * l + 0, dA, H, 3 * H, NBEST_EPI_RES, dR, nullptr, nullptr, -1, nullptr));
+    if (!input_grad) {
+    } else if (f8b) RUN(dgrad8(dqkv8, 4 * l + 3, o.wqkv, 4 * l + 0, dA, H, 3 * H, NBEST_EPI_RES, dR, nullptr, nullptr, -1, nullptr));
     else RUN(gemm(dt, dqkv, PT.W(o.wqkv), dA, M, H, 3 * H, 3 * H, wt ? 3 * H : H, H, 0, tbd, NBEST_EPI_RES, nullptr, dR, H, nullptr, 0, nullptr, 0, 0, 0.f, 0, 0, st, nullptr, PKT(o.wqkv)));
     stamp(0);
-    if (f8b && paired)
+    if (paired && skip(l, 0)) {   // only the attention-out gradient of the pair (if any): a single launch
+      if (!pair_wo) {
+      } else if (f8b) RUN(nbest_wgrad_fp8(dRd8, ctx8, G(o.wo), H, H, M, H, H, H, d->gamax_prev + 4 * l + 2, d->aamax_prev + 4 * l + 1, accumulate, slab, w.slab_bytes, stream));
+      else RUN(gemm(dt, dRd, ctx, G(o.wo), H, H, M, H, H, H, 1, 1, NBEST_EPI_F32_SPLITK, nullptr, nullptr, 0, nullptr, 0, slab, w.slab_bytes,
+                    accumulate, 0.f, 0, 0, st));
+    } else if (skip(l, 0)) {
+    } else if (f8b && pair_wo)
       RUN(nbest_wgrad_fp8_pair(dqkv8, x8, G(o.wqkv), 3 * H, 3 * H, H, H, d->gamax_prev + 4 * l + 3, d->aamax_prev + 4 * l + 0, dRd8, ctx8, G(o.wo), H, H,
                                H, H, d->gamax_prev + 4 * l + 2, d->aamax_prev + 4 * l + 1, H, M, accumulate, slab, w.slab_bytes, stream));
     else if (f8b) RUN(nbest_wgrad_fp8(dqkv8, x8, G(o.wqkv), 3 * H, H, M, 3 * H, H, H, d->gamax_prev + 4 * l + 3, d->aamax_prev + 4 * l + 0, accumulate, slab,
                                       w.slab_bytes, stream));
-    else if (paired) {
+    else if (pair_wo) {
       nbest_gemm_args g1 = {}, g2 = {};
       g1.A = dqkv; g1.B = X(l); g1.C = G(o.wqkv); g1.M = 3 * H; g1.lda = 3 * H;
       g2.A = dRd; g2.B = ctx; g2.C = G(o.wo); g2.M = H; g2.lda = H;

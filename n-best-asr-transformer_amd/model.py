@@ -47,11 +47,47 @@ def _attach(root, dotted, param):
     mod.register_parameter(parts[-1], param)
 
 
+class FreezePlan(collections.namedtuple("FreezePlan", "key trainable first_trainable no_input_grad with_embeddings skip")):
+    """what a training pass derives from the parameters' ``requires_grad`` flags: ``trainable`` names (never the pooler),
+    ``first_trainable`` (nothing of the embeddings or of the layers below it is trainable: those run without a stash),
+    ``no_input_grad`` (the embeddings are frozen: the backward forms no gradient below its lowest layer), ``with_embeddings``
+    (the embedding backward runs) and ``skip`` (ctypes uint8 [4 L]: frozen QKV / attention-out / FFN-up / FFN-down matrices,
+    whose weight-gradient GEMMs the backward leaves out; None = none)"""
+    __slots__ = ()
+
+    @property
+    def skip_ptr(self):
+        return None if self.skip is None else C.cast(self.skip, C.c_void_p)
+
+
+def freeze_plan(model):
+    """the FreezePlan of the model's current ``requires_grad`` flags (cached per flag pattern)"""
+    flags = tuple(p.requires_grad and "pooler" not in n for n, p in model._params)
+    plan = model._plans.get(flags)
+    if plan is not None:
+        return plan
+    trainable = frozenset(n for (n, _), f in zip(model._params, flags) if f)
+    L = model.cfg.num_hidden_layers
+    emb = any(n.startswith("bert_encoder.embeddings.") for n in trainable)
+    layer = [any(n.startswith("bert_encoder.encoder.layer.%d." % l) for n in trainable) for l in range(L)]
+    first = 0 if emb else next((l for l in range(L) if layer[l]), L)
+    pre = "bert_encoder.encoder.layer.%d."
+    mats = (["attention.self.%s.weight" % q for q in ("query", "key", "value")], ["attention.output.dense.weight"],
+            ["intermediate.dense.weight"], ["output.dense.weight"])
+    skip = [int(not any((pre % l) + m in trainable for m in ms)) for l in range(L) for ms in mats]
+    plan = FreezePlan(flags, trainable, first, int(not emb), emb, (C.c_uint8 * len(skip))(*skip) if any(skip) else None)
+    if len(model._plans) >= 64:
+        model._plans.clear()
+    model._plans[flags] = plan
+    return plan
+
+
 class _Pass:
     """descriptor of one encoder pass shape (B, S); the activation stash it writes belongs to the slot.  Slots 0 / 1 are the
-    training path's ASR / transcript passes; a named slot ("infer") is a forward-only inference descriptor without fp8 fields."""
+    training path's ASR / transcript passes; a named slot ("infer") is a forward-only inference descriptor without fp8 fields.
+    ``first_trainable``: layers below it run without a stash (FreezePlan)."""
 
-    def __init__(self, model, B, S, slot):
+    def __init__(self, model, B, S, slot, first_trainable=0):
         a, cfg = model.arena, model.cfg
         train = isinstance(slot, int)
         d = hb.EncoderDesc()
@@ -69,6 +105,7 @@ class _Pass:
         d.off_emb_ln_b = a.by_name[pre + "LayerNorm.bias"].offset
         d.layers_host = C.cast(a.layer_offsets, C.POINTER(hb.LayerOffsets))
         d.drop_stream_base = 1000 * slot if train else 0
+        d.first_trainable = first_trainable
         if model.fp8_forward and train:    # set before the stash is sized: the fp8 mode keeps e4m3 copies of the GEMM inputs per layer
             d.w8, d.w8_inv_scale = a.w8.data_ptr(), a.w8_inv_scale.data_ptr()
         self.desc = d
@@ -76,9 +113,10 @@ class _Pass:
         self.B, self.S = B, S
 
 
-class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen")):
+class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen plan")):
     """one call's encoder pass: its _Pass, slot, (ids, seg, pos, mask), token permutation (None: sorted on the device when the
-    backward asks), hidden states [B*S, H] (a view into the slot's stash) and the generation of that stash it wrote"""
+    backward asks), hidden states [B*S, H] (a view into the slot's stash), the generation of that stash it wrote and the
+    FreezePlan it ran with (None: everything trainable, full stash)"""
     __slots__ = ()
 
     @property
@@ -100,8 +138,9 @@ class _STCBridge(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         from_t = bool(feats_from_transcript and trans_input_ids is not None)
         ws = hb.heads_ws(input_ids.shape[0], model.dls.n_rows, model.cfg.hidden_size, model.device)
+        plan = model._training_plan()
         ra, rt, (top, bott, fin, _, _, _, _) = model._passes_and_heads(input_ids, seg_ids, trans_input_ids, trans_seg_ids, True,
-                                                                       from_transcript=from_t, ws=ws)
+                                                                       from_transcript=from_t, ws=ws, plan=plan)
         ctx.model, ctx.ra, ctx.rt, ctx.ws, ctx.seed, ctx.from_t = model, ra, rt, ws, model._step_seed(), from_t
         ctx.save_for_backward(top, bott)
         trans_cls = rt.cls.float() if rt is not None else torch.zeros(0, device=model.device)
@@ -111,6 +150,7 @@ class _STCBridge(torch.autograd.Function):
     def backward(ctx, dtop, dbott, dfin, dasr, dtrans):
         m = ctx.model
         m._check_stash(ctx.ra, ctx.rt)
+        _require_trainable(ctx.ra.plan)
         top, bott = ctx.saved_tensors
         B, H = top.shape[0], m.cfg.hidden_size
         z = lambda g, like: torch.zeros_like(like) if g is None else g.contiguous().float()
@@ -130,6 +170,12 @@ class _STCBridge(torch.autograd.Function):
             m._backward_pass(ctx.ra, d_asr, accumulate=True)
         m._end_of_step(True)
         return (None,) * 7
+
+
+def _require_trainable(plan):
+    if plan is not None and not plan.trainable:
+        raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
+                           "has requires_grad=False)")
 
 
 class NBestSTCModel(nn.Module):
@@ -167,6 +213,9 @@ class NBestSTCModel(nn.Module):
                 p.grad = self.arena.view(self.arena.g, s.name)
             root, rest = s.name.split(".", 1)
             _attach(getattr(self, root), rest, p)
+        self._params = [(s.name, self.get_parameter(s.name)) for s in self.arena.slots]
+        self._plans = {}                   # requires_grad pattern -> FreezePlan
+        self._plan_key = None              # the pattern of the last training pass
         self.dls = hb.DeviceLabelSpace(labels, self.device)
         self.seed = int(seed)
         self.step_counter = 0
@@ -243,14 +292,34 @@ class NBestSTCModel(nn.Module):
         self.arena.load_state(sd, strict=False)
         return missing
 
-    def _desc(self, B, S, slot):
+    def _desc(self, B, S, slot, first_trainable=0):
         """the (cached) descriptor of a pass shape; allocates nothing"""
-        key = (B, S, slot)
+        key = (B, S, slot, first_trainable)
         if key not in self._passes:
             if len(self._passes) >= 4096:
                 self._passes.clear()
-            self._passes[key] = _Pass(self, B, S, slot)
+            self._passes[key] = _Pass(self, B, S, slot, first_trainable)
         return self._passes[key]
+
+    def _training_plan(self):
+        """the FreezePlan of a training pass from the parameters' current ``requires_grad`` flags: frozen tensors get
+        ``.grad = None``, tensors trainable again their arena view back; a new frozen set drops the fp8 gradient amax history
+        (layers that had no backward have none: the next backward is a bf16 calibration pass)"""
+        plan = freeze_plan(self)
+        if plan.key != self._plan_key:
+            for (n, p), f in zip(self._params, plan.key):
+                if "pooler" in n:
+                    continue
+                if not f:
+                    p.grad = None
+                elif p.grad is None:
+                    p.grad = self.arena.view(self.arena.g, n)
+            if self._plan_key is not None and self.fp8_backward and self._gamax_valid:
+                self._gamax_valid = False
+                self.arena.gamax.zero_()
+                self.arena.gamax_slots.zero_()
+            self._plan_key = plan.key
+        return plan
 
     def _grow(self, table, key, n, dtype=torch.uint8):
         """``table[key]``: a device buffer of at least n elements that only grows (``table``: ``self._stash`` keyed by slot, or
@@ -263,10 +332,10 @@ class NBestSTCModel(nn.Module):
             table[key] = buf = torch.empty(n, dtype=dtype, device=self.device)
         return buf
 
-    def _pass(self, B, S, slot):
+    def _pass(self, B, S, slot, first_trainable=0):
         """the descriptor of a training pass shape, with the slot's activation stash (ASR pass / transcript pass) and the
         workspace grown to fit it.  Handing the stash to a pass moves its generation on: records of earlier passes are stale."""
-        ps = self._desc(B, S, slot)
+        ps = self._desc(B, S, slot, first_trainable)
         self._grow(self._stash, slot, ps.act_bytes)
         self._grow(vars(self), "_ws", hb.lib().nbest_encoder_ws_bytes(C.byref(ps.desc)))
         self._stash_gen[slot] += 1
@@ -300,12 +369,13 @@ class NBestSTCModel(nn.Module):
             seg = seg.contiguous()
         return ids, seg, pos, mask
 
-    def _encode(self, slot, ids, seg, train, perm=None):
+    def _encode(self, slot, ids, seg, train, perm=None, plan=None):
         """one encoder pass through the C-ABI into the slot's stash; returns its _PassRecord.
         ``perm``: the pass's tokens sorted by word id (hipabi.word_perm; host-built by the data loaders) - only the backward
-        reads it; None = sorted on the device when a backward pass asks for it."""
+        reads it; None = sorted on the device when a backward pass asks for it.  ``plan``: the FreezePlan of a pass a backward
+        may follow (None: full stash)."""
         B, S = ids.shape
-        ps = self._pass(B, S, slot)
+        ps = self._pass(B, S, slot, plan.first_trainable if plan is not None else 0)
         ids, seg, pos, mask = inputs = self._inputs(ids, seg)
         d = ps.desc
         d.hidden_drop = self.cfg.hidden_dropout_prob if train else 0.0
@@ -322,7 +392,7 @@ class NBestSTCModel(nn.Module):
         M, H = B * S, self.cfg.hidden_size
         esz = 2 if self.compute_dtype == torch.bfloat16 else 4
         hidden = act[off:off + M * H * esz].view(self.compute_dtype).view(M, H)
-        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot])
+        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot], plan)
 
     def _packed_bf16_ok(self):
         """the packed bf16 weight copies (arena.wpk / wpkt) exist and are current: they are refreshed with the bf16 transposed
@@ -379,13 +449,21 @@ class NBestSTCModel(nn.Module):
         perm = rec.perm if rec.perm is not None else hb.word_perm(ids)
         d.word_perm = perm.data_ptr()
         act, ws = self._stash[rec.slot][:ps.act_bytes], self._ws
+        plan = rec.plan
+        ft = plan.first_trainable if plan is not None else 0
+        d.no_input_grad = plan.no_input_grad if plan is not None else 0
+        d.wgrad_skip_host = plan.skip_ptr if plan is not None else None
+        with_emb = plan.with_embeddings if plan is not None else True
         bounds = chunks or [(0, self.cfg.num_hidden_layers)]
         for (lo, hi) in sorted(bounds, reverse=True):
-            hb.check(hb.lib().nbest_encoder_backward(C.byref(d), hb.ptr(self.arena.weights), hb.ptr(self.arena.w16t),
-                                                     hb.ptr(self.arena.p),
-                                                     hb.ptr(self.arena.g), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos), hb.ptr(mask),
-                                                     hb.ptr(act), act.numel(), hb.ptr(dh), hb.ptr(ws), ws.numel(),
-                                                     int(accumulate), lo, hi, int(lo == 0), hb.stream_ptr()), "encoder_backward")
+            lo_t = max(lo, ft)                    # nothing below first_trainable is stashed or trainable
+            if hi > lo_t:
+                hb.check(hb.lib().nbest_encoder_backward(C.byref(d), hb.ptr(self.arena.weights), hb.ptr(self.arena.w16t),
+                                                         hb.ptr(self.arena.p),
+                                                         hb.ptr(self.arena.g), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos), hb.ptr(mask),
+                                                         hb.ptr(act), act.numel(), hb.ptr(dh), hb.ptr(ws), ws.numel(),
+                                                         int(accumulate), lo_t, hi, int(lo_t == 0 and with_emb), hb.stream_ptr()),
+                         "encoder_backward")
             if on_chunk_done is not None:
                 on_chunk_done(lo, hi)
 
@@ -401,11 +479,11 @@ class NBestSTCModel(nn.Module):
                             seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
-                          accumulate=False, perm=None, trans_perm=None, ws=None):
+                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None):
         """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
         ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs)."""
-        ra = self._encode(0, ids, seg, train, perm)
-        rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm)
+        ra = self._encode(0, ids, seg, train, perm, plan)
+        rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan)
         r = rt if from_transcript else ra
         return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws)
 
@@ -449,10 +527,15 @@ class NBestSTCModel(nn.Module):
         ``encoder_grad_scale``: multiplies the gradient entering the encoder (the CLS rows) - a loss-scaling knob; the tests use it to
         make every gradient amax of the fp8 backward jump between two consecutive steps.
         ``tok_perm`` / ``trans_tok_perm``: int32 [B*S] token indices sorted (stably) by word id, for the deterministic embedding
-        backward; the data loaders build them on the host next to the ids (None: sorted on the device)."""
+        backward; the data loaders build them on the host next to the ids (None: sorted on the device).
+        Frozen parameters (``requires_grad`` False) get no gradient (FreezePlan); with none trainable this raises."""
+        plan = None
+        if need_grad:
+            plan = self._training_plan()
+            _require_trainable(plan)
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
             input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
-            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm)
+            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan)
         B, H = ra.ps.B, self.cfg.hidden_size
         dt = None
         if rt is not None:

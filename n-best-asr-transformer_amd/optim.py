@@ -10,6 +10,7 @@ import torch
 import torch.distributed as dist
 
 from . import hipabi as hb
+from .model import freeze_plan
 
 
 def warmup_linear(step, t_total, warmup):
@@ -47,6 +48,11 @@ class HipBertAdam:
         self.b1, self.b2, self.e, self.max_grad_norm = b1, b2, e, max_grad_norm
         self.step_count = 0
         a = self.arena
+        self._frozen_key = None     # requires_grad pattern the descriptors were built for (model.FreezePlan.key)
+        self._trainable = None      # its trainable tensor names (None: every tensor but the pooler)
+        if hasattr(model, "_params"):
+            plan = freeze_plan(model)
+            self._frozen_key, self._trainable = plan.key, plan.trainable
         if a.m is None:
             a.m = torch.zeros_like(a.p)
             a.v = torch.zeros_like(a.p)
@@ -73,7 +79,7 @@ class HipBertAdam:
         a, W = self.arena, self.world
         self.blk_bounds, self.elem_ranges, self.small_idx, self.partials, self.coefs = [], [], [], [], []
         for part, sel in enumerate(self._selects):
-            blocks = a.block_table(sel)
+            blocks = a.block_table(sel, self._active())
             n_t, n_b = self.parts[part][1], self.parts[part][2]
             assert len(blocks) == n_b, (len(blocks), n_b)
             weight = [n if act else 0 for _, n, act in blocks]
@@ -103,7 +109,38 @@ class HipBertAdam:
                              for r in range(W)]
 
     def _build_descs(self, select):
-        return self.arena.build_descs(self.lr, self.bert_lr, select=select)
+        return self.arena.build_descs(self.lr, self.bert_lr, select=select, active=self._active())
+
+    def _active(self):
+        """``active(name)`` of the descriptors: the tensors whose ``requires_grad`` is set (the pooler never; None: all others)"""
+        t = self._trainable
+        return None if t is None else (lambda n: n in t)
+
+    def sync_frozen(self):
+        """rebuild the descriptors (and the sharding plan, which balances by active elements) when the model's frozen set has
+        changed since they were built.  Called by every step; the trainer calls it before the forward, so that a sharded plan
+        and the gradient exchange of that step agree.  A tensor frozen since construction has zero moments when it becomes
+        trainable (nothing updates them meanwhile), as a torch optimizer creates its state on the first gradient it sees."""
+        if not hasattr(self.model, "_params"):
+            return False
+        plan = freeze_plan(self.model)
+        if plan.key == self._frozen_key:
+            return False
+        self._frozen_key, self._trainable = plan.key, plan.trainable
+        for part, sel in enumerate(self._selects):
+            descs, n_t, n_b = self._build_descs(sel)
+            assert (n_t, n_b) == self.parts[part][1:3]
+            self.parts[part] = (descs, n_t, n_b, self.parts[part][3])
+        if self.sharded:
+            # the cut points move (the plan balances by active elements): a range's new owner must start from the current master
+            # and moments, which only its old owner holds - make them current everywhere first (a collective: every rank reaches
+            # this at the same step, the frozen set being the same on every rank)
+            self.gather_master()
+            old = self.owner_ranges
+            self._plan_shards()
+            old[:] = self.owner_ranges          # the list trainer.GradReducer holds
+            self.owner_ranges = old
+        return True
 
     def get_lr_mult(self):
         return warmup_linear(self.step_count, self.t_total, self.warmup)
@@ -169,6 +206,7 @@ class HipBertAdam:
 
     def step_main(self):
         """every tensor except the embedding tables (+ the k-contiguous weight copy the next forward / dgrad reads)"""
+        self.sync_frozen()
         self._launch(0)
         self.arena.refresh_transposed()
 
@@ -266,8 +304,8 @@ class HipAdam(HipBertAdam):
 
     def _build_descs(self, select):
         if self.kind == "adam":
-            return self.arena.build_descs(self.lr, self.lr, select=select, wd=self.l2)
-        return self.arena.build_descs(self.lr, self.bert_lr, select=select)
+            return self.arena.build_descs(self.lr, self.lr, select=select, wd=self.l2, active=self._active())
+        return self.arena.build_descs(self.lr, self.bert_lr, select=select, active=self._active())
 
     def get_lr_mult(self):
         return 1.0 if self.scheduler is None else self.scheduler.get_lr_mult()
@@ -286,6 +324,7 @@ class HipAdam(HipBertAdam):
 
     def step_main(self):
         """the block norms of every tensor but the embedding tables: nothing is updated before their gradients are in"""
+        self.sync_frozen()
         if self.sharded and self.max_grad_norm > 0:
             self.partial.zero_()
         self._norms(0)

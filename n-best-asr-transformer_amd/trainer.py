@@ -22,6 +22,7 @@ import torch.distributed as dist
 from . import hipabi as hb
 from .fscore import compute_f1, update_f1
 from .inputs import collate, encode_utterance, prepare_inputs_for_roberta
+from .model import freeze_plan
 
 
 # ------------------------------------------------------------------------------------------------
@@ -109,6 +110,33 @@ class GradReducer:
         self._sparse = None
         self._side = None         # side stream + pinned buffer that bring the per-rank row counts to the host
         self._cnt_host = None
+        self.trainable = None     # arena ranges of the trainable tensors (set_trainable); None = every tensor
+        self.word_frozen = False
+        self._trainable_names = None
+
+    def set_trainable(self, names):
+        """only the gradients of the tensors ``names`` (model.FreezePlan.trainable) are exchanged from the next step on: frozen
+        ranges are never launched, a frozen word table skips the sparse row exchange and its count all-gather.  Every rank must
+        pass the same set.  With every tensor but the pooler trainable the buckets are the full ones.  Cached per set (one pass
+        over the slots when it changes)."""
+        if names is self._trainable_names:
+            return
+        self._trainable_names = names
+        ranges, cur, all_on = [], None, True
+        for s in sorted(self.arena.slots, key=lambda s: s.offset):
+            if s.name not in names:
+                all_on = all_on and "pooler" in s.name
+                cur = None                               # a frozen tensor (or the pooler) ends the running range
+            elif cur is not None:
+                cur[1] = s.offset + s.numel              # nothing frozen in between: one range
+            else:
+                cur = [s.offset, s.offset + s.numel]
+                ranges.append(cur)
+        if all_on:
+            self.trainable, self.word_frozen = None, False
+            return
+        self.trainable = [tuple(r) for r in ranges]
+        self.word_frozen = "bert_encoder.embeddings.word_embeddings.weight" not in names
 
     # ---- sparse word-embedding rows ------------------------------------------------------------------------------------
     def set_step_tokens(self, *id_tensors, rows=None):
@@ -116,7 +144,7 @@ class GradReducer:
         size the host already knows - EncodedSplit / bench.py build it on the host, so nothing synchronises), or the
         token-id tensors themselves (then the unique rows are computed on the device, which costs one host
         synchronisation at the start of the step).  The per-rank row counts are exchanged asynchronously right away."""
-        if not (self.sparse and self.world > 1):
+        if not (self.sparse and self.world > 1) or self.word_frozen:
             return
         dev = self.arena.device
         if rows is None:
@@ -186,6 +214,14 @@ class GradReducer:
     def _launch(self, lo, hi, last=False):
         if not (dist.is_available() and dist.is_initialized() and hi > lo):
             return
+        if self.trainable is not None:                          # the trainable pieces of the bucket only
+            for tlo, thi in self.trainable:
+                if min(hi, thi) > max(lo, tlo):
+                    self._launch_range(max(lo, tlo), min(hi, thi), last)
+            return
+        self._launch_range(lo, hi, last)
+
+    def _launch_range(self, lo, hi, last):
         todo = self.pending_emb if last else self.pending
         if self.owner_ranges is None:
             todo.append(dist.all_reduce(self.arena.g[lo:hi], op=dist.ReduceOp.SUM, async_op=True))
@@ -201,7 +237,7 @@ class GradReducer:
             self._launch(*self.arena.heads_range)    # head gradients were complete before the encoder backward began
         self._launch(self.arena.layer_range[l_lo][0], self.arena.layer_range[l_hi - 1][1])
         if l_lo == 0:                                # embedding backward is the last kernel of the chunk
-            if self.sparse and self.world > 1:
+            if self.sparse and self.world > 1 and not self.word_frozen:
                 if self._tok is None:
                     raise RuntimeError("GradReducer: sparse word-embedding exchange needs set_step_tokens() before the step")
                 self._launch(self.word[1], self.arena.emb_range[1], last=True)
@@ -238,6 +274,15 @@ class GradReducer:
         self.reduce_all()
 
 
+def sync_frozen(model, optimizer, reducer=None):
+    """the model's frozen set (requires_grad) into the optimizer's descriptors and the reducer's ranges, before the step's
+    exchange: a sharded plan and its reduce-to-owner then agree"""
+    if hasattr(optimizer, "sync_frozen"):
+        optimizer.sync_frozen()
+    if reducer is not None:
+        reducer.set_trainable(freeze_plan(model).trainable)
+
+
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
@@ -249,6 +294,7 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
     # B_local rows, so after the SUM all-reduce the term needs the weight B_local / B_global (= 1/world for equal shards)
     mse_scale = b_local / float(global_batch) if global_batch else 1.0 / world
+    sync_frozen(model, optimizer, reducer)
     if reducer is not None:
         reducer.set_step_tokens(batch["ids"], batch.get("tids") if add_l2_loss else None, rows=batch.get("word_rows"))
     out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
@@ -657,6 +703,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             if first:
                 model.arena.g.zero_()
             if last:
+                sync_frozen(model, opt.optimizer, reducer)
                 if reducer is not None:
                     reducer.set_step_tokens(*group_rows)
                     reducer.reduce_all()
@@ -677,6 +724,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"))
             group_rows.append(b["word_rows"])
             if last:
+                sync_frozen(model, opt.optimizer, reducer)
                 if reducer is not None:
                     reducer.set_step_tokens(*group_rows)
                     reducer.reduce_all()
