@@ -240,6 +240,20 @@ int nbest_attention_fwd(const void* qkv, const uint8_t* key_mask, void* ctx, flo
  * kv = qkv + H, ldkv = 3 H.)                                                                                                   */
 int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
                             int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
+/* Attention probabilities (an eval / predict output; the forward kernels keep P in registers).  From what the forward stashed,
+ * qkv [M][3H] (layout, scale and key_mask rule of nbest_attention_fwd) and its lse [B][heads][S] (natural-log units):
+ *   probs[b][h][i][j] = exp(scale q_i . k_j - lse[b][h][i]) for key_mask[b][j] != 0, exactly 0 for masked keys; fp32
+ *   [B][heads][S][S], every element written.  A row with no unmasked key is all 0 in both dtypes (the bf16 forward gives NaN ctx
+ *   there).  No dropout: the pre-dropout probabilities.  d = 64, 1 <= S <= 512; qkv 16-byte aligned.  bf16: Q K^T on the
+ *   16x16x32 bf16 MFMA with fp32 accumulation; fp32: one sequential fma chain over d per score, as the fp32 forward.  Bit-
+ *   reproducible (no atomics).  Writes S^2 x 4 bytes per (utterance, head).                                                  */
+int nbest_attention_probs(const void* qkv, const uint8_t* key_mask, const float* lse, float* probs, int B, int S, int heads, int d,
+                          int dtype, nbest_stream_t stream);
+/* The CLS row of it (inference): arguments, strides and semantics of nbest_attention_cls_fwd, no LSE - the row is normalised with
+ * the scores, max and sum that kernel computes - and no P.V.  Writes fp32 probs[(b heads + h) ldp + j], j < S (ldp >= S); masked
+ * keys 0, a fully masked row all 0; unrounded in both dtypes.                                                                 */
+int nbest_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
+                              int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 /* dqkv [M][3H] receives dQ | dK | dV (overwritten, no accumulation).  dbias != NULL: dbias[3H] (+)= column
  * sums of dqkv (the Q|K|V bias gradient), fused into the kernel; ws >= nbest_attention_bwd_ws_bytes().   */
 size_t nbest_attention_bwd_ws_bytes(int B, int S, int heads);
@@ -519,6 +533,10 @@ typedef struct nbest_encoder_desc {
   const uint8_t* wgrad_skip_host;
 } nbest_encoder_desc;
 size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
+/* Pointers into a stash `act` written by nbest_encoder_forward with descriptor d: layer `layer`'s qkv [M][3H] (dtype; also in the fp8
+ * forward and its calibration pass) and lse [B][heads][S] (fp32) - the inputs of nbest_attention_probs.  Refuses (NBEST_ERR_ARG) a
+ * layer outside [first_trainable, L): frozen layers are not stashed.  Enqueues nothing.                                           */
+int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, int layer, void** qkv, float** lse);
 size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d);
 /* weight-gradient launches nbest_encoder_backward enqueues per layer for this descriptor: 3 when the attention-output gradient
  * rides with the QKV gradient (nbest_wgrad_pair; bf16, shapes that fit), else 4 */
@@ -547,6 +565,12 @@ int nbest_encoder_backward(const nbest_encoder_desc* d, const void* wts, const v
 size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d);
 int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                         const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, nbest_stream_t stream);
+/* nbest_encoder_infer plus cls_attn [L][B][heads][S] fp32: the CLS row's attention probabilities of every layer
+ * (nbest_attention_cls_probs, launched after the layer's QKV projection; last layer: from the CLS-row Q and the K|V it forms).
+ * cls_attn == NULL is nbest_encoder_infer, launch for launch.  Same workspace.                                                  */
+int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                             const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, float* cls_attn,
+                             nbest_stream_t stream);
 
 #ifdef __cplusplus
 }

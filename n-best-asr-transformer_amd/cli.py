@@ -71,6 +71,10 @@ def parse_arguments(argv=None):
                    help="label an n-best file with <exp_dir>/model.pt (loaded as --testing does): one 'ASR \\t<=>\\t labels' line per "
                         "input line, in input order.  Input lines need only the ASR field.  One GPU")
     g.add_argument("--predict_output", default=None, metavar="PATH", help="--predict output (default: <exp_dir>/<basename of FILE>.pred)")
+    g.add_argument("--predict_attention", default=None, metavar="PATH",
+                   help="with --predict: also write one JSON line per input line, in input order - the segments of the utterance "
+                        "(cls, sys, h1, h2, ..), their token counts and, per layer, the share of the CLS row's attention (mean over "
+                        "heads) that falls on each segment")
     g.add_argument("--deviceId", type=int, default=-1,
                    help="as the reference (n_best_asr_bert.py:116-126): 0 = pick a GPU automatically (here: the first visible one; "
                         "the reference asks gpustat / NVML for the least loaded), k > 0 = GPU k-1, -1 = CPU (refused: the path is "
@@ -137,6 +141,8 @@ def parse_arguments(argv=None):
                  "with an IndexError; use bert or xlm-roberta")
     if opt.pre_trained_model and opt.pre_trained_model not in ncfg.NAMED:
         ap.error("--pre_trained_model %s: known shapes are %s" % (opt.pre_trained_model, ", ".join(sorted(ncfg.NAMED))))
+    if opt.predict_attention is not None and opt.predict is None:
+        ap.error("--predict_attention is an output of --predict: pass --predict FILE too")
     if opt.predict is not None:
         if not os.path.isfile(opt.predict):
             ap.error("--predict %s: no such file" % opt.predict)
@@ -275,7 +281,12 @@ def main(argv=None):
         model.load_model(os.path.join(opt.exp_dir, "model.pt"))
         out_path = predict_output_path(opt)
         t0 = time.time()
-        cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory)
+        attn_fp = open(opt.predict_attention, "w") if opt.predict_attention else None
+        try:
+            cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp)
+        finally:
+            if attn_fp is not None:
+                attn_fp.close()
         with open(out_path, "w") as fp:
             for raw, pc in cases:
                 fp.write("%s\t<=>\t%s\n" % (" ".join(raw), ";".join(pc)))

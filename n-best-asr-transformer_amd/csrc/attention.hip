@@ -1236,11 +1236,13 @@ static void launch_fwd(const bf16* qkv, const uint8_t* mask, bf16* ctx, float* l
 // chain over d (attn_fwd_f32_kernel), p = exp(s - lse); bf16 - the probabilities are rounded to bf16 before P.V, in log2 units for
 // S <= 256 (attn_fwd_bf16_kernel) and natural units above (attn_fwd_long_bf16_kernel).
 // Fully masked row (S = 1 under XLM-R, quirk Q1): fp32 writes 0 and bf16 writes NaN, as those kernels do.
+// PROBS (nbest_attention_cls_probs): the same scores, max and sum, then the fp32 probabilities of the row go to
+// probs[bh * ldp + j] and P.V is skipped - unrounded in both dtypes, 0 on masked keys (a fully masked row: all 0).
 // =================================================================================================
-template <typename T>
+template <typename T, bool PROBS>
 __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kv, int64_t ldkv,
                                                            const uint8_t* __restrict__ mask, T* __restrict__ ctx, int64_t ldctx, int S,
-                                                           int heads, int H, float scale) {
+                                                           int heads, int H, float scale, float* __restrict__ probs, int64_t ldp) {
   constexpr bool kF32 = sizeof(T) == 4;
   constexpr int VEC = 16 / (int)sizeof(T);   // elements per 16-byte load
   constexpr int LPK = 64 / VEC;              // lanes per 64-wide head row: 8 (bf16) / 16 (fp32)
@@ -1299,6 +1301,14 @@ __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__
   sum = (red[4] + red[5]) + (red[6] + red[7]);
   // ---- probabilities: fp32 exp(s - lse) (masked keys 0); bf16 rounded to bf16 after normalising ----
   const float lse = mxs + logf(sum), inv = 1.0f / sum;
+  if constexpr (PROBS) {
+    float* pr = probs + (int64_t)bh * ldp;
+    for (int j = tid; j < S; j += 256) {
+      const float v = sc[j];
+      pr[j] = (v == -INFINITY) ? 0.f : (kF32 ? expf(v - lse) : ex(v) * inv);
+    }
+    return;
+  }
   for (int j = tid; j < S; j += 256) {
     const float v = sc[j];
     sc[j] = kF32 ? (v == -INFINITY ? 0.f : expf(v - lse)) : (float)(bf16)(ex(v) * inv);
@@ -1326,6 +1336,129 @@ __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__
     T* op = ctx + (int64_t)b * ldctx + h * 64 + tid;
     if constexpr (kF32) *op = acc;
     else *op = (bf16)acc;
+  }
+}
+
+// =================================================================================================
+// Attention probabilities from the forward's stash (nbest_attention_probs): P[b,h,i,j] = exp(scale q_i.k_j - lse[b,h,i]) on
+// unmasked keys, 0 on masked ones, fp32 [B][heads][S][S].  The kernels are bound by the stores (S^2 x 4 B written per head against
+// 2 S x 64 x esz read), so both write the output as 16-byte stores of 4 consecutive keys, every element exactly once (no atomics:
+// reproducible run to run).  A row without an unmasked key (lse = -inf) is all 0.
+//   bf16: wave = 16 queries x 64 keys per step.  Scores SWAPPED, S^T = K . Q^T on v_mfma_f32_16x16x32_bf16 (two k-steps over
+//         d = 64; A = 16 key rows, B = Q^T, both fetched as 16-byte row fragments straight from qkv), so a lane holds 4
+//         consecutive keys of one query (col = lane & 15, rows 4 (lane >> 4) + r).  The [16][64] fp32 tile goes through a
+//         per-wave LDS image and leaves as 4 stores of 4 rows x 256 B each: whole 128-B lines when S % 32 == 0.
+//   fp32: thread = (query, 4 consecutive keys); each score is one sequential fma chain over d, as attn_fwd_f32_kernel.
+// VEC: S % 4 == 0 and a 16-byte aligned output (else one 4-byte store per element).
+// =================================================================================================
+template <bool VEC>
+__global__ __launch_bounds__(256) void attn_probs_bf16_kernel(const bf16* __restrict__ qkv, const uint8_t* __restrict__ mask,
+                                                              const float* __restrict__ lse, float* __restrict__ probs, int S,
+                                                              int heads, int H, float scale) {
+  constexpr int LDI = 68;                       // image row stride (floats): 4 banks of skew per row
+  __shared__ __attribute__((aligned(16))) float img[4][16 * LDI];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+  const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+  const int q0 = 64 * blockIdx.y + 16 * wave;
+  if (q0 >= S) return;                          // (no barrier below: every wave works alone)
+  const int64_t ld = 3 * (int64_t)H;
+  const bf16* base = qkv + (int64_t)b * S * ld;
+  const uint8_t* mk = mask + (int64_t)b * S;
+  float* im = img[wave];
+  const int qrow = q0 + c;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const i32x4 raw = (qrow < S) ? *(const i32x4*)(base + (int64_t)qrow * ld + h * 64 + 32 * ks + 8 * g) : i32x4{0, 0, 0, 0};
+    qf[ks] = __builtin_bit_cast(bf16x8, raw);
+  }
+  const float lq = (qrow < S) ? lse[(int64_t)bh * S + qrow] : 0.f;
+  float* out = probs + (int64_t)bh * S * S;
+  const int nkb = (S + 63) / 64;
+  for (int kb = 0; kb < nkb; ++kb) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int key = 64 * kb + 16 * t + c;
+      acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const i32x4 raw = (key < S) ? *(const i32x4*)(base + (int64_t)key * ld + H + h * 64 + 32 * ks + 8 * g) : i32x4{0, 0, 0, 0};
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, raw), qf[ks], acc[t], 0, 0, 0);
+      }
+    }
+    // acc[t][r] = q_(q0 + c) . k_(64 kb + 16 t + 4 g + r): probabilities into row c of the image
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      f32x4 p;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = 64 * kb + 16 * t + 4 * g + r;
+        p[r] = (key < S && mk[key]) ? expf(acc[t][r] * scale - lq) : 0.f;
+      }
+      *(f32x4*)(im + c * LDI + 16 * t + 4 * g) = p;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // rows 4 i + g, keys 64 kb + 4 c .. + 3: 16 lanes per 256-byte row segment
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * i + g, q = q0 + row, key = 64 * kb + 4 * c;
+      const f32x4 v = *(const f32x4*)(im + row * LDI + 4 * c);
+      if (q < S && key < S) {
+        float* dst = out + (int64_t)q * S + key;
+        if (VEC) {
+          *(f32x4*)dst = v;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (key + e < S) dst[e] = v[e];
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the image is rewritten by the next key block
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void attn_probs_f32_kernel(const float* __restrict__ qkv, const uint8_t* __restrict__ mask,
+                                                             const float* __restrict__ lse, float* __restrict__ probs, int S, int heads,
+                                                             int H, float scale) {
+  const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+  const int n4 = (S + 3) / 4;
+  const int idx = blockIdx.y * 256 + threadIdx.x;
+  if (idx >= S * n4) return;
+  const int i = idx / n4, j0 = 4 * (idx - i * n4);
+  const int64_t ld = 3 * (int64_t)H;
+  const float* base = qkv + (int64_t)b * S * ld;
+  const float* qp = base + i * ld + h * 64;
+  float q[64];
+#pragma unroll
+  for (int d = 0; d < 64; d += 4) {
+    const f32x4 x = *(const f32x4*)(qp + d);
+    q[d] = x[0]; q[d + 1] = x[1]; q[d + 2] = x[2]; q[d + 3] = x[3];
+  }
+  const float lse_i = lse[(int64_t)bh * S + i];
+  f32x4 p;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = j0 + e;
+    float pv = 0.f;
+    if (j < S && mask[b * S + j]) {
+      const float* kp = base + j * ld + H + h * 64;
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < 64; ++d) s = fmaf(q[d], kp[d], s);
+      pv = expf(s * scale - lse_i);
+    }
+    p[e] = pv;
+  }
+  float* dst = probs + ((int64_t)bh * S + i) * S + j0;
+  if (VEC) {
+    *(f32x4*)dst = p;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (j0 + e < S) dst[e] = p[e];
   }
 }
 
@@ -1397,9 +1530,11 @@ int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv,
   const float scale = 1.0f / sqrtf((float)d);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == NBEST_F32)
-    attn_cls_fwd_kernel<float><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, (float*)ctx, ldctx, S, heads, H, scale);
+    attn_cls_fwd_kernel<float, false><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, (float*)ctx, ldctx, S,
+                                                                 heads, H, scale, nullptr, 0);
   else
-    attn_cls_fwd_kernel<bf16><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, (bf16*)ctx, ldctx, S, heads, H, scale);
+    attn_cls_fwd_kernel<bf16, false><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, (bf16*)ctx, ldctx, S,
+                                                                heads, H, scale, nullptr, 0);
   NB_LAUNCH_CHECK();
   return NBEST_OK;
 }
@@ -1407,6 +1542,58 @@ int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv,
 extern "C" int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
                                        int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
   return nbest_attention_cls_fwd_internal(q, ldq, kv, ldkv, key_mask, ctx, ldctx, B, S, heads, d, dtype, stream);
+}
+
+extern "C" int nbest_attention_probs(const void* qkv, const uint8_t* key_mask, const float* lse, float* probs, int B, int S, int heads,
+                                     int d, int dtype, nbest_stream_t stream) {
+  NB_CHECK(qkv && key_mask && lse && probs, NBEST_ERR_ARG, "attention_probs: null pointer");
+  if (int e = check_common("attention_probs", B, S, heads, d, dtype)) return e;
+  NB_CHECK(S <= 512, NBEST_ERR_SHAPE, "attention_probs: S=%d > 512", S);
+  NB_CHECK(((uintptr_t)qkv & 15) == 0, NBEST_ERR_ALIGN, "attention_probs: qkv must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int H = heads * d;
+  const float scale = 1.0f / sqrtf((float)d);
+  const bool vec = (S % 4) == 0 && ((uintptr_t)probs & 15) == 0;
+  if (dtype == NBEST_F32) {
+    const dim3 grid(B * heads, (S * ((S + 3) / 4) + 255) / 256);
+    if (vec) attn_probs_f32_kernel<true><<<grid, 256, 0, st>>>((const float*)qkv, key_mask, lse, probs, S, heads, H, scale);
+    else attn_probs_f32_kernel<false><<<grid, 256, 0, st>>>((const float*)qkv, key_mask, lse, probs, S, heads, H, scale);
+  } else {
+    const dim3 grid(B * heads, (S + 63) / 64);
+    if (vec) attn_probs_bf16_kernel<true><<<grid, 256, 0, st>>>((const bf16*)qkv, key_mask, lse, probs, S, heads, H, scale);
+    else attn_probs_bf16_kernel<false><<<grid, 256, 0, st>>>((const bf16*)qkv, key_mask, lse, probs, S, heads, H, scale);
+  }
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+int nbest_internal_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
+                                       int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
+  NB_CHECK(q && kv && key_mask && probs, NBEST_ERR_ARG, "attention_cls_probs: null pointer");
+  NB_CHECK(B > 0 && S > 0 && heads > 0, NBEST_ERR_SHAPE, "attention_cls_probs: bad shape");
+  NB_CHECK(d == 64, NBEST_ERR_SHAPE, "attention_cls_probs: head dimension %d not supported (64 only)", d);
+  NB_CHECK(dtype == NBEST_F32 || dtype == NBEST_BF16, NBEST_ERR_DTYPE, "attention_cls_probs: bad dtype %d", dtype);
+  NB_CHECK(S <= 512, NBEST_ERR_SHAPE, "attention_cls_probs: S=%d > 512", S);
+  const int H = heads * d;
+  const int vec = dtype == NBEST_BF16 ? 8 : 4;
+  NB_CHECK(ldq >= H && ldkv >= 2 * H && ldp >= S && ldq % vec == 0 && ldkv % vec == 0, NBEST_ERR_ALIGN,
+           "attention_cls_probs: leading dimensions must cover the heads / keys and be multiples of %d elements", vec);
+  NB_CHECK(((uintptr_t)q & 15) == 0 && ((uintptr_t)kv & 15) == 0, NBEST_ERR_ALIGN, "attention_cls_probs: q and kv must be 16-byte aligned");
+  const float scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == NBEST_F32)
+    attn_cls_fwd_kernel<float, true><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, nullptr, 0, S,
+                                                                heads, H, scale, probs, ldp);
+  else
+    attn_cls_fwd_kernel<bf16, true><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, nullptr, 0, S,
+                                                               heads, H, scale, probs, ldp);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
+                                         int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
+  return nbest_internal_attention_cls_probs(q, ldq, kv, ldkv, key_mask, probs, ldp, B, S, heads, d, dtype, stream);
 }
 
 extern "C" size_t nbest_attention_bwd_ws_bytes(int B, int S, int heads) {

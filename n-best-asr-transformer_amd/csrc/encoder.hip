@@ -217,6 +217,18 @@ static int gemm(int dtype, const void* A, const void* B, void* C, int64_t M, int
 }  // namespace
 
 extern "C" size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d) { return d ? act_layout(d).total : 0; }
+
+extern "C" int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, int layer, void** qkv, float** lse) {
+  RUN(check_desc(d));
+  NB_CHECK(act && qkv && lse, NBEST_ERR_ARG, "encoder_act_view: null pointer");
+  NB_CHECK(0 <= layer && layer < d->L, NBEST_ERR_ARG, "encoder_act_view: layer %d outside [0, L=%d)", layer, d->L);
+  const ActLayout a = act_layout(d);
+  NB_CHECK(layer >= a.K, NBEST_ERR_ARG, "encoder_act_view: layer %d < first_trainable %d (frozen layers are not stashed)", layer, a.K);
+  char* Lb = (char*)act + a.layer0 + (size_t)(layer - a.K) * a.layer_stride;
+  *qkv = Lb + a.o_qkv;
+  *lse = (float*)(Lb + a.o_lse);
+  return NBEST_OK;
+}
 extern "C" size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d) { return d ? ws_layout(d).total : 0; }
 extern "C" int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d) {
   return d ? (wgrad_paired(d, fp8_backward_active(d)) ? 3 : 4) : 0;
@@ -542,9 +554,11 @@ static InferLayout infer_layout(const nbest_encoder_desc* d) {
 
 extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(d).total : 0; }
 
-extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
-                                   const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
-                                   nbest_stream_t stream) {
+// cls_attn != NULL: also the CLS row's attention probabilities of every layer, [L][B][heads][S] fp32, each launched right after the
+// layer's QKV projection (last layer: after the CLS-row Q)
+extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                        const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                        float* cls_attn, nbest_stream_t stream) {
   RUN(check_desc(d));
   NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
            "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
@@ -572,6 +586,9 @@ extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts,
     const uint32_t s0 = sb + 1 + 4 * l;
     RUN(gemm(dt, xin, P.W(o.wqkv), qkv, M, 3 * H, H, H, H, 3 * H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv), nullptr, 0, nullptr, 0,
              nullptr, 0, 0, 0.f, 0, 0, st, nullptr, PK(o.wqkv)));
+    if (cls_attn)   // q = row 0 of each utterance (ldq = S 3H), K | V = the second and third thirds of every row
+      RUN(nbest_internal_attention_cls_probs(qkv, SH * 3, (const char*)qkv + H * esz, 3 * H, key_mask, cls_attn + (int64_t)l * B * d->heads * d->S,
+                                             d->S, d->B, d->S, d->heads, 64, dt, stream));
     RUN(nbest_internal_attention_fwd8(qkv, key_mask, ctx, nullptr, lse, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream,
                                       nullptr, nullptr, nullptr));
     RUN(gemm(dt, ctx, P.W(o.wo), r1, M, H, H, H, H, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo), xin, H, nullptr, 0, nullptr, 0, 0,
@@ -592,6 +609,9 @@ extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts,
            nullptr, 0, nullptr, 0, 0, 0.f, 0, 0, st));                                                    // K | V, all rows
   RUN(gemm(dt, xin, P.W(o.wqkv), q, B, H, H, SH, H, H, 0, 0, NBEST_EPI_BIAS, P.P(o.bqkv), nullptr, 0, nullptr, 0, nullptr, 0, 0, 0.f,
            0, 0, st));                                                                                    // Q, CLS rows (lda = S H)
+  if (cls_attn)
+    RUN(nbest_internal_attention_cls_probs(q, H, kv, 2 * H, key_mask, cls_attn + (int64_t)l * B * d->heads * d->S, d->S, d->B, d->S, d->heads,
+                                           64, dt, stream));
   RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream));
   RUN(gemm(dt, cctx, P.W(o.wo), cr, B, H, H, H, H, H, 0, 0, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo), xin, SH, nullptr, 0, nullptr, 0, 0, 0.f,
            0, 0, st));                                                                                    // residual: the CLS rows
@@ -602,4 +622,10 @@ extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts,
            0, 0, st));
   RUN(nbest_internal_layernorm_fwd8(cr, P.P(o.ln2_g), P.P(o.ln2_b), cls_out, nullptr, st2, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
   return NBEST_OK;
+}
+
+extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                   const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                   nbest_stream_t stream) {
+  return nbest_encoder_infer_attn(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, stream);
 }

@@ -37,6 +37,8 @@ int nbest_internal_attention_bwd8(const void* qkv, const uint8_t* key_mask, cons
 size_t nbest_internal_attention_keep_bytes(int B, int S, int heads);
 int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
                                      int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
+int nbest_internal_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
+                                       int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 
 // ---- gemm.hip: what the GEMM generations share ---------------------------------------------------
 // Split-K plan of a grid of `tiles` output tiles: the smallest split count whose grid fills whole rounds of the `slots`

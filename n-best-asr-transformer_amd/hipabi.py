@@ -25,6 +25,7 @@ EXPORTS = [
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_forward",
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
     "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
+    "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
 ]
 
 
@@ -145,6 +146,10 @@ def lib():
         L.nbest_encoder_infer_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_infer.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp]
         L.nbest_attention_cls_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
+        L.nbest_encoder_infer_attn.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp, vp]
+        L.nbest_encoder_act_view.argtypes = [C.POINTER(EncoderDesc), vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.nbest_attention_probs.argtypes = [vp] * 4 + [i32] * 5 + [vp]
+        L.nbest_attention_cls_probs.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
         L.nbest_encoder_backward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 9 + [sz, vp, vp, sz, i32, i32, i32, i32, vp]
         L.nbest_transpose_weights.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nbest_pack_bn.argtypes = [i64]
@@ -440,6 +445,44 @@ def attention_cls_fwd(q, ldq, kv, ldkv, key_mask, B, S, heads, out=None):
     check(lib().nbest_attention_cls_fwd(ptr(q), ldq, ptr(kv), ldkv, ptr(key_mask), ptr(ctx), ctx.stride(0), B, S, heads, 64,
                                         dtype_code(kv.dtype), stream_ptr()), "attention_cls_fwd")
     return ctx
+
+
+def attention_probs(qkv, key_mask, lse, B, S, heads, out=None):
+    """nbest_attention_probs: the softmax probabilities of the forward that stashed ``qkv`` and ``lse`` -> fp32 [B, heads, S, S]
+    (masked keys 0, no dropout)"""
+    probs = torch.empty(B, heads, S, S, dtype=torch.float32, device=qkv.device) if out is None else out
+    check(lib().nbest_attention_probs(ptr(qkv), ptr(key_mask), ptr(lse), ptr(probs), B, S, heads, 64, dtype_code(qkv.dtype),
+                                      stream_ptr()), "attention_probs")
+    return probs
+
+
+def attention_cls_probs(q, ldq, kv, ldkv, key_mask, B, S, heads, out=None):
+    """nbest_attention_cls_probs: the probabilities of one query row per (utterance, head) -> fp32 [B, heads, S]
+    (arguments of attention_cls_fwd; ``out``: rows of stride out.stride(1))"""
+    probs = torch.empty(B, heads, S, dtype=torch.float32, device=kv.device) if out is None else out
+    check(lib().nbest_attention_cls_probs(ptr(q), ldq, ptr(kv), ldkv, ptr(key_mask), ptr(probs), probs.stride(1), B, S, heads, 64,
+                                          dtype_code(kv.dtype), stream_ptr()), "attention_cls_probs")
+    return probs
+
+
+def encoder_act_view(desc, act, layer):
+    """nbest_encoder_act_view: (qkv, lse) device addresses of ``layer`` inside the stash ``act`` (a uint8 tensor) that
+    nbest_encoder_forward wrote with ``desc``; raises for a frozen (unstashed) layer"""
+    q, l = C.c_void_p(), C.c_void_p()
+    check(lib().nbest_encoder_act_view(C.byref(desc), ptr(act), layer, C.byref(q), C.byref(l)), "encoder_act_view")
+    return q.value, l.value
+
+
+def encoder_infer(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, cls_attn=None):
+    """nbest_encoder_infer -> cls_out [B, H]; with ``cls_attn`` (fp32 [L, B, heads, S]) nbest_encoder_infer_attn, which also
+    writes the CLS row's attention probabilities of every layer"""
+    if cls_attn is None:
+        check(lib().nbest_encoder_infer(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
+                                        ws.numel(), ptr(cls_out), stream_ptr()), "encoder_infer")
+    else:
+        check(lib().nbest_encoder_infer_attn(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
+                                             ws.numel(), ptr(cls_out), ptr(cls_attn), stream_ptr()), "encoder_infer_attn")
+    return cls_out
 
 
 def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, dbias=None, keep=None):

@@ -183,6 +183,52 @@ def encode_utterance(seq, tokenizer, opt, n_best=None, max_seq_len=None):
     return tokenizer.convert_tokens_to_ids(toks), seg
 
 
+def utterance_segments(seq, tokenizer, opt, n_best=None, max_seq_len=None):
+    """the token spans of one utterance as ``encode_utterance`` lays it out (same arguments): ``[("cls", 0, 1), ("sys", 1, b),
+    ("h1", b, c), ...]``, half-open, covering every token of ``encode_utterance(...)[0]`` in order.  A separator (run) belongs to
+    the segment it closes: the first separator (XLM-R: the "</s></s>" token) ends "sys", each hypothesis ends with the separator
+    after it, the last one with the closing separator.  ToD markers: "[SYS]" opens "sys", "[USR]" opens "h1".
+    ``--without_system_act`` (not ToD): no "sys" span.  A ``max_seq_len`` cut clips the spans and gives the re-closing
+    separator to the last span it keeps."""
+    family = getattr(opt, "pre_trained_model", None)
+    tod = getattr(opt, "tod_pre_trained_model", None)
+    no_sys = getattr(opt, "without_system_act", False)
+    sep = tokenizer.sep_token
+    first_sep = sep + sep if family == "xlm-roberta" else sep
+    seq = cut_n_best(list(seq), n_best)
+    usr = seq.index("[USR]")
+    a_words, b_words = seq[2:usr], seq[usr + 1:]
+    ntok = lambda words: sum(len(tokenizer.tokenize(w)) for w in words)
+    spans = [["cls", 1]]                                     # [name, length]: the layout of encode_utterance, piece by piece
+    if tod:
+        spans.append(["sys", ntok(["[SYS]"] + a_words)])
+    elif not no_sys:
+        spans.append(["sys", ntok(a_words) + 1])             # + the first separator, one entry of the token list
+    hyps, cur = [], ntok(["[USR]"]) if tod else 0
+    for w in b_words:
+        if w == "[SEP]":
+            hyps.append(cur + ntok([first_sep]))
+            cur = 0
+        else:
+            cur += ntok([w])
+    hyps.append(cur + 1)                                     # the closing separator
+    spans += [["h%d" % (i + 1), n] for i, n in enumerate(hyps)]
+    if max_seq_len and sum(n for _, n in spans) > max_seq_len:
+        keep, room = [], max_seq_len - 1
+        for name, n in spans:
+            if room <= 0:
+                break
+            keep.append([name, min(n, room)])
+            room -= n
+        keep[-1][1] += 1                                     # the separator that re-closes the cut sequence
+        spans = keep
+    out, a = [], 0
+    for name, n in spans:
+        out.append((name, a, a + n))
+        a += n
+    return out
+
+
 def collate(rows, pad_id, pin=False, alloc=None):
     """[(ids, seg | None)] -> right-padded int64 host tensors ``ids [B,S]``, ``seg [B,S] | None`` and the lengths
     (bert_xlnet_inputs.py:87-102: pad id for ids, 0 for segments, width = batch maximum).  One masked numpy assignment per

@@ -3,7 +3,8 @@
 Mirrors the reference interface of /root/reference/models/model.py:
   * ``make_model(opt)``                                                        (:7-9)
   * ``model(opt, input_ids, trans_input_ids, seg_ids=, trans_seg_ids=, classifier_input_type=)``
-    -> ``(top_scores, bottom_scores_dict, final_scores, asr_cls, trans_cls)``  (:35-73)
+    -> ``(top_scores, bottom_scores_dict, final_scores, asr_cls, trans_cls)``  (:35-73); ``return_attns=True`` (eval / no_grad)
+    -> ``(top_scores, bottom_scores_dict, final_scores, attns, asr_cls, trans_cls)``  (:68-69)
   * ``save_model / load_model`` with the reference's state-dict keys            (:75-83)
   * parameters named ``bert_encoder.*`` / ``clf.*`` with HF sub-names, so the learning-rate and
     weight-decay grouping of /root/reference/n_best_asr_bert.py:540-550 applies unchanged.
@@ -479,10 +480,13 @@ class NBestSTCModel(nn.Module):
                             seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
-                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None):
+                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None):
         """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
-        ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs)."""
+        ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs).
+        ``after_asr(record)``: called right after the ASR pass, before any other pass can touch a stash."""
         ra = self._encode(0, ids, seg, train, perm, plan)
+        if after_asr is not None:
+            after_asr(ra)
         rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan)
         r = rt if from_transcript else ra
         return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws)
@@ -499,8 +503,13 @@ class NBestSTCModel(nn.Module):
     def forward(self, opt, input_ids, trans_input_ids=None, seg_ids=None, trans_seg_ids=None, return_attns=False,
                 classifier_input_type="asr"):
         """Training mode under autograd: graph-attached outputs (``_STCBridge``), so the reference's
-        ``total_loss.backward(); optimizer.step()`` loop body runs unmodified.  Otherwise (eval / no_grad): plain tensors."""
+        ``total_loss.backward(); optimizer.step()`` loop body runs unmodified.  Otherwise (eval / no_grad): plain tensors.
+        ``return_attns`` (eval / no_grad only): also ``attns``, a tuple of L fp32 tensors [B, heads, S, S] - the attention
+        probabilities of every layer of the ASR pass (the reference's return_attns branch), 4th in the 6-tuple."""
         if self.training and torch.is_grad_enabled():
+            if return_attns:
+                raise RuntimeError("nbest_amd: return_attns=True: attention maps are an eval / predict output - call model.eval() "
+                                   "or run the forward under torch.no_grad() (a training forward has no post-dropout maps)")
             if self._anchor is None:
                 self._anchor = torch.zeros(1, device=self.device, requires_grad=True)    # what makes the outputs require grad
             top, bott, fin, asr_cls, trans_cls = _STCBridge.apply(self._anchor, self, input_ids.contiguous(),
@@ -508,13 +517,36 @@ class NBestSTCModel(nn.Module):
                                                                   trans_seg_ids, classifier_input_type == "transcript")
             return top, self._bottoms_dict(bott), fin, asr_cls, (trans_cls if trans_input_ids is not None else None)
         with torch.no_grad():
-            return self._forward_plain(input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type)
+            return self._forward_plain(input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type, return_attns)
 
-    def _forward_plain(self, input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type):
+    def _forward_plain(self, input_ids, trans_input_ids, seg_ids, trans_seg_ids, classifier_input_type, return_attns=False):
+        attns = []
+        after = (lambda rec: attns.extend(self._attention_maps(rec))) if return_attns else None
         ra, rt, (top, bott, fin, _, _, _, _) = self._passes_and_heads(input_ids, seg_ids, trans_input_ids, trans_seg_ids, self.training,
-                                                                      from_transcript=classifier_input_type == "transcript")
+                                                                      from_transcript=classifier_input_type == "transcript",
+                                                                      after_asr=after)
         self._end_of_step(False, advance=False)
-        return top, self._bottoms_dict(bott), fin, ra.cls.float(), None if rt is None else rt.cls.float()
+        trans_cls = None if rt is None else rt.cls.float()
+        if return_attns:
+            return top, self._bottoms_dict(bott), fin, tuple(attns), ra.cls.float(), trans_cls
+        return top, self._bottoms_dict(bott), fin, ra.cls.float(), trans_cls
+
+    def _attention_maps(self, rec):
+        """fp32 [B, heads, S, S] per layer: the attention probabilities of the pass ``rec`` recorded, from the qkv and lse its
+        forward left in the slot's stash (nbest_encoder_act_view + nbest_attention_probs)"""
+        self._check_stash(rec)
+        ps = rec.ps
+        B, S, H, heads = ps.B, ps.S, self.cfg.hidden_size, self.cfg.num_attention_heads
+        act = self._stash[rec.slot]
+        base, esz = act.data_ptr(), (2 if self.compute_dtype == torch.bfloat16 else 4)
+        n_qkv, n_lse = B * S * 3 * H * esz, B * heads * S * 4
+        out = []
+        for l in range(self.cfg.num_hidden_layers):
+            qp, lp = hb.encoder_act_view(ps.desc, act, l)
+            qkv = act[qp - base:qp - base + n_qkv].view(self.compute_dtype)
+            lse = act[lp - base:lp - base + n_lse].view(torch.float32)
+            out.append(hb.attention_probs(qkv, rec.inputs[3], lse, B, S, heads))
+        return out
 
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
@@ -557,9 +589,11 @@ class NBestSTCModel(nn.Module):
         return dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
-    def predict(self, input_ids, seg_ids=None):
+    def predict(self, input_ids, seg_ids=None, return_attns=False):
         """Scores and decoded labels of one batch through nbest_encoder_infer: no activation stash, no dropout (in either
         mode), the heads on the compact CLS rows.  Returns dict(top, bott, final, cls [B, H] compute dtype, pred int32 [B, n_top]).
+        ``return_attns``: also ``cls_attn``, fp32 [L, B, heads, S] - the CLS row's attention probabilities of every layer
+        (nbest_encoder_infer_attn); the other outputs are the same bits as without it.
         Touches no training state: stashes, gradients, optimizer moments, step_counter and the fp8 amax histories stay as they
         are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it)."""
         cfg = self.cfg
@@ -576,12 +610,16 @@ class NBestSTCModel(nn.Module):
         ws = self._grow(vars(self), "_infer_ws", hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d)))
         a = self.arena
         cls = torch.empty(B, H, dtype=self.compute_dtype, device=self.device)
-        hb.check(hb.lib().nbest_encoder_infer(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos),
-                                              hb.ptr(mask), hb.ptr(ws), ws.numel(), hb.ptr(cls), hb.stream_ptr()), "encoder_infer")
+        cls_attn = torch.empty(cfg.num_hidden_layers, B, cfg.num_attention_heads, S, dtype=torch.float32,
+                               device=self.device) if return_attns else None
+        hb.encoder_infer(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, cls_attn)
         Wh, bh = a.heads_wb()
         labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
         top, bott, fin, _, _, _, _ = hb.stc_heads(cls, H, Wh, bh, self.dls, labels_f, B, H, need_grad=False, drop_p=0.0)
-        return dict(top=top, bott=bott, final=fin, cls=cls, pred=self.decode(top, bott))
+        out = dict(top=top, bott=bott, final=fin, cls=cls, pred=self.decode(top, bott))
+        if return_attns:
+            out["cls_attn"] = cls_attn
+        return out
 
     def decode(self, top, bott, out=None):
         """device decode of pred_one_sample -> int32 [B, n_top] bottom-label index or -1 (``out``: see hipabi.stc_decode)"""

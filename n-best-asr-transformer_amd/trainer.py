@@ -12,6 +12,7 @@ chunk's gradients are complete their slice of the flat gradient arena is all-red
 (RCCL on its own stream over xGMI; 6 chunks of 2 layers for bert-base) while the remaining backward - ending with the embedding backward -
 keeps the compute stream busy.  Per-tensor clipping + BertAdam run after the last reduce.
 """
+import json
 import os
 import time
 
@@ -21,7 +22,7 @@ import torch.distributed as dist
 
 from . import hipabi as hb
 from .fscore import compute_f1, update_f1
-from .inputs import collate, encode_utterance, prepare_inputs_for_roberta
+from .inputs import collate, encode_utterance, prepare_inputs_for_roberta, utterance_segments
 from .model import freeze_plan
 
 
@@ -786,11 +787,25 @@ def eval_epoch(model, data, opt, memory, fp=None, efp=None):
     return _finish(losses, counts, model.device, len(lists)) + (cases,)
 
 
+def attention_record(line, spans, cls_attn):
+    """one --predict_attention JSON record.  ``cls_attn``: fp32 [L, heads, >= tokens], the CLS row's attention probabilities of
+    one utterance (model.predict(return_attns=True)["cls_attn"][:, b]); ``spans``: inputs.utterance_segments of it.  ``mass``
+    [L][segments] = per layer, the mean over heads of the probability that falls on each span, normalised over the utterance's
+    own tokens (under XLM-R the reference's ids > 0 mask, quirk Q1, leaves padding keys unmasked: their share is left out)."""
+    a = cls_attn.detach().double().cpu().mean(dim=1)
+    m = torch.stack([a[:, lo:hi].sum(dim=1) for _, lo, hi in spans], dim=1)
+    m = m / m.sum(dim=1, keepdim=True).clamp_min(1e-300)
+    return {"line": line, "segments": [n for n, _, _ in spans], "tokens": [hi - lo for _, lo, hi in spans],
+            "mass": [[round(x, 6) for x in row] for row in m.tolist()]}
+
+
 @torch.no_grad()
-def predict_split(model, data, opt, memory):
+def predict_split(model, data, opt, memory, attn_fp=None):
     """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
     [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
-    ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only."""
+    ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only.
+    ``attn_fp`` (--predict_attention): a text file that receives one attention_record JSON line per utterance, in split order
+    ("line": 1-based index in the split)."""
     _, world = dist_info()
     if world > 1:
         raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
@@ -801,8 +816,16 @@ def predict_split(model, data, opt, memory):
     lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
     for bi, mine, b in Prefetcher(split, lists, model.device):
         seg = b["seg"] if opt.add_segment_ids else None
-        out = model.predict(b["ids"], seg_ids=seg)
+        out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None)
         pipe.push(out, [split.labels[j] for j in mine], tag=mine)
+        if attn_fp is not None:
+            ca = out["cls_attn"].cpu()
+            for k, j in enumerate(mine):
+                spans = utterance_segments(split.asr[j], opt.tokenizer, opt, getattr(opt, "n_best", None), getattr(opt, "max_seq_len", None))
+                if spans[-1][2] != len(split.rows[j][0]):
+                    raise RuntimeError("nbest_amd: line %d: segment spans cover %d tokens, the encoded utterance has %d"
+                                       % (j + 1, spans[-1][2], len(split.rows[j][0])))
+                attn_fp.write(json.dumps(attention_record(j + 1, spans, ca[:, k])) + "\n")
     _, tagged = pipe.finish()
     return [(split.asr[j], pc) for mine, preds in tagged for j, pc in zip(mine, preds)]
 
