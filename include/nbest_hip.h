@@ -73,6 +73,29 @@ int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const int64_t* po
                        int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
                        uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
 size_t nbest_embed_bwd_ws_bytes(int64_t M, int64_t H);
+/* Integrated gradients (new functionality: the reference has no attribution; Sundararajan et al., 2017).
+ * Interpolated forward: nbest_embed_ln_fwd with the word row of token m of sequence b = m / S moved along the path from the
+ * baseline id base_ids[m] to ids[m] (int64 [B*S] each; alpha fp32 [B], device):
+ *   E[m,:] = ((1 - a) word[base_ids[m]] + a word[ids[m]]) + type[seg[m]] + ptab[pos[m]],   a = alpha[b]
+ * the lerp in fp32 from the stored table rows (one fma per element), the additions in nbest_embed_ln_fwd's order: a = 1 is
+ * bit-for-bit nbest_embed_ln_fwd on ids, a = 0 on base_ids.  Then LayerNorm, dropout and stats as there.  One wave per row.   */
+int nbest_embed_ln_fwd_interp(const int64_t* ids, const int64_t* base_ids, const float* alpha, const int64_t* seg, const int64_t* pos,
+                              const void* word, const void* type, const void* ptab, const float* gamma, const float* beta, void* out,
+                              float* stats, int B, int S, int H, float eps, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
+                              nbest_stream_t stream);
+/* The per-token reduction of integrated gradients.  ids / base_ids / seg / pos / alpha / dhidden are those of an encoder call whose
+ * embeddings were interpolated (nbest_embed_ln_fwd_interp, no dropout) and whose backward left dhidden [.][H] (dtype) = the gradient
+ * w.r.t. the embedding LayerNorm output (nbest_encoder_backward with no_param_grad).  Pair p owns the m sequences p m .. p m + m - 1
+ * of that call, all with the ids of sequence p m; for every token t < S
+ *   attr[p S + t] = (1/m) sum_{k = 0..m-1} < LN'(dhidden[(p m + k) S + t]), word[x_t] - word[x'_t] >
+ * LN' = the embedding LayerNorm backward at the row E(alpha[p m + k]), recomputed in the kernel: the row from the same lerp and
+ * additions as nbest_embed_ln_fwd_interp, its mean and rstd by a restatement of the forward's statistics code, which the compiler
+ * may contract differently - equal to the forward's statistics to rounding, not necessarily in every bit.  The sum
+ * over k runs in ascending order in fp32; tokens with x = x' (padding included) get exactly 0.  attr fp32 [pairs][S], overwritten.
+ * One wave per (pair, token), no LDS, no atomics: bit-reproducible.  Reads m S H esz bytes of dhidden per pair.                   */
+int nbest_embed_attrib(const int64_t* ids, const int64_t* base_ids, const float* alpha, const int64_t* seg, const int64_t* pos,
+                       const void* word, const void* type, const void* ptab, const float* gamma, const void* dhidden, float* attr,
+                       int pairs, int m, int S, int H, float eps, int dtype, nbest_stream_t stream);
 
 /* Sparse exchange of word-embedding gradient rows between data-parallel ranks (new functionality: the reference is single-process,
  * /root/reference/n_best_asr_bert.py:232-294; the table is the nn.Embedding of the installed modeling_bert.py:154-177).  With a
@@ -282,6 +305,7 @@ int nbest_attention_bwd_keep(const void* qkv, const uint8_t* key_mask, const voi
 int nbest_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,
                         int64_t M, int H, float eps, int dtype, nbest_stream_t stream);
 /* dx = LN'(dy); dgamma = sum_m dy*xhat; dbeta = sum_m dy (+= when accumulate).
+ * dgamma, dbeta and dbias all NULL: dx (and dx_drop) only - no column sums, no workspace (ws may be NULL).
  * The LayerNorm input was x = drop(dense_out) + residual, so two gradients leave this kernel:
  *   dx      - gradient of the residual branch (unmasked), and
  *   dx_drop - gradient of dense_out = dropout mask (regenerated from seed/drop_stream) applied to dx;
@@ -527,10 +551,22 @@ typedef struct nbest_encoder_desc {
    * K == 0.  no_input_grad != 0: the backward leaves out the gradient w.r.t. the input of layer K (its QKV dgrad GEMM and residual
    * add; dhidden is not valid afterwards); refuses with_embeddings.  wgrad_skip_host: HOST memory [4 L] (NULL = none), non-zero =
    * the weight-gradient GEMM of that matrix (QKV, attention-out, FFN-up, FFN-down per layer) is left out and its gradient is not
-   * written.  Bias and LayerNorm gradients are always written.                                                                 */
+   * written.  Bias and LayerNorm gradients are always written (except with no_param_grad below).                               */
   int32_t first_trainable;
   int32_t no_input_grad;
   const uint8_t* wgrad_skip_host;
+  /* optional interpolated embeddings (integrated gradients): base_ids int64 [B*S] and alpha fp32 [B], device memory, set per call
+   * like `seed`.  Both non-NULL: nbest_encoder_forward's embedding is nbest_embed_ln_fwd_interp; NULL: nbest_embed_ln_fwd, launch for
+   * launch as before.  nbest_encoder_infer refuses them.                                                                         */
+  const int64_t* base_ids;
+  const float* alpha;
+  /* no_param_grad != 0: nbest_encoder_backward forms dhidden only (down to the gradient w.r.t. the embedding LayerNorm output with
+   * layer_begin = 0); grad may be NULL.  It enqueues no weight-gradient GEMM and no split-K reduce, and writes no bias or
+   * LayerNorm-parameter gradient (no column sums in the LayerNorm backward, the attention backward or the DGELU epilogue, no
+   * row-reduction finalize).  dhidden is bit-equal to that of the ordinary backward on the same stash.  Refuses with_embeddings,
+   * first_trainable > 0, no_input_grad and the fp8 forward (w8).                                                                 */
+  int32_t no_param_grad;
+  int32_t pad5;
 } nbest_encoder_desc;
 size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
 /* Pointers into a stash `act` written by nbest_encoder_forward with descriptor d: layer `layer`'s qkv [M][3H] (dtype; also in the fp8
@@ -561,7 +597,8 @@ int nbest_encoder_backward(const nbest_encoder_desc* d, const void* wts, const v
 /* Inference: the encoder forward without an activation stash, for the final hidden state of the B CLS rows only.  Same descriptor,
  * arenas and inputs as nbest_encoder_forward; cls_out [B][H] in the compute dtype.  Layers 0 .. L-2 are nbest_encoder_forward's
  * kernels (FFN-up without the GELU' rows); the last layer projects K|V on all B S rows and runs everything else on the B CLS rows.
- * ws >= nbest_encoder_infer_ws_bytes(d) (independent of L).  Refuses (NBEST_ERR_ARG) non-zero dropout and the fp8 forward (w8).   */
+ * ws >= nbest_encoder_infer_ws_bytes(d) (independent of L).  Refuses (NBEST_ERR_ARG) non-zero dropout, the fp8 forward (w8) and
+ * interpolated embeddings (base_ids / alpha).                                                                                   */
 size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d);
 int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                         const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, nbest_stream_t stream);

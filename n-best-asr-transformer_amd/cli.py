@@ -75,6 +75,12 @@ def parse_arguments(argv=None):
                    help="with --predict: also write one JSON line per input line, in input order - the segments of the utterance "
                         "(cls, sys, h1, h2, ..), their token counts and, per layer, the share of the CLS row's attention (mean over "
                         "heads) that falls on each segment")
+    g.add_argument("--predict_attribution", default=None, metavar="PATH",
+                   help="with --predict: also write one JSON line per input line, in input order - for every label of the .pred line, "
+                        "its score, the score at the all-padding baseline and the integrated-gradients attribution of the score to each "
+                        "token and each segment (cls, sys, h1, h2, ..)")
+    g.add_argument("--attribution_steps", type=int, default=32, metavar="M",
+                   help="--predict_attribution: path points of the integrated-gradients midpoint rule (>= 1)")
     g.add_argument("--deviceId", type=int, default=-1,
                    help="as the reference (n_best_asr_bert.py:116-126): 0 = pick a GPU automatically (here: the first visible one; "
                         "the reference asks gpustat / NVML for the least loaded), k > 0 = GPU k-1, -1 = CPU (refused: the path is "
@@ -143,6 +149,10 @@ def parse_arguments(argv=None):
         ap.error("--pre_trained_model %s: known shapes are %s" % (opt.pre_trained_model, ", ".join(sorted(ncfg.NAMED))))
     if opt.predict_attention is not None and opt.predict is None:
         ap.error("--predict_attention is an output of --predict: pass --predict FILE too")
+    if opt.predict_attribution is not None and opt.predict is None:
+        ap.error("--predict_attribution is an output of --predict: pass --predict FILE too")
+    if opt.attribution_steps < 1:
+        ap.error("--attribution_steps must be >= 1 (got %d)" % opt.attribution_steps)
     if opt.predict is not None:
         if not os.path.isfile(opt.predict):
             ap.error("--predict %s: no such file" % opt.predict)
@@ -282,11 +292,14 @@ def main(argv=None):
         out_path = predict_output_path(opt)
         t0 = time.time()
         attn_fp = open(opt.predict_attention, "w") if opt.predict_attention else None
+        attr_fp = open(opt.predict_attribution, "w") if opt.predict_attribution else None
         try:
-            cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp)
+            cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp, attr_fp=attr_fp,
+                                          attr_steps=opt.attribution_steps)
         finally:
-            if attn_fp is not None:
-                attn_fp.close()
+            for fp in (attn_fp, attr_fp):
+                if fp is not None:
+                    fp.close()
         with open(out_path, "w") as fp:
             for raw, pc in cases:
                 fp.write("%s\t<=>\t%s\n" % (" ".join(raw), ";".join(pc)))

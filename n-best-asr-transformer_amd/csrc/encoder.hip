@@ -183,6 +183,7 @@ static int check_desc(const nbest_encoder_desc* d) {
                       "encoder(fp8 forward): needs the bf16 path, inverse scales and H, F multiples of 256");
   NB_CHECK(0 <= d->first_trainable && d->first_trainable <= d->L, NBEST_ERR_ARG, "encoder: first_trainable %d outside [0, L=%d]",
            d->first_trainable, d->L);
+  NB_CHECK(!d->base_ids == !d->alpha, NBEST_ERR_ARG, "encoder: interpolated embeddings need both base_ids and alpha (or neither)");
   return NBEST_OK;
 }
 
@@ -261,9 +262,14 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   auto X = [&](int l) { return l >= FT ? (void*)(A + a.X + (size_t)(l - FT) * MH) : (void*)(W + ((l & 1) ? wl.fz_x1 : wl.fz_x0)); };
   const uint32_t sb = d->drop_stream_base;
 
-  RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
-                         P.P(d->off_emb_ln_b), X(0), (float*)(FT > 0 ? W + wl.fz_emb_stats : A + a.emb_stats), M, H, d->ln_eps, dt,
-                         d->hidden_drop, d->seed, sb, st));
+  float* emb_stats = (float*)(FT > 0 ? W + wl.fz_emb_stats : A + a.emb_stats);
+  if (d->base_ids)   // integrated gradients: the word rows at the path points alpha (desc.base_ids / alpha)
+    RUN(nbest_embed_ln_fwd_interp(ids, d->base_ids, d->alpha, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos),
+                                  P.P(d->off_emb_ln_g), P.P(d->off_emb_ln_b), X(0), emb_stats, d->B, d->S, H, d->ln_eps, dt,
+                                  d->hidden_drop, d->seed, sb, st));
+  else
+    RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
+                           P.P(d->off_emb_ln_b), X(0), emb_stats, M, H, d->ln_eps, dt, d->hidden_drop, d->seed, sb, st));
   // fp8 forward: the four GEMMs of a layer on the block-scaled fp8 MFMA; their A operands are e4m3 copies in `ws`
   // (kept per layer in the activation stash: the fp8 weight gradients of the backward read them again; a frozen layer's in ws.f8)
   auto L8 = [&](int l, size_t off) -> uint8_t* {
@@ -348,7 +354,12 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                                       int layer_begin, int layer_end, int with_embeddings, nbest_stream_t stream) {
   RUN(check_desc(d));
   NB_CHECK(0 <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_backward: bad layer range");
-  NB_CHECK(wts && prm && grad && ids && pos && key_mask && act && dhidden && ws, NBEST_ERR_ARG, "encoder_backward: null pointer");
+  // no_param_grad: dhidden only (attribution) - no weight-gradient GEMM, no bias / LayerNorm-parameter gradient, grad may be NULL
+  const bool npg = d->no_param_grad != 0;
+  NB_CHECK(!npg || (!with_embeddings && d->first_trainable == 0 && !d->no_input_grad && !d->w8), NBEST_ERR_ARG,
+           "encoder_backward: no_param_grad refuses with_embeddings (%d), first_trainable > 0 (%d), no_input_grad (%d) and the fp8 "
+           "forward (w8): it forms the input gradient only, of a full stash", with_embeddings, d->first_trainable, d->no_input_grad);
+  NB_CHECK(wts && prm && (grad || npg) && ids && pos && key_mask && act && dhidden && ws, NBEST_ERR_ARG, "encoder_backward: null pointer");
   NB_CHECK(!with_embeddings || d->word_perm, NBEST_ERR_ARG, "encoder_backward: desc.word_perm (stable argsort of this pass's ids) is required");
   NB_CHECK(layer_begin >= d->first_trainable, NBEST_ERR_ARG, "encoder_backward: layer_begin %d < first_trainable %d (those layers are not stashed)",
            layer_begin, d->first_trainable);
@@ -373,8 +384,9 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   const int FT = a.K;
   auto X = [&](int l) { return (void*)(A + a.X + (size_t)(l - FT) * MH); };
   auto G = [&](int64_t off) { return grad + off; };
+  auto GP = [&](int64_t off) -> float* { return npg ? nullptr : grad + off; };   // a bias / LayerNorm-parameter gradient (none: no_param_grad)
   // frozen matrices (desc.wgrad_skip_host[4 l + {0: QKV, 1: attention-out, 2: FFN-up, 3: FFN-down}]): no weight-gradient GEMM
-  auto skip = [&](int l, int j) -> bool { return d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]; };
+  auto skip = [&](int l, int j) -> bool { return npg || (d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]); };
   void* dA = dhidden;
   void* dR = W + w.dR;
   const bool hdrop = d->hidden_drop > 0.f;
@@ -394,7 +406,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
 
   // fp8 dgrads (descriptor: w8t, gamax_prev / gamax_new, fp8_bwd): the gradient amax of every dgrad operand is recorded in
   // every pass; with a history (fp8_bwd) the producers also write e4m3 copies and the four dgrad GEMMs of a layer run in fp8
-  const bool rec = d->gamax_new && dt == NBEST_BF16;
+  const bool rec = !npg && d->gamax_new && dt == NBEST_BF16;
   uint8_t* dqkv8 = f8b ? (uint8_t*)W + w.f8 : nullptr;                       // [M][3H]
   uint8_t* dBig8 = f8b ? dqkv8 + 3 * al((size_t)M * H) : nullptr;            // [M][F]
   uint8_t* dRd8 = f8b ? dBig8 + al((size_t)M * F) : nullptr;                 // [M][H]
@@ -424,12 +436,12 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     void* r1 = Lb + a.o_r1; float* st1 = (float*)(Lb + a.o_st1); void* x1 = Lb + a.o_x1;
     void* u = Lb + a.o_u; void* hact = Lb + a.o_hact; void* r2 = Lb + a.o_r2; float* st2 = (float*)(Lb + a.o_st2);
     const uint32_t s0 = sb + 1 + 4 * l;
-    nbest_internal_rowred_batch_begin();    // the layer's four bias / LayerNorm-parameter reductions: one finalize launch at its end
+    if (!npg) nbest_internal_rowred_batch_begin();    // the layer's four bias / LayerNorm-parameter reductions: one finalize launch at its end
     const uint8_t* x8 = (const uint8_t*)(Lb + a.o_x8); const uint8_t* ctx8 = (const uint8_t*)(Lb + a.o_ctx8);
     const uint8_t* x18 = (const uint8_t*)(Lb + a.o_x18); const uint8_t* h8 = (const uint8_t*)(Lb + a.o_h8);
     // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
     // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
-    RUN(nbest_internal_layernorm_bwd8(dA, r2, st2, P.P(o.ln2_g), dR, (hdrop && !f8b) ? dRd : nullptr, G(o.ln2_g), G(o.ln2_b), G(o.b2), M, H, dt,
+    RUN(nbest_internal_layernorm_bwd8(dA, r2, st2, P.P(o.ln2_g), dR, (hdrop && !f8b) ? dRd : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H, dt,
                                       accumulate, d->hidden_drop, d->seed, s0 + 2, red, w.red_bytes, stream, fg(dRd8, 4 * l + 0)));   // partial rows: region 0
     // FFN-down: dgrad fused with GELU' -> dU ; wgrad
     // (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
@@ -437,7 +449,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       RUN(dgrad8(dRd8, 4 * l + 0, o.w2, 4 * l + 3, nullptr, F, H, NBEST_EPI_DGELU, nullptr, u, dBig8, 4 * l + 1, G(o.b1)));
     } else {
       RUN(gemm(dt, dRd, PT.W(o.w2), dBig, M, F, H, H, wt ? H : F, F, 0, tbd, NBEST_EPI_DGELU, nullptr, nullptr, 0, u, F, red1, w.red_bytes, accumulate,
-               0.f, 0, 0, st, G(o.b1), PKT(o.w2)));
+               0.f, 0, 0, st, GP(o.b1), PKT(o.w2)));
       if (rec) RUN(nbest_internal_amax_bf16(dBig, M * F, d->gamax_new + (int64_t)(4 * l + 1) * NBEST_AMAX_TENSOR_WORDS, st));   // calibration pass: this producer is a bf16 kernel
     }
     stamp(0);
@@ -456,7 +468,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                   accumulate, 0.f, 0, 0, st));
     stamp(1);
     // LN1 backward
-    RUN(nbest_internal_layernorm_bwd8(dB1, r1, st1, P.P(o.ln1_g), dR, (hdrop && !f8b) ? dRd : nullptr, G(o.ln1_g), G(o.ln1_b), G(o.bo), M, H, dt,
+    RUN(nbest_internal_layernorm_bwd8(dB1, r1, st1, P.P(o.ln1_g), dR, (hdrop && !f8b) ? dRd : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H, dt,
                                       accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, 4 * l + 2)));
     // attention output projection: dgrad ; wgrad
     if (f8b) RUN(dgrad8(dRd8, 4 * l + 2, o.wo, 4 * l + 1, dctx, H, H, NBEST_EPI_NONE, nullptr, nullptr, nullptr, -1, nullptr));
@@ -471,7 +483,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       stamp(1);
     }
     // attention backward -> dqkv ; QKV bias gradient
-    RUN(nbest_internal_attention_bwd8(qkv, key_mask, ctx, dctx, lse, f8b ? nullptr : dqkv, G(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S, d->heads, 64,
+    RUN(nbest_internal_attention_bwd8(qkv, key_mask, ctx, dctx, lse, f8b ? nullptr : dqkv, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S, d->heads, 64,
                                       dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, 4 * l + 3),
                                       (a.keep_bytes && d->attn_drop > 0.f) ? (const uint32_t*)(Lb + a.o_keep) : nullptr));
     // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad
@@ -501,7 +513,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     } else RUN(gemm(dt, dqkv, X(l), G(o.wqkv), 3 * H, H, M, 3 * H, H, H, 1, 1, NBEST_EPI_F32_SPLITK, nullptr, nullptr, 0, nullptr, 0, slab,
                   w.slab_bytes, accumulate, 0.f, 0, 0, st));
     stamp(1);
-    RUN(nbest_internal_rowred_batch_flush(st));
+    if (!npg) RUN(nbest_internal_rowred_batch_flush(st));
   }
   if (!with_embeddings) return NBEST_OK;
   if (!accumulate) {
@@ -563,6 +575,8 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
            "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
   NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");
+  NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder_infer: interpolated embeddings (desc.base_ids / alpha) are not supported; "
+                                                     "run nbest_encoder_forward");
   NB_CHECK(wts && prm && ids && pos && key_mask && ws && cls_out, NBEST_ERR_ARG, "encoder_infer: null pointer");
   const InferLayout w = infer_layout(d);
   NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes, w.total);

@@ -137,7 +137,8 @@ __global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const bf16* __restrict
 }
 
 // partials layout: part[k][blk][H], k = 0 dgamma, 1 dbeta, 2 dbias(sum of dx)
-template <typename T, int VPL>
+// PARAMS = false (nbest_encoder_desc.no_param_grad): dx / dx_drop only - no column sums, no LDS, no partial rows, no barrier
+template <typename T, int VPL, bool PARAMS = true>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ stats, const float* __restrict__ gamma,
                                                      T* __restrict__ dx, T* __restrict__ dx_drop, float* __restrict__ part,
@@ -145,8 +146,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   extern __shared__ __attribute__((aligned(16))) float acc[];  // [3][H]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6, nvec = H >> 2;
   const float invH = 1.0f / (float)H;
-  for (int i = threadIdx.x; i < 3 * H; i += blockDim.x) acc[i] = 0.f;
-  __syncthreads();
+  if constexpr (PARAMS) {
+    for (int i = threadIdx.x; i < 3 * H; i += blockDim.x) acc[i] = 0.f;
+    __syncthreads();
+  }
   f32x4 ag[VPL], ab[VPL], ad[VPL], gm[VPL];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
@@ -207,18 +210,21 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
       if (c < nvec) {
         f32x4 o = (g[i] - s1 - xh[i] * s2) * rstd;
         Vec4<T>::store(dx + row * H + 4 * c, o);
-        ag[i] += d[i] * xh[i];
-        ab[i] += d[i];
+        if constexpr (PARAMS) {
+          ag[i] += d[i] * xh[i];
+          ab[i] += d[i];
+        }
         if (drop.thr16) {  // gradient that flows into the dense layer under the (regenerated) dropout mask
           const uint32_t k = nb_keep4(drop, (uint32_t)(row * H + 4 * c));
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (k >> e & 1) ? o[e] * drop.scale : 0.f;
           Vec4<T>::store(dx_drop + row * H + 4 * c, o);
         }
-        ad[i] += o;
+        if constexpr (PARAMS) ad[i] += o;
       }
     }
   }
+  if constexpr (!PARAMS) return;
   // the waves add their column sums into the block's LDS row one after the other (plain read-modify-write:
   // LDS float atomics cost ~10 us per workgroup here)
   for (int w = 0; w < wpb; ++w) {
@@ -251,7 +257,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 __device__ __forceinline__ f32x2 unpack_bf16x2(uint32_t w) { return unpack2(w); }
 __device__ __forceinline__ uint32_t pack_bf16x2(f32x2 v) { return pack2(v); }
 
-template <int VPL, bool DROP, bool DBIAS, int WAVES>
+template <int VPL, bool DROP, bool DBIAS, int WAVES, bool PARAMS = true>   // PARAMS = false: dx / dx_drop only (see ln_bwd_kernel)
 __global__ __launch_bounds__(WAVES * 64) void ln_bwd_fast_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
                                                           const float* __restrict__ stats, const float* __restrict__ gamma,
                                                           bf16* __restrict__ dx, bf16* __restrict__ dx_drop,
@@ -320,8 +326,10 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_fast_kernel(const bf16* __r
         for (int h = 0; h < 2; ++h) o[h] = xh[i][h] * a2 + (g[i][h] * rstd + a1);
         const int64_t off = row * H + 4 * (lane + 64 * i);
         *(uint2*)(dx + off) = uint2{pack_bf16x2(o[0]), pack_bf16x2(o[1])};
+        if constexpr (PARAMS) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) { ag[i][h] += d[i][h] * xh[i][h]; ab[i][h] += d[i][h]; }
+          for (int h = 0; h < 2; ++h) { ag[i][h] += d[i][h] * xh[i][h]; ab[i][h] += d[i][h]; }
+        }
         if (DROP) {
           const uint32_t q = (uint32_t)(2 * (lane + 64 * i));   // pair index inside the row
           const uint32_t h0 = nb_hash32(hbase + q * 0x9E3779B9U), h1 = nb_hash32(hbase + (q + 1) * 0x9E3779B9U);
@@ -331,7 +339,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_fast_kernel(const bf16* __r
           o[1][1] = ((h1 >> 16) >= drop.thr16) ? o[1][1] * drop.scale : 0.f;
           if (dx_drop) *(uint2*)(dx_drop + off) = uint2{pack_bf16x2(o[0]), pack_bf16x2(o[1])};   // (null: only its e4m3 copy is wanted)
         }
-        if (DBIAS) { ad[i][0] += o[0]; ad[i][1] += o[1]; }
+        if (PARAMS && DBIAS) { ad[i][0] += o[0]; ad[i][1] += o[1]; }
         if (f8.amax_new) {   // o = the gradient the dense-layer dgrad / wgrad GEMMs read (after the dropout mask)
           amax8 = fmaxf(fmaxf(amax8, fmaxf(fabsf(o[0][0]), fabsf(o[0][1]))), fmaxf(fabsf(o[1][0]), fabsf(o[1][1])));
           if (f8.out8) {
@@ -346,6 +354,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_fast_kernel(const bf16* __r
     amax8 = wave_max(amax8);
     if (lane == 0) amax_update(f8.amax_new, amax8);
   }
+  if constexpr (!PARAMS) return;
   float* mine = acc + wave * 3 * H;
 #pragma unroll
   for (int i = 0; i < VPL; ++i)
@@ -423,26 +432,61 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, fl
 }
 
 // ------------------------------------------------------------------------------------------------
-template <typename T, int VPL>
+// Embedding row arithmetic of the interpolated forward (integrated gradients) and nbest_embed_attrib.  emb_row_stats restates
+// embed_fwd_kernel's statistics code (that kernel keeps its inline copy, so its plain instantiations compute the bits they computed
+// before); the compiler may contract the two copies differently, so the attribution kernel's statistics agree with the forward's to
+// rounding.
+// Word part of a row at path point a: ((1 - a) wb + a w) in fp32 from the stored table rows, one fma per element
+// (a = 1: exactly w; a = 0: exactly wb).
+__device__ __forceinline__ f32x4 emb_lerp4(f32x4 w, f32x4 wb, float a) {
+  const float b = 1.0f - a;
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a, w[e], b * wb[e]);
+  return r;
+}
+// mean and rstd of the row v (chunk c = lane + 64 i, c < nvec), s = this lane's sum of its chunks in ascending i
+template <int VPL>
+__device__ __forceinline__ void emb_row_stats(const f32x4* v, float s, int lane, int nvec, float invH, float eps, float& mean,
+                                              float& rstd) {
+  mean = wave_sum(s) * invH;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nvec) { f32x4 d = v[i] - mean; q += sum4(d * d); }
+  }
+  rstd = 1.0f / sqrtf(wave_sum(q) * invH + eps);
+}
+
+// INTERP (nbest_embed_ln_fwd_interp): the word part of row m is emb_lerp4(word[ids[m]], word[base_ids[m]], alpha[m / S]); one kernel
+// for both, so that an alpha = 1 row runs the plain forward's instructions
+template <typename T, int VPL, bool INTERP = false>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seg,
                                                         const int64_t* __restrict__ pos, const T* __restrict__ word,
                                                         const T* __restrict__ type, const T* __restrict__ ptab,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         T* __restrict__ out, float* __restrict__ stats, int64_t M, int H,
-                                                        float eps, DropCfg drop) {
+                                                        float eps, DropCfg drop, const int64_t* __restrict__ base_ids = nullptr,
+                                                        const float* __restrict__ alpha = nullptr, int S = 1) {
   const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6, nvec = H >> 2;
   const float invH = 1.0f / (float)H;
   for (int64_t row = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * wpb) {
     const T* wr = word + ids[row] * H;
     const T* tr = type + (seg ? seg[row] : 0) * H;
     const T* pr = ptab + pos[row] * H;
+    const T* br = INTERP ? word + base_ids[row] * H : nullptr;
+    const float a = INTERP ? alpha[row / S] : 1.f;
     f32x4 v[VPL];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + 64 * i;
       if (c < nvec) {
-        v[i] = (Vec4<T>::load(wr + 4 * c) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
+        if constexpr (INTERP)
+          v[i] = (emb_lerp4(Vec4<T>::load(wr + 4 * c), Vec4<T>::load(br + 4 * c), a) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
+        else
+          v[i] = (Vec4<T>::load(wr + 4 * c) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
         s += sum4(v[i]);
       } else v[i] = f32x4{0, 0, 0, 0};
     }
@@ -469,6 +513,104 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
       }
     }
     if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+  }
+}
+
+// Integrated-gradients reduction (nbest_embed_attrib).  One wave per (pair p, token t); the pair's m path points are the rows
+// r_k = (p m + k) S + t, k = 0 .. m-1, of an encoder call whose embeddings were interpolated (embed_fwd_kernel<INTERP>, no dropout).
+// word[x], word[x'], the type row, the position row and gamma stay in registers; for each k in ascending order the wave recomputes
+// the row E(alpha[p m + k]) with the forward's lerp and additions and its statistics with emb_row_stats, applies the LayerNorm
+// backward to dh[r_k] (the formula of emb_tok_grad) and adds the dot product with delta = word[x] - word[x'] to an fp32 sum:
+//   attr[p S + t] = (sum_k <LN'(dh[r_k]), delta>) / m      (x == x', padding included: exactly 0, dh not read).
+// No LDS, no barrier, no atomics: the same additions in the same order on every run.  The next path point's dh row is in flight
+// while this one is reduced.
+template <typename T, int VPL>
+__global__ __launch_bounds__(256) void embed_attrib_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ base_ids,
+                                                           const float* __restrict__ alpha, const int64_t* __restrict__ seg,
+                                                           const int64_t* __restrict__ pos, const T* __restrict__ word,
+                                                           const T* __restrict__ type, const T* __restrict__ ptab,
+                                                           const float* __restrict__ gamma, const T* __restrict__ dh,
+                                                           float* __restrict__ attr, int64_t n_items, int m, int S, int H, float eps) {
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6, nvec = H >> 2;
+  const float invH = 1.0f / (float)H;
+  for (int64_t it = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); it < n_items; it += (int64_t)gridDim.x * wpb) {
+    const int64_t p = it / S;
+    const int64_t row0 = p * m * S + (it - p * S);   // path point k: row0 + k S
+    const int64_t id = ids[row0], bid = base_ids[row0];
+    if (id == bid) {   // wave-uniform: no displacement, no attribution
+      if (lane == 0) attr[it] = 0.f;
+      continue;
+    }
+    const T* wr = word + id * H;
+    const T* br = word + bid * H;
+    const T* tr = type + (seg ? seg[row0] : 0) * H;
+    const T* pr = ptab + pos[row0] * H;
+    f32x4 w[VPL], wb[VPL], tp[VPL], pp[VPL], gm[VPL], dl[VPL];
+    typename Vec4<T>::raw_t nd[VPL];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nvec) {
+        w[i] = Vec4<T>::load(wr + 4 * c); wb[i] = Vec4<T>::load(br + 4 * c);
+        tp[i] = Vec4<T>::load(tr + 4 * c); pp[i] = Vec4<T>::load(pr + 4 * c);
+        gm[i] = *(const f32x4*)(gamma + 4 * c);
+        dl[i] = w[i] - wb[i];
+        nd[i] = Vec4<T>::raw_load(dh + row0 * H + 4 * c);
+      } else {
+        w[i] = wb[i] = tp[i] = pp[i] = gm[i] = dl[i] = f32x4{0, 0, 0, 0};
+      }
+    }
+    float acc = 0.f;
+    for (int k = 0; k < m; ++k) {
+      typename Vec4<T>::raw_t cd[VPL];
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) cd[i] = nd[i];
+      if (k + 1 < m) {
+        const T* nr = dh + (row0 + (int64_t)(k + 1) * S) * H;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+          const int c = lane + 64 * i;
+          if (c < nvec) nd[i] = Vec4<T>::raw_load(nr + 4 * c);
+        }
+      }
+      const float a = alpha[p * m + k];
+      f32x4 v[VPL];
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) {
+          v[i] = (emb_lerp4(w[i], wb[i], a) + tp[i]) + pp[i];
+          s += sum4(v[i]);
+        } else v[i] = f32x4{0, 0, 0, 0};
+      }
+      float mean, rstd;
+      emb_row_stats<VPL>(v, s, lane, nvec, invH, eps, mean, rstd);
+      f32x4 xh[VPL], g[VPL];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) {
+          xh[i] = (v[i] - mean) * rstd;
+          g[i] = Vec4<T>::cvt(cd[i]) * gm[i];
+          s1 += sum4(g[i]);
+          s2 += sum4(g[i] * xh[i]);
+        } else {
+          xh[i] = g[i] = f32x4{0, 0, 0, 0};
+        }
+      }
+      wave_sum2(s1, s2);
+      s1 *= invH; s2 *= invH;
+      float dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) dot += sum4(((g[i] - s1 - xh[i] * s2) * rstd) * dl[i]);
+      }
+      acc += wave_sum(dot);
+    }
+    if (lane == 0) attr[it] = acc / (float)m;
   }
 }
 
@@ -1088,8 +1230,10 @@ int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* st
                                   size_t ws_bytes, nbest_stream_t stream, Fp8Grad f8) {
   if (int e = check_h(H)) return e;
   NB_CHECK(!f8.amax_new || (dtype == NBEST_BF16 && H % 256 == 0 && H <= 1024), NBEST_ERR_SHAPE, "layernorm_bwd: fp8 copy needs bf16 and H in {256..1024}");
-  NB_CHECK(dy && x && stats && gamma && dx && dgamma && dbeta && ws && M > 0, NBEST_ERR_ARG, "layernorm_bwd: null pointer");
-  NB_CHECK(ws_bytes >= nbest_rowred_ws_bytes(M, H), NBEST_ERR_WORKSPACE, "layernorm_bwd: workspace too small");
+  // dgamma == dbeta == dbias == NULL (the no_param_grad backward of nbest_encoder_backward): dx / dx_drop only, no workspace, no finalize
+  const bool params = dgamma || dbeta || dbias;
+  NB_CHECK(dy && x && stats && gamma && dx && M > 0 && (!params || (dgamma && dbeta && ws)), NBEST_ERR_ARG, "layernorm_bwd: null pointer");
+  NB_CHECK(!params || ws_bytes >= nbest_rowred_ws_bytes(M, H), NBEST_ERR_WORKSPACE, "layernorm_bwd: workspace too small");
   const DropCfg d = make_drop(drop_p, seed, drop_stream);
   NB_CHECK(d.thr16 == 0 || (dx_drop && dx_drop != dx) || (!dx_drop && f8.out8), NBEST_ERR_ARG, "layernorm_bwd: dropout needs a separate dx_drop buffer");
   NB_CHECK(M * (int64_t)H < (int64_t)1 << 32 || d.thr16 == 0, NBEST_ERR_SHAPE, "layernorm_bwd: dropout counter overflow");
@@ -1102,6 +1246,33 @@ int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* st
   float* part = (float*)ws;
   const size_t smem = (size_t)3 * H * sizeof(float);
   const int wb = dbias ? 1 : 0;
+  if (!params) {   // the PARAMS = false instantiations: same grid, same dx arithmetic, no column sums
+    if (dtype == NBEST_F32) {
+      DISPATCH_VPL(H, (ln_bwd_kernel<float, VPL, false><<<nblk, 256, 0, st>>>((const float*)dy, (const float*)x, stats, gamma,
+                                                                               (float*)dx, (float*)dx_drop, nullptr, M, H, rpb, 0, d)));
+    } else if (dtype == NBEST_BF16 && H % 256 == 0 && H <= 1024) {
+#define NB_LNB0(V, D) ln_bwd_fast_kernel<V, D, false, waves, false><<<nblk, waves * 64, 0, st>>>((const bf16*)dy, (const bf16*)x, stats, gamma, \
+                                                                                               (bf16*)dx, (bf16*)dx_drop, nullptr, M, rpb, d, f8)
+#define NB_LNB0_V(V)                      \
+  do {                                     \
+    if (d.thr16) NB_LNB0(V, true);         \
+    else NB_LNB0(V, false);                \
+  } while (0)
+      switch (H / 256) {
+        case 1: NB_LNB0_V(1); break;
+        case 2: NB_LNB0_V(2); break;
+        case 3: NB_LNB0_V(3); break;
+        default: NB_LNB0_V(4); break;
+      }
+#undef NB_LNB0_V
+#undef NB_LNB0
+    } else if (dtype == NBEST_BF16) {
+      DISPATCH_VPL(H, (ln_bwd_kernel<bf16, VPL, false><<<nblk, 256, 0, st>>>((const bf16*)dy, (const bf16*)x, stats, gamma,
+                                                                              (bf16*)dx, (bf16*)dx_drop, nullptr, M, H, rpb, 0, d)));
+    } else NB_CHECK(false, NBEST_ERR_DTYPE, "layernorm_bwd: bad dtype %d", dtype);
+    NB_LAUNCH_CHECK();
+    return NBEST_OK;
+  }
   if (dtype == NBEST_F32) {
     DISPATCH_VPL(H, (ln_bwd_kernel<float, VPL><<<nblk, 256, smem, st>>>((const float*)dy, (const float*)x, stats, gamma,
                                                                          (float*)dx, (float*)dx_drop, part, M, H, rpb, wb, d)));
@@ -1179,6 +1350,51 @@ extern "C" int nbest_embed_ln_fwd(const int64_t* ids, const int64_t* seg, const 
     DISPATCH_VPL(H, (embed_fwd_kernel<bf16, VPL><<<grid, 256, 0, st>>>(ids, seg, pos, (const bf16*)word, (const bf16*)type,
                                                                        (const bf16*)ptab, gamma, beta, (bf16*)out, stats, M, H, eps, d)));
   } else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_ln_fwd: bad dtype %d", dtype);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_embed_ln_fwd_interp(const int64_t* ids, const int64_t* base_ids, const float* alpha, const int64_t* seg,
+                                         const int64_t* pos, const void* word, const void* type, const void* ptab, const float* gamma,
+                                         const float* beta, void* out, float* stats, int B, int S, int H, float eps, int dtype,
+                                         float drop_p, uint64_t seed, uint32_t drop_stream, nbest_stream_t stream) {
+  if (int e = check_h(H)) return e;
+  NB_CHECK(ids && base_ids && alpha && pos && word && type && ptab && gamma && beta && out && stats && B > 0 && S > 0, NBEST_ERR_ARG,
+           "embed_ln_fwd_interp: null pointer or empty batch");
+  const int64_t M = (int64_t)B * S;
+  NB_CHECK(M * (int64_t)H < (int64_t)1 << 32, NBEST_ERR_SHAPE, "embed_ln_fwd_interp: M*H must fit 32 bits (dropout counter)");
+  hipStream_t st = (hipStream_t)stream;
+  const DropCfg d = make_drop(drop_p, seed, drop_stream);
+  const int grid = grid_rows(M, 4);
+  if (dtype == NBEST_F32) {
+    DISPATCH_VPL(H, (embed_fwd_kernel<float, VPL, true><<<grid, 256, 0, st>>>(ids, seg, pos, (const float*)word, (const float*)type, (const float*)ptab,
+                                                                              gamma, beta, (float*)out, stats, M, H, eps, d, base_ids, alpha, S)));
+  } else if (dtype == NBEST_BF16) {
+    DISPATCH_VPL(H, (embed_fwd_kernel<bf16, VPL, true><<<grid, 256, 0, st>>>(ids, seg, pos, (const bf16*)word, (const bf16*)type, (const bf16*)ptab,
+                                                                             gamma, beta, (bf16*)out, stats, M, H, eps, d, base_ids, alpha, S)));
+  } else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_ln_fwd_interp: bad dtype %d", dtype);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_embed_attrib(const int64_t* ids, const int64_t* base_ids, const float* alpha, const int64_t* seg, const int64_t* pos,
+                                  const void* word, const void* type, const void* ptab, const float* gamma, const void* dhidden,
+                                  float* attr, int pairs, int m, int S, int H, float eps, int dtype, nbest_stream_t stream) {
+  if (int e = check_h(H)) return e;
+  NB_CHECK(ids && base_ids && alpha && pos && word && type && ptab && gamma && dhidden && attr, NBEST_ERR_ARG, "embed_attrib: null pointer");
+  NB_CHECK(pairs > 0 && m > 0 && S > 0, NBEST_ERR_SHAPE, "embed_attrib: pairs=%d, m=%d, S=%d must be positive", pairs, m, S);
+  NB_CHECK((int64_t)pairs * m <= INT32_MAX, NBEST_ERR_SHAPE, "embed_attrib: pairs x m = %lld sequences does not fit int32",
+           (long long)pairs * m);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = (int64_t)pairs * S;
+  const int grid = grid_rows(n, 4);
+  if (dtype == NBEST_F32) {
+    DISPATCH_VPL(H, (embed_attrib_kernel<float, VPL><<<grid, 256, 0, st>>>(ids, base_ids, alpha, seg, pos, (const float*)word, (const float*)type,
+                                                                           (const float*)ptab, gamma, (const float*)dhidden, attr, n, m, S, H, eps)));
+  } else if (dtype == NBEST_BF16) {
+    DISPATCH_VPL(H, (embed_attrib_kernel<bf16, VPL><<<grid, 256, 0, st>>>(ids, base_ids, alpha, seg, pos, (const bf16*)word, (const bf16*)type,
+                                                                          (const bf16*)ptab, gamma, (const bf16*)dhidden, attr, n, m, S, H, eps)));
+  } else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_attrib: bad dtype %d", dtype);
   NB_LAUNCH_CHECK();
   return NBEST_OK;
 }

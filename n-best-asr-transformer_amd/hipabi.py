@@ -26,6 +26,7 @@ EXPORTS = [
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
     "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
     "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
+    "nbest_embed_ln_fwd_interp", "nbest_embed_attrib",
 ]
 
 
@@ -81,7 +82,8 @@ class EncoderDesc(C.Structure):
                 ("gamax_new", C.c_void_p), ("fp8_bwd", C.c_int32), ("pad2", C.c_int32),
                 ("wpk", C.c_void_p), ("wpkt", C.c_void_p), ("w8p", C.c_void_p), ("w8tp", C.c_void_p),
                 ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("pad4", C.c_int32),
-                ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p)]
+                ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p),
+                ("base_ids", C.c_void_p), ("alpha", C.c_void_p), ("no_param_grad", C.c_int32), ("pad5", C.c_int32)]
 
 
 _lib = None
@@ -118,6 +120,8 @@ def lib():
         vp, i64, i32, f32, u64, u32, sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_size_t
         L.nbest_embed_ln_fwd.argtypes = [vp] * 10 + [i64, i32, f32, i32, f32, u64, u32, vp]
         L.nbest_embed_ln_bwd.argtypes = [vp] * 15 + [i32, i32, i32, i32, i32, i64, i64, i32, i32, f32, u64, u32, vp, sz, vp]
+        L.nbest_embed_ln_fwd_interp.argtypes = [vp] * 12 + [i32, i32, i32, f32, i32, f32, u64, u32, vp]
+        L.nbest_embed_attrib.argtypes = [vp] * 11 + [i32, i32, i32, i32, f32, i32, vp]
         L.nbest_attention_fwd.argtypes = [vp] * 4 + [i32] * 5 + [f32, u64, u32, vp]
         L.nbest_attention_bwd.argtypes = [vp] * 7 + [i32, vp, sz] + [i32] * 5 + [f32, u64, u32, vp]
         L.nbest_attention_bwd_ws_bytes.argtypes = [i32, i32, i32]
@@ -507,6 +511,29 @@ def embed_ln_fwd(ids, seg, pos, word, type_tab, ptab, gamma, beta, eps, drop_p=0
                                    ptr(out), ptr(stats), M, H, eps, dtype_code(word.dtype), drop_p, seed, drop_stream,
                                    stream_ptr()), "embed_ln_fwd")
     return out, stats
+
+
+def embed_ln_fwd_interp(ids, base_ids, alpha, seg, pos, word, type_tab, ptab, gamma, beta, eps, drop_p=0.0, seed=0, drop_stream=0):
+    """nbest_embed_ln_fwd_interp: ids / base_ids [B, S] int64, alpha fp32 [B] -> (out [B*S, H], stats [B*S, 2]); the word row of
+    sequence b moves from word[base_ids] (alpha 0) to word[ids] (alpha 1)"""
+    B, S = ids.shape
+    H = word.shape[1]
+    out = torch.empty(B * S, H, dtype=word.dtype, device=word.device)
+    stats = torch.empty(B * S, 2, dtype=torch.float32, device=word.device)
+    check(lib().nbest_embed_ln_fwd_interp(ptr(ids), ptr(base_ids), ptr(alpha), ptr(seg), ptr(pos), ptr(word), ptr(type_tab), ptr(ptab),
+                                          ptr(gamma), ptr(beta), ptr(out), ptr(stats), B, S, H, eps, dtype_code(word.dtype), drop_p, seed,
+                                          drop_stream, stream_ptr()), "embed_ln_fwd_interp")
+    return out, stats
+
+
+def embed_attrib(ids, base_ids, alpha, seg, pos, word, type_tab, ptab, gamma, dhidden, pairs, m, S, eps, out=None):
+    """nbest_embed_attrib -> fp32 [pairs, S]: integrated-gradients attribution of every token of each pair, from the interpolated
+    call's inputs (pair p = sequences p m .. p m + m - 1) and ``dhidden``, the gradient w.r.t. its embedding LayerNorm output"""
+    H = word.shape[1]
+    attr = torch.empty(pairs, S, dtype=torch.float32, device=word.device) if out is None else out
+    check(lib().nbest_embed_attrib(ptr(ids), ptr(base_ids), ptr(alpha), ptr(seg), ptr(pos), ptr(word), ptr(type_tab), ptr(ptab), ptr(gamma),
+                                   ptr(dhidden), ptr(attr), pairs, m, S, H, eps, dtype_code(word.dtype), stream_ptr()), "embed_attrib")
+    return attr
 
 
 def word_perm(ids):

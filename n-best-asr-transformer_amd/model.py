@@ -621,6 +621,138 @@ class NBestSTCModel(nn.Module):
             out["cls_attn"] = cls_attn
         return out
 
+    # ---- integrated-gradients attribution (forward + input-gradient backward, no parameter gradient) ------------------------
+    def default_baseline(self, input_ids):
+        """the default IG baseline: every non-padding token except position 0 ([CLS] / <s>) replaced by the pad id"""
+        pad = self.cfg.pad_token_id
+        base = torch.where(input_ids.ne(pad), torch.full_like(input_ids, pad), input_ids)
+        base[:, 0] = input_ids[:, 0]
+        return base
+
+    def attribute(self, input_ids, seg_ids=None, targets=None, steps=32, baseline_ids=None, max_rows=256):
+        """Integrated gradients (Sundararajan et al., 2017) of the STC final score F = final[row, c] w.r.t. the word embeddings of
+        the ASR pass, one share per token: A[t] = (1/m) sum_k dF/dE_t(a_k) . (word[x_t] - word[x'_t]), a_k = (k + 1/2) / m,
+        E_t(a) = ((1 - a) word[x'_t] + a word[x_t]) + type + position (positions, token types and key mask those of x).
+        ``targets``: [P, 2] (row, bottom label); None = every label predict() decodes, rows in order.  ``baseline_ids``: x' (must
+        keep the padding of input_ids); None = default_baseline.  Path rows (m per pair) and a forward-only a = 0 and a = 1 row per
+        utterance run in encoder calls of at most ``max_rows`` sequences; a pair's rows are never split and every call holds at least
+        one pair, so a call exceeds ``max_rows`` only when one pair's m + 2 rows do (any ``steps`` >= 1 runs).
+        Returns dict(attr fp32 [P, S], row, label (int64 [P]), score = F at a = 1, baseline_score = F at a = 0 (fp32 [P])):
+        sum_t attr ~ score - baseline_score (completeness, up to the Riemann error of m points).
+        Touches no training state, as predict(); an fp8w model attributes on its bf16 weight copy.  One GPU."""
+        cfg, a = self.cfg, self.arena
+        m, max_rows = int(steps), int(max_rows)
+        if m < 1:
+            raise ValueError("nbest_amd attribute: steps must be >= 1 (got %d)" % m)
+        if max_rows < 1:
+            raise ValueError("nbest_amd attribute: max_rows must be >= 1 (got %d)" % max_rows)
+        B, S = input_ids.shape
+        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
+        if S > 512 or S + first_pos > cfg.max_position_embeddings:
+            raise RuntimeError("nbest_amd attribute: S=%d does not fit the position table (%d rows)" % (S, cfg.max_position_embeddings))
+        ids = input_ids.to(self.device).long().contiguous()
+        pad = cfg.pad_token_id
+        if baseline_ids is None:
+            base = self.default_baseline(ids)
+        else:
+            base = baseline_ids.to(self.device).long().contiguous()
+            if base.shape != ids.shape:
+                raise ValueError("nbest_amd attribute: baseline_ids %s != input_ids %s" % (tuple(base.shape), tuple(ids.shape)))
+            if bool(base[ids.eq(pad)].ne(pad).any()):
+                raise ValueError("nbest_amd attribute: baseline_ids must keep the padding of input_ids (pad id %d)" % pad)
+        seg = None if seg_ids is None else seg_ids.to(self.device).long().contiguous()
+        if targets is None:
+            pred = self.predict(ids, seg)["pred"].cpu().tolist()
+            targets = [(b, c) for b in range(B) for c in pred[b] if c >= 0]
+        tg = [(int(b), int(c)) for b, c in (targets.tolist() if torch.is_tensor(targets) else targets)]
+        for b, c in tg:
+            if not (0 <= b < B and 0 <= c < self.labels.n_bottom):
+                raise ValueError("nbest_amd attribute: target (%d, %d) outside rows [0, %d) / labels [0, %d)" % (b, c, B, self.labels.n_bottom))
+        P = len(tg)
+        f = dict(dtype=torch.float32, device=self.device)
+        out = dict(attr=torch.zeros(P, S, **f), row=torch.tensor([b for b, _ in tg], dtype=torch.long),
+                   label=torch.tensor([c for _, c in tg], dtype=torch.long), score=torch.zeros(P, **f), baseline_score=torch.zeros(P, **f))
+        if P == 0:
+            return out
+        # calls: a pair's m rows never split, every call holds at least one pair (then it may exceed max_rows); an utterance's
+        # a = 0 / a = 1 rows ride in the call of its first pair
+        calls, cur, rows, seen = [], [], 0, set()
+        for i, (b, _) in enumerate(tg):
+            cost = m + (0 if b in seen else 2)
+            if cur and rows + cost > max_rows:
+                calls.append(cur)
+                cur, rows = [], 0
+            cur.append(i)
+            rows += cost
+            seen.add(b)
+        calls.append(cur)
+        pre = "bert_encoder.embeddings."
+        w16 = a.weights
+        word, ttab, ptab = (a.view(w16, pre + n) for n in ("word_embeddings.weight", "token_type_embeddings.weight", "position_embeddings.weight"))
+        gamma = a.view(a.p, pre + "LayerNorm.weight")
+        Wh, bh = a.heads_wb()
+        R, nt, nb = self.dls.n_rows, self.labels.n_top, self.labels.n_bottom
+        path_alpha = (torch.arange(m, dtype=torch.float64) + 0.5) / m
+        extras, ends = set(), {}                             # utterances whose a = 0 / a = 1 rows already ran; their final rows
+        for call in calls:
+            rows_b = [tg[i][0] for i in call]
+            xs = []
+            for b in rows_b:
+                if b not in extras and b not in xs:
+                    xs.append(b)
+            extras.update(xs)
+            n = len(call)
+            Bc = n * m + 2 * len(xs)
+            seq = torch.tensor([b for b in rows_b for _ in range(m)] + [b for b in xs for _ in range(2)], dtype=torch.long, device=self.device)
+            alpha = torch.cat([path_alpha.repeat(n), torch.tensor([0.0, 1.0], dtype=torch.float64).repeat(len(xs))]).to(**f)
+            ids_c, base_c = ids[seq].contiguous(), base[seq].contiguous()
+            ids_c, seg_c, pos_c, mask_c = self._inputs(ids_c, None if seg is None else seg[seq])
+            ps = self._desc(Bc, S, "attrib")
+            d = ps.desc
+            act = self._grow(self._stash, "attrib", ps.act_bytes)[:ps.act_bytes]
+            ws = self._grow(vars(self), "_attr_ws", hb.lib().nbest_encoder_ws_bytes(C.byref(d)))
+            d.hidden_drop = d.attn_drop = 0.0
+            d.seed = 0
+            d.base_ids, d.alpha = base_c.data_ptr(), alpha.data_ptr()
+            self._set_weights(d, "infer")
+            hid = C.c_void_p()
+            hb.check(hb.lib().nbest_encoder_forward(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids_c), hb.ptr(seg_c), hb.ptr(pos_c),
+                                                    hb.ptr(mask_c), hb.ptr(act), act.numel(), hb.ptr(ws), ws.numel(), C.byref(hid),
+                                                    hb.stream_ptr()), "encoder_forward(attribute)")
+            esz = 2 if self.compute_dtype == torch.bfloat16 else 4
+            off = hid.value - act.data_ptr()
+            hidden = act[off:off + Bc * S * H * esz].view(self.compute_dtype).view(Bc * S, H)
+            hws = self._grow(vars(self), "_attr_heads_ws", hb.lib().nbest_heads_ws_bytes(Bc, R, H))
+            top, bott, fin, _, _, _, _ = hb.stc_heads(hidden, S * H, Wh, bh, self.dls, torch.zeros(Bc, nb, **f), Bc, H, need_grad=False,
+                                                      drop_p=0.0, ws=hws)
+            dfin = torch.zeros(Bc, nb, **f)
+            lab = torch.tensor([tg[i][1] for i in call], dtype=torch.long, device=self.device)
+            dfin[torch.arange(n * m, device=self.device), lab.repeat_interleave(m)] = 1.0
+            dWh_s, dbh_s = torch.empty(R, H, **f), torch.empty(R, **f)   # the heads' parameter gradients: scratch, never read
+            dcls = hb.stc_heads_vjp(Wh, self.dls, top, bott, torch.zeros(Bc, nt, **f), torch.zeros(Bc, R - nt, **f), dfin, Bc, H, dWh_s, dbh_s,
+                                    hws, accumulate=False)
+            dh = self._grow(vars(self), "_attr_dh", Bc * S * H, self.compute_dtype)[:Bc * S * H].view(Bc * S, H)
+            dh = hb.cls_grad_scatter(dcls, Bc, S, H, self.compute_dtype, out=dh)
+            d.no_param_grad = 1
+            wt = None if a.w16t_stale else a.w16t           # a stale transposed copy is not read (and not refreshed): transposed reads of wts
+            if wt is None:
+                d.wpkt = None
+            hb.check(hb.lib().nbest_encoder_backward(C.byref(d), hb.ptr(a.weights), hb.ptr(wt), hb.ptr(a.p), None, hb.ptr(ids_c),
+                                                     hb.ptr(seg_c), hb.ptr(pos_c), hb.ptr(mask_c), hb.ptr(act), act.numel(), hb.ptr(dh),
+                                                     hb.ptr(ws), ws.numel(), 0, 0, L, 0, hb.stream_ptr()), "encoder_backward(attribute)")
+            d.no_param_grad = 0
+            d.base_ids = d.alpha = None
+            # the pairs of a call are consecutive targets: their rows of attr are written in place
+            hb.embed_attrib(ids_c, base_c, alpha, seg_c, pos_c, word, ttab, ptab, gamma, dh, n, m, S, cfg.layer_norm_eps,
+                            out=out["attr"][call[0]:call[-1] + 1])
+            for j, b in enumerate(xs):                       # F at a = 0 and a = 1 of the utterances whose extra rows ran here
+                ends[b] = fin[n * m + 2 * j:n * m + 2 * j + 2]
+        for i, (b, c) in enumerate(tg):
+            out["baseline_score"][i] = ends[b][0, c]
+            out["score"][i] = ends[b][1, c]
+        return out
+
     def decode(self, top, bott, out=None):
         """device decode of pred_one_sample -> int32 [B, n_top] bottom-label index or -1 (``out``: see hipabi.stc_decode)"""
         return hb.stc_decode(top, bott, self.dls, out=out)

@@ -799,13 +799,29 @@ def attention_record(line, spans, cls_attn):
             "mass": [[round(x, 6) for x in row] for row in m.tolist()]}
 
 
+def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
+    """one --predict_attribution JSON record.  ``attr_row``: per label, fp32 [>= tokens] integrated-gradients attribution of one
+    utterance (model.attribute); ``spans``: inputs.utterance_segments of it (as attention_record); ``labels`` / ``scores`` /
+    ``baselines``: the label strings in the .pred line's order and F at alpha = 1 / alpha = 0.  ``mass`` = per-span sums of
+    ``token_attr`` (fp64), so sum(mass) ~ score - baseline_score."""
+    ntok = spans[-1][2] if spans else 0
+    out = []
+    for a, lbl, sc, bs in zip(attr_row, labels, scores, baselines):
+        t = [float(x) for x in a.detach().double().cpu()[:ntok].tolist()]
+        out.append({"label": lbl, "score": round(float(sc), 6), "baseline_score": round(float(bs), 6),
+                    "mass": [round(sum(t[lo:hi]), 6) for _, lo, hi in spans], "token_attr": [round(x, 6) for x in t]})
+    return {"line": line, "segments": [n for n, _, _ in spans], "tokens": [hi - lo for _, lo, hi in spans], "steps": int(steps),
+            "labels": out}
+
+
 @torch.no_grad()
-def predict_split(model, data, opt, memory, attn_fp=None):
+def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32):
     """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
     [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
     ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only.
     ``attn_fp`` (--predict_attention): a text file that receives one attention_record JSON line per utterance, in split order
-    ("line": 1-based index in the split)."""
+    ("line": 1-based index in the split).  ``attr_fp`` (--predict_attribution): one attribution_record JSON line per utterance, in
+    split order - integrated gradients (model.attribute, ``attr_steps`` path points) of every label the .pred line lists."""
     _, world = dist_info()
     if world > 1:
         raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
@@ -818,14 +834,34 @@ def predict_split(model, data, opt, memory, attn_fp=None):
         seg = b["seg"] if opt.add_segment_ids else None
         out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None)
         pipe.push(out, [split.labels[j] for j in mine], tag=mine)
+        spans_of = {}
+        for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None) else []):
+            spans = utterance_segments(split.asr[j], opt.tokenizer, opt, getattr(opt, "n_best", None), getattr(opt, "max_seq_len", None))
+            if spans[-1][2] != len(split.rows[j][0]):
+                raise RuntimeError("nbest_amd: line %d: segment spans cover %d tokens, the encoded utterance has %d"
+                                   % (j + 1, spans[-1][2], len(split.rows[j][0])))
+            spans_of[j] = spans
         if attn_fp is not None:
             ca = out["cls_attn"].cpu()
             for k, j in enumerate(mine):
-                spans = utterance_segments(split.asr[j], opt.tokenizer, opt, getattr(opt, "n_best", None), getattr(opt, "max_seq_len", None))
-                if spans[-1][2] != len(split.rows[j][0]):
-                    raise RuntimeError("nbest_amd: line %d: segment spans cover %d tokens, the encoded utterance has %d"
-                                       % (j + 1, spans[-1][2], len(split.rows[j][0])))
-                attn_fp.write(json.dumps(attention_record(j + 1, spans, ca[:, k])) + "\n")
+                attn_fp.write(json.dumps(attention_record(j + 1, spans_of[j], ca[:, k])) + "\n")
+        if attr_fp is not None:
+            # the labels of the .pred line: decoded rows -> label strings (ontology filter as MetricsPipe) -> their bottom ids
+            rows = out["pred"].cpu().tolist()
+            kept = []
+            for k, row in enumerate(rows):
+                names = pred_labels_from_indices(row, memory["idx2label"])
+                keep = set(filter_informative(names, onto)) if onto is not None else set(names)
+                kept.append([(c, memory["idx2label"][c]) for c in row if c >= 0 and memory["idx2label"][c] in keep])
+            targets = [(k, c) for k, lst in enumerate(kept) for c, _ in lst]
+            res = model.attribute(b["ids"], seg_ids=seg, targets=targets, steps=attr_steps)
+            at, sc, bs = res["attr"].cpu(), res["score"].cpu(), res["baseline_score"].cpu()
+            i = 0
+            for k, j in enumerate(mine):
+                n = len(kept[k])
+                attr_fp.write(json.dumps(attribution_record(j + 1, spans_of[j], at[i:i + n], [nm for _, nm in kept[k]], sc[i:i + n],
+                                                            bs[i:i + n], attr_steps)) + "\n")
+                i += n
     _, tagged = pipe.finish()
     return [(split.asr[j], pc) for mine, preds in tagged for j, pc in zip(mine, preds)]
 
