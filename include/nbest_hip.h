@@ -174,6 +174,15 @@ int nbest_gemm(const nbest_gemm_args* a, nbest_stream_t stream);
  * nbest_wgrad_pair_ws_bytes returns 0 and nbest_wgrad_pair NBEST_ERR_SHAPE for pairs that do not fit (issue two nbest_gemm).   */
 size_t nbest_wgrad_pair_ws_bytes(const nbest_gemm_args* a, const nbest_gemm_args* b);
 int nbest_wgrad_pair(const nbest_gemm_args* a, const nbest_gemm_args* b, nbest_stream_t stream);
+/* n (1 .. 8) weight gradients dW_i[M_i][N_i] (fp32) (+)= dY_i^T . X_i (bf16 operands, trans_a = trans_b = 1, NBEST_EPI_F32_SPLITK) that share
+ * the token dimension K and `accumulate`, in ONE launch WITHOUT K-splits: the 256 x 256 output tiles of all problems are concatenated, one
+ * workgroup walks the whole K of one tile and writes (accumulate: adds) it straight into its gradient - no slabs (ws / ws_bytes are not
+ * read), no reduce launch.  Each problem has its own pointers and leading dimensions; every M_i, N_i a multiple of 256, else
+ * NBEST_ERR_SHAPE and nothing is launched.  It pays when the tiles of the group fill most of the 256 CUs in one round: used by
+ * nbest_encoder_backward for the four gradients of TWO bert-base layers (2 x 108 tiles) - the backward of the nn.Linear of installed
+ * modeling_bert.py:154-177, 282-293, 325-351.  Each element is one fp32 chain over K in a fixed order: equal to nbest_gemm's result up to
+ * the summation order, bit-reproducible run to run.                                                                                    */
+int nbest_wgrad_group(const nbest_gemm_args* problems, int n, nbest_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * fp8 forward GEMMs (dtype path NBEST "fp8w": BASELINE configs[4], "fp8 weights (CDNA4 fp8 MFMA)")
@@ -504,7 +513,11 @@ typedef struct nbest_encoder_desc {
    * handles; nbest_encoder_backward records wgrad_events[2*i] before and [2*i+1] after the i-th weight-gradient
    * launch it enqueues (nbest_encoder_wgrad_launches_per_layer() per layer, highest layer first: FFN-down, FFN-up,
    * attention-out, QKV - or, bf16, FFN-down, FFN-up, QKV + attention-out as one nbest_wgrad_pair launch), on the
-   * caller's stream, while i < wgrad_events_n / 2.  The library never creates, waits on or destroys events.      */
+   * caller's stream, while i < wgrad_events_n / 2.  The library never creates, waits on or destroys events.
+   * Grouped weight gradients (wgrad_group below; launches per layer == 1): ONE pair per layer, recorded so that the pairs of the
+   * layers of a group add up to the group's launch - the pair of the group's first (highest) layer brackets the grouped launch, the
+   * pair of its second layer is recorded back to back right after it - so the mean over the pairs is the time per LAYER's worth
+   * of gradients.  A layer left without a partner issues its split-K launches back to back at its end, inside its one pair.  */
   void** wgrad_events;
   /* optional fp8 forward ("fp8w"; dtype must be NBEST_BF16): e4m3 copy of the weight arena (one byte per element at the
    * same element offsets) and its per-matrix inverse scales [4 L] (QKV, attention-out, FFN-up, FFN-down per layer), both
@@ -566,15 +579,25 @@ typedef struct nbest_encoder_desc {
    * row-reduction finalize).  dhidden is bit-equal to that of the ordinary backward on the same stash.  Refuses with_embeddings,
    * first_trainable > 0, no_input_grad and the fp8 forward (w8).                                                                 */
   int32_t no_param_grad;
-  int32_t pad5;
+  /* (the descriptor's last field, in the slot that was padding: zero = the plan decides, the size of the struct is unchanged)
+   * weight gradients of two layers in one launch without K-splits (nbest_wgrad_group; bf16 without the fp8 forward, H and F multiples
+   * of 256): NBEST_WGRAD_GROUP_PLAN (0) - the library's plan decides from the tile counts and the token count (it groups where its
+   * launch-cost model predicts a gain: bert-base / xlm-roberta-base shapes; not xlm-roberta-large, whose 192 tiles per layer leave no
+   * room for a second layer), NBEST_WGRAD_GROUP_NEVER - the split-K launches of every layer, NBEST_WGRAD_GROUP_ALWAYS - group wherever the
+   * shapes allow.  Layers l, l-1 of a backward call's [layer_begin, layer_end) form a group, from the top; a group never crosses the
+   * range, and a layer left over runs the split-K launches.  The dY tensors of a layer then live until the group's launch: two sets
+   * of them in the workspace (nbest_encoder_ws_bytes follows this field).  Same results up to the fp32 summation order over K.      */
+  int32_t wgrad_group;
 } nbest_encoder_desc;
+enum { NBEST_WGRAD_GROUP_PLAN = 0, NBEST_WGRAD_GROUP_NEVER = 1, NBEST_WGRAD_GROUP_ALWAYS = 2 };
 size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
 /* Pointers into a stash `act` written by nbest_encoder_forward with descriptor d: layer `layer`'s qkv [M][3H] (dtype; also in the fp8
  * forward and its calibration pass) and lse [B][heads][S] (fp32) - the inputs of nbest_attention_probs.  Refuses (NBEST_ERR_ARG) a
  * layer outside [first_trainable, L): frozen layers are not stashed.  Enqueues nothing.                                           */
 int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, int layer, void** qkv, float** lse);
 size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d);
-/* weight-gradient launches nbest_encoder_backward enqueues per layer for this descriptor: 3 when the attention-output gradient
+/* weight-gradient launches nbest_encoder_backward enqueues per layer for this descriptor = event pairs per layer in wgrad_events:
+ * 1 when the gradients of two layers share one grouped launch (desc.wgrad_group), else 3 when the attention-output gradient
  * rides with the QKV gradient (nbest_wgrad_pair; bf16, shapes that fit), else 4 */
 int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d);
 /* hidden_out: pointer to the final hidden states [M][H] inside act (returned through *hidden_out) */

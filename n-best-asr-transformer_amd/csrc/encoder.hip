@@ -11,7 +11,8 @@
 //              u = gelu'(pre-activation) [M][F] (fp32, or 8-bit fixed point in the bf16 path) | hact [M][F] T | r2 [M][H] T |
 //              st2 [M][2] f32 | keep: the attention-dropout keep words (bf16) |
 //              fp8 forward (desc.w8) only: x8 | ctx8 | x18 [M][H] e4m3, h8 [M][F] e4m3, the copies of the layer's four GEMM inputs
-// Scratch `ws` (ws_layout): dR | dRd | dB1 | dctx [M][H] T, dBig [M][F] T, dqkv [M][3H] T, four regions of column-reduction
+// Scratch `ws` (ws_layout): dR | dRd | dB1 | dctx [M][H] T, dBig [M][F] T, dqkv [M][3H] T, (grouped weight gradients: the dY buffers
+//   of the group positions, WsLayout::gset), four regions of column-reduction
 //   partials, split-K slabs, embedding-backward buffer, f8 (bf16: the e4m3 copies of ONE layer - forward: a frozen layer's GEMM
 //   inputs, backward: the gradients the fp8 dgrads read), fz (K > 0: X0 | X1 | emb_stats | lse | st1 | st2 | u).
 //   Layers 0..K-1 are not stashed: their forward runs on fz plus the backward's layer-gradient buffers, which are idle
@@ -82,6 +83,9 @@ static ActLayout act_layout(const nbest_encoder_desc* d, const Sizes& z) {
 
 struct WsLayout {
   size_t dR, dRd, dB1, dctx, dBig, dqkv, red, slab, slab_bytes, red_bytes, emb, emb_bytes, f8, f8_bytes, total;
+  // grouped weight gradients (wgrad_group_layers > 0): the four dY tensors of a layer - dRd after LN2, dBig, dRd after LN1, dqkv - per
+  // position of the layer in its group; set 0 shares dRd, dBig and dqkv above
+  size_t gset[2][4];
   size_t fz_x0, fz_x1, fz_emb_stats, fz_lse, fz_st1, fz_st2, fz_u;   // forward of the frozen layers 0..K-1 (first_trainable = K > 0)
 };
 
@@ -119,12 +123,45 @@ static size_t max_splitk_bytes(const nbest_encoder_desc* d, int64_t M) {
 // 3 weight-gradient launches per layer instead of 4) when the pair fits one 256 x 256 split-K launch
 static bool wgrad_paired(const nbest_encoder_desc* d, bool f8b) { return d->dtype == NBEST_BF16 && wgrad_pair_bytes(d, f8b) > 0; }
 
+// ---- grouped weight gradients: the plan ----------------------------------------------------------------------------------------
+// Launch-cost model of the 256 x 256 weight-gradient kernel (us), fitted on the FFN-down gradient alone, cold operands, at K = 32 768,
+// 65 536 and 131 072 token rows: a launch costs kWgA + kWgB per 32-row K stage a workgroup walks, per round of 256
+// workgroups; a split-K reduce launch costs kWgRed.
+constexpr double kWgA = 24.5, kWgB = 0.705, kWgRed = 12.7;
+static double wgrad_splitk_us(int64_t rows, int64_t cols, int64_t M) {
+  const nbest_gemm_args g = wgrad_args(NBEST_BF16, rows, cols, M);
+  const size_t ws = nbest_gemm_ws_bytes(&g);
+  const int64_t splits = ws ? (int64_t)(ws / ((size_t)rows * cols * sizeof(float))) : 1;
+  const int64_t stages = ((M + splits - 1) / splits + 31) / 32, wgs = (rows / 256) * (cols / 256) * splits;
+  return kWgA + kWgB * (double)(stages * ((wgs + 255) / 256)) + (splits > 1 ? kWgRed : 0.0);
+}
+// Layers per grouped weight-gradient launch (nbest_wgrad_group; include/nbest_hip.h, desc.wgrad_group): 0 = every layer issues its
+// split-K launches.  Grouping needs the bf16 path without the fp8 forward (whose backward has its own weight-gradient kernels) and
+// whole 256 x 256 tiles.  The plan groups two layers when their tiles fit one round of the 256 CUs and the model above predicts
+// at least 5 % less time than the three split-K launches + reduces of each layer.
+static int wgrad_group_layers(const nbest_encoder_desc* d) {
+  if (d->wgrad_group == NBEST_WGRAD_GROUP_NEVER) return 0;
+  if (d->dtype != NBEST_BF16 || d->w8 || d->H % 256 || d->F % 256) return 0;
+  const int64_t H = d->H, F = d->F, M = (int64_t)d->B * d->S;
+  const int64_t tiles = (4 * H * H + 2 * H * F) / (256 * 256);   // of one layer's four gradients
+  if (d->wgrad_group == NBEST_WGRAD_GROUP_ALWAYS) return 2 * tiles <= 256 ? 2 : 1;
+  if (2 * tiles > 256 || !wgrad_paired(d, false)) return 0;
+  const double today = wgrad_splitk_us(4 * H, H, M) + wgrad_splitk_us(F, H, M) + wgrad_splitk_us(H, F, M);
+  const double grouped = (kWgA + kWgB * (double)((M + 31) / 32)) / 2.0;
+  return grouped < 0.95 * today ? 2 : 0;
+}
+
 static WsLayout ws_layout(const nbest_encoder_desc* d, const Sizes& z) {
   WsLayout w;
   const int64_t M = z.M;
   size_t o = 0;
   w.dR = take(o, z.MH); w.dRd = take(o, z.MH); w.dB1 = take(o, z.MH); w.dctx = take(o, z.MH);
   w.dBig = take(o, z.MF); w.dqkv = take(o, z.M3H);
+  for (int s = 0; s < 2; ++s) { w.gset[s][0] = w.dRd; w.gset[s][1] = w.dBig; w.gset[s][2] = w.dRd; w.gset[s][3] = w.dqkv; }
+  if (wgrad_group_layers(d) > 0) {
+    w.gset[0][2] = take(o, z.MH);
+    if (wgrad_group_layers(d) > 1) { w.gset[1][0] = take(o, z.MH); w.gset[1][1] = take(o, z.MF); w.gset[1][2] = take(o, z.MH); w.gset[1][3] = take(o, z.M3H); }
+  }
   const int64_t maxN = d->F > 3 * d->H ? d->F : 3 * d->H;
   w.red_bytes = al(nbest_rowred_ws_bytes(M, maxN));
   w.red_bytes = std::max(w.red_bytes, al(nbest_attention_bwd_ws_bytes(d->B, d->S, d->heads)));
@@ -393,7 +430,9 @@ extern "C" int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, in
 }
 extern "C" size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d) { return d ? ws_layout(d, sizes(d)).total : 0; }
 extern "C" int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d) {
-  return d ? (wgrad_paired(d, fp8_backward_active(d)) ? 3 : 4) : 0;
+  if (!d) return 0;
+  if (wgrad_group_layers(d) > 0) return 1;
+  return wgrad_paired(d, fp8_backward_active(d)) ? 3 : 4;
 }
 
 extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids,
@@ -486,7 +525,10 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   // optional in-step timing of the weight-gradient GEMMs (see nbest_encoder_desc::wgrad_events)
   const bool f8b = fp8_backward_active(d);
   const bool paired = wgrad_paired(d, f8b);
-  int ev_i = (paired ? 3 : 4) * (d->L - layer_end);
+  // grouped weight gradients: gl layers per nbest_wgrad_group launch, groups formed from layer_end - 1 downwards
+  const int gl = wgrad_group_layers(d);
+  const bool grouped = gl > 0;
+  int ev_i = (grouped ? 1 : paired ? 3 : 4) * (d->L - layer_end);
   auto stamp = [&](int which) {
     if (d->wgrad_events && 2 * ev_i + which < d->wgrad_events_n) (void)hipEventRecord((hipEvent_t)d->wgrad_events[2 * ev_i + which], st);
     ev_i += which;
@@ -509,11 +551,15 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                        d->w8t, d->w8tp, d->w8_inv_scale, d->gamax_prev, d->gamax_new, red1, w.red_bytes, accumulate};
   // Weight gradient j of the layer described by wg[4], between its two event stamps, or gradients j and j2 as one paired launch.
   // A skipped gradient launches nothing (its stamps are still recorded); of a pair with one half skipped the other goes alone.
-  auto wgrad = [&](int l, const WGrad* wg, int j, int j2) -> int {
+  auto wgrad_args_of = [&](const WGrad* x) {
+    nbest_gemm_args g = wgrad_args(dt, x->rows, x->cols, M);
+    g.A = x->dY; g.B = x->X; g.C = G(x->w_off); g.accumulate = accumulate;
+    return g;
+  };
+  auto wgrad_launch = [&](int l, const WGrad* wg, int j, int j2) -> int {
     const WGrad* p = skip(l, j) ? nullptr : wg + j;
     const WGrad* q = (j2 >= 0 && !skip(l, j2)) ? wg + j2 : nullptr;
     if (!p) { p = q; q = nullptr; }
-    stamp(0);
     if (p && f8b) {
       const uint32_t *gp = d->gamax_prev, *ap = d->aamax_prev;
       if (q)
@@ -524,18 +570,24 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
         RUN(nbest_wgrad_fp8(p->dY8, p->X8, G(p->w_off), p->rows, p->cols, M, p->rows, p->cols, p->cols, gp + p->g_idx, ap + p->a_idx,
                             accumulate, slab, w.slab_bytes, stream));
     } else if (p) {
-      auto args = [&](const WGrad* x) {
-        nbest_gemm_args g = wgrad_args(dt, x->rows, x->cols, M);
-        g.A = x->dY; g.B = x->X; g.C = G(x->w_off); g.accumulate = accumulate;
-        return g;
-      };
-      nbest_gemm_args g1 = args(p), g2 = args(q ? q : p);
+      nbest_gemm_args g1 = wgrad_args_of(p), g2 = wgrad_args_of(q ? q : p);
       g1.ws = slab; g1.ws_bytes = w.slab_bytes;   // (a pair: the slabs of both)
       RUN(q ? nbest_wgrad_pair(&g1, &g2, stream) : nbest_gemm(&g1, stream));
     }
+    return NBEST_OK;
+  };
+  auto wgrad = [&](int l, const WGrad* wg, int j, int j2) -> int {
+    stamp(0);
+    RUN(wgrad_launch(l, wg, j, j2));
     stamp(1);
     return NBEST_OK;
   };
+  // Grouped: the gradients of a layer are deferred to the end of its group (their dY tensors live in the group position's buffer set,
+  // their X tensors in the stash, which the backward only reads) and go out as ONE nbest_wgrad_group launch: per layer QKV,
+  // attention-out, FFN-up, FFN-down, the higher layer first.  A layer left without a partner (odd range; plan mode) issues its
+  // split-K launches back to back instead.  One event pair per layer (include/nbest_hip.h, wgrad_events).
+  nbest_gemm_args pend[8];
+  int n_pend = 0;
 
   struct BatchGuard { ~BatchGuard() { nbest_internal_rowred_batch_abort(); } } batch_guard;   // an error return mid-layer must not leave it open
   for (int l = layer_end - 1; l >= layer_begin; --l) {
@@ -544,45 +596,74 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     const bool input_grad = !(d->no_input_grad && l == FT);   // the gradient w.r.t. the input of layer FT has no reader
     const int t = 4 * l;
     const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
-    const WGrad wg[4] = {{dqkv, X(l), dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0},
-                         {dRd, b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},
-                         {dBig, b.x1, dBig8, b.x18, o.w1, F, H, t + 1, t + 2},
-                         {dRd, b.hact, dRd8, b.h8, o.w2, H, F, t + 0, t + 3}};
+    // this layer's gradient buffers: the shared ones, or (grouped) those of its position in the group, which the next layer leaves alone.
+    // dR2 / dRd2: residual- and dense-branch gradients out of the LN2 backward, dR1 / dRd1: out of the LN1 backward (one buffer
+    // without hidden dropout)
+    const int gpos = grouped ? (layer_end - 1 - l) % gl : 0;
+    const bool group_ends = grouped && (gpos == gl - 1 || l == layer_begin);
+    void *dR2 = dR, *dR1 = dR, *dRd2 = dRd, *dRd1 = dRd, *dBigL = dBig, *dqkvL = dqkv;
+    if (grouped) {
+      dRd2 = W + w.gset[gpos][0]; dBigL = W + w.gset[gpos][1]; dRd1 = W + w.gset[gpos][2]; dqkvL = W + w.gset[gpos][3];
+      if (!hdrop) { dR2 = dRd2; dR1 = dRd1; }
+    }
+    const WGrad wg[4] = {{dqkvL, X(l), dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0},
+                         {dRd1, b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},
+                         {dBigL, b.x1, dBig8, b.x18, o.w1, F, H, t + 1, t + 2},
+                         {dRd2, b.hact, dRd8, b.h8, o.w2, H, F, t + 0, t + 3}};
     if (!npg) nbest_internal_rowred_batch_begin();    // the layer's four bias / LayerNorm-parameter reductions: one finalize launch at its end
     // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
     // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
-    RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), dR, (hdrop && !f8b) ? dRd : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H,
+    RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), dR2, (hdrop && !f8b) ? dRd2 : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H,
                                       dt, accumulate, d->hidden_drop, d->seed, s0 + 2, red, w.red_bytes, stream, fg(dRd8, t + 0)));   // partial rows: region 0
     // FFN-down: dgrad fused with GELU' -> dU ; wgrad
     // (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
-    GemmOp dw2 = {dRd, dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : dBig, F, H, NBEST_EPI_DGELU};
+    GemmOp dw2 = {dRd2, dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : dBigL, F, H, NBEST_EPI_DGELU};
     dw2.U = b.u; dw2.colsum = GP(o.b1); dw2.C8 = dBig8; dw2.c_idx = t + 1;
     RUN(layer_gemm(dg, dw2));
-    if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBig, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
-    RUN(wgrad(l, wg, 3, -1));
+    if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBigL, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
+    if (!grouped) RUN(wgrad(l, wg, 3, -1));
     // FFN-up: dgrad + residual gradient ; wgrad
-    GemmOp dw1 = {dBig, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
-    dw1.R = dR;
+    GemmOp dw1 = {dBigL, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
+    dw1.R = dR2;
     RUN(layer_gemm(dg, dw1));
-    RUN(wgrad(l, wg, 2, -1));
+    if (!grouped) RUN(wgrad(l, wg, 2, -1));
     // LN1 backward
-    RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR, (hdrop && !f8b) ? dRd : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
+    RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, (hdrop && !f8b) ? dRd1 : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
                                       dt, accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, t + 2)));
     // attention output projection: dgrad ; wgrad
-    const GemmOp dwo = {dRd, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
+    const GemmOp dwo = {dRd1, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
     RUN(layer_gemm(dg, dwo));
     // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
-    if (!paired) RUN(wgrad(l, wg, 1, -1));
+    if (!paired && !grouped) RUN(wgrad(l, wg, 1, -1));
     // attention backward -> dqkv ; QKV bias gradient
-    RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkv, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
+    RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkvL, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
                                       d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, t + 3), b.keep));
     // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad (with the attention-out gradient when paired)
     if (input_grad) {
-      GemmOp dwqkv = {dqkv, dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
-      dwqkv.R = dR;
+      GemmOp dwqkv = {dqkvL, dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
+      dwqkv.R = dR1;
       RUN(layer_gemm(dg, dwqkv));
     }
-    RUN(wgrad(l, wg, 0, paired ? 1 : -1));
+    if (!grouped) {
+      RUN(wgrad(l, wg, 0, paired ? 1 : -1));
+    } else if (group_ends && gpos + 1 < gl && d->wgrad_group != NBEST_WGRAD_GROUP_ALWAYS) {   // no partner: today's launches, one event pair
+      stamp(0);
+      RUN(wgrad_launch(l, wg, 3, -1));
+      RUN(wgrad_launch(l, wg, 2, -1));
+      if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
+      RUN(wgrad_launch(l, wg, 0, paired ? 1 : -1));
+      stamp(1);
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (!skip(l, j)) pend[n_pend++] = wgrad_args_of(wg + j);
+      if (group_ends) {
+        stamp(0);
+        if (n_pend) RUN(nbest_wgrad_group(pend, n_pend, stream));
+        stamp(1);
+        for (int i = 0; i < gpos; ++i) { stamp(0); stamp(1); }
+        n_pend = 0;
+      }
+    }
     if (!npg) RUN(nbest_internal_rowred_batch_flush(st));
   }
   if (!with_embeddings) return NBEST_OK;

@@ -130,3 +130,18 @@ extern "C" int nbest_wgrad_pair(const nbest_gemm_args* a, const nbest_gemm_args*
   if (int rc = check_bf16(b)) return rc;
   return nbest_wgrad_pair_bf16(a, b, (hipStream_t)stream);
 }
+
+// ---- up to 8 weight gradients, one launch without K-splits (include/nbest_hip.h) ----------------------------------------
+extern "C" int nbest_wgrad_group(const nbest_gemm_args* problems, int n, nbest_stream_t stream) {
+  NB_CHECK(problems && n >= 1 && n <= 8, NBEST_ERR_ARG, "wgrad_group: needs 1 .. 8 problems");
+  for (int i = 0; i < n; ++i) {
+    const nbest_gemm_args* a = problems + i;
+    NB_CHECK(a->A && a->B && a->C, NBEST_ERR_ARG, "wgrad_group: null pointer in problem %d", i);
+    NB_CHECK(a->M > 0 && a->N > 0 && a->K > 0, NBEST_ERR_SHAPE, "wgrad_group: bad shape in problem %d", i);
+    NB_CHECK(a->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "wgrad_group: bf16 operands only");
+    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_group: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", i,
+             (long long)a->M, (long long)a->N);
+    if (int rc = check_bf16(a)) return rc;
+  }
+  return nbest_wgrad_group_bf16(problems, n, (hipStream_t)stream);
+}

@@ -268,8 +268,10 @@ __device__ __forceinline__ void tt_mfma(const bf16x8* af, const bf16x8* bfr, f32
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// the whole workgroup program of gemm2_kernel; `id`: the workgroup's tile id (split-major, tile-minor) within the problem `p`.  A function
+// of its own so that gemm2_kernel_grouped can run it on a problem it picks per workgroup.
 template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, int EPI>
-__global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
+__device__ __forceinline__ void gemm2_body(const GemmP2& p, const int id) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   constexpr int NT = WM * WN * 64;                   // 256 threads (2 x 2 waves) or 512 (2 x 4 waves)
   constexpr int WTM = BM / WM, WTN = BN / WN;
@@ -284,8 +286,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
 
-  const int nwg = gridDim.x;
-  const int id = xcd_remap(blockIdx.x, nwg);
   const int tiles = p.tiles_m * p.tiles_n;
   const int z = id / tiles, t = id - z * tiles;
   int tile_m, tile_n;
@@ -949,6 +949,51 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
   }
 }
 
+template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, int EPI>
+__global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
+  gemm2_body<BM, BN, WM, WN, STAGES, TA, TB, EPI>(p, xcd_remap(blockIdx.x, gridDim.x));
+}
+
+// ---- grouped weight gradients (nbest_wgrad_group): up to kMaxGroup problems dW_i[rows_i][cols_i] (fp32) (+)= dY_i^T . X_i with the same K in ONE
+// launch of the weight-gradient workgroup program above, every workgroup walking the WHOLE K of one 256 x 256 tile (splits == 1: the tile goes
+// straight into its gradient - no slabs, no reduce).  The tiles of a problem are consecutive tile ids, so that xcd_remap keeps a problem on as
+// few XCDs as it can; the problem of a workgroup is picked by an unrolled scan of the table in the kernel arguments (workgroup-uniform: scalar
+// selects, no dynamic indexing of the argument block), nothing is added to the K loop.
+constexpr int kMaxGroup = 8;
+struct WgradProb {
+  const bf16* A; const bf16* B; float* C;
+  int64_t lda, ldb, ldc;
+  uint32_t a_bytes, b_bytes;
+  int tiles_m, tiles_n, gn, tile_start;
+};
+struct WgradGroupP {
+  WgradProb pr[kMaxGroup];
+  int64_t K, k_pad;    // k_pad: K rounded up to whole stages (the one K-split's length)
+  int n, accumulate;
+};
+
+// (named after the kernel whose program it runs, with that kernel's template arguments: the per-kernel tables of tools/ and the benchmark's
+// roofline object find the weight-gradient launches by the gemm2_kernel prefix and the trailing epilogue constant)
+template <int BM, int BN, int WM, int WN, int STAGES, bool TA, bool TB, int EPI>
+__global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel_grouped(WgradGroupP g) {
+  static_assert(BM == 256 && BN == 256 && TA && TB && EPI == NBEST_EPI_F32_SPLITK, "grouped launch: the 256 x 256 weight-gradient program only");
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  WgradProb q = g.pr[0];
+#pragma unroll
+  for (int i = 1; i < kMaxGroup; ++i)
+    if (i < g.n && id >= g.pr[i].tile_start) q = g.pr[i];
+  GemmP2 p = {};
+  p.A = q.A; p.B = q.B; p.C = q.C;
+  p.M = (int64_t)q.tiles_m * 256; p.N = (int64_t)q.tiles_n * 256; p.K = g.K;
+  p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
+  p.k_per_split = g.k_pad;
+  p.tiles_m = q.tiles_m; p.tiles_n = q.tiles_n; p.splits = 1; p.accumulate = g.accumulate;
+  p.a_bytes = q.a_bytes; p.b_bytes = q.b_bytes;
+  p.stream_out = 1;
+  p.gn = q.gn;
+  gemm2_body<BM, BN, WM, WN, STAGES, TA, TB, EPI>(p, id - q.tile_start);
+}
+
 // B operand (a weight matrix [N][K], k-contiguous) -> the order the 256 x bn ping-pong kernel stages it: for every tile column and
 // K stage the bn x 32 LDS image (chunk swizzle and the register epilogue's row permutation applied), contiguous.  LDS-DMA with
 // 64-byte row segments delivers 22 B/clk/CU, contiguous 47 (tools/micro/dma_rate.hip); with MFMAs removed the k-contiguous GEMMs
@@ -1225,6 +1270,40 @@ int nbest_wgrad_pair_bf16(const nbest_gemm_args* a, const nbest_gemm_args* b, hi
   nbest_gemm_args v;
   NB_CHECK(pair_virtual(a, b, &v), NBEST_ERR_SHAPE, "wgrad pair: the two problems do not share one 256 x 256 split-K launch");
   return gemm_v2_impl(&v, b, a->M, st);
+}
+
+// Up to kMaxGroup weight gradients with the same K in one launch without K-splits (gemm2_kernel_grouped).  The caller (gemm.hip) has checked
+// pointers, alignment and operand extents of every problem (check_bf16).
+// Tile order inside a problem: row-major, except that a gradient wider than tall (FFN-down: 3 x 12 tiles) goes by groups of 3 tile columns -
+// 9-tile blocks that read 3 column panels of X and all of dY - so that a block boundary of xcd_remap (27 tiles per XCD for the 216 tiles
+// of two bert-base layers) cuts a problem between two such blocks and never through a tile row of 12.
+int nbest_wgrad_group_bf16(const nbest_gemm_args* pr, int n, hipStream_t st) {
+  NB_CHECK(n >= 1 && n <= kMaxGroup, NBEST_ERR_ARG, "wgrad_group: %d problems (1 .. %d)", n, kMaxGroup);
+  WgradGroupP g = {};
+  g.n = n; g.K = pr[0].K; g.k_pad = round_up(pr[0].K, 64); g.accumulate = pr[0].accumulate;
+  int tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    const nbest_gemm_args* a = pr + i;
+    NB_CHECK(a->dtype == NBEST_BF16 && a->trans_a && a->trans_b && a->epilogue == NBEST_EPI_F32_SPLITK, NBEST_ERR_ARG,
+             "wgrad_group: problem %d is not a bf16 weight gradient (trans_a = trans_b = 1, NBEST_EPI_F32_SPLITK)", i);
+    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_group: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", i,
+             (long long)a->M, (long long)a->N);
+    NB_CHECK(a->K == g.K && a->accumulate == g.accumulate, NBEST_ERR_ARG, "wgrad_group: problem %d differs in K or accumulate", i);
+    WgradProb& q = g.pr[i];
+    q.A = (const bf16*)a->A; q.B = (const bf16*)a->B; q.C = (float*)a->C;
+    q.lda = a->lda; q.ldb = a->ldb; q.ldc = a->ldc;
+    q.a_bytes = (uint32_t)(((a->K - 1) * a->lda + a->M) * 2); q.b_bytes = (uint32_t)(((a->K - 1) * a->ldb + a->N) * 2);
+    q.tiles_m = (int)(a->M / 256); q.tiles_n = (int)(a->N / 256);
+    q.gn = (q.tiles_n > q.tiles_m && q.tiles_n % 3 == 0) ? 3 : q.tiles_n;
+    q.tile_start = tiles;
+    tiles += q.tiles_m * q.tiles_n;
+  }
+  constexpr int lds_bytes = 4 * (256 + 256) * BK * 2;
+  const auto kernel = gemm2_kernel_grouped<256, 256, 2, 4, 4, true, true, NBEST_EPI_F32_SPLITK>;
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  kernel<<<tiles, 512, lds_bytes, st>>>(g);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
 }
 
 // tile width the k-contiguous GEMM of an [N][K] weight matrix is packed for (0: not packed): the rule of make_plan at training-size

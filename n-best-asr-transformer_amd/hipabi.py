@@ -18,7 +18,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
-    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
+    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
     "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step",
@@ -84,6 +84,8 @@ class EncoderDesc(C.Structure):
                 ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("pad4", C.c_int32),
                 ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p),
                 ("base_ids", C.c_void_p), ("alpha", C.c_void_p), ("no_param_grad", C.c_int32), ("pad5", C.c_int32)]
+    # nbest_encoder_desc.wgrad_group (WGRAD_GROUP_*): the descriptor's last field, in the slot that was padding
+    wgrad_group = property(lambda self: self.pad5, lambda self, v: setattr(self, "pad5", int(v)))
 
 
 _lib = None
@@ -114,6 +116,7 @@ def lib():
         L.nbest_gemm.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
         L.nbest_wgrad_pair_ws_bytes.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs)]
         L.nbest_wgrad_pair.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_void_p]
+        L.nbest_wgrad_group.argtypes = [C.POINTER(GemmArgs), C.c_int32, C.c_void_p]
         L.nbest_encoder_act_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_wgrad_launches_per_layer.argtypes = [C.POINTER(EncoderDesc)]
@@ -311,6 +314,29 @@ def wgrad_pair(dY1, X1, dY2, X2, out1=None, out2=None, accumulate=False):
     gs[0].ws, gs[0].ws_bytes = ws.data_ptr(), ws.numel()
     check(lib().nbest_wgrad_pair(C.byref(gs[0]), C.byref(gs[1]), stream_ptr()), "wgrad_pair")
     return outs
+
+
+WGRAD_GROUP_PLAN, WGRAD_GROUP_NEVER, WGRAD_GROUP_ALWAYS = 0, 1, 2     # EncoderDesc.wgrad_group
+
+
+def wgrad_group(problems, outs=None, accumulate=False):
+    """[dY_i^T . X_i] in fp32 by ONE launch without K-splits (nbest_wgrad_group): problems = [(dY_i [K, M_i], X_i [K, N_i]), ...] bf16,
+    token-major, 1 .. 8 of them with the same K; outs[i] [M_i, N_i] fp32 (accumulate: added to)"""
+    n = len(problems)
+    gs = (GemmArgs * max(n, 1))()
+    res = []
+    for i, (dY, X) in enumerate(problems):
+        M, N = dY.shape[1], X.shape[1]
+        out = outs[i] if outs is not None else torch.empty(M, N, dtype=torch.float32, device=X.device)
+        g = gs[i]
+        g.A, g.B, g.C = dY.data_ptr(), X.data_ptr(), out.data_ptr()
+        g.M, g.N, g.K = M, N, X.shape[0]
+        g.lda, g.ldb, g.ldc = dY.stride(0), X.stride(0), out.stride(0)
+        g.trans_a = g.trans_b = 1
+        g.epilogue, g.dtype, g.accumulate = EPI_F32_SPLITK, dtype_code(X.dtype), int(accumulate)
+        res.append(out)
+    check(lib().nbest_wgrad_group(gs, n, stream_ptr()), "wgrad_group")
+    return res
 
 
 def rows_gather(table, rows, cap):

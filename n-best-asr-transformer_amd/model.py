@@ -107,6 +107,7 @@ class _Pass:
         d.layers_host = C.cast(a.layer_offsets, C.POINTER(hb.LayerOffsets))
         d.drop_stream_base = 1000 * slot if train else 0
         d.first_trainable = first_trainable
+        d.wgrad_group = model.wgrad_group
         if model.fp8_forward and train:    # set before the stash is sized: the fp8 mode keeps e4m3 copies of the GEMM inputs per layer
             d.w8, d.w8_inv_scale = a.w8.data_ptr(), a.w8_inv_scale.data_ptr()
         self.desc = d
@@ -181,11 +182,14 @@ def _require_trainable(plan):
 
 class NBestSTCModel(nn.Module):
     def __init__(self, cfg: EncoderConfig, labels: LabelSpace, device="cuda", compute_dtype=torch.bfloat16, dropout=0.0,
-                 seed=999, fp8_forward=False, fp8_backward=None):
+                 seed=999, fp8_forward=False, fp8_backward=None, wgrad_group=hb.WGRAD_GROUP_PLAN):
         super().__init__()
         self.cfg, self.labels, self.compute_dtype = cfg, labels, compute_dtype
         self.dropout = float(dropout)                  # --dropout: feature dropout of the STC heads
         self.device = torch.device(device)
+        # weight gradients of two layers in one launch without K-splits (nbest_encoder_desc.wgrad_group): the library's plan decides,
+        # never (every layer's split-K launches), or wherever the shapes allow
+        self.wgrad_group = int(wgrad_group)
         self.arena = ParamArena(cfg, labels, self.device, compute_dtype)
         # "fp8w" (BASELINE configs[4]): forward GEMMs on the block-scaled fp8 MFMA from an e4m3 copy of the weights; the
         # master weights, the backward and everything between the GEMMs stay as in the bf16 path

@@ -5,12 +5,15 @@
     rocprofv3 --pmc FETCH_SIZE      -d F -- python3 bench.py ...      HBM-side read traffic   (own pass: TCC slots)
     rocprofv3 --pmc WRITE_SIZE      -d W -- python3 bench.py ...      HBM-side write traffic  (own pass)
 
-    python tools/pmc_table.py T/*/*.db F/*/*.db W/*/*.db STEPS > profiles/rNN_pmc.csv
+    python tools/pmc_table.py T/*/*.db F/*/*.db W/*/*.db STEPS [LAYERS_PER_GROUP] > profiles/rNN_pmc.csv
 
 STEPS = steps the command ran (warm-up + timed), to turn call counts into launches per step.  Kernels are keyed by
 (name, grid size) so that the shapes of one template show up separately.  traffic_bytes applies the corrections of
 MI355X_MICROARCH.md (HBM section): FETCH_SIZE is reported in KiB and, on gfx950, at half the bytes of wide streaming
 reads -> x 2 x 1024; WRITE_SIZE KiB -> x 1024.  bench.py reads this file for `roofline.traffic`.
+A grouped weight-gradient launch (gemm2_kernel_grouped: the gradients of LAYERS_PER_GROUP layers, default 2, in one launch) is listed
+PER LAYER it covers - launches x LAYERS_PER_GROUP, duration and bytes / LAYERS_PER_GROUP - because that is the unit bench.py's
+`roofline` object counts in (one event pair and one layer's algorithmic bytes per "launch").
 """
 import csv
 import re
@@ -44,12 +47,15 @@ def counter(path, which):
 
 def main():
     trace, fetch, write, steps = sys.argv[1], sys.argv[2], sys.argv[3], float(sys.argv[4])
+    group = float(sys.argv[5]) if len(sys.argv) > 5 else 2.0
     d, f, w = durations(trace), counter(fetch, "FETCH_SIZE"), counter(write, "WRITE_SIZE")
     rows = []
     for key, (n, us) in d.items():
         if n < steps * 0.5:          # set-up kernels (initialisation, casts before the loop)
             continue
         fk, wk = f.get(key, (0, float("nan")))[1], w.get(key, (0, float("nan")))[1]
+        if "gemm2_kernel_grouped" in key[0]:
+            n, us, fk, wk = n * group, us / group, fk / group, wk / group
         rows.append((n / steps * us, key[0], key[1], n / steps, us, fk, wk, (2.0 * fk + wk) * 1024.0))
     rows.sort(reverse=True)
     out = csv.writer(sys.stdout)
