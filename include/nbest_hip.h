@@ -308,6 +308,25 @@ int nbest_attention_bwd_keep(const void* qkv, const uint8_t* key_mask, const voi
                              int B, int S, int heads, int d, int dtype, float drop_p, uint64_t seed,
                              uint32_t drop_stream, const void* keep, nbest_stream_t stream);
 
+/* Head gates (HF's head_mask: BertModel.forward(head_mask=), installed modeling_bert.py, where the post-dropout probabilities of
+ * head h are multiplied by the mask; Michel et al., 2019): a factor gate[h] (fp32 [heads], device; any float: 0 prunes, 1 is the
+ * identity) on head h's slice of the attention context, applied between the attention kernel and the attention-output GEMM -
+ * ctx_h = (gate[h] P_h) V_h = gate[h] (P_h V_h).  d = 64, fp32 or bf16, 16-byte accesses, no atomics, bit-reproducible.
+ *   nbest_head_gate_fwd: out[m][h d + k] = T(gate[h] * float(in[m][h d + k])) for the M rows (row strides ld_in, ld_out >= H =
+ *     heads d, in elements, multiples of 16 bytes; both pointers 16-byte aligned).  In place (ctx_out == ctx_in, ld_out == ld_in)
+ *     is allowed.  A gate of 1 leaves the bits as they are, a gate of 0 gives zeros.  Reads and writes [M][H] once.
+ *   nbest_head_gate_bwd: ctx [B S][H] = the UN-gated context the forward stashed, dctx [B S][H] = the gradient w.r.t. the gated
+ *     context.  One workgroup per (utterance, head): dgate[b][h] = sum_{s,k} float(ctx[b,s,h,k]) * float(dctx[b,s,h,k]) (fp32
+ *     [B][heads], OVERWRITTEN; fp32 accumulation in a fixed order) = d loss / d gate[h] restricted to utterance b; then
+ *     dctx <- T(gate[h] * dctx) in place = the gradient w.r.t. the un-gated context, which nbest_attention_bwd takes together with
+ *     the un-gated ctx (its delta = rowsum(O * dO) is then exact for every gate value, 0 included).  The store is skipped for
+ *     gate[h] == 1: an all-ones gate leaves dctx bit-identical.  dgate == NULL: scale only (ctx is not read and may be NULL).
+ *     Reads [M][H] twice, writes it once.                                                                                       */
+int nbest_head_gate_fwd(const void* ctx_in, int64_t ld_in, void* ctx_out, int64_t ld_out, const float* gate, int64_t M, int heads,
+                        int d, int dtype, nbest_stream_t stream);
+int nbest_head_gate_bwd(const void* ctx, void* dctx, const float* gate, float* dgate, int B, int S, int heads, int d, int dtype,
+                        nbest_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K5  LayerNorm over the hidden dimension (BertSelfOutput / BertOutput LayerNorm,
  * installed modeling_bert.py:282-293, 340-351).  stats[m] = {mean, rstd} fp32.                      */
@@ -568,6 +587,20 @@ typedef struct nbest_encoder_desc {
   int32_t first_trainable;
   int32_t no_input_grad;
   const uint8_t* wgrad_skip_host;
+  /* optional head gates (NULL = none: every entry point then enqueues exactly the launches it did without these fields; the two
+   * pointers sit here, ahead of the attribution fields, which stay the descriptor's last).
+   * head_gate: fp32 [L][heads], device.  Layer l multiplies head h's slice of its attention context by head_gate[l][h] after
+   * dropout and P.V, before the attention-output GEMM (nbest_head_gate_fwd).  nbest_encoder_forward keeps the UN-gated context in
+   * the stash and writes the gated copy into the workspace (which it then needs: nbest_encoder_ws_bytes); nbest_encoder_infer /
+   * _infer_attn gate in place.  Attention maps (nbest_attention_probs on the stash, cls_attn) stay the un-gated probabilities.
+   * nbest_encoder_backward launches nbest_head_gate_bwd between a layer's attention-output dgrad GEMM and its attention backward.
+   * head_gate_grad: fp32 [L][B][heads], device (needs head_gate): the backward writes d loss / d head_gate[l][h] per utterance b for
+   * the layers of [layer_begin, layer_end) (overwritten; other layers untouched).
+   * Refused (NBEST_ERR_ARG, nothing enqueued): head_gate with the fp8 forward (w8) or with first_trainable > 0, head_gate_grad
+   * without head_gate, and a backward with head_gate but without no_param_grad (the attention-output weight gradient would need
+   * the gated context, which is not kept).                                                                                       */
+  const float* head_gate;
+  float* head_gate_grad;
   /* optional interpolated embeddings (integrated gradients): base_ids int64 [B*S] and alpha fp32 [B], device memory, set per call
    * like `seed`.  Both non-NULL: nbest_encoder_forward's embedding is nbest_embed_ln_fwd_interp; NULL: nbest_embed_ln_fwd, launch for
    * launch as before.  nbest_encoder_infer refuses them.                                                                         */

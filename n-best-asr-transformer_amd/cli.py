@@ -81,6 +81,16 @@ def parse_arguments(argv=None):
                         "token and each segment (cls, sys, h1, h2, ..)")
     g.add_argument("--attribution_steps", type=int, default=32, metavar="M",
                    help="--predict_attribution: path points of the integrated-gradients midpoint rule (>= 1)")
+    g.add_argument("--head_mask", default=None, metavar="FILE",
+                   help="gate the attention heads (HF's head_mask) for --testing, --predict and --head_importance: a JSON list of L rows "
+                        "of `heads` numbers, 0 = head pruned, 1 = kept (any float scales the head's output).  Not for a training run")
+    g.add_argument("--head_importance", default=None, metavar="PATH",
+                   help="score every attention head on the --valid_file split with <exp_dir>/model.pt (Michel et al., 2019: the mean "
+                        "over utterances of |d loss / d head gate|) and write one JSON object to PATH: importance and normalized "
+                        "(per-layer l2) [L][heads] tables, the head mask in force and, with --prune_heads, pruned_mask.  One GPU")
+    g.add_argument("--prune_heads", type=int, default=None, metavar="N",
+                   help="with --head_importance: also write pruned_mask, the mask in force with its N lowest-importance heads set to "
+                        "0 (at least one head per layer stays); feed it back through --head_mask")
     g.add_argument("--deviceId", type=int, default=-1,
                    help="as the reference (n_best_asr_bert.py:116-126): 0 = pick a GPU automatically (here: the first visible one; "
                         "the reference asks gpustat / NVML for the least loaded), k > 0 = GPU k-1, -1 = CPU (refused: the path is "
@@ -158,6 +168,20 @@ def parse_arguments(argv=None):
             ap.error("--predict %s: no such file" % opt.predict)
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             ap.error("--predict runs on one GPU: start it without torchrun (world size %s)" % os.environ["WORLD_SIZE"])
+    if opt.prune_heads is not None and opt.head_importance is None:
+        ap.error("--prune_heads prunes by the scores of --head_importance: pass --head_importance PATH too")
+    if opt.prune_heads is not None and opt.prune_heads < 0:
+        ap.error("--prune_heads must be >= 0 (got %d)" % opt.prune_heads)
+    if opt.head_importance is not None:
+        if opt.testing or opt.predict is not None:
+            ap.error("--head_importance is a run of its own: pass it without --testing / --predict")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--head_importance runs on one GPU: start it without torchrun (world size %s)" % os.environ["WORLD_SIZE"])
+    if opt.head_mask is not None:
+        if not (opt.testing or opt.predict is not None or opt.head_importance is not None):
+            ap.error("--head_mask applies to --testing, --predict and --head_importance; training under a head mask is not built")
+        if not os.path.isfile(opt.head_mask):
+            ap.error("--head_mask %s: no such file" % opt.head_mask)
     opt.gpu_index = 0 if opt.deviceId == 0 else opt.deviceId - 1            # n_best_asr_bert.py:116-126 (0: auto -> first GPU)
     # gradient accumulation exactly as the reference derives it (n_best_asr_bert.py:522): 4 micro-batches of batchSize / 4
     # per optimizer step when --n_layers 12 is passed (the shipped script never passes it -> 1)
@@ -286,6 +310,33 @@ def main(argv=None):
         if not os.path.exists(fn):
             return None
         return trainer.EncodedSplit(trainer.read_wcn_data(fn, coverage), opt, memory)       # tokenised once per run
+
+    if opt.head_mask is not None:
+        try:
+            model.set_head_mask(trainer.read_head_mask(opt.head_mask, cfg.num_hidden_layers, cfg.num_attention_heads))
+        except ValueError as e:
+            raise SystemExit("--head_mask: %s" % e)
+
+    if opt.head_importance is not None:
+        model.load_model(os.path.join(opt.exp_dir, "model.pt"))
+        data = load(opt.valid_file)
+        if data is None:
+            raise SystemExit("--head_importance: no split at %s" % os.path.join(opt.dataroot, opt.valid_file))
+        t0 = time.time()
+        model.eval()
+        res = trainer.head_importance(model, data, opt, memory)
+        mask = model.head_mask
+        res["head_mask"] = [[1.0] * cfg.num_attention_heads for _ in range(cfg.num_hidden_layers)] if mask is None else mask.cpu().tolist()
+        if opt.prune_heads is not None:
+            try:
+                res["pruned_mask"] = trainer.prune_lowest(res["importance"], res["head_mask"], opt.prune_heads)
+            except ValueError as e:
+                raise SystemExit("--prune_heads: %s" % e)
+        with open(opt.head_importance, "w") as fp:
+            json.dump(res, fp)
+            fp.write("\n")
+        print("head importance of %d utterances in %.2f s -> %s" % (res["utterances"], time.time() - t0, opt.head_importance), flush=True)
+        return 0
 
     if opt.predict is not None:
         model.load_model(os.path.join(opt.exp_dir, "model.pt"))

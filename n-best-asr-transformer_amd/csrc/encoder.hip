@@ -17,6 +17,7 @@
 //   inputs, backward: the gradients the fp8 dgrads read), fz (K > 0: X0 | X1 | emb_stats | lse | st1 | st2 | u).
 //   Layers 0..K-1 are not stashed: their forward runs on fz plus the backward's layer-gradient buffers, which are idle
 //   during a forward (frozen_layer).
+// Head gates (desc.head_gate): the forward's gated copy of a layer's ctx borrows dctx; the stash keeps the un-gated ctx.
 // Inference workspace: infer_layout, below.
 #include <algorithm>
 
@@ -216,6 +217,11 @@ static int check_desc(const nbest_encoder_desc* d) {
   NB_CHECK(0 <= d->first_trainable && d->first_trainable <= d->L, NBEST_ERR_ARG, "encoder: first_trainable %d outside [0, L=%d]",
            d->first_trainable, d->L);
   NB_CHECK(!d->base_ids == !d->alpha, NBEST_ERR_ARG, "encoder: interpolated embeddings need both base_ids and alpha (or neither)");
+  // head gates (desc.head_gate): the gated context is a scratch copy the bf16 / fp32 attention-output GEMM reads - the fp8 forward's
+  // e4m3 copy of ctx comes out of the attention kernel, and a frozen layer's forward already lives in that scratch
+  NB_CHECK(!d->head_gate || !d->w8, NBEST_ERR_ARG, "encoder: head_gate is not supported with the fp8 forward (desc.w8)");
+  NB_CHECK(!d->head_gate || d->first_trainable == 0, NBEST_ERR_ARG, "encoder: head_gate needs first_trainable == 0 (got %d)", d->first_trainable);
+  NB_CHECK(!d->head_gate_grad || d->head_gate, NBEST_ERR_ARG, "encoder: head_gate_grad without head_gate");
   return NBEST_OK;
 }
 
@@ -354,6 +360,8 @@ struct Fwd {
   GemmPass g;   // g.fp8: the four GEMMs of a layer on the block-scaled fp8 MFMA, their A operands the e4m3 copies x8 | ctx8 | x18 | h8
   const uint8_t* key_mask;
   bool arec;    // record the activation amax of this pass (fp8, or the calibration pass: fp8 mode without an activation history)
+  // head gates (desc.head_gate): where a layer's gated context goes - [M][H] scratch, or NULL: in place (nothing reads the un-gated one)
+  void* gated_ctx;
   // delayed scale of activation idx = 4 l + {x, ctx, x1, gelu} and the slot block its producer records this pass's amax in (fp8 pass)
   const uint32_t* AP(int idx) const { return g.fp8 ? d->aamax_prev + idx : nullptr; }
   uint32_t* AN(int idx) const { return (g.fp8 && arec) ? d->aamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS : nullptr; }
@@ -368,7 +376,7 @@ static Fwd make_fwd(const nbest_encoder_desc* d, const void* wts, const float* p
                     nbest_stream_t stream) {
   const GemmPass g = {d->dtype, z.M, stream, d->seed, Ptrs{(const char*)wts, prm, z.esz}, d->wpk, false, fp8_forward_active(d),
                       d->w8, d->w8p, d->w8_inv_scale, d->aamax_prev, d->aamax_new, nullptr, 0, 0};
-  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16};
+  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16, nullptr};
 }
 
 // Layer l over all M rows: xin -> xout through the buffers `b`.  x8_next: where the last LayerNorm leaves the e4m3 copy of xout for
@@ -394,8 +402,14 @@ static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const
   RUN(nbest_internal_attention_fwd8(b.qkv, c.key_mask, b.ctx, b.ctx8, b.lse, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0,
                                     stream, b.keep, c.AP(t + 1), c.AN(t + 1)));
   RUN(c.calib(b.ctx, M * H, t + 1));
+  const void* ctx = b.ctx;   // what the attention-output GEMM reads: the context, or its gated copy
+  if (d->head_gate) {
+    void* gated = c.gated_ctx ? c.gated_ctx : b.ctx;
+    RUN(nbest_head_gate_fwd(b.ctx, H, gated, H, d->head_gate + (int64_t)l * d->heads, M, d->heads, 64, dt, stream));
+    ctx = gated;
+  }
   // attention output projection + dropout + residual, then LayerNorm
-  GemmOp wo = {b.ctx, b.ctx8, t + 1, o.wo, t + 1, b.r1, H, H, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo)};
+  GemmOp wo = {ctx, b.ctx8, t + 1, o.wo, t + 1, b.r1, H, H, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo)};
   wo.R = xin; wo.drop_p = d->hidden_drop; wo.drop_stream = s0 + 1;
   RUN(layer_gemm(c.g, wo));
   RUN(nbest_internal_layernorm_fwd8(b.r1, P.P(o.ln1_g), P.P(o.ln1_b), b.x1, b.x18, b.st1, M, H, d->ln_eps, dt, stream, c.AP(t + 2), c.AN(t + 2)));
@@ -443,12 +457,15 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   const Sizes z = sizes(d);
   const ActLayout a = act_layout(d, z);
   NB_CHECK(act_bytes >= a.total, NBEST_ERR_WORKSPACE, "encoder_forward: activation stash too small (%zu < %zu)", act_bytes, a.total);
-  const Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
+  Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
   const WsLayout wl = ws_layout(d, z);
   const int FT = a.K;   // layers 0..FT-1 are frozen: run on scratch in ws, nothing of them stashed
-  if (c.g.fp8 || FT > 0)
+  if (c.g.fp8 || FT > 0 || d->head_gate)
     NB_CHECK(ws && ws_bytes >= wl.total, NBEST_ERR_WORKSPACE, "encoder_forward(%s): workspace too small (%zu < %zu)",
-             FT > 0 ? "first_trainable > 0" : "fp8", ws_bytes, wl.total);
+             FT > 0 ? "first_trainable > 0" : d->head_gate ? "head_gate" : "fp8", ws_bytes, wl.total);
+  // head gates: the stash keeps the un-gated context (the backward's operand); the gated copy lives in the backward's dctx buffer,
+  // idle during a forward (first_trainable == 0: no frozen layer borrows it)
+  if (d->head_gate) c.gated_ctx = (char*)ws + wl.dctx;
   const Ptrs& P = c.g.W;
   char *A = (char*)act, *W = (char*)ws;
   const int H = d->H, dt = d->dtype;
@@ -493,6 +510,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   NB_CHECK(!npg || (!with_embeddings && d->first_trainable == 0 && !d->no_input_grad && !d->w8), NBEST_ERR_ARG,
            "encoder_backward: no_param_grad refuses with_embeddings (%d), first_trainable > 0 (%d), no_input_grad (%d) and the fp8 "
            "forward (w8): it forms the input gradient only, of a full stash", with_embeddings, d->first_trainable, d->no_input_grad);
+  NB_CHECK(!d->head_gate || npg, NBEST_ERR_ARG, "encoder_backward: head_gate needs no_param_grad (the attention-output weight gradient would "
+           "need the gated context, which the forward does not keep)");
   NB_CHECK(wts && prm && (grad || npg) && ids && pos && key_mask && act && dhidden && ws, NBEST_ERR_ARG, "encoder_backward: null pointer");
   NB_CHECK(!with_embeddings || d->word_perm, NBEST_ERR_ARG, "encoder_backward: desc.word_perm (stable argsort of this pass's ids) is required");
   NB_CHECK(layer_begin >= d->first_trainable, NBEST_ERR_ARG, "encoder_backward: layer_begin %d < first_trainable %d (those layers are not stashed)",
@@ -635,6 +654,11 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     RUN(layer_gemm(dg, dwo));
     // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
     if (!paired && !grouped) RUN(wgrad(l, wg, 1, -1));
+    // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
+    // (per utterance), and scaled by the gate it is the gradient the attention backward takes
+    if (d->head_gate)
+      RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads,
+                              d->head_gate_grad ? d->head_gate_grad + (int64_t)l * d->B * d->heads : nullptr, d->B, d->S, d->heads, 64, dt, stream));
     // attention backward -> dqkv ; QKV bias gradient
     RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkvL, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
                                       d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, t + 3), b.keep));
@@ -686,7 +710,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
 // rows only (row 0 of each utterance: the one row the STC heads read).
 //   X[2] [M][H] T (ping-pong) | emb_stats [M][2] f32 | qkv [M][3H] T (last layer: K|V [M][2H]) | ctx | r1 | x1 | r2 [M][H] T |
 //   hact [M][F] T | lse [B heads S] f32 | st1 | st2 [M][2] f32.   Last layer: Q -> ctx, context -> r1, x1 -> x1, gelu -> hact,
-//   attention-out and FFN-down sums -> r2.  Independent of L.
+//   attention-out and FFN-down sums -> r2.  Independent of L.  Head gates (desc.head_gate) are applied in place, on ctx [M][H] of
+//   layers 0 .. L-2 and on the [B][H] CLS context of the last layer.
 namespace {
 struct InferLayout {
   size_t X0, X1, emb_stats, qkv, ctx, r1, x1, r2, hact, lse, st1, st2, total;
@@ -754,6 +779,7 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   RUN(nbest_gemm(&g, stream));
   if (cls_attn) RUN(nbest_internal_attention_cls_probs(q, H, kv, 2 * H, key_mask, probs(l), d->S, d->B, d->S, d->heads, 64, dt, stream));
   RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream));
+  if (d->head_gate) RUN(nbest_head_gate_fwd(cctx, H, cctx, H, d->head_gate + (int64_t)l * d->heads, B, d->heads, 64, dt, stream));
   g = gemm_nt(dt, cctx, P.W(o.wo), cr, B, H, H);
   g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.bias = P.P(o.bo); g.R = xin; g.ldr = SH;        // residual: the CLS rows
   RUN(nbest_gemm(&g, stream));

@@ -27,6 +27,7 @@ EXPORTS = [
     "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
     "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
     "nbest_embed_ln_fwd_interp", "nbest_embed_attrib",
+    "nbest_head_gate_fwd", "nbest_head_gate_bwd",
 ]
 
 
@@ -83,6 +84,7 @@ class EncoderDesc(C.Structure):
                 ("wpk", C.c_void_p), ("wpkt", C.c_void_p), ("w8p", C.c_void_p), ("w8tp", C.c_void_p),
                 ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("pad4", C.c_int32),
                 ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p),
+                ("head_gate", C.c_void_p), ("head_gate_grad", C.c_void_p),
                 ("base_ids", C.c_void_p), ("alpha", C.c_void_p), ("no_param_grad", C.c_int32), ("pad5", C.c_int32)]
     # nbest_encoder_desc.wgrad_group (WGRAD_GROUP_*): the descriptor's last field, in the slot that was padding
     wgrad_group = property(lambda self: self.pad5, lambda self, v: setattr(self, "pad5", int(v)))
@@ -125,6 +127,8 @@ def lib():
         L.nbest_embed_ln_bwd.argtypes = [vp] * 15 + [i32, i32, i32, i32, i32, i64, i64, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_embed_ln_fwd_interp.argtypes = [vp] * 12 + [i32, i32, i32, f32, i32, f32, u64, u32, vp]
         L.nbest_embed_attrib.argtypes = [vp] * 11 + [i32, i32, i32, i32, f32, i32, vp]
+        L.nbest_head_gate_fwd.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp]
+        L.nbest_head_gate_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         L.nbest_attention_fwd.argtypes = [vp] * 4 + [i32] * 5 + [f32, u64, u32, vp]
         L.nbest_attention_bwd.argtypes = [vp] * 7 + [i32, vp, sz] + [i32] * 5 + [f32, u64, u32, vp]
         L.nbest_attention_bwd_ws_bytes.argtypes = [i32, i32, i32]
@@ -493,6 +497,26 @@ def attention_cls_probs(q, ldq, kv, ldkv, key_mask, B, S, heads, out=None):
     check(lib().nbest_attention_cls_probs(ptr(q), ldq, ptr(kv), ldkv, ptr(key_mask), ptr(probs), probs.stride(1), B, S, heads, 64,
                                           dtype_code(kv.dtype), stream_ptr()), "attention_cls_probs")
     return probs
+
+
+def head_gate_fwd(ctx, gate, heads, out=None):
+    """nbest_head_gate_fwd: ctx [M, >= heads * 64] (rows of stride ctx.stride(0)), gate fp32 [heads] -> gate[h] * ctx per head slice.
+    ``out``: where the result goes (rows of stride out.stride(0); ``out is ctx``: in place); None = a fresh [M, heads * 64] tensor"""
+    M = ctx.shape[0]
+    if out is None:
+        out = torch.empty(M, heads * 64, dtype=ctx.dtype, device=ctx.device)
+    check(lib().nbest_head_gate_fwd(ptr(ctx), ctx.stride(0), ptr(out), out.stride(0), ptr(gate), M, heads, 64, dtype_code(ctx.dtype),
+                                    stream_ptr()), "head_gate_fwd")
+    return out
+
+
+def head_gate_bwd(ctx, dctx, gate, B, S, heads, want_dgate=True):
+    """nbest_head_gate_bwd: ctx (the un-gated context) and dctx (the gradient w.r.t. the gated one) [B * S, heads * 64], gate fp32
+    [heads] -> dgate fp32 [B, heads] (None without ``want_dgate``); dctx is scaled by the gate IN PLACE (left alone where gate == 1)"""
+    dgate = torch.empty(B, heads, dtype=torch.float32, device=dctx.device) if want_dgate else None
+    check(lib().nbest_head_gate_bwd(ptr(ctx), ptr(dctx), ptr(gate), ptr(dgate), B, S, heads, 64, dtype_code(dctx.dtype), stream_ptr()),
+          "head_gate_bwd")
+    return dgate
 
 
 def encoder_act_view(desc, act, layer):

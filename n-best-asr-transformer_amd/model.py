@@ -231,6 +231,7 @@ class NBestSTCModel(nn.Module):
         self._dh = None                    # grow-only scratch of the backward's input gradient
         self._infer_ws = None              # grow-only workspace of predict() (nbest_encoder_infer)
         self._anchor = None                # autograd bridge: a leaf that makes the outputs of forward() require grad
+        self._head_mask = None             # set_head_mask: fp32 [L, heads] on the device (not a parameter, not in state_dict)
 
     # ---- plumbing ------------------------------------------------------------------------------
     def zero_grad(self, set_to_none=False):
@@ -296,6 +297,39 @@ class NBestSTCModel(nn.Module):
             raise RuntimeError("checkpoint lacks encoder tensors: %s" % hard[:5])
         self.arena.load_state(sd, strict=False)
         return missing
+
+    # ---- head mask (HF's head_mask) ---------------------------------------------------------------
+    @property
+    def head_mask(self):
+        """the mask set_head_mask installed (fp32 [L, heads] on the device), or None"""
+        return self._head_mask
+
+    def set_head_mask(self, mask):
+        """Gate the attention heads, as ``BertModel.forward(head_mask=)``: ``mask`` [L, heads] of any floats (0 prunes head h of
+        layer l, 1 is the identity) multiplies each head's attention context after dropout and P.V, before the attention-output
+        projection; None removes it.  Held on the device, not part of ``state_dict``.  While set it applies to the eval / no_grad
+        ``forward``, ``forward_backward(need_grad=False)`` (what eval_epoch runs), ``predict``, ``attribute`` and ``head_gate_grad``;
+        the attention maps (``return_attns``, ``cls_attn``) stay the un-gated probabilities.  Training under a mask is not built:
+        ``forward_backward(need_grad=True)`` and the autograd-bridge forward raise, and so does the stash forward of an fp8w model
+        (its ``predict`` / ``attribute`` run the bf16 copy and work).  Without a mask every pass enqueues what it always did."""
+        if mask is None:
+            self._head_mask = None
+            return
+        L, heads = self.cfg.num_hidden_layers, self.cfg.num_attention_heads
+        m = torch.as_tensor(mask)
+        if tuple(m.shape) != (L, heads):
+            raise ValueError("nbest_amd set_head_mask: the mask must be [L=%d, heads=%d] (got %s)" % (L, heads, list(m.shape)))
+        self._head_mask = m.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+
+    def _refuse_training_under_mask(self, what):
+        if self._head_mask is not None:
+            raise RuntimeError("nbest_amd: %s with a head mask set: training under a head mask is not built (the attention-output "
+                               "weight gradient needs the gated context); call set_head_mask(None) first" % what)
+
+    def _set_head_gate(self, d, grad=None):
+        """the head-gate fields of descriptor ``d`` for this call: the mask in force (None: no gate, today's launches)"""
+        d.head_gate = None if self._head_mask is None else self._head_mask.data_ptr()
+        d.head_gate_grad = None if grad is None else grad.data_ptr()
 
     def _desc(self, B, S, slot, first_trainable=0):
         """the (cached) descriptor of a pass shape; allocates nothing"""
@@ -386,6 +420,7 @@ class NBestSTCModel(nn.Module):
         d.hidden_drop = self.cfg.hidden_dropout_prob if train else 0.0
         d.attn_drop = self.cfg.attention_probs_dropout_prob if train else 0.0
         d.seed = self._step_seed()
+        self._set_head_gate(d)
         self._set_weights(d, "forward")
         act, ws = self._stash[slot][:ps.act_bytes], self._ws
         out = C.c_void_p()
@@ -514,6 +549,7 @@ class NBestSTCModel(nn.Module):
             if return_attns:
                 raise RuntimeError("nbest_amd: return_attns=True: attention maps are an eval / predict output - call model.eval() "
                                    "or run the forward under torch.no_grad() (a training forward has no post-dropout maps)")
+            self._refuse_training_under_mask("the training forward (autograd bridge)")
             if self._anchor is None:
                 self._anchor = torch.zeros(1, device=self.device, requires_grad=True)    # what makes the outputs require grad
             top, bott, fin, asr_cls, trans_cls = _STCBridge.apply(self._anchor, self, input_ids.contiguous(),
@@ -567,6 +603,7 @@ class NBestSTCModel(nn.Module):
         Frozen parameters (``requires_grad`` False) get no gradient (FreezePlan); with none trainable this raises."""
         plan = None
         if need_grad:
+            self._refuse_training_under_mask("forward_backward(need_grad=True)")
             plan = self._training_plan()
             _require_trainable(plan)
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
@@ -610,6 +647,7 @@ class NBestSTCModel(nn.Module):
         ids, seg, pos, mask = self._inputs(input_ids, seg_ids)
         d.hidden_drop = d.attn_drop = 0.0
         d.seed = 0
+        self._set_head_gate(d)
         self._set_weights(d, "infer")
         ws = self._grow(vars(self), "_infer_ws", hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d)))
         a = self.arena
@@ -719,6 +757,7 @@ class NBestSTCModel(nn.Module):
             d.hidden_drop = d.attn_drop = 0.0
             d.seed = 0
             d.base_ids, d.alpha = base_c.data_ptr(), alpha.data_ptr()
+            self._set_head_gate(d)                           # a mask gates the forward and scales the backward's dctx; no gate gradient
             self._set_weights(d, "infer")
             hid = C.c_void_p()
             hb.check(hb.lib().nbest_encoder_forward(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids_c), hb.ptr(seg_c), hb.ptr(pos_c),
@@ -756,6 +795,62 @@ class NBestSTCModel(nn.Module):
             out["baseline_score"][i] = ends[b][0, c]
             out["score"][i] = ends[b][1, c]
         return out
+
+    # ---- head importance: the gradient of the loss w.r.t. the head gates (Michel et al., 2019) ----------------------------------
+    def head_gate_grad(self, input_ids, labels_f, seg_ids=None):
+        """d L_b / d xi[l, h] for every utterance b of the batch: ``grad`` fp32 [L, B, heads], the gradient of the training loss of
+        the ASR pass (BCE(final) + BCE(top) + mean-CE, a sum over utterances - no MSE term) w.r.t. a gate xi on head h of layer l,
+        at the current mask (ones when none is set).  A pruned head (gate 0) has a gradient too, in general non-zero.
+        The stash forward without dropout (in either mode), the heads' analytic backward, then nbest_encoder_backward with
+        no_param_grad and head_gate_grad: no parameter gradient is formed (the heads' go to scratch).  Returns dict(grad,
+        loss_parts[4] (device)).  Touches no training state, as predict() and attribute() (a stash slot of its own); an fp8w model
+        runs its bf16 weight copy.  One GPU."""
+        cfg, a = self.cfg, self.arena
+        B, S = input_ids.shape
+        H, L, heads = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads
+        first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
+        if S > 512 or S + first_pos > cfg.max_position_embeddings:
+            raise RuntimeError("nbest_amd head_gate_grad: S=%d does not fit the position table (%d rows)" % (S, cfg.max_position_embeddings))
+        f = dict(dtype=torch.float32, device=self.device)
+        ids, seg, pos, mask = self._inputs(input_ids.to(self.device).long(), None if seg_ids is None else seg_ids.to(self.device).long())
+        gate = self._head_mask if self._head_mask is not None else torch.ones(L, heads, **f)
+        grad = torch.empty(L, B, heads, **f)
+        ps = self._desc(B, S, "headgrad")
+        d = ps.desc
+        act = self._grow(self._stash, "headgrad", ps.act_bytes)[:ps.act_bytes]
+        ws = self._grow(vars(self), "_hg_ws", hb.lib().nbest_encoder_ws_bytes(C.byref(d)))
+        d.hidden_drop = d.attn_drop = 0.0
+        d.seed = 0
+        d.head_gate, d.head_gate_grad = gate.data_ptr(), None
+        try:                                                 # whatever raises, the cached descriptor keeps no pointer of this call
+            self._set_weights(d, "infer")
+            hid = C.c_void_p()
+            hb.check(hb.lib().nbest_encoder_forward(C.byref(d), hb.ptr(a.weights), hb.ptr(a.p), hb.ptr(ids), hb.ptr(seg), hb.ptr(pos),
+                                                    hb.ptr(mask), hb.ptr(act), act.numel(), hb.ptr(ws), ws.numel(), C.byref(hid),
+                                                    hb.stream_ptr()), "encoder_forward(head_gate_grad)")
+            esz = 2 if self.compute_dtype == torch.bfloat16 else 4
+            off = hid.value - act.data_ptr()
+            hidden = act[off:off + B * S * H * esz].view(self.compute_dtype).view(B * S, H)
+            Wh, bh = a.heads_wb()
+            R = self.dls.n_rows
+            hws = self._grow(vars(self), "_hg_heads_ws", hb.lib().nbest_heads_ws_bytes(B, R, H))
+            dWh_s, dbh_s = torch.empty(R, H, **f), torch.empty(R, **f)       # the heads' parameter gradients: scratch, never read
+            _, _, _, loss, dcls, _, _ = hb.stc_heads(hidden, S * H, Wh, bh, self.dls, labels_f.to(**f).contiguous(), B, H, need_grad=True,
+                                                     accumulate=False, drop_p=0.0, dWh=dWh_s, dbh=dbh_s, ws=hws)
+            dh = self._grow(vars(self), "_hg_dh", B * S * H, self.compute_dtype)[:B * S * H].view(B * S, H)
+            dh = hb.cls_grad_scatter(dcls, B, S, H, self.compute_dtype, out=dh)
+            d.no_param_grad = 1
+            d.head_gate_grad = grad.data_ptr()
+            wt = None if a.w16t_stale else a.w16t               # as attribute(): a stale transposed copy is neither read nor refreshed
+            if wt is None:
+                d.wpkt = None
+            hb.check(hb.lib().nbest_encoder_backward(C.byref(d), hb.ptr(a.weights), hb.ptr(wt), hb.ptr(a.p), None, hb.ptr(ids), hb.ptr(seg),
+                                                     hb.ptr(pos), hb.ptr(mask), hb.ptr(act), act.numel(), hb.ptr(dh), hb.ptr(ws), ws.numel(),
+                                                     0, 0, L, 0, hb.stream_ptr()), "encoder_backward(head_gate_grad)")
+        finally:
+            d.no_param_grad = 0
+            d.head_gate = d.head_gate_grad = None
+        return dict(grad=grad, loss_parts=loss)
 
     def decode(self, top, bott, out=None):
         """device decode of pred_one_sample -> int32 [B, n_top] bottom-label index or -1 (``out``: see hipabi.stc_decode)"""

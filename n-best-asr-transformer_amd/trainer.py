@@ -866,6 +866,84 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     return [(split.asr[j], pc) for mine, preds in tagged for j, pc in zip(mine, preds)]
 
 
+def read_head_mask(path, L, heads):
+    """--head_mask FILE: a JSON list of L rows of ``heads`` numbers (0 prunes a head, 1 keeps it, any float gates it) -> the rows
+    as floats; ValueError names what is wrong with the file"""
+    try:
+        with open(path) as fp:
+            rows = json.load(fp)
+    except (OSError, ValueError) as e:
+        raise ValueError("head mask %s: %s" % (path, e))
+    num = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool)
+    if not isinstance(rows, list) or not all(isinstance(r, list) for r in rows):
+        raise ValueError("head mask %s: expected a JSON list of %d rows of %d numbers" % (path, L, heads))
+    if len(rows) != L or any(len(r) != heads for r in rows):
+        raise ValueError("head mask %s: shape [%d][%s] does not match the encoder's [L=%d][heads=%d]"
+                         % (path, len(rows), ",".join(sorted({str(len(r)) for r in rows})), L, heads))
+    if not all(num(x) and x == x and abs(x) != float("inf") for r in rows for x in r):
+        raise ValueError("head mask %s: every entry must be a finite number" % path)
+    return [[float(x) for x in r] for r in rows]
+
+
+def head_importance_table(grads):
+    """Michel et al. (2019) from per-utterance gate gradients: ``grads`` yields fp32 [L, B_i, heads] tensors (model.head_gate_grad's
+    ``grad`` per batch).  importance[l][h] = mean over all utterances of |d L_b / d xi[l, h]| (accumulated in fp64);
+    normalized = importance with every layer's row divided by its l2 norm (their per-layer normalisation; a zero row stays zero)."""
+    total, n = None, 0
+    for g in grads:
+        part = g.detach().double().abs().sum(dim=1)
+        total = part if total is None else total + part
+        n += g.shape[1]
+    if total is None or n == 0:
+        raise ValueError("head importance: no utterance")
+    imp = (total / n).cpu()
+    norm = imp / imp.pow(2).sum(dim=1, keepdim=True).sqrt().clamp_min(1e-300)
+    return {"importance": imp.tolist(), "normalized": norm.tolist(), "utterances": n}
+
+
+def prune_lowest(importance, mask, n):
+    """A new mask with the ``n`` lowest-importance heads that ``mask`` still keeps (entry != 0; None = all ones) set to 0: heads in
+    ascending importance, ties by (layer, head) index; a head that is the last one kept in its layer is passed over, so every layer
+    keeps at least one.  ValueError when fewer than ``n`` heads can go.  Pure: neither argument is modified."""
+    imp = [[float(x) for x in row] for row in (importance.tolist() if torch.is_tensor(importance) else importance)]
+    new = [[1.0] * len(r) for r in imp] if mask is None else [[float(x) for x in row] for row in (mask.tolist() if torch.is_tensor(mask) else mask)]
+    if [len(r) for r in new] != [len(r) for r in imp]:
+        raise ValueError("prune_lowest: importance and mask differ in shape")
+    if n < 0:
+        raise ValueError("prune_lowest: n must be >= 0 (got %d)" % n)
+    kept = [sum(1 for x in row if x != 0.0) for row in new]
+    order = sorted((imp[l][h], l, h) for l in range(len(new)) for h in range(len(new[l])) if new[l][h] != 0.0)
+    left = n
+    for _, l, h in order:
+        if left == 0:
+            break
+        if kept[l] > 1:
+            new[l][h] = 0.0
+            kept[l] -= 1
+            left -= 1
+    if left:
+        raise ValueError("prune_lowest: only %d of %d heads can be pruned with one head kept per layer" % (n - left, n))
+    return new
+
+
+def head_importance(model, data, opt, memory):
+    """Head importance of a split (Michel et al., 2019, "Are sixteen heads better than one?"): model.head_gate_grad over eval_epoch's
+    batches, at the model's current head mask -> {"importance": [L][heads], "normalized": [L][heads], "utterances": n}
+    (head_importance_table).  No dropout, no parameter gradient, no training state touched.  One GPU only."""
+    _, world = dist_info()
+    if world > 1:
+        raise RuntimeError("nbest_amd: head importance runs on one GPU (world size %d); start it without torchrun" % world)
+    split = encoded(data, opt, memory)
+    n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
+    lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
+
+    def grads():
+        for _, mine, b in Prefetcher(split, lists, model.device):
+            if mine:
+                yield model.head_gate_grad(b["ids"], b["labels"], seg_ids=b["seg"] if opt.add_segment_ids else None)["grad"]
+    return head_importance_table(grads())
+
+
 def _finish(losses, counts, device, n_batches=None):
     """losses: [(loss_parts[4] = BCE(final), BCE(top), mean-CE, MSE of this rank's shard, B_local, B_global)] per batch.
     loss_record of a batch = sum(parts) / batch_size (n_best_asr_bert.py:168-192), mean over batches (:290).  The BCE / CE
