@@ -183,6 +183,15 @@ int nbest_wgrad_pair(const nbest_gemm_args* a, const nbest_gemm_args* b, nbest_s
  * modeling_bert.py:154-177, 282-293, 325-351.  Each element is one fp32 chain over K in a fixed order: equal to nbest_gemm's result up to
  * the summation order, bit-reproducible run to run.                                                                                    */
 int nbest_wgrad_group(const nbest_gemm_args* problems, int n, nbest_stream_t stream);
+/* One window of a queue of weight-gradient tiles: the launch of nbest_wgrad_group (the same kernel program, a tile by one workgroup over
+ * the whole K in the same order: bit-equal results), but entry i covers only the tiles [tile_first[i], tile_first[i] + tile_count[i]) of
+ * problems[i], in the problem's tile order - row-major over its 256 x 256 tiles, a gradient wider than tall (FFN-down) by groups of 3
+ * tile columns.  1 .. 16 entries (a 256-tile window touches at most 4 layers' matrices at 108 tiles per layer), at most 256 tiles in
+ * all: one round of the 256 CUs.  Tiles outside the ranges are not touched.  Checked on the host before anything is enqueued: every
+ * range non-empty and inside its problem, the tile total, K and `accumulate` shared by all entries (NBEST_ERR_ARG), whole tiles
+ * (NBEST_ERR_SHAPE).  Used by nbest_encoder_backward in mode NBEST_WGRAD_GROUP_WINDOW, where the launch boundaries fall every 256 pending
+ * tiles whichever layers they belong to.                                                                                            */
+int nbest_wgrad_window(const nbest_gemm_args* problems, const int32_t* tile_first, const int32_t* tile_count, int n, nbest_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * fp8 forward GEMMs (dtype path NBEST "fp8w": BASELINE configs[4], "fp8 weights (CDNA4 fp8 MFMA)")
@@ -536,7 +545,11 @@ typedef struct nbest_encoder_desc {
    * Grouped weight gradients (wgrad_group below; launches per layer == 1): ONE pair per layer, recorded so that the pairs of the
    * layers of a group add up to the group's launch - the pair of the group's first (highest) layer brackets the grouped launch, the
    * pair of its second layer is recorded back to back right after it - so the mean over the pairs is the time per LAYER's worth
-   * of gradients.  A layer left without a partner issues its split-K launches back to back at its end, inside its one pair.  */
+   * of gradients.  A layer left without a partner issues its split-K launches back to back at its end, inside its one pair.
+   * Rolling windows (NBEST_WGRAD_GROUP_WINDOW; launches per layer == 1): ONE pair per layer of the call's range; a pair brackets each
+   * window launch (the peeled split-K pair launch inside the pair of the window next to it), the pairs left over are recorded back to
+   * back at the end of the call - the sum over the range's pairs is the weight-gradient time of the call, the mean the time per
+   * LAYER's worth of gradients.                                                                                                     */
   void** wgrad_events;
   /* optional fp8 forward ("fp8w"; dtype must be NBEST_BF16): e4m3 copy of the weight arena (one byte per element at the
    * same element offsets) and its per-matrix inverse scales [4 L] (QKV, attention-out, FFN-up, FFN-down per layer), both
@@ -619,10 +632,19 @@ typedef struct nbest_encoder_desc {
    * room for a second layer), NBEST_WGRAD_GROUP_NEVER - the split-K launches of every layer, NBEST_WGRAD_GROUP_ALWAYS - group wherever the
    * shapes allow.  Layers l, l-1 of a backward call's [layer_begin, layer_end) form a group, from the top; a group never crosses the
    * range, and a layer left over runs the split-K launches.  The dY tensors of a layer then live until the group's launch: two sets
-   * of them in the workspace (nbest_encoder_ws_bytes follows this field).  Same results up to the fp32 summation order over K.      */
+   * of them in the workspace (nbest_encoder_ws_bytes follows this field).  Same results up to the fp32 summation order over K.
+   * NBEST_WGRAD_GROUP_WINDOW - rolling windows (also at most 256 tiles per layer; else as _NEVER): the gradients of a call's layers,
+   * the highest first, QKV | attention-out | FFN-up | FFN-down within a layer, are a queue of 256 x 256 tiles, and a launch
+   * (nbest_wgrad_window) takes the next 256 pending tiles whichever layers they belong to - 1 296 tiles of 12 bert-base layers in 5
+   * rounds of the 256 CUs where the grouped launches of 216 take 6.  The rest is flushed at the end of the call (every call leaves
+   * its gradients written).  Where it saves a whole round, the QKV + attention-out pair of the range's lowest layer runs as today's
+   * split-K pair launch instead (bert-base: 1 260 tiles = 256 + 256 + 256 + 256 + 236).  The dY tensors of a layer live until its last
+   * tile is launched: N buffer sets in rotation, N from the tile counts (4 at 108 tiles per layer, 2 at 192).  The plan (_PLAN) takes
+   * the windows where its launch-cost model predicts at least 5 % less weight-gradient time than the better of the other two.  Window
+   * launches give the bits of _ALWAYS, the peeled pair those of _NEVER.  nbest_encoder_wgrad_plan reports the resolved schedule.      */
   int32_t wgrad_group;
 } nbest_encoder_desc;
-enum { NBEST_WGRAD_GROUP_PLAN = 0, NBEST_WGRAD_GROUP_NEVER = 1, NBEST_WGRAD_GROUP_ALWAYS = 2 };
+enum { NBEST_WGRAD_GROUP_PLAN = 0, NBEST_WGRAD_GROUP_NEVER = 1, NBEST_WGRAD_GROUP_ALWAYS = 2, NBEST_WGRAD_GROUP_WINDOW = 3 };
 size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
 /* Pointers into a stash `act` written by nbest_encoder_forward with descriptor d: layer `layer`'s qkv [M][3H] (dtype; also in the fp8
  * forward and its calibration pass) and lse [B][heads][S] (fp32) - the inputs of nbest_attention_probs.  Refuses (NBEST_ERR_ARG) a
@@ -630,9 +652,16 @@ size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d);
 int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, int layer, void** qkv, float** lse);
 size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d);
 /* weight-gradient launches nbest_encoder_backward enqueues per layer for this descriptor = event pairs per layer in wgrad_events:
- * 1 when the gradients of two layers share one grouped launch (desc.wgrad_group), else 3 when the attention-output gradient
+ * 1 when the gradients of two layers share one grouped launch or go out in rolling windows (desc.wgrad_group), else 3 when the attention-output gradient
  * rides with the QKV gradient (nbest_wgrad_pair; bf16, shapes that fit), else 4 */
 int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d);
+/* Host only, enqueues nothing: the weight-gradient schedule nbest_encoder_backward follows for this descriptor over the layers
+ * [layer_begin, layer_end), as int32 words: out[0] the resolved mode (NBEST_WGRAD_GROUP_NEVER / _ALWAYS / _WINDOW), out[1] the dY
+ * buffer sets (grouped: layers per launch; 0: split-K launches), out[2] the layer whose QKV + attention-out pair is peeled (-1: none),
+ * out[3] the number of window launches, then per launch: the layer at whose end it is issued, its tiles, its entries n, and per entry:
+ * layer, matrix (0 QKV, 1 attention-out, 2 FFN-up, 3 FFN-down), tile_first, tile_count.  Honours first_trainable, wgrad_skip_host and
+ * no_param_grad.  Returns the number of words (written only when `cap` holds them all) or a negative NBEST_ERR_*.                   */
+int nbest_encoder_wgrad_plan(const nbest_encoder_desc* d, int layer_begin, int layer_end, int32_t* out, int cap);
 /* hidden_out: pointer to the final hidden states [M][H] inside act (returned through *hidden_out) */
 int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids,
                           const int64_t* seg, const int64_t* pos, const uint8_t* key_mask, void* act,

@@ -12,7 +12,7 @@
 //              st2 [M][2] f32 | keep: the attention-dropout keep words (bf16) |
 //              fp8 forward (desc.w8) only: x8 | ctx8 | x18 [M][H] e4m3, h8 [M][F] e4m3, the copies of the layer's four GEMM inputs
 // Scratch `ws` (ws_layout): dR | dRd | dB1 | dctx [M][H] T, dBig [M][F] T, dqkv [M][3H] T, (grouped weight gradients: the dY buffers
-//   of the group positions, WsLayout::gset), four regions of column-reduction
+//   of the group positions; weight gradients in rolling windows: the dY buffer sets the layers rotate over, WsLayout::gset), four regions of column-reduction
 //   partials, split-K slabs, embedding-backward buffer, f8 (bf16: the e4m3 copies of ONE layer - forward: a frozen layer's GEMM
 //   inputs, backward: the gradients the fp8 dgrads read), fz (K > 0: X0 | X1 | emb_stats | lse | st1 | st2 | u).
 //   Layers 0..K-1 are not stashed: their forward runs on fz plus the backward's layer-gradient buffers, which are idle
@@ -20,6 +20,7 @@
 // Head gates (desc.head_gate): the forward's gated copy of a layer's ctx borrows dctx; the stash keeps the un-gated ctx.
 // Inference workspace: infer_layout, below.
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 
@@ -84,9 +85,9 @@ static ActLayout act_layout(const nbest_encoder_desc* d, const Sizes& z) {
 
 struct WsLayout {
   size_t dR, dRd, dB1, dctx, dBig, dqkv, red, slab, slab_bytes, red_bytes, emb, emb_bytes, f8, f8_bytes, total;
-  // grouped weight gradients (wgrad_group_layers > 0): the four dY tensors of a layer - dRd after LN2, dBig, dRd after LN1, dqkv - per
-  // position of the layer in its group; set 0 shares dRd, dBig and dqkv above
-  size_t gset[2][4];
+  // deferred weight gradients (grouped or in windows): the four dY tensors of a layer - dRd after LN2, dBig, dRd after LN1, dqkv - per
+  // position of the layer in its group / per buffer set of the windows; set 0 shares dRd, dBig and dqkv above
+  size_t gset[8][4];
   size_t fz_x0, fz_x1, fz_emb_stats, fz_lse, fz_st1, fz_st2, fz_u;   // forward of the frozen layers 0..K-1 (first_trainable = K > 0)
 };
 
@@ -136,32 +137,131 @@ static double wgrad_splitk_us(int64_t rows, int64_t cols, int64_t M) {
   const int64_t stages = ((M + splits - 1) / splits + 31) / 32, wgs = (rows / 256) * (cols / 256) * splits;
   return kWgA + kWgB * (double)(stages * ((wgs + 255) / 256)) + (splits > 1 ? kWgRed : 0.0);
 }
-// Layers per grouped weight-gradient launch (nbest_wgrad_group; include/nbest_hip.h, desc.wgrad_group): 0 = every layer issues its
-// split-K launches.  Grouping needs the bf16 path without the fp8 forward (whose backward has its own weight-gradient kernels) and
-// whole 256 x 256 tiles.  The plan groups two layers when their tiles fit one round of the 256 CUs and the model above predicts
-// at least 5 % less time than the three split-K launches + reduces of each layer.
-static int wgrad_group_layers(const nbest_encoder_desc* d) {
-  if (d->wgrad_group == NBEST_WGRAD_GROUP_NEVER) return 0;
-  if (d->dtype != NBEST_BF16 || d->w8 || d->H % 256 || d->F % 256) return 0;
-  const int64_t H = d->H, F = d->F, M = (int64_t)d->B * d->S;
-  const int64_t tiles = (4 * H * H + 2 * H * F) / (256 * 256);   // of one layer's four gradients
-  if (d->wgrad_group == NBEST_WGRAD_GROUP_ALWAYS) return 2 * tiles <= 256 ? 2 : 1;
-  if (2 * tiles > 256 || !wgrad_paired(d, false)) return 0;
-  const double today = wgrad_splitk_us(4 * H, H, M) + wgrad_splitk_us(F, H, M) + wgrad_splitk_us(H, F, M);
-  const double grouped = (kWgA + kWgB * (double)((M + 31) / 32)) / 2.0;
-  return grouped < 0.95 * today ? 2 : 0;
+// ---- rolling windows (NBEST_WGRAD_GROUP_WINDOW): the schedule ----------------------------------------------------------------------------
+// The non-skipped gradients of the layers of a backward call's range form a queue of 256 x 256 tiles: the highest layer first, QKV |
+// attention-out | FFN-up | FFN-down within a layer, a matrix's tiles in the order of nbest_wgrad_group.  A launch (nbest_wgrad_window)
+// takes the next 256 pending tiles whichever layers they belong to, as soon as 256 are pending; the rest goes out at the end of the
+// call, so a call leaves all of its gradients written.  Where it saves a whole round, the QKV + attention-out pair of the range's lowest
+// layer is peeled off the queue and runs as the split-K launches of mode NEVER (one pair launch where the two fit it).  A layer's dY tensors live until its last tile is launched:
+// `sets` buffer sets in rotation (layer i of the range from the top takes set i % sets); a window is also cut short where the table
+// is full (kWinEntries) and the queue is flushed where the next layer would find no free set (skipped matrices make layers small).
+constexpr int kWinEntries = 16, kMaxSets = 8, kWinTiles = 256;
+// a window of more than 216 tiles against the launch of 216: 1.023 for lone launches (profiles/wgrad_window_fit.txt), 1.078 inside the
+// training step (profiles/wgrad_window_ab.txt) - the plan decides for the step, so it takes the in-step figure
+constexpr double kWgFull = 1.078;
+struct WinEntry { int layer, j, first, count; };
+struct WinLaunch { int after_layer, tiles, n; WinEntry e[kWinEntries]; };   // issued at the end of layer `after_layer`
+struct WinPlan {
+  int sets = 0, peel_layer = -1, max_live = 0;   // max_live: most layers with unlaunched tiles while a further layer writes its dY
+  std::vector<WinLaunch> launches;
+};
+static void matrix_tiles(const nbest_encoder_desc* d, int t[4]) {
+  const int h = d->H / 256, f = d->F / 256;
+  t[0] = 3 * h * h; t[1] = h * h; t[2] = f * h; t[3] = h * f;
+}
+// skip: [4 L] flags as desc.wgrad_skip_host or NULL; peel: the schedule of a call (false: only the buffer sets are asked for)
+static WinPlan window_plan(const nbest_encoder_desc* d, int layer_begin, int layer_end, const uint8_t* skip, bool all_skipped, bool peel,
+                           int sets) {
+  WinPlan wp;
+  wp.sets = sets;
+  int t[4];
+  matrix_tiles(d, t);
+  auto live = [&](int l, int j) { return !all_skipped && !(skip && skip[4 * l + j]); };
+  int64_t total = 0;
+  for (int l = layer_begin; l < layer_end; ++l)
+    for (int j = 0; j < 4; ++j) total += live(l, j) ? t[j] : 0;
+  if (peel && layer_begin < layer_end) {
+    const int64_t pair = (live(layer_begin, 0) ? t[0] : 0) + (live(layer_begin, 1) ? t[1] : 0);
+    if (pair > 0 && (total - pair + kWinTiles - 1) / kWinTiles < (total + kWinTiles - 1) / kWinTiles) wp.peel_layer = layer_begin;
+  }
+  std::vector<WinEntry> q;   // pending, front at `head`
+  size_t head = 0;
+  int64_t pending = 0;
+  auto emit = [&](int after) {
+    WinLaunch w = {};
+    w.after_layer = after;
+    while (head < q.size() && w.tiles < kWinTiles && w.n < kWinEntries) {
+      WinEntry& f = q[head];
+      const int c = std::min(f.count, kWinTiles - w.tiles);
+      w.e[w.n++] = WinEntry{f.layer, f.j, f.first, c};
+      w.tiles += c; f.first += c; f.count -= c; pending -= c;
+      if (f.count == 0) ++head;
+    }
+    wp.launches.push_back(w);
+  };
+  for (int l = layer_end - 1; l >= layer_begin; --l) {
+    const int n_live = head < q.size() ? q[head].layer - l : 0;   // layers l + 1 .. q[head].layer still have tiles pending
+    wp.max_live = std::max(wp.max_live, n_live);
+    if (n_live >= sets)   // no free set for this layer: everything pending goes out now, at the end of layer l + 1
+      while (pending > 0) emit(l + 1);
+    for (int j = 0; j < 4; ++j)
+      if (live(l, j) && !(l == wp.peel_layer && j < 2)) { q.push_back(WinEntry{l, j, 0, t[j]}); pending += t[j]; }
+    while (pending >= kWinTiles) emit(l);
+  }
+  while (pending > 0) emit(layer_begin);
+  return wp;
+}
+static bool window_shapes_ok(const nbest_encoder_desc* d) {
+  if (d->dtype != NBEST_BF16 || d->w8 || d->H % 256 || d->F % 256) return false;
+  return (4 * (int64_t)d->H * d->H + 2 * (int64_t)d->H * d->F) / (256 * 256) <= kWinTiles;
+}
+// The window schedule of the whole trainable range, nothing skipped, built once: its buffer sets (a shorter range runs a prefix of the
+// same schedule; skipped matrices are covered by the flush rule of window_plan) and its model time (us).  The time is that of ONE call
+// over the whole range: a backward in chunks (the 2-layer chunks of the data-parallel reducer) flushes per call and runs today's
+// 216-tile launches at bert-base tile counts, 256 + 128 tiles per chunk at 192 tiles per layer - the prediction does not hold there.
+struct WindowModel { int sets; double us; };
+static WindowModel window_model(const nbest_encoder_desc* d) {
+  const int64_t H = d->H, M = (int64_t)d->B * d->S;
+  const WinPlan wp = window_plan(d, first_trainable(d), d->L, nullptr, false, true, kMaxSets);   // (the peel does not change max_live)
+  const double round = kWgA + kWgB * (double)((M + 31) / 32);
+  double us = 0.0;
+  if (wp.peel_layer >= 0) us = wgrad_paired(d, false) ? wgrad_splitk_us(4 * H, H, M) : wgrad_splitk_us(3 * H, H, M) + wgrad_splitk_us(H, H, M);
+  for (const WinLaunch& w : wp.launches) us += round * (w.tiles > 216 ? kWgFull : 1.0);
+  return WindowModel{std::min(wp.max_live + 1, kMaxSets), us};
 }
 
-static WsLayout ws_layout(const nbest_encoder_desc* d, const Sizes& z) {
+// How the weight gradients of this descriptor are launched (include/nbest_hip.h, desc.wgrad_group), resolved:
+//   mode NEVER: every layer issues its split-K launches (gl = 0);  ALWAYS / the plan's grouping: gl layers per nbest_wgrad_group launch;
+//   WINDOW: rolling windows over `sets` dY buffer sets (gl = 0).
+// Grouping and windows need the bf16 path without the fp8 forward (whose backward has its own weight-gradient kernels) and whole
+// 256 x 256 tiles.  The plan groups two layers when their tiles fit one round of the 256 CUs and the model above predicts at least 5 %
+// less time than the three split-K launches + reduces of each layer; it takes the windows where the model predicts at least 5 % less
+// than the better of those two over the trainable layers.  At small token counts the fixed cost of a launch dominates and the
+// windows' extra pair launch keeps them out.
+struct WgradMode { int mode, gl, sets; };
+static WgradMode wgrad_mode(const nbest_encoder_desc* d) {
+  const WgradMode never = {NBEST_WGRAD_GROUP_NEVER, 0, 0};
+  if (d->wgrad_group == NBEST_WGRAD_GROUP_NEVER) return never;
+  if (d->dtype != NBEST_BF16 || d->w8 || d->H % 256 || d->F % 256) return never;
+  const int64_t H = d->H, F = d->F, M = (int64_t)d->B * d->S;
+  const int64_t tiles = (4 * H * H + 2 * H * F) / (256 * 256);   // of one layer's four gradients
+  if (d->wgrad_group == NBEST_WGRAD_GROUP_ALWAYS) return WgradMode{NBEST_WGRAD_GROUP_ALWAYS, 2 * tiles <= 256 ? 2 : 1, 0};
+  if (d->wgrad_group == NBEST_WGRAD_GROUP_WINDOW)
+    return window_shapes_ok(d) ? WgradMode{NBEST_WGRAD_GROUP_WINDOW, 0, window_model(d).sets} : never;
+  const int nl = d->L - first_trainable(d);
+  const double today = wgrad_splitk_us(4 * H, H, M) + wgrad_splitk_us(F, H, M) + wgrad_splitk_us(H, F, M);
+  const double round = kWgA + kWgB * (double)((M + 31) / 32);
+  if (window_shapes_ok(d) && nl > 0) {   // against the better of the other two modes, whichever of them the plan would take
+    const int gl = 2 * tiles <= 256 ? 2 : 1;
+    const WindowModel wm = window_model(d);
+    if (wm.us < 0.95 * std::min(today * nl, round * ((nl + gl - 1) / gl))) return WgradMode{NBEST_WGRAD_GROUP_WINDOW, 0, wm.sets};
+  }
+  if (2 * tiles > 256 || !wgrad_paired(d, false)) return never;
+  return round / 2.0 < 0.95 * today ? WgradMode{NBEST_WGRAD_GROUP_ALWAYS, 2, 0} : never;
+}
+// wm: wgrad_mode(d), resolved once by the caller
+static WsLayout ws_layout(const nbest_encoder_desc* d, const Sizes& z, const WgradMode& wm) {
   WsLayout w;
   const int64_t M = z.M;
   size_t o = 0;
   w.dR = take(o, z.MH); w.dRd = take(o, z.MH); w.dB1 = take(o, z.MH); w.dctx = take(o, z.MH);
   w.dBig = take(o, z.MF); w.dqkv = take(o, z.M3H);
-  for (int s = 0; s < 2; ++s) { w.gset[s][0] = w.dRd; w.gset[s][1] = w.dBig; w.gset[s][2] = w.dRd; w.gset[s][3] = w.dqkv; }
-  if (wgrad_group_layers(d) > 0) {
+  static_assert(sizeof(w.gset) / sizeof(w.gset[0]) == kMaxSets, "one row per buffer set");
+  for (int s = 0; s < kMaxSets; ++s) { w.gset[s][0] = w.dRd; w.gset[s][1] = w.dBig; w.gset[s][2] = w.dRd; w.gset[s][3] = w.dqkv; }
+  const int n_sets = wm.gl + wm.sets;   // one of the two is 0
+  if (n_sets > 0) {
     w.gset[0][2] = take(o, z.MH);
-    if (wgrad_group_layers(d) > 1) { w.gset[1][0] = take(o, z.MH); w.gset[1][1] = take(o, z.MF); w.gset[1][2] = take(o, z.MH); w.gset[1][3] = take(o, z.M3H); }
+    for (int s = 1; s < n_sets; ++s) { w.gset[s][0] = take(o, z.MH); w.gset[s][1] = take(o, z.MF); w.gset[s][2] = take(o, z.MH); w.gset[s][3] = take(o, z.M3H); }
   }
   const int64_t maxN = d->F > 3 * d->H ? d->F : 3 * d->H;
   w.red_bytes = al(nbest_rowred_ws_bytes(M, maxN));
@@ -442,11 +542,35 @@ extern "C" int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, in
   *qkv = b.qkv; *lse = b.lse;
   return NBEST_OK;
 }
-extern "C" size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d) { return d ? ws_layout(d, sizes(d)).total : 0; }
+extern "C" size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d) { return d ? ws_layout(d, sizes(d), wgrad_mode(d)).total : 0; }
 extern "C" int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d) {
   if (!d) return 0;
-  if (wgrad_group_layers(d) > 0) return 1;
+  const WgradMode wm = wgrad_mode(d);
+  if (wm.gl > 0 || wm.sets > 0) return 1;
   return wgrad_paired(d, fp8_backward_active(d)) ? 3 : 4;
+}
+
+// host only, enqueues nothing: the resolved weight-gradient schedule of a backward call over [layer_begin, layer_end) as int32 words
+//   out[0] mode (NBEST_WGRAD_GROUP_NEVER / _ALWAYS / _WINDOW), out[1] dY buffer sets (layers per grouped launch; 0: split-K launches),
+//   out[2] the layer whose QKV + attention-out pair is peeled (-1: none), out[3] window launches, then per launch: the layer at whose
+//   end it is issued, its tiles, its entries n, and per entry: layer, matrix (0 QKV, 1 attention-out, 2 FFN-up, 3 FFN-down), tile_first,
+//   tile_count.  Returns the number of words of the schedule (written only when cap holds them all) or a negative NBEST_ERR_*.
+extern "C" int nbest_encoder_wgrad_plan(const nbest_encoder_desc* d, int layer_begin, int layer_end, int32_t* out, int cap) {
+  NB_CHECK(d && d->B > 0 && d->S > 0 && d->L > 0 && d->H > 0 && d->F > 0, NBEST_ERR_ARG, "encoder_wgrad_plan: bad descriptor");
+  NB_CHECK(first_trainable(d) <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_wgrad_plan: bad layer range");
+  NB_CHECK(out || cap <= 0, NBEST_ERR_ARG, "encoder_wgrad_plan: null pointer");
+  const WgradMode wm = wgrad_mode(d);
+  std::vector<int32_t> v = {wm.mode, wm.gl + wm.sets, -1, 0};
+  if (wm.sets > 0) {
+    const WinPlan wp = window_plan(d, layer_begin, layer_end, d->wgrad_skip_host, d->no_param_grad != 0, true, wm.sets);
+    v[2] = wp.peel_layer; v[3] = (int32_t)wp.launches.size();
+    for (const WinLaunch& w : wp.launches) {
+      v.insert(v.end(), {w.after_layer, w.tiles, w.n});
+      for (int i = 0; i < w.n; ++i) v.insert(v.end(), {w.e[i].layer, w.e[i].j, w.e[i].first, w.e[i].count});
+    }
+  }
+  if ((int)v.size() <= cap) std::copy(v.begin(), v.end(), out);
+  return (int)v.size();
 }
 
 extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids,
@@ -458,7 +582,7 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   const ActLayout a = act_layout(d, z);
   NB_CHECK(act_bytes >= a.total, NBEST_ERR_WORKSPACE, "encoder_forward: activation stash too small (%zu < %zu)", act_bytes, a.total);
   Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
-  const WsLayout wl = ws_layout(d, z);
+  const WsLayout wl = ws_layout(d, z, wgrad_mode(d));
   const int FT = a.K;   // layers 0..FT-1 are frozen: run on scratch in ws, nothing of them stashed
   if (c.g.fp8 || FT > 0 || d->head_gate)
     NB_CHECK(ws && ws_bytes >= wl.total, NBEST_ERR_WORKSPACE, "encoder_forward(%s): workspace too small (%zu < %zu)",
@@ -520,7 +644,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
            "encoder_backward: with_embeddings needs first_trainable == 0 and no_input_grad == 0");
   const Sizes z = sizes(d);
   const ActLayout a = act_layout(d, z);
-  const WsLayout w = ws_layout(d, z);
+  const WgradMode wm = wgrad_mode(d);   // once per call: the workspace layout and the launches below follow it
+  const WsLayout w = ws_layout(d, z, wm);
   NB_CHECK(act_bytes >= a.total, NBEST_ERR_WORKSPACE, "encoder_backward: activation stash too small");
   NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_backward: workspace too small (%zu < %zu)", ws_bytes, w.total);
   hipStream_t st = (hipStream_t)stream;
@@ -545,9 +670,10 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   const bool f8b = fp8_backward_active(d);
   const bool paired = wgrad_paired(d, f8b);
   // grouped weight gradients: gl layers per nbest_wgrad_group launch, groups formed from layer_end - 1 downwards
-  const int gl = wgrad_group_layers(d);
-  const bool grouped = gl > 0;
-  int ev_i = (grouped ? 1 : paired ? 3 : 4) * (d->L - layer_end);
+  // or in rolling windows of 256 tiles (window_plan): the layers' dY tensors rotate over wm.sets buffer sets
+  const int gl = wm.gl;
+  const bool grouped = gl > 0, window = wm.sets > 0, deferred = grouped || window;
+  int ev_i = (deferred ? 1 : paired ? 3 : 4) * (d->L - layer_end);
   auto stamp = [&](int which) {
     if (d->wgrad_events && 2 * ev_i + which < d->wgrad_events_n) (void)hipEventRecord((hipEvent_t)d->wgrad_events[2 * ev_i + which], st);
     ev_i += which;
@@ -607,6 +733,22 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   // split-K launches back to back instead.  One event pair per layer (include/nbest_hip.h, wgrad_events).
   nbest_gemm_args pend[8];
   int n_pend = 0;
+  // Windows: the gradients of a layer wait in the queue of window_plan; its launches go out at the end of the layer that completes them,
+  // the peeled pair and the remainder at the end of the range's lowest layer.  One event pair per layer of the range: a pair brackets each
+  // window launch (the peeled pair launch inside the pair of the window next to it), the pairs left over are recorded back to back at
+  // the end, so the sum over the range's pairs is the weight-gradient time of the call.
+  const int nl = layer_end - layer_begin;
+  WinPlan wp;
+  std::vector<nbest_gemm_args> wargs;   // [4 (layer_end - 1 - l) + j]
+  if (window) {
+    wp = window_plan(d, layer_begin, layer_end, d->wgrad_skip_host, npg, true, wm.sets);
+    wargs.resize((size_t)4 * nl);
+  }
+  size_t wi = 0;            // next launch of wp
+  int pairs_used = 0;
+  bool pair_open = false;
+  auto pair_begin = [&] { if (!pair_open && pairs_used < nl) { stamp(0); pair_open = true; } };
+  auto pair_end = [&] { if (pair_open) { stamp(1); ++pairs_used; pair_open = false; } };
 
   struct BatchGuard { ~BatchGuard() { nbest_internal_rowred_batch_abort(); } } batch_guard;   // an error return mid-layer must not leave it open
   for (int l = layer_end - 1; l >= layer_begin; --l) {
@@ -615,13 +757,14 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     const bool input_grad = !(d->no_input_grad && l == FT);   // the gradient w.r.t. the input of layer FT has no reader
     const int t = 4 * l;
     const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
-    // this layer's gradient buffers: the shared ones, or (grouped) those of its position in the group, which the next layer leaves alone.
+    // this layer's gradient buffers: the shared ones, or (grouped) those of its position in the group, which the next layer leaves alone,
+    // or (windows) those of its buffer set, which the next sets - 1 layers leave alone.
     // dR2 / dRd2: residual- and dense-branch gradients out of the LN2 backward, dR1 / dRd1: out of the LN1 backward (one buffer
     // without hidden dropout)
-    const int gpos = grouped ? (layer_end - 1 - l) % gl : 0;
+    const int gpos = grouped ? (layer_end - 1 - l) % gl : window ? (layer_end - 1 - l) % wm.sets : 0;
     const bool group_ends = grouped && (gpos == gl - 1 || l == layer_begin);
     void *dR2 = dR, *dR1 = dR, *dRd2 = dRd, *dRd1 = dRd, *dBigL = dBig, *dqkvL = dqkv;
-    if (grouped) {
+    if (deferred) {
       dRd2 = W + w.gset[gpos][0]; dBigL = W + w.gset[gpos][1]; dRd1 = W + w.gset[gpos][2]; dqkvL = W + w.gset[gpos][3];
       if (!hdrop) { dR2 = dRd2; dR1 = dRd1; }
     }
@@ -640,12 +783,12 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     dw2.U = b.u; dw2.colsum = GP(o.b1); dw2.C8 = dBig8; dw2.c_idx = t + 1;
     RUN(layer_gemm(dg, dw2));
     if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBigL, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
-    if (!grouped) RUN(wgrad(l, wg, 3, -1));
+    if (!deferred) RUN(wgrad(l, wg, 3, -1));
     // FFN-up: dgrad + residual gradient ; wgrad
     GemmOp dw1 = {dBigL, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
     dw1.R = dR2;
     RUN(layer_gemm(dg, dw1));
-    if (!grouped) RUN(wgrad(l, wg, 2, -1));
+    if (!deferred) RUN(wgrad(l, wg, 2, -1));
     // LN1 backward
     RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, (hdrop && !f8b) ? dRd1 : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
                                       dt, accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, t + 2)));
@@ -653,7 +796,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     const GemmOp dwo = {dRd1, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
     RUN(layer_gemm(dg, dwo));
     // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
-    if (!paired && !grouped) RUN(wgrad(l, wg, 1, -1));
+    if (!paired && !deferred) RUN(wgrad(l, wg, 1, -1));
     // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
     // (per utterance), and scaled by the gate it is the gradient the attention backward takes
     if (d->head_gate)
@@ -668,7 +811,30 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       dwqkv.R = dR1;
       RUN(layer_gemm(dg, dwqkv));
     }
-    if (!grouped) {
+    if (window) {
+      for (int j = 0; j < 4; ++j)
+        if (!skip(l, j)) wargs[(size_t)4 * (layer_end - 1 - l) + j] = wgrad_args_of(wg + j);
+      if (l == wp.peel_layer) {
+        pair_begin();   // today's split-K launches of the two: one launch where the pair fits it
+        if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
+        RUN(wgrad_launch(l, wg, 0, paired ? 1 : -1));
+      }
+      for (; wi < wp.launches.size() && wp.launches[wi].after_layer == l; ++wi) {
+        const WinLaunch& wl = wp.launches[wi];
+        nbest_gemm_args tab[kWinEntries];
+        int32_t first[kWinEntries], count[kWinEntries];
+        for (int i = 0; i < wl.n; ++i) {
+          tab[i] = wargs[(size_t)4 * (layer_end - 1 - wl.e[i].layer) + wl.e[i].j];
+          first[i] = wl.e[i].first; count[i] = wl.e[i].count;
+        }
+        pair_begin();
+        RUN(nbest_wgrad_window(tab, first, count, wl.n, stream));
+        pair_end();
+      }
+      pair_end();   // (a peeled pair with no window after it)
+      if (l == layer_begin)
+        for (; pairs_used < nl; ++pairs_used) { stamp(0); stamp(1); }
+    } else if (!grouped) {
       RUN(wgrad(l, wg, 0, paired ? 1 : -1));
     } else if (group_ends && gpos + 1 < gl && d->wgrad_group != NBEST_WGRAD_GROUP_ALWAYS) {   // no partner: today's launches, one event pair
       stamp(0);

@@ -132,16 +132,29 @@ extern "C" int nbest_wgrad_pair(const nbest_gemm_args* a, const nbest_gemm_args*
 }
 
 // ---- up to 8 weight gradients, one launch without K-splits (include/nbest_hip.h) ----------------------------------------
-extern "C" int nbest_wgrad_group(const nbest_gemm_args* problems, int n, nbest_stream_t stream) {
-  NB_CHECK(problems && n >= 1 && n <= 8, NBEST_ERR_ARG, "wgrad_group: needs 1 .. 8 problems");
+static int check_wgrad_table(const char* who, const nbest_gemm_args* problems, int n) {
   for (int i = 0; i < n; ++i) {
     const nbest_gemm_args* a = problems + i;
-    NB_CHECK(a->A && a->B && a->C, NBEST_ERR_ARG, "wgrad_group: null pointer in problem %d", i);
-    NB_CHECK(a->M > 0 && a->N > 0 && a->K > 0, NBEST_ERR_SHAPE, "wgrad_group: bad shape in problem %d", i);
-    NB_CHECK(a->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "wgrad_group: bf16 operands only");
-    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_group: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", i,
+    NB_CHECK(a->A && a->B && a->C, NBEST_ERR_ARG, "%s: null pointer in problem %d", who, i);
+    NB_CHECK(a->M > 0 && a->N > 0 && a->K > 0, NBEST_ERR_SHAPE, "%s: bad shape in problem %d", who, i);
+    NB_CHECK(a->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "%s: bf16 operands only", who);
+    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "%s: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", who, i,
              (long long)a->M, (long long)a->N);
     if (int rc = check_bf16(a)) return rc;
   }
+  return NBEST_OK;
+}
+
+extern "C" int nbest_wgrad_group(const nbest_gemm_args* problems, int n, nbest_stream_t stream) {
+  NB_CHECK(problems && n >= 1 && n <= 8, NBEST_ERR_ARG, "wgrad_group: needs 1 .. 8 problems");
+  if (int rc = check_wgrad_table("wgrad_group", problems, n)) return rc;
   return nbest_wgrad_group_bf16(problems, n, (hipStream_t)stream);
+}
+
+// ---- one window of at most 256 tiles out of up to 16 weight gradients (include/nbest_hip.h) ------------------------------
+extern "C" int nbest_wgrad_window(const nbest_gemm_args* problems, const int32_t* tile_first, const int32_t* tile_count, int n,
+                                  nbest_stream_t stream) {
+  NB_CHECK(problems && tile_first && tile_count && n >= 1 && n <= 16, NBEST_ERR_ARG, "wgrad_window: needs 1 .. 16 entries");
+  if (int rc = check_wgrad_table("wgrad_window", problems, n)) return rc;
+  return nbest_wgrad_window_bf16(problems, tile_first, tile_count, n, (hipStream_t)stream);
 }

@@ -959,12 +959,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel(GemmP2 p) {
 // straight into its gradient - no slabs, no reduce).  The tiles of a problem are consecutive tile ids, so that xcd_remap keeps a problem on as
 // few XCDs as it can; the problem of a workgroup is picked by an unrolled scan of the table in the kernel arguments (workgroup-uniform: scalar
 // selects, no dynamic indexing of the argument block), nothing is added to the K loop.
-constexpr int kMaxGroup = 8;
+// A table entry covers the tiles [tile_first, tile_first + its share of the launch) of its problem, in the problem's tile order:
+// nbest_wgrad_group takes every problem whole (tile_first == 0, at most 8 entries), nbest_wgrad_window a sub-range, so that the launch
+// boundaries can fall anywhere in the queue of pending tiles (at most 256 tiles: 4 layers' matrices at 108 tiles per layer = 16 entries).
+constexpr int kMaxGroup = 16;
 struct WgradProb {
   const bf16* A; const bf16* B; float* C;
   int64_t lda, ldb, ldc;
   uint32_t a_bytes, b_bytes;
-  int tiles_m, tiles_n, gn, tile_start;
+  int tiles_m, tiles_n, gn, tile_start, tile_first;
 };
 struct WgradGroupP {
   WgradProb pr[kMaxGroup];
@@ -991,7 +994,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm2_kernel_grouped(WgradGro
   p.a_bytes = q.a_bytes; p.b_bytes = q.b_bytes;
   p.stream_out = 1;
   p.gn = q.gn;
-  gemm2_body<BM, BN, WM, WN, STAGES, TA, TB, EPI>(p, id - q.tile_start);
+  gemm2_body<BM, BN, WM, WN, STAGES, TA, TB, EPI>(p, id - q.tile_start + q.tile_first);
 }
 
 // B operand (a weight matrix [N][K], k-contiguous) -> the order the 256 x bn ping-pong kernel stages it: for every tile column and
@@ -1272,38 +1275,56 @@ int nbest_wgrad_pair_bf16(const nbest_gemm_args* a, const nbest_gemm_args* b, hi
   return gemm_v2_impl(&v, b, a->M, st);
 }
 
-// Up to kMaxGroup weight gradients with the same K in one launch without K-splits (gemm2_kernel_grouped).  The caller (gemm.hip) has checked
-// pointers, alignment and operand extents of every problem (check_bf16).
+// Weight gradients with the same K in one launch without K-splits (gemm2_kernel_grouped): entry i runs the tiles [first[i], first[i] + count[i])
+// of problem i (first == NULL: every problem whole).  The caller (gemm.hip) has checked pointers, alignment and operand extents of every
+// problem (check_bf16); the ranges are checked here, before anything is enqueued: the kernel trusts them.
 // Tile order inside a problem: row-major, except that a gradient wider than tall (FFN-down: 3 x 12 tiles) goes by groups of 3 tile columns -
 // 9-tile blocks that read 3 column panels of X and all of dY - so that a block boundary of xcd_remap (27 tiles per XCD for the 216 tiles
 // of two bert-base layers) cuts a problem between two such blocks and never through a tile row of 12.
-int nbest_wgrad_group_bf16(const nbest_gemm_args* pr, int n, hipStream_t st) {
-  NB_CHECK(n >= 1 && n <= kMaxGroup, NBEST_ERR_ARG, "wgrad_group: %d problems (1 .. %d)", n, kMaxGroup);
+static int wgrad_table_launch(const char* who, const nbest_gemm_args* pr, const int32_t* first, const int32_t* count, int n, int max_n,
+                              int64_t max_tiles, hipStream_t st) {
+  NB_CHECK(n >= 1 && n <= max_n, NBEST_ERR_ARG, "%s: %d problems (1 .. %d)", who, n, max_n);
   WgradGroupP g = {};
   g.n = n; g.K = pr[0].K; g.k_pad = round_up(pr[0].K, 64); g.accumulate = pr[0].accumulate;
-  int tiles = 0;
+  int64_t tiles = 0;
   for (int i = 0; i < n; ++i) {
     const nbest_gemm_args* a = pr + i;
     NB_CHECK(a->dtype == NBEST_BF16 && a->trans_a && a->trans_b && a->epilogue == NBEST_EPI_F32_SPLITK, NBEST_ERR_ARG,
-             "wgrad_group: problem %d is not a bf16 weight gradient (trans_a = trans_b = 1, NBEST_EPI_F32_SPLITK)", i);
-    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_group: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", i,
+             "%s: problem %d is not a bf16 weight gradient (trans_a = trans_b = 1, NBEST_EPI_F32_SPLITK)", who, i);
+    NB_CHECK(a->M % 256 == 0 && a->N % 256 == 0, NBEST_ERR_SHAPE, "%s: problem %d: %lld x %lld is not a multiple of the 256 x 256 tile", who, i,
              (long long)a->M, (long long)a->N);
-    NB_CHECK(a->K == g.K && a->accumulate == g.accumulate, NBEST_ERR_ARG, "wgrad_group: problem %d differs in K or accumulate", i);
+    NB_CHECK(a->K == g.K && a->accumulate == g.accumulate, NBEST_ERR_ARG, "%s: problem %d differs in K or accumulate", who, i);
+    const int64_t all = (a->M / 256) * (a->N / 256);
+    const int64_t f = first ? first[i] : 0, c = first ? count[i] : all;
+    NB_CHECK(c >= 1, NBEST_ERR_ARG, "%s: entry %d: empty tile range", who, i);
+    NB_CHECK(f >= 0 && f + c <= all, NBEST_ERR_ARG, "%s: entry %d: tiles [%lld, %lld) outside the problem's %lld", who, i, (long long)f,
+             (long long)(f + c), (long long)all);
     WgradProb& q = g.pr[i];
     q.A = (const bf16*)a->A; q.B = (const bf16*)a->B; q.C = (float*)a->C;
     q.lda = a->lda; q.ldb = a->ldb; q.ldc = a->ldc;
     q.a_bytes = (uint32_t)(((a->K - 1) * a->lda + a->M) * 2); q.b_bytes = (uint32_t)(((a->K - 1) * a->ldb + a->N) * 2);
     q.tiles_m = (int)(a->M / 256); q.tiles_n = (int)(a->N / 256);
     q.gn = (q.tiles_n > q.tiles_m && q.tiles_n % 3 == 0) ? 3 : q.tiles_n;
-    q.tile_start = tiles;
-    tiles += q.tiles_m * q.tiles_n;
+    q.tile_start = (int)tiles; q.tile_first = (int)f;
+    tiles += c;
+    NB_CHECK(tiles <= max_tiles, NBEST_ERR_ARG, "%s: more than %lld tiles in one launch", who, (long long)max_tiles);
   }
   constexpr int lds_bytes = 4 * (256 + 256) * BK * 2;
   const auto kernel = gemm2_kernel_grouped<256, 256, 2, 4, 4, true, true, NBEST_EPI_F32_SPLITK>;
   (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  kernel<<<tiles, 512, lds_bytes, st>>>(g);
+  kernel<<<(int)tiles, 512, lds_bytes, st>>>(g);
   NB_LAUNCH_CHECK();
   return NBEST_OK;
+}
+
+// up to 8 whole problems, any number of tiles (more than 256 run in further rounds)
+int nbest_wgrad_group_bf16(const nbest_gemm_args* pr, int n, hipStream_t st) {
+  return wgrad_table_launch("wgrad_group", pr, nullptr, nullptr, n, 8, (int64_t)1 << 30, st);
+}
+
+// up to kMaxGroup tile ranges, at most one round of the 256 CUs
+int nbest_wgrad_window_bf16(const nbest_gemm_args* pr, const int32_t* first, const int32_t* count, int n, hipStream_t st) {
+  return wgrad_table_launch("wgrad_window", pr, first, count, n, kMaxGroup, 256, st);
 }
 
 // tile width the k-contiguous GEMM of an [N][K] weight matrix is packed for (0: not packed): the rule of make_plan at training-size

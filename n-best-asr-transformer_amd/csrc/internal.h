@@ -62,6 +62,7 @@ bool nbest_gemm_bf16_v2_wins(const nbest_gemm_args* a);   // per-shape choice of
 size_t nbest_wgrad_pair_bf16_ws_bytes(const nbest_gemm_args* a, const nbest_gemm_args* b);
 int nbest_wgrad_pair_bf16(const nbest_gemm_args* a, const nbest_gemm_args* b, hipStream_t st);
 int nbest_wgrad_group_bf16(const nbest_gemm_args* problems, int n, hipStream_t st);
+int nbest_wgrad_window_bf16(const nbest_gemm_args* problems, const int32_t* tile_first, const int32_t* tile_count, int n, hipStream_t st);
 int nbest_pack_bn_internal(int64_t N);
 int nbest_pack_weights_bf16(const void* src, void* dst, const nbest_matrix_desc* descs, int n_matrices, int n_stages, hipStream_t st);
 

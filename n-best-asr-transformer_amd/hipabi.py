@@ -18,11 +18,11 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
-    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
+    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
     "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step",
-    "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_forward",
+    "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
     "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
     "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
@@ -119,9 +119,11 @@ def lib():
         L.nbest_wgrad_pair_ws_bytes.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs)]
         L.nbest_wgrad_pair.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_void_p]
         L.nbest_wgrad_group.argtypes = [C.POINTER(GemmArgs), C.c_int32, C.c_void_p]
+        L.nbest_wgrad_window.argtypes = [C.POINTER(GemmArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
         L.nbest_encoder_act_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_wgrad_launches_per_layer.argtypes = [C.POINTER(EncoderDesc)]
+        L.nbest_encoder_wgrad_plan.argtypes = [C.POINTER(EncoderDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
         vp, i64, i32, f32, u64, u32, sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_size_t
         L.nbest_embed_ln_fwd.argtypes = [vp] * 10 + [i64, i32, f32, i32, f32, u64, u32, vp]
         L.nbest_embed_ln_bwd.argtypes = [vp] * 15 + [i32, i32, i32, i32, i32, i64, i64, i32, i32, f32, u64, u32, vp, sz, vp]
@@ -320,7 +322,7 @@ def wgrad_pair(dY1, X1, dY2, X2, out1=None, out2=None, accumulate=False):
     return outs
 
 
-WGRAD_GROUP_PLAN, WGRAD_GROUP_NEVER, WGRAD_GROUP_ALWAYS = 0, 1, 2     # EncoderDesc.wgrad_group
+WGRAD_GROUP_PLAN, WGRAD_GROUP_NEVER, WGRAD_GROUP_ALWAYS, WGRAD_GROUP_WINDOW = 0, 1, 2, 3     # EncoderDesc.wgrad_group
 
 
 def wgrad_group(problems, outs=None, accumulate=False):
@@ -341,6 +343,46 @@ def wgrad_group(problems, outs=None, accumulate=False):
         res.append(out)
     check(lib().nbest_wgrad_group(gs, n, stream_ptr()), "wgrad_group")
     return res
+
+
+def wgrad_window(entries, outs=None, accumulate=False):
+    """one window of weight-gradient tiles (nbest_wgrad_window): entries = [(dY_i [K, M_i], X_i [K, N_i], tile_first, tile_count), ...],
+    1 .. 16 of them, at most 256 tiles in all; outs[i] [M_i, N_i] fp32 - only the tiles of the ranges are written (accumulate: added to)"""
+    n = len(entries)
+    gs = (GemmArgs * max(n, 1))()
+    first, count = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    res = []
+    for i, (dY, X, f, c) in enumerate(entries):
+        M, N = dY.shape[1], X.shape[1]
+        out = outs[i] if outs is not None else torch.empty(M, N, dtype=torch.float32, device=X.device)
+        g = gs[i]
+        g.A, g.B, g.C = dY.data_ptr(), X.data_ptr(), out.data_ptr()
+        g.M, g.N, g.K = M, N, X.shape[0]
+        g.lda, g.ldb, g.ldc = dY.stride(0), X.stride(0), out.stride(0)
+        g.trans_a = g.trans_b = 1
+        g.epilogue, g.dtype, g.accumulate = EPI_F32_SPLITK, dtype_code(X.dtype), int(accumulate)
+        first[i], count[i] = int(f), int(c)
+        res.append(out)
+    check(lib().nbest_wgrad_window(gs, first, count, n, stream_ptr()), "wgrad_window")
+    return res
+
+
+def encoder_wgrad_plan(desc, layer_begin, layer_end):
+    """the weight-gradient schedule of a backward call (nbest_encoder_wgrad_plan; host only): dict(mode, sets, peel_layer,
+    launches=[dict(after_layer, tiles, entries=[(layer, matrix, tile_first, tile_count), ...]), ...])"""
+    n = lib().nbest_encoder_wgrad_plan(C.byref(desc), layer_begin, layer_end, None, 0)
+    check(min(n, 0), "encoder_wgrad_plan")
+    buf = (C.c_int32 * n)()
+    check(min(lib().nbest_encoder_wgrad_plan(C.byref(desc), layer_begin, layer_end, buf, n), 0), "encoder_wgrad_plan")
+    v = list(buf)
+    plan = {"mode": v[0], "sets": v[1], "peel_layer": v[2], "launches": []}
+    at = 4
+    for _ in range(v[3]):
+        after, tiles, ne = v[at:at + 3]
+        at += 3
+        plan["launches"].append({"after_layer": after, "tiles": tiles, "entries": [tuple(v[at + 4 * i:at + 4 * i + 4]) for i in range(ne)]})
+        at += 4 * ne
+    return plan
 
 
 def rows_gather(table, rows, cap):

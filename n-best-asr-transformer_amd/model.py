@@ -187,8 +187,8 @@ class NBestSTCModel(nn.Module):
         self.cfg, self.labels, self.compute_dtype = cfg, labels, compute_dtype
         self.dropout = float(dropout)                  # --dropout: feature dropout of the STC heads
         self.device = torch.device(device)
-        # weight gradients of two layers in one launch without K-splits (nbest_encoder_desc.wgrad_group): the library's plan decides,
-        # never (every layer's split-K launches), or wherever the shapes allow
+        # weight gradients without K-splits (nbest_encoder_desc.wgrad_group, hipabi.WGRAD_GROUP_*): the library's plan decides, never (every
+        # layer's split-K launches), two layers per launch wherever the shapes allow, or rolling windows of 256 tiles across the layers
         self.wgrad_group = int(wgrad_group)
         self.arena = ParamArena(cfg, labels, self.device, compute_dtype)
         # "fp8w" (BASELINE configs[4]): forward GEMMs on the block-scaled fp8 MFMA from an e4m3 copy of the weights; the
