@@ -163,6 +163,34 @@ typedef struct nbest_gemm_args {
 #define NBEST_GEMM_DEFER_REDUCE 1
 size_t nbest_gemm_ws_bytes(const nbest_gemm_args* a);
 int nbest_gemm(const nbest_gemm_args* a, nbest_stream_t stream);
+/* What nbest_gemm would launch for an argument block, without launching it: the argument checks of nbest_gemm in its order (the same
+ * NBEST_ERR_* for the same block, nbest_last_error() set) and then the kernel the dispatcher resolves to.  Host arithmetic on the
+ * argument block only - no HIP call, nothing enqueued, no pointer dereferenced (pointers are tested for NULL and alignment, so any
+ * aligned non-NULL value serves) - it answers on a machine without a GPU.  The launch path switches on this same result, so a
+ * change of the shape heuristics shows here first; tests/test_gemm_plan_cpu.py pins the set the encoder's GEMMs reach.
+ *   generation       0: fp32 parity kernel (gemm_f32.hip), 1: 128 x 128 x 64 bf16 (gemm_bf16.hip), 2: the LDS-ring kernels (gemm_bf16_v2.hip)
+ *   bm, bn, bk       block tile; bk = the K extent of one stage
+ *   wave_rows/_cols  wave grid of a workgroup (64 x rows x cols threads; 0 x 0: generation 0, no MFMA wave grid)
+ *   stages           LDS stages of the operand ring
+ *   form             NBEST_GEMM_FORM_*: how the operands are stored (NN: trans_a = trans_b = 0, NT: trans_b only, TT: both; TN: fp32 only)
+ *   reg_epilogue     1: the epilogue runs on the accumulator registers, 0: restaged through LDS
+ *   splits, k_per_split  K-splits of NBEST_EPI_F32_SPLITK (1, K rounded up: none)
+ *   b_packed         1: the kernel reads B_packed instead of B
+ *   kernel_epilogue  the epilogue the kernel is instantiated with: `epilogue`, or 0x102 for BIAS_GELU with U = NULL                  */
+enum { NBEST_GEMM_FORM_NN = 0, NBEST_GEMM_FORM_NT = 1, NBEST_GEMM_FORM_TT = 2, NBEST_GEMM_FORM_TN = 3 };
+typedef struct nbest_gemm_plan_info {
+  int32_t generation;
+  int32_t bm, bn, bk;
+  int32_t wave_rows, wave_cols;
+  int32_t stages;
+  int32_t form;
+  int32_t reg_epilogue;
+  int32_t splits;
+  int64_t k_per_split;
+  int32_t b_packed;
+  int32_t kernel_epilogue;
+} nbest_gemm_plan_info;
+int nbest_gemm_plan(const nbest_gemm_args* a, nbest_gemm_plan_info* out);
 
 /* Two weight gradients dW = dY^T . X (bf16 operands, trans_a = trans_b = 1, NBEST_EPI_F32_SPLITK) that share the token dimension K
  * and the column count N, in ONE launch: the 256 x 256 output tiles of `b` are appended to those of `a`, every tile takes the same

@@ -295,7 +295,9 @@ __device__ __forceinline__ uint32_t gd_pack4(const float* g) {
 }
 __device__ __forceinline__ void gd_unpack4(uint32_t w, float* g) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) g[e] = fmaf((float)((w >> (8 * e)) & 255u), 0.005f, -0.13f);
+  // (q - 26) * 0.005f: the difference is exact, so q = 26 decodes to 0 and q = 226 to 1 (200 * 0.005f rounds to 1.0f) as the format
+  // promises.  The one-instruction form fmaf(q, 0.005f, -0.13f) gave 2.4e-9 for a dead unit: its gradient came out as acc * 2.4e-9, not 0.
+  for (int e = 0; e < 4; ++e) g[e] = ((float)((w >> (8 * e)) & 255u) - 26.f) * 0.005f;
 }
 
 // four floats -> four OCP e4m3 bytes (unit scale, saturating at +-448): operands of the fp8 forward GEMMs

@@ -85,6 +85,29 @@ extern "C" size_t nbest_gemm_ws_bytes(const nbest_gemm_args* a) {
   return w1 > w2 ? w1 : w2;
 }
 
+// The argument checks of nbest_gemm and the kernel it resolves to, without the launch: host arithmetic on the argument block only - no
+// HIP call, no pointer is dereferenced - so it answers on a machine without a GPU.  Every check is the one nbest_gemm runs, in its order.
+extern "C" int nbest_gemm_plan(const nbest_gemm_args* a, nbest_gemm_plan_info* out) {
+  NB_CHECK(out, NBEST_ERR_ARG, "gemm_plan: null output");
+  *out = nbest_gemm_plan_info{};
+  NB_CHECK(a && a->A && a->B && a->C, NBEST_ERR_ARG, "gemm: null pointer");
+  NB_CHECK(a->M > 0 && a->N > 0 && a->K > 0, NBEST_ERR_SHAPE, "gemm: bad shape %lld x %lld x %lld", (long long)a->M,
+           (long long)a->N, (long long)a->K);
+  if (a->dtype == NBEST_F32) {
+    if (int rc = check_epilogue_operands(a, 1, 1)) return rc;
+    if (int rc = nbest_gemm_f32_resolve(a, out)) return rc;
+    if (a->colsum_out && a->epilogue != NBEST_EPI_F32_SPLITK)
+      NB_CHECK(a->ws && a->ws_bytes >= nbest_rowred_ws_bytes(a->M, a->N), NBEST_ERR_WORKSPACE, "gemm(f32): column-sum workspace too small");
+    return NBEST_OK;
+  }
+  if (a->dtype == NBEST_BF16) {
+    if (int rc = check_bf16(a)) return rc;
+    return nbest_gemm_bf16_v2_wins(a) ? nbest_gemm_bf16_v2_resolve(a, out) : nbest_gemm_bf16_resolve(a, out);
+  }
+  nbest_set_error("gemm: bad dtype %d", a->dtype);
+  return NBEST_ERR_DTYPE;
+}
+
 extern "C" int nbest_gemm(const nbest_gemm_args* a, nbest_stream_t stream) {
   NB_CHECK(a && a->A && a->B && a->C, NBEST_ERR_ARG, "gemm: null pointer");
   NB_CHECK(a->M > 0 && a->N > 0 && a->K > 0, NBEST_ERR_SHAPE, "gemm: bad shape %lld x %lld x %lld", (long long)a->M,

@@ -332,22 +332,44 @@ size_t nbest_gemm_bf16_ws_bytes(const nbest_gemm_args* a) {
   return splits > 1 ? (size_t)splits * a->M * a->N * sizeof(float) : 0;
 }
 
-int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
+// The generation-1 kernel a problem runs on and every refusal that needs no device, resolved once for the launch (nbest_gemm_bf16)
+// and for nbest_gemm_plan.  Host arithmetic only.
+int nbest_gemm_bf16_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* o) {
   NB_CHECK(a->N % BN == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld must be a multiple of %d", (long long)a->N, BN);
   NB_CHECK(a->trans_a || a->K % BK == 0, NBEST_ERR_SHAPE, "gemm(bf16): K=%lld must be a multiple of %d", (long long)a->K, BK);
+  o->generation = 1;
+  o->bm = BM; o->bn = BN; o->bk = BK;
+  o->wave_rows = 2; o->wave_cols = 2; o->stages = 2;
+  o->form = a->trans_a ? NBEST_GEMM_FORM_TT : (a->trans_b ? NBEST_GEMM_FORM_NT : NBEST_GEMM_FORM_NN);
+  o->reg_epilogue = 0;   // fp32 restage through wave-private LDS
+  o->b_packed = 0;
+  int splits;
+  int64_t kps;
+  plan_splits(a, &splits, &kps);
+  o->splits = splits; o->k_per_split = kps;
+  const int epi = a->epilogue;
+  if (a->colsum_out && epi != NBEST_EPI_F32_SPLITK)
+    NB_CHECK(a->ws && a->ws_bytes >= nbest_gemm_bf16_ws_bytes(a), NBEST_ERR_WORKSPACE, "gemm: column-sum workspace too small");
+  if (epi == NBEST_EPI_F32_SPLITK && splits > 1)
+    NB_CHECK(a->ws && a->ws_bytes >= (size_t)splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
+             "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)splits * a->M * a->N * sizeof(float));
+  const int ke = o->kernel_epilogue = nb_kernel_epilogue(epi, a->U);
+  NB_CHECK((ke >= NBEST_EPI_NONE && ke <= NBEST_EPI_F32_SPLITK) || ke == kEpiBiasGeluNoU, NBEST_ERR_ARG, "gemm: bad epilogue %d", ke);
+  return NBEST_OK;
+}
+
+int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
+  nbest_gemm_plan_info v;
+  if (int rc = nbest_gemm_bf16_resolve(a, &v)) return rc;
   GemmP p;
   p.A = (const bf16*)a->A; p.B = (const bf16*)a->B; p.C = a->C; p.bias = a->bias; p.R = (const bf16*)a->R; p.U = (bf16*)a->U;
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldu = a->ldu;
   p.tiles_m = (int)((a->M + BM - 1) / BM);
   p.tiles_n = (int)(a->N / BN);
-  plan_splits(a, &p.splits, &p.k_per_split);
+  p.splits = v.splits; p.k_per_split = v.k_per_split;
   p.accumulate = a->accumulate;
   p.slab = (float*)a->ws;
-  p.colpart = nullptr;
-  if (a->colsum_out && a->epilogue != NBEST_EPI_F32_SPLITK) {
-    NB_CHECK(a->ws && a->ws_bytes >= nbest_gemm_bf16_ws_bytes(a), NBEST_ERR_WORKSPACE, "gemm: column-sum workspace too small");
-    p.colpart = (float*)a->ws;
-  }
+  p.colpart = (a->colsum_out && a->epilogue != NBEST_EPI_F32_SPLITK) ? (float*)a->ws : nullptr;   // size checked by the resolve
   const int64_t a_rows = a->trans_a ? a->K : a->M, a_cols = a->trans_a ? a->M : a->K;
   const int64_t b_rows = a->trans_b ? a->K : a->N, b_cols = a->trans_b ? a->N : a->K;
   const int64_t ab = ((a_rows - 1) * a->lda + a_cols) * 2, bb = ((b_rows - 1) * a->ldb + b_cols) * 2;
@@ -356,14 +378,11 @@ int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st) {
   p.stream_out = 1;   // every output is streamed (common.h st_stream)
   p.gn = (int)(a->N / BN);      // row-major tile order (column groups measured neutral to negative on the N = 768 shapes this kernel serves)
   const int epi = a->epilogue;
-  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
-    NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
-             "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
   const int grid = p.tiles_m * p.tiles_n * p.splits;
   int rc;
-  const int kepi = nb_kernel_epilogue(epi, a->U);
-  if (!a->trans_a && !a->trans_b) rc = launch_epi<false, false>(p, kepi, grid, st);
-  else if (!a->trans_a && a->trans_b) rc = launch_epi<false, true>(p, kepi, grid, st);
+  const int kepi = v.kernel_epilogue;
+  if (v.form == NBEST_GEMM_FORM_NN) rc = launch_epi<false, false>(p, kepi, grid, st);
+  else if (v.form == NBEST_GEMM_FORM_NT) rc = launch_epi<false, true>(p, kepi, grid, st);
   else rc = launch_epi<true, true>(p, kepi, grid, st);
   if (rc) return rc;
   if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * 2, (int)a->N, a->colsum_out, a->colsum_accumulate, st);

@@ -1137,37 +1137,98 @@ size_t nbest_gemm_bf16_v2_ws_bytes(const nbest_gemm_args* a) {
   return pl.splits > 1 ? (size_t)pl.splits * a->M * a->N * sizeof(float) : 0;
 }
 
-// `b2` (with `a` = the VIRTUAL problem of M1 + M2 output rows carrying the first problem's pointers, m_split = M1): the second
-// problem of a weight-gradient pair, see nbest_wgrad_pair_bf16
-static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int64_t m_split, hipStream_t st) {
+// Which instantiation of gemm2_kernel a problem runs on, and every refusal that needs no device: resolved HERE once, for the launch
+// (gemm_v2_impl switches on the result) and for nbest_gemm_plan (which reports it).  Host arithmetic only: no HIP call, no pointer
+// is dereferenced.
+int nbest_gemm_bf16_v2_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* o) {
   NB_CHECK(a->N % 64 == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld must be a multiple of 64", (long long)a->N);
   NB_CHECK(a->trans_a || a->K % BK == 0, NBEST_ERR_SHAPE, "gemm(bf16): K=%lld must be a multiple of %d", (long long)a->K, BK);
   const Plan pl = make_plan(a);
+  const int epi = a->epilogue;
+  o->generation = 2;
+  o->bm = pl.bm; o->bn = pl.bn; o->bk = BK;
+  o->form = a->trans_a ? NBEST_GEMM_FORM_TT : (a->trans_b ? NBEST_GEMM_FORM_NT : NBEST_GEMM_FORM_NN);
+  o->reg_epilogue = (!a->trans_a && !a->trans_b && epi != NBEST_EPI_F32_SPLITK) ? 1 : 0;   // gemm2_body kDirect
+  o->splits = pl.splits;
+  o->k_per_split = pl.kps;
+  o->kernel_epilogue = nb_kernel_epilogue(epi, a->U);   // the plan above was chosen on the public epilogue
+  o->b_packed = (a->B_packed && ((a->b_pack_bn == pl.bn && pl.bm == 256 && (pl.bn == 256 || pl.bn == 192)) || (pl.bm == 128 && pl.bn == 384 && a->b_pack_bn == 192) || (pl.bm == 128 && pl.bn == 512 && a->b_pack_bn == 256)) &&
+                 !a->trans_a && !a->trans_b &&
+                 epi != NBEST_EPI_F32_SPLITK && a->K % BK == 0 && a->N * a->K * 2 < ((int64_t)1 << 32) && ((uintptr_t)a->B_packed & 15) == 0) ? 1 : 0;
+  if (a->colsum_out && epi != NBEST_EPI_F32_SPLITK) {
+    NB_CHECK(epi == NBEST_EPI_DGELU || a->trans_a || a->trans_b, NBEST_ERR_ARG,
+             "gemm(bf16, generation 2): column sums are fused into the x GELU' epilogue only (nbest_gemm routes the others to generation 1)");
+    NB_CHECK(a->ws && a->ws_bytes >= nbest_gemm_bf16_v2_ws_bytes(a), NBEST_ERR_WORKSPACE, "gemm: column-sum workspace too small");
+  }
+  if (epi != NBEST_EPI_F32_SPLITK) {   // 32-bit byte offsets, also for the rows of a ragged last tile (dropped by the range check)
+    const int64_t mpad = a->M + 256;
+    NB_CHECK(mpad * a->ldc * 2 < ((int64_t)1 << 32) && mpad * a->ldr * 2 < ((int64_t)1 << 32) && mpad * a->ldu < ((int64_t)1 << 32),
+             NBEST_ERR_SHAPE, "gemm(bf16): output / residual larger than 4 GiB");
+  }
+  if (epi == NBEST_EPI_F32_SPLITK && pl.splits > 1)
+    NB_CHECK(a->ws && a->ws_bytes >= (size_t)pl.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
+             "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)pl.splits * a->M * a->N * sizeof(float));
+  NB_CHECK(a->N % pl.bn == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld is not a multiple of the %d-column tile", (long long)a->N, pl.bn);
+  // wave grid (rows x columns) and ring depth
+  if (pl.bm == 128 && pl.bn == 512) {
+    o->wave_rows = 2; o->wave_cols = 4; o->stages = 4;
+  } else if ((pl.bm == 128 && pl.bn == 384) || (pl.bm == 256 && pl.bn == 192)) {
+    // ring depth: the operand delivery of these kernels is bound by bytes in flight against the LDS-DMA latency (3 stages of 28-32 KB
+    // against ~2 us); a fifth stage (all 160 KB of LDS at 256 x 256) pays at long K - FFN-down forward 162 -> 155 us, FFN-up dgrad 157 ->
+    // 154, QKV dgrad 122 -> 120 - and costs 1-2 % at K = 768, where the longer prologue of each tile weighs more (same-call A/B, twice)
+    o->wave_rows = (pl.bm == 128) ? 2 : 4; o->wave_cols = (pl.bm == 128) ? 4 : 2;
+    o->stages = (a->K >= 2048) ? 5 : 4;
+  } else if (pl.bm == 256 && pl.bn == 256) {
+    // k-contiguous operands: 4 x 2 waves with 64 x 128 wave tiles (register epilogue: 16-byte stores, whole 128-byte lines)
+    if (o->reg_epilogue) { o->wave_rows = 4; o->wave_cols = 2; o->stages = (a->K >= 2048) ? 5 : 4; }
+    else { o->wave_rows = 2; o->wave_cols = 4; o->stages = 4; }
+    // make_plan gives 256 x 256 to k-contiguous problems and weight gradients only: there is no NT instantiation of this tile
+    NB_CHECK(o->form != NBEST_GEMM_FORM_NT, NBEST_ERR_SHAPE, "gemm(bf16, generation 2): no NT kernel for the 256 x 256 plan");
+  } else if (pl.bm == 256 && pl.bn == 128) {
+    NB_CHECK(o->form != NBEST_GEMM_FORM_TT, NBEST_ERR_SHAPE, "gemm(bf16, generation 2): no TT kernel for the 256 x 128 plan");
+    if (o->reg_epilogue) { o->wave_rows = 4; o->wave_cols = 1; } else { o->wave_rows = 2; o->wave_cols = 2; }
+    o->stages = 3;
+  } else {   // 128-row tiles narrower than 384 columns run on generation 1 (nbest_gemm_bf16_v2_wins)
+    nbest_set_error("gemm(bf16, generation 2): no kernel for the %d x %d plan", pl.bm, pl.bn);
+    return NBEST_ERR_SHAPE;
+  }
+  // epilogues each instantiation is built with (launch2)
+  const int ke = o->kernel_epilogue;
+  if (epi == NBEST_EPI_F32_SPLITK) {   // the fp32 split-K output goes through the LDS-restaged epilogue (64-column wave tiles)
+    NB_CHECK(o->bn / o->wave_cols == 64, NBEST_ERR_ARG, "gemm: bad epilogue %d", ke);
+  } else if (o->bn / o->wave_cols == 96) {   // 96-column wave tiles: no 8-bit GELU' rows
+    NB_CHECK(ke == NBEST_EPI_NONE || ke == NBEST_EPI_BIAS || ke == NBEST_EPI_BIAS_DROP_RES || ke == NBEST_EPI_RES, NBEST_ERR_ARG,
+             "gemm: epilogue %d is not built for 192-column tiles", ke);
+  } else {
+    NB_CHECK(ke == NBEST_EPI_NONE || ke == NBEST_EPI_BIAS || ke == NBEST_EPI_BIAS_GELU || ke == NBEST_EPI_BIAS_DROP_RES || ke == NBEST_EPI_DGELU ||
+             ke == NBEST_EPI_RES || ke == kEpiBiasGeluNoU, NBEST_ERR_ARG, "gemm: bad epilogue %d", ke);
+  }
+  return NBEST_OK;
+}
+
+// `b2` (with `a` = the VIRTUAL problem of M1 + M2 output rows carrying the first problem's pointers, m_split = M1): the second
+// problem of a weight-gradient pair, see nbest_wgrad_pair_bf16
+static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int64_t m_split, hipStream_t st) {
+  nbest_gemm_plan_info v;
+  if (int rc = nbest_gemm_bf16_v2_resolve(a, &v)) return rc;
   GemmP2 p;
   p.A = (const bf16*)a->A; p.B = (const bf16*)a->B; p.C = a->C; p.bias = a->bias; p.R = (const bf16*)a->R; p.U = (bf16*)a->U;
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldu = a->ldu;
-  p.tiles_m = (int)((a->M + pl.bm - 1) / pl.bm);
-  p.tiles_n = (int)(a->N / pl.bn);
-  p.splits = pl.splits;
-  p.k_per_split = pl.kps;
+  p.tiles_m = (int)((a->M + v.bm - 1) / v.bm);
+  p.tiles_n = (int)(a->N / v.bn);
+  p.splits = v.splits;
+  p.k_per_split = v.k_per_split;
   p.accumulate = a->accumulate;
   p.slab = (float*)a->ws;
   p.colpart = nullptr;
   p.A2 = p.B2 = nullptr; p.lda2 = p.ldb2 = p.m_split = 0; p.a2_bytes = p.b2_bytes = 0;
   p.Bp = nullptr; p.bp_bytes = 0; p.bp_bn = 0;
-  if (a->B_packed && ((a->b_pack_bn == pl.bn && pl.bm == 256 && (pl.bn == 256 || pl.bn == 192)) || (pl.bm == 128 && pl.bn == 384 && a->b_pack_bn == 192) || (pl.bm == 128 && pl.bn == 512 && a->b_pack_bn == 256)) &&
-      !a->trans_a && !a->trans_b &&
-      a->epilogue != NBEST_EPI_F32_SPLITK && a->K % BK == 0 && a->N * a->K * 2 < ((int64_t)1 << 32) && ((uintptr_t)a->B_packed & 15) == 0) {
+  if (v.b_packed) {
     p.Bp = (const bf16*)a->B_packed;
     p.bp_bytes = (uint32_t)(a->N * a->K * 2);
     p.bp_bn = a->b_pack_bn;
   }
-  if (a->colsum_out && a->epilogue != NBEST_EPI_F32_SPLITK) {
-    NB_CHECK(a->epilogue == NBEST_EPI_DGELU || a->trans_a || a->trans_b, NBEST_ERR_ARG,
-             "gemm(bf16, generation 2): column sums are fused into the x GELU' epilogue only (nbest_gemm routes the others to generation 1)");
-    NB_CHECK(a->ws && a->ws_bytes >= nbest_gemm_bf16_v2_ws_bytes(a), NBEST_ERR_WORKSPACE, "gemm: column-sum workspace too small");
-    p.colpart = (float*)a->ws;
-  }
+  if (a->colsum_out && a->epilogue != NBEST_EPI_F32_SPLITK) p.colpart = (float*)a->ws;   // checked by the resolve
   const int64_t a_rows = a->trans_a ? a->K : a->M, a_cols = a->trans_a ? (b2 ? m_split : a->M) : a->K;
   const int64_t b_rows = a->trans_b ? a->K : a->N, b_cols = a->trans_b ? a->N : a->K;
   const int64_t ab = ((a_rows - 1) * a->lda + a_cols) * 2, bb = ((b_rows - 1) * a->ldb + b_cols) * 2;
@@ -1176,71 +1237,59 @@ static int gemm_v2_impl(const nbest_gemm_args* a, const nbest_gemm_args* b2, int
     const int64_t ab2 = ((a->K - 1) * b2->lda + b2->M) * 2, bb2 = ((a->K - 1) * b2->ldb + a->N) * 2;
     p.A2 = (const bf16*)b2->A; p.B2 = (const bf16*)b2->B; p.lda2 = b2->lda; p.ldb2 = b2->ldb; p.m_split = m_split;
     p.a2_bytes = (uint32_t)ab2; p.b2_bytes = (uint32_t)bb2;
-    NB_CHECK(pl.bm == 256 && pl.bn == 256 && pl.splits > 1 && m_split % 256 == 0, NBEST_ERR_SHAPE, "wgrad pair: not a 256 x 256 split-K plan");
+    NB_CHECK(v.bm == 256 && v.bn == 256 && v.splits > 1 && m_split % 256 == 0, NBEST_ERR_SHAPE, "wgrad pair: not a 256 x 256 split-K plan");
   }
   p.c_bytes = p.r_bytes = p.u_bytes = 0;
-  if (a->epilogue != NBEST_EPI_F32_SPLITK) {   // 32-bit byte offsets, also for the rows of a ragged last tile (dropped by the range check)
-    const int64_t mpad = a->M + 256;
-    NB_CHECK(mpad * a->ldc * 2 < ((int64_t)1 << 32) && mpad * a->ldr * 2 < ((int64_t)1 << 32) && mpad * a->ldu < ((int64_t)1 << 32),
-             NBEST_ERR_SHAPE, "gemm(bf16): output / residual larger than 4 GiB");
+  if (a->epilogue != NBEST_EPI_F32_SPLITK) {   // extents of the M valid rows (below 4 GiB: checked by the resolve)
     p.c_bytes = (uint32_t)(a->M * a->ldc * 2);
     p.r_bytes = a->R ? (uint32_t)(a->M * a->ldr * 2) : 0;
     p.u_bytes = a->U ? (uint32_t)(a->M * a->ldu) : 0;
   }
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
   p.stream_out = 1;   // every output is streamed (common.h st_stream)
-  // B is a weight matrix (k-contiguous [N][K]) in the forward / dgrad GEMMs; the weight gradients have no small operand
   // B is a weight matrix (k-contiguous [N][K]) in the forward / dgrad GEMMs; the weight gradients have no small operand.
   // (Column groups re-read the ACTIVATION panel once per group: 490 MB of HBM-side traffic per launch for 277 MB of operands on the
   // N = 768 dgrads, profiles/r03_pmc.csv - the re-read panel was written by the previous kernel and comes out of the Infinity
   // Cache.  Same-box sweep of the five N = 768 launches of a layer: 606 / 584 / 578 us with 1 / 2 / 4 tile columns per group - one
   // column per group loses 4 %, two (the rule's choice at K >= 2304) and row-major tie.)
-  p.gn = (!a->trans_a && !a->trans_b) ? nb_group_cols(a->N / pl.bn, (int64_t)pl.bn * a->K * 2, 2400) : (int)(a->N / pl.bn);
+  p.gn = (!a->trans_a && !a->trans_b) ? nb_group_cols(a->N / v.bn, (int64_t)v.bn * a->K * 2, 2400) : (int)(a->N / v.bn);
   // 128 x 384 tiles: the two tile columns of an M row run back to back on one XCD, so the (cold) activation panel crosses the fabric once -
   // the weight panels of two columns (2 x 2.4 MB at K = 3072) exceed the 2 400 KB slice rule above, but the workgroups of an XCD walk K
   // in step and only a few stages of them are live at a time.  Same call: the five N = 768 GEMMs of a layer 587 / 600 -> 570 / 576 us cold,
   // the step 21.02 / 21.01 -> 20.86 / 20.85 ms.
-  if (pl.bm == 128 && pl.bn >= 384 && (a->N / pl.bn) % 2 == 0) p.gn = 2;
+  if (v.bm == 128 && v.bn >= 384 && (a->N / v.bn) % 2 == 0) p.gn = 2;
   const int epi = a->epilogue;
-  if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1)
-    NB_CHECK(a->ws && a->ws_bytes >= (size_t)p.splits * a->M * a->N * sizeof(float), NBEST_ERR_WORKSPACE,
-             "gemm: split-K workspace too small (%zu < %zu)", a->ws_bytes, (size_t)p.splits * a->M * a->N * sizeof(float));
   const int grid = p.tiles_m * p.tiles_n * p.splits;
-  const int kepi = nb_kernel_epilogue(epi, a->U);   // the plan above was chosen on the public epilogue
-  int rc, wave_rows = 2;   // wave rows per tile = partial rows of the fused column sums
-  NB_CHECK(a->N % pl.bn == 0, NBEST_ERR_SHAPE, "gemm(bf16): N=%lld is not a multiple of the %d-column tile", (long long)a->N, pl.bn);
-  if (pl.bm == 128 && pl.bn == 512) {
-    rc = launch2<128, 512, 2, 4, 4, false, false>(p, kepi, grid, st);
-  } else if (pl.bm == 128 && pl.bn == 384) {
-    if (a->K >= 2048) rc = launch2<128, 384, 2, 4, 5, false, false>(p, kepi, grid, st);
-    else rc = launch2<128, 384, 2, 4, 4, false, false>(p, kepi, grid, st);
-  } else if (pl.bm == 256 && pl.bn == 192) {
-    // ring depth: the operand delivery of these kernels is bound by bytes in flight against the LDS-DMA latency (3 stages of 28-32 KB
-    // against ~2 us); a fifth stage (all 160 KB of LDS at 256 x 256) pays at long K - FFN-down forward 162 -> 155 us, FFN-up dgrad 157 ->
-    // 154, QKV dgrad 122 -> 120 - and costs 1-2 % at K = 768, where the longer prologue of each tile weighs more (same-call A/B, twice)
-    if (a->K >= 2048) rc = launch2<256, 192, 4, 2, 5, false, false>(p, kepi, grid, st);
-    else rc = launch2<256, 192, 4, 2, 4, false, false>(p, kepi, grid, st);
-    wave_rows = 4;
-  } else if (pl.bm == 256 && pl.bn == 256) {
-    // k-contiguous operands: 4 x 2 waves with 64 x 128 wave tiles (register epilogue: 16-byte stores, whole 128-byte lines)
-    if (!a->trans_a && !a->trans_b && epi != NBEST_EPI_F32_SPLITK) {
-      if (a->K >= 2048) rc = launch2<256, 256, 4, 2, 5, false, false>(p, kepi, grid, st);
-      else rc = launch2<256, 256, 4, 2, 4, false, false>(p, kepi, grid, st);
-      wave_rows = 4;
-    }
-    else if (!a->trans_a && !a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, false>(p, kepi, grid, st);
-    else if (!a->trans_a && a->trans_b) rc = launch2<256, 256, 2, 4, 4, false, true>(p, kepi, grid, st);
-    else rc = launch2<256, 256, 2, 4, 4, true, true>(p, kepi, grid, st);
-  } else if (pl.bm == 256) {
-    if (!a->trans_b && epi != NBEST_EPI_F32_SPLITK) { rc = launch2<256, 128, 4, 1, 3, false, false>(p, kepi, grid, st); wave_rows = 4; }
-    else if (!a->trans_b) rc = launch2<256, 128, 2, 2, 3, false, false>(p, kepi, grid, st);
-    else rc = launch2<256, 128, 2, 2, 3, false, true>(p, kepi, grid, st);
-  } else {   // 128-row tiles narrower than 384 columns run on generation 1 (nbest_gemm_bf16_v2_wins)
-    nbest_set_error("gemm(bf16, generation 2): no kernel for the %d x %d plan", pl.bm, pl.bn);
+  const int kepi = v.kernel_epilogue;
+  const bool ta = v.form == NBEST_GEMM_FORM_TT, tb = v.form != NBEST_GEMM_FORM_NN;
+  int rc = NBEST_ERR_SHAPE;
+  bool found = false;
+  // every instantiation of gemm2_kernel the library holds: the resolve names one of them
+#define V2(BM_, BN_, WM_, WN_, ST_, TA_, TB_)                                                                                         \
+  if (!found && v.bm == BM_ && v.bn == BN_ && v.wave_rows == WM_ && v.wave_cols == WN_ && v.stages == ST_ && ta == TA_ && tb == TB_) { \
+    found = true;                                                                                                                     \
+    rc = launch2<BM_, BN_, WM_, WN_, ST_, TA_, TB_>(p, kepi, grid, st);                                                               \
+  }
+  V2(128, 512, 2, 4, 4, false, false)
+  V2(128, 384, 2, 4, 4, false, false)
+  V2(128, 384, 2, 4, 5, false, false)
+  V2(256, 192, 4, 2, 4, false, false)
+  V2(256, 192, 4, 2, 5, false, false)
+  V2(256, 256, 4, 2, 4, false, false)   // register epilogue
+  V2(256, 256, 4, 2, 5, false, false)
+  V2(256, 256, 2, 4, 4, false, false)   // NBEST_EPI_F32_SPLITK of k-contiguous operands (no caller in the project)
+  V2(256, 256, 2, 4, 4, true, true)     // weight gradients
+  V2(256, 128, 4, 1, 3, false, false)   // register epilogue
+  V2(256, 128, 2, 2, 3, false, false)   // NBEST_EPI_F32_SPLITK of k-contiguous operands (no caller in the project)
+  V2(256, 128, 2, 2, 3, false, true)
+#undef V2
+  if (!found) {
+    nbest_set_error("gemm(bf16, generation 2): the %d x %d plan names no built kernel", v.bm, v.bn);
     return NBEST_ERR_SHAPE;
   }
   if (rc) return rc;
-  if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * wave_rows, (int)a->N, a->colsum_out, a->colsum_accumulate, st);
+  // wave rows per tile = partial rows of the fused column sums
+  if (p.colpart) return nbest_internal_partial_rows_sum(p.colpart, p.tiles_m * v.wave_rows, (int)a->N, a->colsum_out, a->colsum_accumulate, st);
   if (epi == NBEST_EPI_F32_SPLITK && p.splits > 1 && !(a->flags & NBEST_GEMM_DEFER_REDUCE))
     return nbest_internal_splitk_reduce(p.slab, (float*)a->C, a->M, a->N, a->ldc, p.splits, a->accumulate, b2 ? (float*)b2->C : nullptr,
                                         b2 ? m_split : a->M, b2 ? b2->ldc : 0, st);

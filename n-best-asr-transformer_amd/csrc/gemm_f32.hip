@@ -100,7 +100,25 @@ static int launch_epi(const GemmF& p, int epi, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
+// what the fp32 parity path runs (generation 0) and its one refusal, for the launch and for nbest_gemm_plan; host arithmetic only
+int nbest_gemm_f32_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* o) {
+  o->generation = 0;
+  o->bm = TM; o->bn = TN; o->bk = TK;
+  o->wave_rows = 0; o->wave_cols = 0;   // no MFMA wave grid: 256 threads of 4 x 4 outputs
+  o->stages = 1;
+  o->form = a->trans_a ? (a->trans_b ? NBEST_GEMM_FORM_TT : NBEST_GEMM_FORM_TN) : (a->trans_b ? NBEST_GEMM_FORM_NT : NBEST_GEMM_FORM_NN);
+  o->reg_epilogue = 1;
+  o->splits = 1;
+  o->k_per_split = a->K;
+  o->b_packed = 0;
+  const int ke = o->kernel_epilogue = nb_kernel_epilogue(a->epilogue, a->U);
+  NB_CHECK((ke >= NBEST_EPI_NONE && ke <= NBEST_EPI_F32_SPLITK) || ke == kEpiBiasGeluNoU, NBEST_ERR_ARG, "gemm: bad epilogue %d", ke);
+  return NBEST_OK;
+}
+
 int nbest_gemm_f32(const nbest_gemm_args* a, hipStream_t st) {
+  nbest_gemm_plan_info v;
+  if (int rc = nbest_gemm_f32_resolve(a, &v)) return rc;
   GemmF p;
   p.A = (const float*)a->A; p.B = (const float*)a->B; p.C = (float*)a->C; p.bias = a->bias; p.R = (const float*)a->R;
   p.U = (float*)a->U;
@@ -108,9 +126,9 @@ int nbest_gemm_f32(const nbest_gemm_args* a, hipStream_t st) {
   p.accumulate = a->accumulate;
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
   dim3 grid((unsigned)((a->N + TN - 1) / TN), (unsigned)((a->M + TM - 1) / TM));
-  const int kepi = nb_kernel_epilogue(a->epilogue, a->U);
-  if (!a->trans_a && !a->trans_b) return launch_epi<false, false>(p, kepi, grid, st);
-  if (!a->trans_a && a->trans_b) return launch_epi<false, true>(p, kepi, grid, st);
-  if (a->trans_a && a->trans_b) return launch_epi<true, true>(p, kepi, grid, st);
+  const int kepi = v.kernel_epilogue;
+  if (v.form == NBEST_GEMM_FORM_NN) return launch_epi<false, false>(p, kepi, grid, st);
+  if (v.form == NBEST_GEMM_FORM_NT) return launch_epi<false, true>(p, kepi, grid, st);
+  if (v.form == NBEST_GEMM_FORM_TT) return launch_epi<true, true>(p, kepi, grid, st);
   return launch_epi<true, false>(p, kepi, grid, st);
 }

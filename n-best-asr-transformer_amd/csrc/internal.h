@@ -53,6 +53,11 @@ int nbest_internal_splitk_reduce(const float* slab, float* C, int64_t M, int64_t
 // ---- gemm_f32.hip, gemm_bf16.hip (generation 1), gemm_bf16_v2.hip (generation 2) ----------------
 // Called by the public entries of gemm.hip only, after their argument checks (for bf16: what every generation needs, including
 // the 4 GiB operand extent the kernels' byte offsets rely on); each generation checks its own tile constraints.
+// nbest_gemm_*_resolve: the kernel instantiation a checked problem runs on and the refusals that need no device (tile constraints, workspace
+// sizes, epilogues not built) - host arithmetic only; each generation's launch switches on it and nbest_gemm_plan reports it
+int nbest_gemm_f32_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* out);
+int nbest_gemm_bf16_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* out);
+int nbest_gemm_bf16_v2_resolve(const nbest_gemm_args* a, nbest_gemm_plan_info* out);
 int nbest_gemm_f32(const nbest_gemm_args* a, hipStream_t st);
 size_t nbest_gemm_bf16_ws_bytes(const nbest_gemm_args* a);
 int nbest_gemm_bf16(const nbest_gemm_args* a, hipStream_t st);

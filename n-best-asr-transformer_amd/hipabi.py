@@ -18,7 +18,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
-    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
+    "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
     "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step",
@@ -40,6 +40,13 @@ class GemmArgs(C.Structure):
                 ("accumulate", C.c_int32), ("drop_p", C.c_float), ("drop_stream", C.c_uint32), ("seed", C.c_uint64),
                 ("colsum_out", C.c_void_p), ("colsum_accumulate", C.c_int32), ("flags", C.c_int32),
                 ("B_packed", C.c_void_p), ("b_pack_bn", C.c_int32), ("pad_", C.c_int32)]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("generation", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32),
+                ("wave_rows", C.c_int32), ("wave_cols", C.c_int32), ("stages", C.c_int32), ("form", C.c_int32),
+                ("reg_epilogue", C.c_int32), ("splits", C.c_int32), ("k_per_split", C.c_int64),
+                ("b_packed", C.c_int32), ("kernel_epilogue", C.c_int32)]
 
 
 class GemmFp8Args(C.Structure):
@@ -116,6 +123,7 @@ def lib():
         L.nbest_heads_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.nbest_gemm_ws_bytes.argtypes = [C.POINTER(GemmArgs)]
         L.nbest_gemm.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
+        L.nbest_gemm_plan.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmPlanInfo)]
         L.nbest_wgrad_pair_ws_bytes.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs)]
         L.nbest_wgrad_pair.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_void_p]
         L.nbest_wgrad_group.argtypes = [C.POINTER(GemmArgs), C.c_int32, C.c_void_p]
@@ -267,10 +275,9 @@ def pack_weight_fp8(W8):
     return out, bn
 
 
-def gemm(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=None, R=None, U=None, out=None,
-         accumulate=False, drop_p=0.0, seed=0, drop_stream=0, colsum_out=None, defer_reduce=False, B_packed=None, b_pack_bn=0,
-         want_u=True):
-    """C[M,N] = epi(op(A) . op(B)); returns C (and U for EPI_BIAS_GELU; ``want_u=False``: C only, no GELU' rows written)."""
+def _gemm_args(A, B, M, N, K, trans_a, trans_b, epilogue, bias, R, U, out, accumulate, drop_p, seed, drop_stream, colsum_out,
+               defer_reduce, B_packed, b_pack_bn, want_u):
+    """the argument block of gemm / gemm_plan with its workspace: (GemmArgs, out, U, workspace)"""
     dt = dtype_code(A.dtype)
     dev = A.device
     if out is None:
@@ -295,8 +302,64 @@ def gemm(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=No
     nb = lib().nbest_gemm_ws_bytes(C.byref(g))
     ws = _ws(nb, dev)
     g.ws, g.ws_bytes = ws.data_ptr(), ws.numel()
+    return g, out, U, ws
+
+
+def gemm(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=None, R=None, U=None, out=None,
+         accumulate=False, drop_p=0.0, seed=0, drop_stream=0, colsum_out=None, defer_reduce=False, B_packed=None, b_pack_bn=0,
+         want_u=True):
+    """C[M,N] = epi(op(A) . op(B)); returns C (and U for EPI_BIAS_GELU; ``want_u=False``: C only, no GELU' rows written)."""
+    g, out, U, ws = _gemm_args(A, B, M, N, K, trans_a, trans_b, epilogue, bias, R, U, out, accumulate, drop_p, seed, drop_stream,
+                               colsum_out, defer_reduce, B_packed, b_pack_bn, want_u)
     check(lib().nbest_gemm(C.byref(g), stream_ptr()), "gemm")
     return (out, U) if epilogue == EPI_BIAS_GELU and want_u else out
+
+
+FORM_NN, FORM_NT, FORM_TT, FORM_TN = range(4)                    # include/nbest_hip.h NBEST_GEMM_FORM_*
+EPI_BIAS_GELU_NO_U = 0x102                                       # kernel_epilogue of EPI_BIAS_GELU with U = NULL
+
+
+def gemm_plan_args(g):
+    """nbest_gemm_plan on a filled GemmArgs: what nbest_gemm would launch (host only, nothing enqueued), as a dict of the
+    nbest_gemm_plan_info fields; an argument block nbest_gemm refuses raises with the same code"""
+    info = GemmPlanInfo()
+    check(lib().nbest_gemm_plan(C.byref(g), C.byref(info)), "gemm_plan")
+    return {name: int(getattr(info, name)) for name, _ in GemmPlanInfo._fields_}
+
+
+def gemm_plan(A, B, M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, bias=None, R=None, U=None, out=None,
+              accumulate=False, drop_p=0.0, seed=0, drop_stream=0, colsum_out=None, defer_reduce=False, B_packed=None, b_pack_bn=0,
+              want_u=True):
+    """the kernel ``gemm`` would launch for the same arguments (nbest_gemm_plan), as a dict; launches nothing"""
+    g, out, U, ws = _gemm_args(A, B, M, N, K, trans_a, trans_b, epilogue, bias, R, U, out, accumulate, drop_p, seed, drop_stream,
+                               colsum_out, defer_reduce, B_packed, b_pack_bn, want_u)
+    return gemm_plan_args(g)
+
+
+def gemm_plan_shape(M, N, K, trans_a=False, trans_b=False, epilogue=EPI_NONE, dtype=BF16, lda=None, ldb=None, ldc=None, ldr=None,
+                    ldu=None, with_u=True, colsum=False, packed_bn=0, accumulate=False):
+    """gemm_plan from a shape alone: the operands are stand-in addresses (the plan dereferences none), packed rows unless a leading
+    dimension is given, every operand the epilogue reads present, the workspace as large as nbest_gemm_ws_bytes asks"""
+    g = GemmArgs()
+    fake = 1 << 20
+    g.A, g.B, g.C = fake, fake, fake
+    g.M, g.N, g.K = M, N, K
+    g.lda = lda if lda is not None else (M if trans_a else K)
+    g.ldb = ldb if ldb is not None else (N if trans_b else K)
+    g.ldc = ldc if ldc is not None else N
+    g.trans_a, g.trans_b, g.epilogue, g.dtype, g.accumulate = int(trans_a), int(trans_b), epilogue, dtype, int(accumulate)
+    if epilogue in (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES):
+        g.bias = fake
+    if epilogue in (EPI_BIAS_DROP_RES, EPI_RES):
+        g.R, g.ldr = fake, (ldr if ldr is not None else N)
+    if epilogue == EPI_DGELU or (epilogue == EPI_BIAS_GELU and with_u):
+        g.U, g.ldu = fake, (ldu if ldu is not None else N)
+    if colsum:
+        g.colsum_out = fake
+    if packed_bn:
+        g.B_packed, g.b_pack_bn = fake, packed_bn
+    g.ws, g.ws_bytes = fake, max(int(lib().nbest_gemm_ws_bytes(C.byref(g))), 16)
+    return gemm_plan_args(g)
 
 
 def wgrad_pair(dY1, X1, dY2, X2, out1=None, out2=None, accumulate=False):

@@ -31,6 +31,7 @@ def test_library_exports_every_declared_symbol():
     lib.nbest_rowred_ws_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     assert lib.nbest_rowred_ws_bytes(32768, 768) > 0
     assert ctypes.sizeof(hipabi.TensorDesc) == 32 and ctypes.sizeof(hipabi.LayerOffsets) == 96
+    assert "nbest_gemm_plan" in declared and ctypes.sizeof(hipabi.GemmPlanInfo) == 56      # nbest_gemm_plan_info: 10 x int32, int64, 2 x int32
 
 
 def test_split_k_plans_are_pinned():
