@@ -537,17 +537,19 @@ def layernorm_fwd(x, gamma, beta, eps):
     return y, stats
 
 
-def layernorm_bwd(dy, x, stats, gamma, want_dbias=True, drop_p=0.0, seed=0, drop_stream=0):
+def layernorm_bwd(dy, x, stats, gamma, want_dbias=True, drop_p=0.0, seed=0, drop_stream=0, want_params=True):
+    """``want_params=False``: dx / dx_drop only (dgamma = dbeta = dbias = NULL, no workspace - the call of a no_param_grad backward);
+    the three sums come back as None"""
     M, H = x.shape
     dx = torch.empty_like(x)
     dxd = torch.empty_like(x) if drop_p > 0 else None
-    dg = torch.zeros(H, dtype=torch.float32, device=x.device)
-    db = torch.zeros_like(dg)
-    dbias = torch.zeros_like(dg) if want_dbias else None
-    ws = _ws(lib().nbest_rowred_ws_bytes(M, H), x.device)
+    dg = torch.zeros(H, dtype=torch.float32, device=x.device) if want_params else None
+    db = torch.zeros_like(dg) if want_params else None
+    dbias = torch.zeros_like(dg) if want_params and want_dbias else None
+    ws = _ws(lib().nbest_rowred_ws_bytes(M, H), x.device) if want_params else None
     check(lib().nbest_layernorm_bwd(ptr(dy), ptr(x), ptr(stats), ptr(gamma), ptr(dx), ptr(dxd), ptr(dg), ptr(db), ptr(dbias),
-                                    M, H, dtype_code(x.dtype), 0, drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr()),
-          "layernorm_bwd")
+                                    M, H, dtype_code(x.dtype), 0, drop_p, seed, drop_stream, ptr(ws), ws.numel() if ws is not None else 0,
+                                    stream_ptr()), "layernorm_bwd")
     return dx, dxd, dg, db, dbias
 
 
@@ -644,15 +646,17 @@ def encoder_infer(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, cls_attn
     return cls_out
 
 
-def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, dbias=None, keep=None):
+def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, dbias=None, keep=None,
+                  accumulate=False):
+    """``dbias`` (fp32 [3H]): receives the column sums of dqkv - overwritten, or added to with ``accumulate``"""
     dqkv = torch.empty_like(qkv)
     ws = _ws(lib().nbest_attention_bwd_ws_bytes(B, S, heads), qkv.device) if dbias is not None else None
     if keep is not None:
-        check(lib().nbest_attention_bwd_keep(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dbias), 0, ptr(ws),
-                                             ws.numel() if ws is not None else 0, B, S, heads, 64, dtype_code(qkv.dtype), drop_p, seed,
-                                             drop_stream, ptr(keep), stream_ptr()), "attention_bwd_keep")
+        check(lib().nbest_attention_bwd_keep(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dbias), int(accumulate),
+                                             ptr(ws), ws.numel() if ws is not None else 0, B, S, heads, 64, dtype_code(qkv.dtype), drop_p,
+                                             seed, drop_stream, ptr(keep), stream_ptr()), "attention_bwd_keep")
         return dqkv
-    check(lib().nbest_attention_bwd(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dbias), 0, ptr(ws),
+    check(lib().nbest_attention_bwd(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dbias), int(accumulate), ptr(ws),
                                     ws.numel() if ws is not None else 0, B, S, heads, 64, dtype_code(qkv.dtype), drop_p, seed,
                                     drop_stream, stream_ptr()), "attention_bwd")
     return dqkv
