@@ -501,6 +501,20 @@ int nbest_adam_update(int mode, float* p, const float* g, float* m, float* v, vo
 int nbest_adam_step(int mode, float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                     int n_tensors, int n_blocks, float lr_mult, float bc1, float bc2_sqrt, double b1, double b2, float eps,
                     float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
+ * K9e  exponential moving average of the weights (--ema_decay; new functionality, the reference has none) over the same arenas and
+ * descriptor tables, one launch per table, n_blocks workgroups, no workspace, bit-reproducible.
+ * nbest_ema_update: for every element of every ACTIVE tensor ema = fma(one_minus_decay, p - ema, ema); inactive tensors and the
+ *   elements between tensors are never written; an element whose result compares equal to its old value keeps its bits, so
+ *   one_minus_decay == 0 and ema == p leave it bit-identical.  12 B per parameter (8 read, 4 written).
+ * nbest_ema_exchange: swaps p and ema element by element, in place, for EVERY tensor of the table whatever its `active`; if
+ *   p_lowp != NULL the new p is also written as bf16 at the same element offsets (the conversion of the optimizer kernels).  A
+ *   pure move: two calls restore every bit of p and ema.  16 (+ 2) B per parameter.
+ * A NULL p / ema / descs, n_tensors <= 0 or n_blocks <= 0: NBEST_ERR_ARG, nothing enqueued.                                       */
+int nbest_ema_update(float* ema, const float* p, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
+                     float one_minus_decay, nbest_stream_t stream);
+int nbest_ema_exchange(float* p, float* ema, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
+                       nbest_stream_t stream);
 /* Transposed bf16 copy of the weight matrices (same element offsets in `dst` as in `src`): matrix t is
  * [rows][cols] in src and [cols][rows] in dst.  The backward's dgrad GEMMs read this copy so that both of
  * their operands are k-contiguous (no transposed LDS reads).  descs: DEVICE array ordered by tile_start,

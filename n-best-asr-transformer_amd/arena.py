@@ -2,8 +2,8 @@
 
 All parameters of the model (encoder + STC heads, 109.6 M for bert-base) live in ONE contiguous fp32
 buffer ``p`` (the master copy); gradients ``g`` and the BertAdam moments ``m``/``v`` are buffers of the
-same layout, and the bf16 *compute copy* ``w16`` read by the MFMA GEMMs mirrors it at the same element
-offsets.  Consequences:
+same layout (as is the optional weight average ``ema``), and the bf16 *compute copy* ``w16`` read by the MFMA GEMMs
+mirrors it at the same element offsets.  Consequences:
 
 * the HIP encoder takes two base pointers plus a per-layer offset table (no per-tensor marshalling);
 * the fused Q|K|V weight [3H,H] is simply the three HF tensors placed back to back, so HuggingFace
@@ -103,6 +103,7 @@ class ParamArena:
         self.g = torch.zeros(self.total, **f32)
         self.m = None
         self.v = None
+        self.ema = None             # fp32 weight average in the layout of p: allocated by an optimizer built with ema_decay (optim.py)
         self.w16 = torch.zeros(self.total, dtype=torch.bfloat16, device=self.device) if compute_dtype == torch.bfloat16 else None
         # transposed bf16 copy of the per-layer weight matrices (same offsets): the dgrad GEMMs read it so both of
         # their operands are k-contiguous.  Only allocated on a GPU (the kernel that fills it is HIP).

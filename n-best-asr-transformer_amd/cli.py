@@ -16,6 +16,7 @@ local WordPiece vocabulary (``--vocab``; default: the words of memory.pt).  Addi
 --label_space, --synthetic.  Under torchrun the minibatch is sharded over the ranks (RCCL gradient all-reduce).
 """
 import argparse
+import contextlib
 import json
 import os
 import random
@@ -143,7 +144,21 @@ def parse_arguments(argv=None):
                    help="run --optim_choice adamw.  The reference's AdamW (transformers.optimization.AdamW, correct_bias=False) is "
                         "not in current transformers releases, so its branch cannot run there; this build restates the update rule "
                         "(DESIGN.md, kernel K9b) and checks it against that restatement, not against the reference's own code")
+    g.add_argument("--ema_decay", type=float, default=None, metavar="D",
+                   help="keep an exponential moving average of the weights on the device (0 <= D < 1; decay warmed up as "
+                        "min(D, (1 + t) / (10 + t)) over the optimizer steps t): every epoch's valid / test evaluation and model.pt use "
+                        "the averaged weights, training goes on with the raw ones; last.pt keeps the raw weights and, in the optimizer "
+                        "state, the average.  A training flag: --testing / --predict / --head_importance read model.pt, which already "
+                        "holds the averaged weights.  Not with --shard_optimizer on")
     opt = ap.parse_args(argv)
+    if opt.ema_decay is not None:
+        if not 0.0 <= opt.ema_decay < 1.0:
+            ap.error("--ema_decay %s: must be in [0, 1)" % opt.ema_decay)
+        if opt.shard_optimizer == "on":
+            ap.error("--ema_decay is not built for --shard_optimizer on (the fp32 master is current only on each range's owner)")
+        if opt.testing or opt.predict is not None or opt.head_importance is not None:
+            ap.error("--ema_decay is a training flag: --testing, --predict and --head_importance read model.pt, which already holds "
+                     "the averaged weights of a run that used it")
     if opt.optim_choice == "adamw" and not opt.restated_adamw:
         ap.error("--optim_choice adamw: the reference's AdamW is not in current transformers releases, so the reference cannot run "
                  "it; this build's restatement of its update rule runs when --restated_adamw is passed too")
@@ -199,6 +214,8 @@ def exp_dir(opt):
              "cls_%s" % opt.cls_type]
     if getattr(opt, "freeze_embeddings", False) or getattr(opt, "freeze_layers", 0):     # only then: existing names stay as they are
         parts.append("fz_%s_%s" % ("emb" if opt.freeze_embeddings else "none", opt.freeze_layers))
+    if getattr(opt, "ema_decay", None) is not None:                                      # the same rule
+        parts.append("ema_%s" % opt.ema_decay)
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -377,14 +394,16 @@ def main(argv=None):
     t_total = (len(train) // opt.batchSize + 1) * opt.max_epoch            # n_best_asr_bert.py:556
     if opt.optim_choice == "bertadam":
         opt.optimizer = HipBertAdam(model, lr=opt.lr, bert_lr=opt.bert_lr, warmup=opt.warmup_proportion, t_total=t_total,
-                                    shard=opt.shard_optimizer == "on")
+                                    shard=opt.shard_optimizer == "on", ema_decay=opt.ema_decay)
     else:                                                                   # n_best_asr_bert.py:551-569
         opt.optimizer = HipAdam(model, kind=opt.optim_choice, lr=opt.lr, bert_lr=opt.bert_lr, l2=opt.l2, warmup=opt.warmup_proportion,
-                                t_total=t_total, max_grad_norm=opt.max_norm, shard=opt.shard_optimizer == "on")
+                                t_total=t_total, max_grad_norm=opt.max_norm, shard=opt.shard_optimizer == "on", ema_decay=opt.ema_decay)
     opt.scheduler = getattr(opt.optimizer, "scheduler", None)
     log = _Log(os.path.join(opt.exp_dir, "log.train"), rank, append=opt.resume and os.path.exists(os.path.join(opt.exp_dir, "last.pt")))
     t_start = time.time()
     log.info("Training starts at %s" % time.asctime(time.localtime(t_start)))
+    if opt.ema_decay is not None:
+        log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)
     first_epoch, last = 0, os.path.join(opt.exp_dir, "last.pt")
     if opt.resume and os.path.exists(last):
@@ -401,32 +420,34 @@ def main(argv=None):
         t0 = time.time()
         loss, (p, r, f), acc = trainer.train_epoch(model, train, opt, memory, epoch=ep)
         log.info("[Train]\tEpoch: %02d\tTime: %.2f\tLoss: %.2f\t(p/r/f): (%.2f/%.2f/%.2f)\tAcc: %.2f" % (ep, time.time() - t0, loss, p, r, f, acc))
-        res = {}
-        for name, data in (("valid", valid), ("test", test)):
-            if data is None:
-                continue
-            fn = os.path.join(opt.exp_dir, "%s.iter%d" % (name, ep))
-            with (open(fn, "w") if rank == 0 else open(os.devnull, "w")) as fp, \
-                    (open(fn + ".err", "w") if rank == 0 else open(os.devnull, "w")) as efp:
-                t0 = time.time()
-                loss, (p, r, f), acc, cases = trainer.eval_epoch(model, data, opt, memory, fp, efp)
-            log.info("[%s]\tEpoch: %02d\tTime: %.2f\tLoss: %.2f\t(p/r/f): (%.2f/%.2f/%.2f)\tAcc: %.2f" % (
-                name.capitalize(), ep, time.time() - t0, loss, p, r, f, acc))
-            if rank == 0:                                                           # n_best_asr_bert.py:416,426
-                observe.observability_lens(observe.EpochInfoCollector.from_cases(cases, loss, (p, r, f), acc), ep, name,
-                                           opt.exp_dir, "tod_asr_bert_stc")
-            res[name] = (f, acc)
-        vf, v_acc = res.get("valid", (0.0, 0.0))
-        tef, te_acc = res.get("test", (0.0, 0.0))
-        if vf > best["vf"]:
-            best.update(epoch=ep, vf=vf, tef=tef, v_acc=v_acc, te_acc=te_acc)
-            # sharded optimizer: the fp32 master is current only on each range's owner.  gather_master is a sequence of
-            # collectives: EVERY rank runs it (vf is the all-reduced F1, so every rank takes this branch together); only
-            # the file write is rank 0's
-            opt.optimizer.gather_master(moments=False)
-            if rank == 0:
-                model.save_model(os.path.join(opt.exp_dir, "model.pt"))
-            log.info("NEW BEST:\tEpoch: %02d\tvalid F1/Acc: %.2f/%.2f\ttest F1/Acc: %.2f/%.2f" % (ep, vf, v_acc, tef, te_acc))
+        # --ema_decay: the evaluations and the model.pt write run on the averaged weights; the raw ones are back afterwards
+        with (opt.optimizer.ema_weights() if opt.ema_decay is not None else contextlib.nullcontext()):
+            res = {}
+            for name, data in (("valid", valid), ("test", test)):
+                if data is None:
+                    continue
+                fn = os.path.join(opt.exp_dir, "%s.iter%d" % (name, ep))
+                with (open(fn, "w") if rank == 0 else open(os.devnull, "w")) as fp, \
+                        (open(fn + ".err", "w") if rank == 0 else open(os.devnull, "w")) as efp:
+                    t0 = time.time()
+                    loss, (p, r, f), acc, cases = trainer.eval_epoch(model, data, opt, memory, fp, efp)
+                log.info("[%s]\tEpoch: %02d\tTime: %.2f\tLoss: %.2f\t(p/r/f): (%.2f/%.2f/%.2f)\tAcc: %.2f" % (
+                    name.capitalize(), ep, time.time() - t0, loss, p, r, f, acc))
+                if rank == 0:                                                           # n_best_asr_bert.py:416,426
+                    observe.observability_lens(observe.EpochInfoCollector.from_cases(cases, loss, (p, r, f), acc), ep, name,
+                                               opt.exp_dir, "tod_asr_bert_stc")
+                res[name] = (f, acc)
+            vf, v_acc = res.get("valid", (0.0, 0.0))
+            tef, te_acc = res.get("test", (0.0, 0.0))
+            if vf > best["vf"]:
+                best.update(epoch=ep, vf=vf, tef=tef, v_acc=v_acc, te_acc=te_acc)
+                # sharded optimizer: the fp32 master is current only on each range's owner.  gather_master is a sequence of
+                # collectives: EVERY rank runs it (vf is the all-reduced F1, so every rank takes this branch together); only
+                # the file write is rank 0's
+                opt.optimizer.gather_master(moments=False)
+                if rank == 0:
+                    model.save_model(os.path.join(opt.exp_dir, "model.pt"))
+                log.info("NEW BEST:\tEpoch: %02d\tvalid F1/Acc: %.2f/%.2f\ttest F1/Acc: %.2f/%.2f" % (ep, vf, v_acc, tef, te_acc))
         if opt.resume:
             opt.optimizer.gather_master()           # all ranks (collectives); master and moments are whole everywhere afterwards
             if rank == 0:                           # ... so the state dicts are built AFTER the gather, on rank 0 only

@@ -205,6 +205,65 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// ---- K9e weight EMA (--ema_decay): the block -> (tensor, chunk) map and float4 path of bertadam_kernel, no LDS, no atomics --------
+// ema += w (p - ema) as ONE explicit fma (no contraction choice left to the compiler).  Where the result compares equal to the old
+// value the old bits are kept: w == 0 and ema == p then leave the arena bit-identical, a -0.0 included (fma(w, +0, -0) is +0).
+__device__ __forceinline__ float ema1(float e, float p, float w) {
+  const float r = fmaf(w, p - e, e);
+  return r == e ? e : r;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p,
+                                                         const nbest_tensor_desc* __restrict__ descs, int n_tensors, float w) {
+  const int blk = blockIdx.x;
+  const int t = find_tensor(descs, n_tensors, blk);
+  const nbest_tensor_desc d = descs[t];
+  if (!d.active) return;
+  const int64_t c0 = (int64_t)(blk - d.block_start) * kChunk;
+  const int64_t c1 = (c0 + kChunk < d.numel) ? c0 + kChunk : d.numel;
+  const int64_t base = d.offset;
+  int64_t v1 = c0;
+  if ((base & 3) == 0) {
+    v1 = c0 + ((c1 - c0) & ~(int64_t)3);
+    for (int64_t i = c0 + 4 * threadIdx.x; i < v1; i += 1024) {
+      f32x4 ee = *(f32x4*)(ema + base + i);
+      const f32x4 pp = *(const f32x4*)(p + base + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ee[e] = ema1(ee[e], pp[e], w);
+      *(f32x4*)(ema + base + i) = ee;
+    }
+  }
+  for (int64_t i = v1 + threadIdx.x; i < c1; i += 256) ema[base + i] = ema1(ema[base + i], p[base + i], w);
+}
+
+// p <-> ema in place for EVERY tensor of the table, active or not (a tensor frozen after it trained has an average of its own);
+// plow: bf16 of the new p, the conversion of the optimizer kernels' compute copy.  A pure move: two calls restore every bit.
+__global__ __launch_bounds__(256) void ema_exchange_kernel(float* __restrict__ p, float* __restrict__ ema, bf16* __restrict__ plow,
+                                                           const nbest_tensor_desc* __restrict__ descs, int n_tensors) {
+  const int blk = blockIdx.x;
+  const int t = find_tensor(descs, n_tensors, blk);
+  const nbest_tensor_desc d = descs[t];
+  const int64_t c0 = (int64_t)(blk - d.block_start) * kChunk;
+  const int64_t c1 = (c0 + kChunk < d.numel) ? c0 + kChunk : d.numel;
+  const int64_t base = d.offset;
+  int64_t v1 = c0;
+  if ((base & 3) == 0) {
+    v1 = c0 + ((c1 - c0) & ~(int64_t)3);
+    for (int64_t i = c0 + 4 * threadIdx.x; i < v1; i += 1024) {
+      const f32x4 pp = *(f32x4*)(p + base + i), ee = *(f32x4*)(ema + base + i);
+      *(f32x4*)(p + base + i) = ee;
+      *(f32x4*)(ema + base + i) = pp;
+      if (plow) Vec4<bf16>::store(plow + base + i, ee);
+    }
+  }
+  for (int64_t i = v1 + threadIdx.x; i < c1; i += 256) {
+    const float pp = p[base + i], ee = ema[base + i];
+    p[base + i] = ee;
+    ema[base + i] = pp;
+    if (plow) plow[base + i] = (bf16)ee;
+  }
+}
+
 // bf16 [rows][cols] -> [cols][rows] for a table of matrices living at the same element offsets in two
 // arenas (the k-contiguous weight copy the dgrad GEMMs read).  One launch: block -> (matrix, 64x64 tile).
 __global__ __launch_bounds__(256) void transpose_multi_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
@@ -327,4 +386,21 @@ extern "C" int nbest_adam_step(int mode, float* p, float* g, float* m, float* v,
   if (int rc = nbest_adam_clip_coef(partial, n_blocks, max_grad_norm, clip, stream)) return rc;
   return nbest_adam_update(mode, p, g, m, v, p_lowp, descs, n_tensors, n_blocks, 0, n_blocks, clip, lr_mult, bc1, bc2_sqrt, b1, b2, eps,
                            stream);
+}
+
+// ---- weight EMA: one launch per descriptor table, n_blocks workgroups (the table's own block count) ----------------------------
+extern "C" int nbest_ema_update(float* ema, const float* p, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
+                                float one_minus_decay, nbest_stream_t stream) {
+  NB_CHECK(ema && p && descs && n_tensors > 0 && n_blocks > 0, NBEST_ERR_ARG, "ema_update: bad arguments");
+  ema_update_kernel<<<n_blocks, 256, 0, (hipStream_t)stream>>>(ema, p, descs, n_tensors, one_minus_decay);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" int nbest_ema_exchange(float* p, float* ema, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
+                                  nbest_stream_t stream) {
+  NB_CHECK(p && ema && descs && n_tensors > 0 && n_blocks > 0, NBEST_ERR_ARG, "ema_exchange: bad arguments");
+  ema_exchange_kernel<<<n_blocks, 256, 0, (hipStream_t)stream>>>(p, ema, (bf16*)p_lowp, descs, n_tensors);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
 }

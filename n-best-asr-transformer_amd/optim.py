@@ -6,6 +6,8 @@ Interface and semantics of /root/reference/models/optimization.py:183-302 as dri
 L2 norm 1.0, no bias correction, eps 1e-6, ``warmup_linear`` schedule evaluated at the step count
 BEFORE the increment.
 """
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -21,6 +23,12 @@ def warmup_linear(step, t_total, warmup):
     if x < warmup:
         return x / warmup
     return max((x - 1.0) / (warmup - 1.0), 0.0)
+
+
+def ema_decay_at(t, decay):
+    """decay of the weight average at optimizer step ``t`` (1-based: the step being taken): the usual warm-up
+    min(decay, (1 + t) / (10 + t)), so that a short run's average is not dominated by the initial weights"""
+    return min(float(decay), (1.0 + t) / (10.0 + t))
 
 
 class HipBertAdam:
@@ -39,9 +47,26 @@ class HipBertAdam:
         the all-reduce: 0.75 x.  With fp32 compute (the parity path) the fp32 range itself is broadcast.
     A rank's fp32 master and moments are then current only inside its own range: ``gather_master()`` (called by ``state_dict`` and
     before a checkpoint is written) re-assembles them everywhere.  Not combined with the fp8 mode (the e4m3 weight copies are
-    quantised from the full fp32 master after every step): ``shard`` is ignored there."""
+    quantised from the full fp32 master after every step): ``shard`` is ignored there.
 
-    def __init__(self, model, lr, bert_lr=None, warmup=-1, t_total=-1, b1=0.9, b2=0.999, e=1e-6, max_grad_norm=1.0, shard=False):
+    ``ema_decay`` (new functionality; None: nothing allocated, nothing launched): ``arena.ema``, an fp32 arena of the layout of ``p``
+    that starts as its clone, follows the trainable tensors as ema += (1 - d_t) (p - ema), d_t = ema_decay_at(t, ema_decay), by one
+    nbest_ema_update per descriptor table right after that table's update (under data parallelism the main table's runs under the
+    embedding exchange, like its update; the replicas compute the same bits).  A frozen tensor is skipped: its average is its
+    value.  ``ema_weights()`` swaps the average in for an evaluation or a checkpoint.  Not built for the sharded optimizer (the
+    master is current only on each range's owner: the kernel would need an owner-range form and every evaluation a gather):
+    ``shard`` together with ``ema_decay`` raises."""
+
+    def __init__(self, model, lr, bert_lr=None, warmup=-1, t_total=-1, b1=0.9, b2=0.999, e=1e-6, max_grad_norm=1.0, shard=False,
+                 ema_decay=None):
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:
+                raise ValueError("ema_decay must be in [0, 1), not %r" % (ema_decay,))
+            if shard:
+                raise ValueError("ema_decay is not built for the sharded optimizer (shard=True): the fp32 master is current only on "
+                                 "each range's owner")
+        self.ema_decay, self._in_ema = ema_decay, False
         self.model, self.arena = model, model.arena
         self.lr, self.bert_lr = lr, lr if bert_lr is None else bert_lr
         self.warmup, self.t_total = max(warmup, 0.0), t_total
@@ -73,6 +98,78 @@ class HipBertAdam:
         self.owner_ranges = None
         if self.sharded:
             self._plan_shards()
+        if self.ema_decay is not None:
+            self.reset_ema()
+
+    # ---- weight average ------------------------------------------------------------------------------------------------------
+    def reset_ema(self):
+        """start the average over from the current weights (for a caller who loads weights after building the optimizer)"""
+        if self.ema_decay is None:
+            raise RuntimeError("reset_ema: the optimizer was built without ema_decay")
+        if self._in_ema:
+            raise RuntimeError("reset_ema inside ema_weights(): the arenas are exchanged")
+        self.arena.ema = self.arena.p.clone()
+
+    def _ema_update(self, part):
+        """ema += (1 - d_t) (p - ema) over the active tensors of one descriptor table, t = the step being taken"""
+        descs, n_t, n_b, _ = self.parts[part]
+        if self.ema_decay is None or n_t == 0:
+            return
+        a = self.arena
+        w = 1.0 - ema_decay_at(self.step_count + 1, self.ema_decay)
+        hb.check(hb.lib().nbest_ema_update(hb.ptr(a.ema), hb.ptr(a.p), hb.ptr(descs), n_t, n_b, w, hb.stream_ptr()), "ema_update")
+
+    def _ema_exchange(self):
+        a = self.arena
+        for descs, n_t, n_b, _ in self.parts:
+            if n_t:
+                hb.check(hb.lib().nbest_ema_exchange(hb.ptr(a.p), hb.ptr(a.ema), hb.ptr(a.w16), hb.ptr(descs), n_t, n_b, hb.stream_ptr()),
+                         "ema_exchange")
+        a.refresh_transposed()          # the derived images an optimizer step refreshes: transposed / packed (or lazily), e4m3
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` - the model computes with (and ``state_dict()`` / ``save_model`` hold) the averaged
+        weights: p and ema are exchanged in place (nbest_ema_exchange, no temporary arena), the bf16 copy is rewritten and the
+        derived weight images refreshed as after an optimizer step; the exit exchanges them back, to the bit.  No optimizer step
+        inside, no nesting.  The fp8 amax histories are left as they are."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weights: the optimizer was built without ema_decay")
+        if self._in_ema:
+            raise RuntimeError("ema_weights() is already entered: it does not nest")
+        self._ema_exchange()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._ema_exchange()
+
+    def _refuse_step_in_ema(self):
+        if self._in_ema:
+            raise RuntimeError("optimizer step inside ema_weights(): the model holds the averaged weights")
+
+    def _ema_state(self):
+        """the state_dict entries of the average ({} without one)"""
+        if self.ema_decay is None:
+            return {}
+        if self._in_ema:
+            raise RuntimeError("state_dict inside ema_weights(): the arenas are exchanged; take it outside")
+        a = self.arena
+        return dict(ema={s.name: a.view(a.ema, s.name).detach().cpu().clone() for s in a.slots}, ema_decay=self.ema_decay)
+
+    def _load_ema_state(self, sd, into):
+        """``into``: how this optimizer is named in the kind-mismatch message"""
+        has = sd.get("ema") is not None
+        if has != (self.ema_decay is not None):
+            raise ValueError("optimizer state %s a weight average cannot be loaded into %s %s one (--ema_decay must match the run "
+                             "that wrote it)" % ("with" if has else "without", into, "without" if has else "with"))
+        if has:
+            if self._in_ema:
+                raise RuntimeError("load_state_dict inside ema_weights(): the arenas are exchanged")
+            a = self.arena
+            for s in a.slots:
+                a.view(a.ema, s.name).copy_(sd["ema"][s.name])
 
     # ---- sharding plan (identical on every rank: pure geometry) -------------------------------------------------------------
     def _plan_shards(self):
@@ -206,12 +303,16 @@ class HipBertAdam:
 
     def step_main(self):
         """every tensor except the embedding tables (+ the k-contiguous weight copy the next forward / dgrad reads)"""
+        self._refuse_step_in_ema()
         self.sync_frozen()
         self._launch(0)
+        self._ema_update(0)
         self.arena.refresh_transposed()
 
     def step_embeddings(self):
+        self._refuse_step_in_ema()
         self._launch(1)
+        self._ema_update(1)
         self.step_count += 1
 
     def step(self):
@@ -228,12 +329,13 @@ class HipBertAdam:
         a = self.arena
         return dict(step=self.step_count, t_total=self.t_total, warmup=self.warmup,
                     state={s.name: dict(next_m=a.view(a.m, s.name).detach().cpu().clone(),
-                                        next_v=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots})
+                                        next_v=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots}, **self._ema_state())
 
     def load_state_dict(self, sd):
         if sd.get("kind", "bertadam") != "bertadam":
             raise ValueError("optimizer state of kind %r cannot be loaded into BertAdam (--optim_choice must match the run that "
                              "wrote it)" % sd["kind"])
+        self._load_ema_state(sd, "BertAdam")
         a = self.arena
         self.step_count = int(sd["step"])
         for s in a.slots:
@@ -286,14 +388,14 @@ class HipAdam(HipBertAdam):
     KINDS = {"adam": hb.ADAM_L2, "adamw": hb.ADAMW}
 
     def __init__(self, model, kind="adamw", lr=5e-4, bert_lr=None, l2=0.0, warmup=0.0, t_total=-1, max_grad_norm=5.0, shard=False,
-                 b1=0.9, b2=0.999):
+                 b1=0.9, b2=0.999, ema_decay=None):
         if kind not in self.KINDS:
             raise ValueError("HipAdam: kind must be 'adam' or 'adamw', not %r" % (kind,))
         self.kind, self.mode, self.l2 = kind, self.KINDS[kind], float(l2)
         if kind == "adam":
             bert_lr = lr
         super().__init__(model, lr, bert_lr=bert_lr, warmup=warmup, t_total=t_total, b1=b1, b2=b2,
-                         e=1e-8 if kind == "adam" else 1e-6, max_grad_norm=max_grad_norm, shard=shard)
+                         e=1e-8 if kind == "adam" else 1e-6, max_grad_norm=max_grad_norm, shard=shard, ema_decay=ema_decay)
         self.scheduler = None
         if kind == "adamw":
             self.scheduler = LinearScheduleWithWarmup(int(self.warmup * t_total), t_total)
@@ -324,12 +426,14 @@ class HipAdam(HipBertAdam):
 
     def step_main(self):
         """the block norms of every tensor but the embedding tables: nothing is updated before their gradients are in"""
+        self._refuse_step_in_ema()
         self.sync_frozen()
         if self.sharded and self.max_grad_norm > 0:
             self.partial.zero_()
         self._norms(0)
 
     def step_embeddings(self):
+        self._refuse_step_in_ema()
         a = self.arena
         self._norms(1)
         if self.max_grad_norm > 0:
@@ -350,6 +454,7 @@ class HipAdam(HipBertAdam):
             hb.check(hb.lib().nbest_adam_update(self.mode, hb.ptr(a.p), hb.ptr(a.g), hb.ptr(a.m), hb.ptr(a.v), hb.ptr(a.w16), hb.ptr(descs),
                                                 n_t, n_b, lo, hi, hb.ptr(self.clip), lr_mult, bc1, bc2s, self.b1, self.b2, self.e,
                                                 hb.stream_ptr()), "adam_update")
+            self._ema_update(part)
         if self.sharded:
             for part in range(len(self.parts)):
                 self._broadcast_owned(part)
@@ -365,13 +470,14 @@ class HipAdam(HipBertAdam):
         return dict(kind=self.kind, step=self.step_count, sched_step=None if self.scheduler is None else self.scheduler.last_epoch,
                     t_total=self.t_total, warmup=self.warmup,
                     state={s.name: dict(exp_avg=a.view(a.m, s.name).detach().cpu().clone(),
-                                        exp_avg_sq=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots})
+                                        exp_avg_sq=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots}, **self._ema_state())
 
     def load_state_dict(self, sd):
         kind = sd.get("kind", "bertadam")
         if kind != self.kind:
             raise ValueError("optimizer state of kind %r cannot be loaded into HipAdam(kind=%r) (--optim_choice must match the run "
                              "that wrote it)" % (kind, self.kind))
+        self._load_ema_state(sd, "HipAdam(kind=%r)" % self.kind)
         a = self.arena
         self.step_count = int(sd["step"])
         if self.scheduler is not None:
