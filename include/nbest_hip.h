@@ -413,6 +413,19 @@ int nbest_stc_heads(const void* hidden, int64_t cls_stride, const float* Wh, con
                     float* loss_parts, float* dcls, float* dWh, float* dbh, int B, int H, int dtype,
                     int need_grad, int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream, void* ws,
                     size_t ws_bytes, nbest_stream_t stream);
+/* K7 kd  knowledge distillation: nbest_stc_heads with a teacher's fp32 probabilities as a second set of targets, in the layout of
+ * top / bott / final: t_top [B][n_top], t_bott [B][R - n_top], t_final [B][n_bottom] (another model's scores for the same
+ * utterances).  The soft loss is the three terms above with the teacher's outputs in place of the labels:
+ *   BCE_sum(final, t_final) + BCE_sum(top, t_top) + mean_k sum_j -t_bott_kj log(s_kj + 1e-12)      (no temperature)
+ *   loss_parts[4] = {the three hard terms as nbest_stc_heads gives them, the soft loss}, all unscaled
+ *   d(logits) = (1 - alpha) d_hard + alpha d_soft, so dcls / dWh / dbh are the gradients of (1 - alpha) hard + alpha soft
+ * Same two launches, same workspace, same dropout bits as nbest_stc_heads; fixed-order sums.  0 <= alpha <= 1; the teacher
+ * arrays may be null (all three) only when alpha == 0, which then is nbest_stc_heads itself (loss_parts[3] = 0).             */
+int nbest_stc_heads_kd(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                       const nbest_label_space* ls, const float* labels, const float* t_top, const float* t_bott,
+                       const float* t_final, float alpha, float* top, float* bott, float* final_scores, float* loss_parts,
+                       float* dcls, float* dWh, float* dbh, int B, int H, int dtype, int need_grad, int accumulate,
+                       float drop_p, uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* Backward of the heads for ARBITRARY upstream gradients dtop [B][n_top], dbott [B][R - n_top], dfin [B][n_bottom] (fp32) - what
  * torch autograd hands to the heads when the reference's loop calls total_loss.backward() on a loss it built itself
  * (/root/reference/n_best_asr_bert.py:255-264; nbest_amd.model's autograd bridge).  `ws` must be the workspace of the

@@ -150,7 +150,43 @@ def parse_arguments(argv=None):
                         "the averaged weights, training goes on with the raw ones; last.pt keeps the raw weights and, in the optimizer "
                         "state, the average.  A training flag: --testing / --predict / --head_importance read model.pt, which already "
                         "holds the averaged weights.  Not with --shard_optimizer on")
+    g.add_argument("--distill_from", default=None, metavar="PATH",
+                   help="knowledge distillation: train this model (the student, e.g. --encoder_layers 6) on the scores of a teacher - "
+                        "PATH is a state dict with the reference's keys (a model.pt of either implementation), loaded into a second "
+                        "model of the same family (bf16, or f32 with --dtype f32; never fp8, dropout 0) whose predict() runs ahead of "
+                        "every training step.  The gradient is that of (1 - A) * hard loss + A * soft loss, the soft loss being the "
+                        "three loss terms with the teacher's scores in place of the labels; the [Train] line's Loss stays the hard "
+                        "loss.  A training flag, one GPU")
+    g.add_argument("--distill_teacher_layers", type=int, default=None, metavar="N",
+                   help="with --distill_from: the teacher's number of encoder layers (default: the family's, whatever "
+                        "--encoder_layers says)")
+    g.add_argument("--distill_alpha", type=float, default=0.5, metavar="A", help="with --distill_from: weight of the soft loss, 0 <= A <= 1")
+    g.add_argument("--distill_init_layers", default=None, metavar="i0,i1,...",
+                   help="with --distill_from: initialise student layer k from teacher layer i_k and copy the teacher's embeddings "
+                        "and heads (one index per student layer, each below the teacher's depth); replaces --init_checkpoint")
     opt = ap.parse_args(argv)
+    if opt.distill_from is None:
+        if opt.distill_teacher_layers is not None or opt.distill_init_layers is not None:
+            ap.error("--distill_teacher_layers / --distill_init_layers describe the teacher of --distill_from: pass --distill_from PATH too")
+    else:
+        if not 0.0 <= opt.distill_alpha <= 1.0:
+            ap.error("--distill_alpha %s: must be in [0, 1]" % opt.distill_alpha)
+        for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--distill_from is a training flag: %s reads the student's model.pt and needs no teacher" % flag)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--distill_from runs on one GPU: a data-parallel teacher is not built (world size %s)" % os.environ["WORLD_SIZE"])
+        if opt.distill_teacher_layers is not None and opt.distill_teacher_layers < 1:
+            ap.error("--distill_teacher_layers %d: must be >= 1" % opt.distill_teacher_layers)
+        if opt.distill_init_layers is not None:
+            if opt.init_checkpoint:
+                ap.error("--distill_init_layers replaces --init_checkpoint (the student starts from the teacher's layers): pass one of them")
+            try:
+                opt.distill_init_layers = [int(x) for x in opt.distill_init_layers.split(",")]
+            except ValueError:
+                ap.error("--distill_init_layers %s: expected comma-separated layer indices, e.g. 1,3,5,7,9,11" % opt.distill_init_layers)
+            if any(i < 0 for i in opt.distill_init_layers):
+                ap.error("--distill_init_layers: layer indices must be >= 0")
     if opt.ema_decay is not None:
         if not 0.0 <= opt.ema_decay < 1.0:
             ap.error("--ema_decay %s: must be in [0, 1)" % opt.ema_decay)
@@ -216,6 +252,8 @@ def exp_dir(opt):
         parts.append("fz_%s_%s" % ("emb" if opt.freeze_embeddings else "none", opt.freeze_layers))
     if getattr(opt, "ema_decay", None) is not None:                                      # the same rule
         parts.append("ema_%s" % opt.ema_decay)
+    if getattr(opt, "distill_from", None) is not None:
+        parts.append("kd_%s" % opt.distill_alpha)
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -234,6 +272,29 @@ def freeze_parameters(model, embeddings=False, layers=0):
             p.requires_grad_(False)
             frozen.add(n)
     return frozen
+
+
+def load_teacher(opt, family, cfg, labels, dev):
+    """--distill_from: (the teacher, its state dict).  A second model of the student's family and vocabulary, --distill_teacher_layers
+    deep (default: the family's depth), bf16 or - with --dtype f32 - f32, never fp8; no dropout, eval mode, no optimizer."""
+    tcfg = ncfg.NAMED[family](hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+    if opt.distill_teacher_layers:
+        tcfg.num_hidden_layers = opt.distill_teacher_layers
+    tcfg.vocab_size = cfg.vocab_size
+    if not os.path.isfile(opt.distill_from):
+        raise SystemExit("--distill_from %s: no such file" % opt.distill_from)
+    sd = torch.load(opt.distill_from, map_location="cpu", weights_only=True)
+    teacher = NBestSTCModel(tcfg, labels, device=dev, compute_dtype=torch.float32 if opt.dtype == "f32" else torch.bfloat16,
+                            dropout=0.0, seed=opt.random_seed)
+    try:
+        teacher.load_reference_state(sd)
+    except (KeyError, RuntimeError, ValueError) as e:
+        raise SystemExit("--distill_from %s does not fit a %d-layer %s teacher (--distill_teacher_layers): %s"
+                         % (opt.distill_from, tcfg.num_hidden_layers, family, e))
+    teacher.eval()
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    return teacher, sd
 
 
 def predict_output_path(opt):
@@ -299,11 +360,22 @@ def main(argv=None):
     cfg = ncfg.NAMED[family](hidden_dropout_prob=opt.bert_dropout, attention_probs_dropout_prob=opt.bert_dropout)
     if opt.encoder_layers:
         cfg.num_hidden_layers = opt.encoder_layers
-    if (family == "bert" and not (opt.init_checkpoint or opt.pretrained_path)) or opt.vocab:
+    if (family == "bert" and not (opt.init_checkpoint or opt.pretrained_path or opt.distill_init_layers)) or opt.vocab:
         cfg.vocab_size = max(opt.tokenizer.vocab_size, 8)          # embedding table sized for the local vocabulary
     model = NBestSTCModel(cfg, labels, device=dev, compute_dtype=torch.float32 if opt.dtype == "f32" else torch.bfloat16,
                           dropout=opt.dropout, seed=opt.random_seed, fp8_forward=(opt.dtype == "fp8w"))
-    if opt.init_checkpoint:
+    teacher = None
+    if opt.distill_from is not None:
+        teacher, tsd = load_teacher(opt, family, cfg, labels, dev)
+        opt.teacher = teacher
+    if opt.distill_from is not None and opt.distill_init_layers is not None:
+        if len(opt.distill_init_layers) != cfg.num_hidden_layers:
+            raise SystemExit("--distill_init_layers: %d indices for a student of %d layers" % (len(opt.distill_init_layers), cfg.num_hidden_layers))
+        try:
+            model.load_reference_state(trainer.student_state_from_teacher(tsd, opt.distill_init_layers))
+        except ValueError as e:
+            raise SystemExit("--distill_init_layers: %s" % e)
+    elif opt.init_checkpoint:
         model.load_model(opt.init_checkpoint)
     else:
         model.load_reference_state(synth.model_state(cfg, labels, seed=opt.random_seed))
@@ -402,6 +474,9 @@ def main(argv=None):
     log = _Log(os.path.join(opt.exp_dir, "log.train"), rank, append=opt.resume and os.path.exists(os.path.join(opt.exp_dir, "last.pt")))
     t_start = time.time()
     log.info("Training starts at %s" % time.asctime(time.localtime(t_start)))
+    if teacher is not None:
+        log.info("Distillation: teacher %s (%d layers), alpha %s; gradient of (1 - alpha) * hard + alpha * soft, Loss below is the hard loss"
+                 % (opt.distill_from, teacher.cfg.num_hidden_layers, opt.distill_alpha))
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)

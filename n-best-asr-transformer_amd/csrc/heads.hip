@@ -65,8 +65,26 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
 // heads_bwd_kernel: weight gradient and input gradient in one grid (blocks [0, nW): an 8-row x 64-column tile of dWh, waves split the
 // batch, the CLS column chunk loaded once per sample for all 8 rows; blocks [nW, nW + nD): 8 samples x 64 columns of dCLS, waves split
 // the head rows, the weight element loaded once for all 8 samples); the last block sums the per-sample losses.  Fixed-order sums.
+//
+// KD (nbest_stc_heads_kd, knowledge distillation): the same kernel with a second set of targets - a teacher's fp32 probabilities
+// t_top / t_bott / t_fin in the layout of top / bott / final.  The soft loss is the three terms with the teacher's outputs in
+// place of the labels: the targets of the two BCEs, and the teacher's distribution over a head's columns where the hard term has
+// the one-hot class.  Its sum goes to sample_loss[4 b + 3]; d(logits) = (1 - alpha) d_hard + alpha d_soft (dz is linear in the
+// upstream gradient, so the two are blended per logit).  Every hard statement is the plain instantiation's; the soft ones sit
+// under `if constexpr (KD)`, so the plain instantiation computes what it always did.
+struct KdArgs {
+  const float* t_top;   // [B][n_top]
+  const float* t_bott;  // [B][R - n_top]
+  const float* t_fin;   // [B][n_bottom]
+  float alpha;
+};
+
+__device__ __forceinline__ float bce_term(float p, float y) {
+  return -(y * fmaxf(logf(p), -100.f) + (1.f - y) * fmaxf(logf(1.f - p), -100.f));
+}
+
 constexpr int kFwdThreads = 512;
-template <typename T>
+template <typename T, bool KD>
 __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restrict__ hidden, int64_t cls_stride, const float* __restrict__ Wh,
                                                                  const float* __restrict__ bh, const float* __restrict__ labels,
                                                                  const int32_t* __restrict__ bottom_off, const int32_t* __restrict__ bottom_ids,
@@ -74,8 +92,8 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
                                                                  int n_heads, int n_lay, float* __restrict__ cls_out, float* __restrict__ top,
                                                                  float* __restrict__ bott, float* __restrict__ fin, float* __restrict__ dz,
                                                                  float* __restrict__ sample_loss, uint32_t* __restrict__ mw,
-                                                                 int32_t* __restrict__ lay_row, DropCfg drop) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3]
+                                                                 int32_t* __restrict__ lay_row, DropCfg drop, KdArgs kd) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3] (KD: | soft [waves])
   const int b = blockIdx.x, B = gridDim.x, W = (H + 31) >> 5;
   float* zs = xs + H;
   int32_t* lay_s = (int32_t*)(zs + R);
@@ -113,12 +131,17 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
   const float* z = zs;
   const float* y = labels + (int64_t)b * n_bottom;
   float l_bot = 0.f, l_top = 0.f, l_ce = 0.f;
+  float l_soft = 0.f;                                       // KD: every lane's own share of the three soft terms
+  const float* tfin = KD ? kd.t_fin + (int64_t)b * n_bottom : nullptr;
+  const float* tbot = KD ? kd.t_bott + (int64_t)b * (R - n_top) : nullptr;
+  const float wh = 1.f - kd.alpha, wsft = kd.alpha;
   for (int t = wave; t < n_top; t += nw) {                  // a wave per top label (lanes parallelise the head columns)
     const int o0 = bottom_off[t], nk = bottom_off[t + 1] - o0, hr = head_row[t];
     const float zt = z[t];
     const float pt = 1.0f / (1.0f + __expf(-zt));
     float dpt = 0.f;  // d(loss)/d(top score)
     float ytop = 0.f;
+    float dpt_s = 0.f;  // KD: d(soft loss)/d(top score)
     if (hr < 0) {
       const int bi = bottom_ids[o0];                        // single bottom label: final = top score
       const float yy = y[bi];
@@ -128,6 +151,11 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
         l_bot += -(yy * fmaxf(logf(pt), -100.f) + (1.f - yy) * fmaxf(logf(1.f - pt), -100.f));
       }
       dpt += (pt - yy) / fmaxf(pt * (1.f - pt), 1e-12f);
+      if constexpr (KD) {
+        const float tf = tfin[bi];
+        if (lane == 0) l_soft += bce_term(pt, tf);
+        dpt_s += (pt - tf) / fmaxf(pt * (1.f - pt), 1e-12f);
+      }
     } else {
       float mx = -INFINITY;                                 // softmax head over nk columns (nk may exceed 64: strided)
       for (int j = lane; j < nk; j += 64) mx = fmaxf(mx, z[hr + j]);
@@ -148,6 +176,7 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
       if (ysum == 0.f) idx = nk - 1;
       ytop = ysum;
       float dot = 0.f, dtop_acc = 0.f, lb = 0.f;
+      float dot_s = 0.f, dtop_s = 0.f;
       for (int j = lane; j < nk; j += 64) {
         const float s = __expf(z[hr + j] - mx) * inv;
         const int bi = bottom_ids[o0 + j];
@@ -161,9 +190,21 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
         if (j == idx) ds += -1.0f / ((s + 1e-12f) * (float)n_heads);
         dot += ds * s;
         dtop_acc += gf * s;
+        if constexpr (KD) {
+          const float tf = tfin[bi], tb = tbot[(hr - n_top) + j];
+          l_soft += bce_term(f, tf);
+          const float gs = (f - tf) / fmaxf(f * (1.f - f), 1e-12f);
+          const float dss = gs * pt - tb / ((s + 1e-12f) * (float)n_heads);
+          dot_s += dss * s;
+          dtop_s += gs * s;
+        }
       }
       dot = wave_sum(dot);
       dpt += wave_sum(dtop_acc);
+      if constexpr (KD) {
+        dot_s = wave_sum(dot_s);
+        dpt_s += wave_sum(dtop_s);
+      }
       l_bot += wave_sum(lb) * (lane == 0 ? 1.f : 0.f);
       for (int j = lane; j < nk; j += 64) {
         const float s = __expf(z[hr + j] - mx) * inv;
@@ -176,25 +217,49 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           ds += -1.0f / ((s + 1e-12f) * (float)n_heads);
           l_ce += -logf(s + 1e-12f) / (float)n_heads;
         }
-        dz[(int64_t)b * R + hr + j] = s * (ds - dot);
+        if constexpr (KD) {
+          const float tf = tfin[bi], tb = tbot[(hr - n_top) + j];
+          const float gs = (f - tf) / fmaxf(f * (1.f - f), 1e-12f);
+          const float dss = gs * pt - tb / ((s + 1e-12f) * (float)n_heads);
+          l_soft += -tb * logf(s + 1e-12f) / (float)n_heads;
+          // alpha = 0 gives the plain kernel's bits because the soft term is finite (|gs|, tb / (s + 1e-12) <= 1e12): 1 * x + 0 * y = x
+          dz[(int64_t)b * R + hr + j] = wh * (s * (ds - dot)) + wsft * (s * (dss - dot_s));
+        } else {
+          dz[(int64_t)b * R + hr + j] = s * (ds - dot);
+        }
       }
     }
     if (lane == 0) l_top += -(ytop * fmaxf(logf(pt), -100.f) + (1.f - ytop) * fmaxf(logf(1.f - pt), -100.f));   // top BCE against y . B2T
     dpt += (pt - ytop) / fmaxf(pt * (1.f - pt), 1e-12f);
+    if constexpr (KD) {
+      const float tt = kd.t_top[(int64_t)b * n_top + t];
+      if (lane == 0) l_soft += bce_term(pt, tt);
+      dpt_s += (pt - tt) / fmaxf(pt * (1.f - pt), 1e-12f);
+    }
     if (lane == 0) {
       top[(int64_t)b * n_top + t] = pt;
-      dz[(int64_t)b * R + t] = dpt * pt * (1.f - pt);
+      if constexpr (KD) dz[(int64_t)b * R + t] = wh * (dpt * pt * (1.f - pt)) + wsft * (dpt_s * pt * (1.f - pt));
+      else dz[(int64_t)b * R + t] = dpt * pt * (1.f - pt);
     }
   }
   l_ce = wave_sum(l_ce);
   if (lane == 0) { lsum[3 * wave] = l_bot; lsum[3 * wave + 1] = l_top; lsum[3 * wave + 2] = l_ce; }
+  if constexpr (KD) {
+    l_soft = wave_sum(l_soft);
+    if (lane == 0) lsum[3 * nw + wave] = l_soft;
+  }
   __syncthreads();
   if (threadIdx.x < 3) {
     float v = 0.f;
     for (int w = 0; w < nw; ++w) v += lsum[3 * w + threadIdx.x];     // wave order: the same sum on every run
     sample_loss[4 * b + threadIdx.x] = v;
   }
-  if (threadIdx.x == 3) sample_loss[4 * b + 3] = 0.f;
+  if (threadIdx.x == 3) {
+    float v = 0.f;
+    if constexpr (KD)
+      for (int w = 0; w < nw; ++w) v += lsum[3 * nw + w];
+    sample_loss[4 * b + 3] = v;
+  }
 }
 
 constexpr int kBwdRows = 8;      // head rows (wgrad) / samples (dgrad) per block
@@ -379,11 +444,12 @@ extern "C" size_t nbest_heads_ws_bytes(int B, int R, int H) {
   return ((size_t)B * H + (size_t)2 * B * R + (size_t)4 * B) * sizeof(float) + (size_t)(R + 1) * B * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)R * sizeof(int32_t);
 }
 
-extern "C" int nbest_stc_heads(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
-                               const nbest_label_space* ls, const float* labels, float* top, float* bott,
-                               float* final_scores, float* loss_parts, float* dcls, float* dWh, float* dbh, int B, int H,
-                               int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream,
-                               void* ws, size_t ws_bytes, nbest_stream_t stream) {
+namespace {
+// the two launches of nbest_stc_heads / nbest_stc_heads_kd (kd: the teacher's arrays and alpha, or nullptr for the plain kernel)
+int heads_launch(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh, const nbest_label_space* ls,
+                 const float* labels, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls, float* dWh,
+                 float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed,
+                 uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream, const KdArgs* kd) {
   NB_CHECK(hidden && Wh && bh && ls && labels && top && bott && final_scores && loss_parts && ws && B > 0 && H > 0,
            NBEST_ERR_ARG, "stc_heads: null pointer");
   NB_CHECK(!need_grad || (dcls && dWh && dbh), NBEST_ERR_ARG, "stc_heads: need_grad without gradient buffers");
@@ -406,13 +472,14 @@ extern "C" int nbest_stc_heads(const void* hidden, int64_t cls_stride, const flo
   const int n_heads = R - n_bottom;
   NB_CHECK(n_heads > 0, NBEST_ERR_SHAPE, "stc_heads: label space has no multi-value head");
   const int n_lay = n_heads + 1;
-  const size_t smemF = ((size_t)H + 2 * (size_t)R) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)3 * (kFwdThreads / 64) * sizeof(float);
-#define NB_HEADS_FWD(TT)                                                                                                              \
-  heads_fwd_kernel<TT><<<B, kFwdThreads, smemF, st>>>((const TT*)hidden, cls_stride, Wh, bh, labels, ls->bottom_off, ls->bottom_ids,      \
-                                                      ls->head_row, n_top, n_bottom, R, H, n_heads, n_lay, cls, top, bott, final_scores,  \
-                                                      dz, sloss, mw, lay_row, d)
-  if (dtype == NBEST_F32) NB_HEADS_FWD(float);
-  else if (dtype == NBEST_BF16) NB_HEADS_FWD(bf16);
+  const size_t smemF = ((size_t)H + 2 * (size_t)R) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)(kd ? 4 : 3) * (kFwdThreads / 64) * sizeof(float);
+  const KdArgs ka = kd ? *kd : KdArgs{nullptr, nullptr, nullptr, 0.f};
+#define NB_HEADS_FWD(TT, KD)                                                                                                          \
+  heads_fwd_kernel<TT, KD><<<B, kFwdThreads, smemF, st>>>((const TT*)hidden, cls_stride, Wh, bh, labels, ls->bottom_off, ls->bottom_ids,  \
+                                                          ls->head_row, n_top, n_bottom, R, H, n_heads, n_lay, cls, top, bott,            \
+                                                          final_scores, dz, sloss, mw, lay_row, d, ka)
+  if (dtype == NBEST_F32) { if (kd) NB_HEADS_FWD(float, true); else NB_HEADS_FWD(float, false); }
+  else if (dtype == NBEST_BF16) { if (kd) NB_HEADS_FWD(bf16, true); else NB_HEADS_FWD(bf16, false); }
   else NB_CHECK(false, NBEST_ERR_DTYPE, "stc_heads: bad dtype %d", dtype);
 #undef NB_HEADS_FWD
   NB_LAUNCH_CHECK();
@@ -426,6 +493,35 @@ extern "C" int nbest_stc_heads(const void* hidden, int64_t cls_stride, const flo
   }
   NB_LAUNCH_CHECK();
   return NBEST_OK;
+}
+}  // namespace
+
+extern "C" int nbest_stc_heads(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                               const nbest_label_space* ls, const float* labels, float* top, float* bott,
+                               float* final_scores, float* loss_parts, float* dcls, float* dWh, float* dbh, int B, int H,
+                               int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream,
+                               void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
+                      need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, nullptr);
+}
+
+// Knowledge distillation: nbest_stc_heads with a teacher's probabilities as a second set of targets (heads_fwd_kernel<T, true>).
+extern "C" int nbest_stc_heads_kd(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                                  const nbest_label_space* ls, const float* labels, const float* t_top, const float* t_bott,
+                                  const float* t_final, float alpha, float* top, float* bott, float* final_scores,
+                                  float* loss_parts, float* dcls, float* dWh, float* dbh, int B, int H, int dtype, int need_grad,
+                                  int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes,
+                                  nbest_stream_t stream) {
+  NB_CHECK(alpha >= 0.f && alpha <= 1.f, NBEST_ERR_ARG, "stc_heads_kd: alpha %g outside [0, 1]", (double)alpha);
+  NB_CHECK(alpha == 0.f || (t_top && t_bott && t_final), NBEST_ERR_ARG, "stc_heads_kd: null teacher pointer with alpha != 0");
+  NB_CHECK((t_top && t_bott && t_final) || !(t_top || t_bott || t_final), NBEST_ERR_ARG,
+           "stc_heads_kd: pass all three teacher arrays or none");
+  if (!t_top)       // alpha = 0 without a teacher: nothing soft to compute, the plain kernel (loss_parts[3] = 0)
+    return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
+                        need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, nullptr);
+  const KdArgs kd{t_top, t_bott, t_final, alpha};
+  return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
+                      need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, &kd);
 }
 
 // Backward of the heads for arbitrary upstream gradients (autograd bridge; hipabi.stc_heads_vjp): `ws` is the workspace a

@@ -19,7 +19,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
     "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
-    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads",
+    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
@@ -149,6 +149,7 @@ def lib():
         L.nbest_layernorm_bwd.argtypes = [vp] * 9 + [i64, i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_colsum.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, sz, vp]
         L.nbest_stc_heads.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
+        L.nbest_stc_heads_kd.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 4 + [f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
         L.nbest_stc_heads_vjp.argtypes = [vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_cls_mse.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp]
         L.nbest_cls_grad_scatter.argtypes = [vp, vp, i32, i32, i32, i32, vp]
@@ -775,8 +776,10 @@ def stc_heads_vjp(Wh, dls, top, bott, dtop, dbott, dfin, B, H, dWh, dbh, ws, acc
     return dcls
 
 
-def stc_heads(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad=True, accumulate=False, drop_p=0.0, seed=0,
-              drop_stream=0, dWh=None, dbh=None, ws=None):
+def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
+                    teacher=None):
+    """the outputs, gradient buffers and workspace of one heads call, then nbest_stc_heads or - ``teacher`` = (t_top, t_bott,
+    t_final, alpha) - nbest_stc_heads_kd"""
     dev = Wh.device
     R, nt, nb = dls.n_rows, dls.labels.n_top, dls.labels.n_bottom
     f = dict(dtype=torch.float32, device=dev)
@@ -787,11 +790,37 @@ def stc_heads(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad=True, a
         dWh, dbh = torch.zeros(R, H, **f), torch.zeros(R, **f)
     if ws is None:
         ws = _ws(lib().nbest_heads_ws_bytes(B, R, H), dev)
-    check(lib().nbest_stc_heads(ptr(hidden), cls_stride, ptr(Wh), ptr(bh), C.byref(dls.c), ptr(labels_f), ptr(top), ptr(bott),
-                                ptr(fin), ptr(loss), ptr(dcls), ptr(dWh), ptr(dbh), B, H, dtype_code(hidden.dtype),
-                                int(need_grad), int(accumulate), drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr()),
-          "stc_heads")
+    head = (ptr(hidden), cls_stride, ptr(Wh), ptr(bh), C.byref(dls.c), ptr(labels_f))
+    tail = (ptr(top), ptr(bott), ptr(fin), ptr(loss), ptr(dcls), ptr(dWh), ptr(dbh), B, H, dtype_code(hidden.dtype), int(need_grad),
+            int(accumulate), drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr())
+    if teacher is None:
+        check(lib().nbest_stc_heads(*head, *tail), "stc_heads")
+    else:
+        t_top, t_bott, t_final, alpha = teacher
+        check(lib().nbest_stc_heads_kd(*head, ptr(t_top), ptr(t_bott), ptr(t_final), float(alpha), *tail), "stc_heads_kd")
     return top, bott, fin, loss, dcls, dWh, dbh
+
+
+def stc_heads(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad=True, accumulate=False, drop_p=0.0, seed=0,
+              drop_stream=0, dWh=None, dbh=None, ws=None):
+    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws)
+
+
+def stc_heads_kd(hidden, cls_stride, Wh, bh, dls, labels_f, t_top, t_bott, t_final, alpha, B, H, need_grad=True, accumulate=False,
+                 drop_p=0.0, seed=0, drop_stream=0, dWh=None, dbh=None, ws=None):
+    """stc_heads with a teacher's probabilities (fp32 [B, n_top] / [B, R - n_top] / [B, n_bottom], the top / bott / final of
+    another model's predict) as a second set of targets: loss[3] = the soft loss, the gradients are those of
+    (1 - alpha) * hard + alpha * soft (nbest_stc_heads_kd)"""
+    dev = Wh.device
+    R, nt, nb = dls.n_rows, dls.labels.n_top, dls.labels.n_bottom
+    for name, t, n in (("t_top", t_top, nt), ("t_bott", t_bott, R - nt), ("t_final", t_final, nb)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (B, n) or not t.is_contiguous():
+            raise ValueError("stc_heads_kd: %s must be a contiguous fp32 [%d, %d] tensor on %s (got %s %s on %s)"
+                             % (name, B, n, dev, t.dtype, tuple(t.shape), t.device))
+    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
+                           teacher=(t_top, t_bott, t_final, alpha))
 
 
 def stc_decode(top, bott, dls, out=None):

@@ -174,6 +174,24 @@ class _STCBridge(torch.autograd.Function):
         return (None,) * 7
 
 
+def _check_distill(distill, B, dls):
+    """forward_backward's ``distill`` argument -> dict(top, bott, final, alpha) with a float alpha in [0, 1]; refused before anything
+    is enqueued"""
+    if not isinstance(distill, dict) or set(distill) != {"top", "bott", "final", "alpha"}:
+        raise ValueError("nbest_amd: distill must be dict(top=, bott=, final=, alpha=) (a teacher's predict() scores and the weight "
+                         "of the soft loss)")
+    alpha = float(distill["alpha"])
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("nbest_amd: distill alpha %r: must be in [0, 1]" % (distill["alpha"],))
+    widths = dict(top=dls.labels.n_top, bott=dls.n_rows - dls.labels.n_top, final=dls.labels.n_bottom)
+    for k in ("top", "bott", "final"):
+        t = distill[k]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (B, widths[k]):
+            raise ValueError("nbest_amd: distill[%r] must be an fp32 device tensor of shape [%d, %d] (the teacher's predict()[%r])"
+                             % (k, B, widths[k], k))
+    return dict(top=distill["top"].contiguous(), bott=distill["bott"].contiguous(), final=distill["final"].contiguous(), alpha=alpha)
+
+
 def _require_trainable(plan):
     if plan is not None and not plan.trainable:
         raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
@@ -507,19 +525,25 @@ class NBestSTCModel(nn.Module):
             if on_chunk_done is not None:
                 on_chunk_done(lo, hi)
 
-    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None):
-        """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch"""
+    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None, distill=None):
+        """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch.
+        ``distill``: forward_backward's teacher scores - the same two launches through nbest_stc_heads_kd"""
         B, H = hidden.shape[0] // S, self.cfg.hidden_size
         Wh, bh = self.arena.heads_wb()
         dWh, dbh = self.arena.heads_grad_wb()
         if labels_f is None:
             labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
+        if distill is not None:
+            return hb.stc_heads_kd(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["top"], distill["bott"],
+                                   distill["final"], distill["alpha"], B, H, need_grad=need_grad, accumulate=accumulate,
+                                   drop_p=self.dropout if train else 0.0, seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh,
+                                   ws=ws)
         return hb.stc_heads(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), B, H, need_grad=need_grad,
                             accumulate=accumulate, drop_p=self.dropout if train else 0.0,
                             seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
-                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None):
+                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None):
         """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
         ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs).
         ``after_asr(record)``: called right after the ASR pass, before any other pass can touch a stash."""
@@ -528,7 +552,7 @@ class NBestSTCModel(nn.Module):
             after_asr(ra)
         rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan)
         r = rt if from_transcript else ra
-        return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws)
+        return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws, distill)
 
     def _bottoms_dict(self, bott):
         out, col = {}, 0
@@ -540,11 +564,14 @@ class NBestSTCModel(nn.Module):
 
     # ---- reference-compatible forward (models/model.py:35-73) -----------------------------------
     def forward(self, opt, input_ids, trans_input_ids=None, seg_ids=None, trans_seg_ids=None, return_attns=False,
-                classifier_input_type="asr"):
+                classifier_input_type="asr", distill=None):
         """Training mode under autograd: graph-attached outputs (``_STCBridge``), so the reference's
         ``total_loss.backward(); optimizer.step()`` loop body runs unmodified.  Otherwise (eval / no_grad): plain tensors.
         ``return_attns`` (eval / no_grad only): also ``attns``, a tuple of L fp32 tensors [B, heads, S, S] - the attention
         probabilities of every layer of the ASR pass (the reference's return_attns branch), 4th in the 6-tuple."""
+        if distill is not None:
+            raise RuntimeError("nbest_amd: distill= belongs to forward_backward (the fused step: train_step, the CLI); the forward "
+                               "returns scores - build the soft loss from them and a teacher's predict() yourself")
         if self.training and torch.is_grad_enabled():
             if return_attns:
                 raise RuntimeError("nbest_amd: return_attns=True: attention maps are an eval / predict output - call model.eval() "
@@ -591,7 +618,7 @@ class NBestSTCModel(nn.Module):
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,
-                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None):
+                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None):
         """Returns dict(top, bott, final, loss_parts[4] (device), asr_cls, trans_cls).  Gradients of the sum
         BCE(final) + BCE(top) + mean-CE (+ MSE) are left in ``arena.g``.  The transcript pass runs only
         when its output is used (--add_l2_loss); the reference computes and discards it otherwise (Q4).
@@ -600,7 +627,14 @@ class NBestSTCModel(nn.Module):
         make every gradient amax of the fp8 backward jump between two consecutive steps.
         ``tok_perm`` / ``trans_tok_perm``: int32 [B*S] token indices sorted (stably) by word id, for the deterministic embedding
         backward; the data loaders build them on the host next to the ids (None: sorted on the device).
-        Frozen parameters (``requires_grad`` False) get no gradient (FreezePlan); with none trainable this raises."""
+        Frozen parameters (``requires_grad`` False) get no gradient (FreezePlan); with none trainable this raises.
+        ``distill`` = dict(top=, bott=, final=, alpha=): knowledge distillation.  top / bott / final are a teacher's scores for the
+        same utterances - fp32 device tensors in ``predict``'s shapes - and 0 <= alpha <= 1.  The heads of the ASR pass then run
+        nbest_stc_heads_kd: ``loss_parts[3]`` is the soft loss (the three terms with the teacher's scores in place of the labels,
+        unscaled) and the gradients left in ``arena.g`` are those of (1 - alpha) * hard + alpha * soft (+ MSE, unweighted).  With
+        ``add_l2_loss`` too, loss_parts[3] stays the soft loss and the MSE is returned as ``mse``.  Same launches as without."""
+        if distill is not None:
+            distill = _check_distill(distill, input_ids.shape[0], self.dls)
         plan = None
         if need_grad:
             self._refuse_training_under_mask("forward_backward(need_grad=True)")
@@ -608,13 +642,14 @@ class NBestSTCModel(nn.Module):
             _require_trainable(plan)
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
             input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
-            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan)
+            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan, distill=distill)
         B, H = ra.ps.B, self.cfg.hidden_size
-        dt = None
+        dt = mse = None
         if rt is not None:
             dt = torch.empty(B, H, dtype=torch.float32, device=self.device) if need_grad else None
             mse = hb.cls_mse(ra.hidden, ra.ps.S * H, rt.hidden, rt.ps.S * H, B, H, dcls, dt, grad_scale=mse_grad_scale)
-            loss[3:4].copy_(mse)
+            if distill is None:
+                loss[3:4].copy_(mse)
         if need_grad and encoder_grad_scale != 1.0:
             dcls.mul_(encoder_grad_scale)
             if dt is not None:
@@ -627,7 +662,10 @@ class NBestSTCModel(nn.Module):
             else:
                 self._backward_pass(ra, dcls, accumulate=accumulate, chunks=chunks, on_chunk_done=on_chunk_done)
         self._end_of_step(need_grad)
-        return dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
+        out = dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
+        if distill is not None and mse is not None:
+            out["mse"] = mse
+        return out
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
     def predict(self, input_ids, seg_ids=None, return_attns=False):

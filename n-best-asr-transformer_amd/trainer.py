@@ -14,6 +14,7 @@ keeps the compute stream busy.  Per-tensor clipping + BertAdam run after the las
 """
 import json
 import os
+import re
 import time
 
 import numpy as np
@@ -284,12 +285,68 @@ def sync_frozen(model, optimizer, reducer=None):
         reducer.set_trainable(freeze_plan(model).trainable)
 
 
-def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None):
+_LAYER_KEY = re.compile(r"^(bert_encoder\.encoder\.layer\.)(\d+)(\..+)$")
+
+
+def student_state_from_teacher(sd, layers):
+    """A shallower student's initial state dict from a teacher's (reference keys): student layer k = teacher layer ``layers[k]``;
+    every other tensor (embeddings, pooler, STC heads) is copied as it is.  Pure: ``sd`` is not modified, the tensors are shared.
+    ValueError for an empty list or an index outside the teacher's depth (the caller checks the list against the student's depth)."""
+    layers = [int(i) for i in layers]
+    by_layer, out = {}, {}
+    for k, v in sd.items():
+        m = _LAYER_KEY.match(k)
+        if m:
+            by_layer.setdefault(int(m.group(2)), []).append((m.group(1), m.group(3), v))
+        else:
+            out[k] = v
+    depth = max(by_layer) + 1 if by_layer else 0
+    if not layers:
+        raise ValueError("student_state_from_teacher: no layers given")
+    for i in layers:
+        if not 0 <= i < depth:
+            raise ValueError("student_state_from_teacher: teacher layer %d does not exist (the teacher has %d layers)" % (i, depth))
+    for k, i in enumerate(layers):
+        for pre, post, v in by_layer[i]:
+            out["%s%d%s" % (pre, k, post)] = v
+    return out
+
+
+def teacher_scores(teacher, ids, seg, alpha):
+    """forward_backward's ``distill`` argument from ``teacher.predict`` on the batch: enqueued on the current stream ahead of the
+    student's step, no host synchronisation; the teacher is put into eval mode and nothing of it is stepped"""
+    if teacher.training:
+        teacher.eval()
+    with torch.no_grad():
+        t = teacher.predict(ids, seg_ids=seg)
+    return dict(top=t["top"], bott=t["bott"], final=t["final"], alpha=float(alpha))
+
+
+def hard_loss_parts(out):
+    """the loss_parts a step without a teacher would have returned: under distillation slot 3 carries the soft loss, the record
+    of the [Train] line keeps the hard terms (+ the MSE of --add_l2_loss)"""
+    lp = out["loss_parts"].clone()
+    if out.get("mse") is not None:
+        lp[3:4].copy_(out["mse"])
+    else:
+        lp[3:4].zero_()
+    return lp
+
+
+def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
+               distill_alpha=0.5):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
+    ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
+    the step (forward_backward's ``distill``), weighted ``distill_alpha``; ``loss_parts[3]`` is then the soft loss.
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
+    distill = None
+    if teacher is not None:
+        if world > 1:
+            raise RuntimeError("nbest_amd: distillation under data parallelism is not built (world size %d)" % world)
+        distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha)
     chunks = reducer.chunks if reducer is not None else None
     b_local = batch["ids"].shape[0]
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
@@ -301,7 +358,7 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
                                  trans_seg_ids=batch.get("tseg"), add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale,
                                  chunks=chunks, on_chunk_done=reducer.layers_ready if reducer is not None else None,
-                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"))
+                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill)
     if reducer is not None:
         reducer.wait_layers()
         optimizer.step_main()             # runs while the embedding tables' all-reduce is still in flight
@@ -696,6 +753,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     # --optim_choice adamw: the loop advances the learning-rate schedule after every optimizer step, as the reference's does
     # (n_best_asr_bert.py:273-275); BertAdam and Adam have none
     sched = getattr(opt.optimizer, "scheduler", None)
+    teacher, alpha = getattr(opt, "teacher", None), getattr(opt, "distill_alpha", 0.5)      # --distill_from
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -715,14 +773,15 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             continue
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
-                             global_batch=len(lists[bi]))
+                             global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha)
             if sched is not None:
                 sched.step()
         else:
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
-                                         accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"))
+                                         accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
+                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha))
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)
@@ -732,7 +791,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                 opt.optimizer.step()
                 if sched is not None:
                     sched.step()
-        losses.append((out["loss_parts"], len(mine), len(lists[bi])))
+        losses.append((out["loss_parts"] if teacher is None else hard_loss_parts(out), len(mine), len(lists[bi])))
         pipe.push(out, [split.labels[j] for j in mine])
     counts, _ = pipe.finish()
     return _finish(losses, counts, model.device, len(lists))
