@@ -426,6 +426,28 @@ int nbest_stc_heads_kd(const void* hidden, int64_t cls_stride, const float* Wh, 
                        const float* t_final, float alpha, float* top, float* bott, float* final_scores, float* loss_parts,
                        float* dcls, float* dWh, float* dbh, int B, int H, int dtype, int need_grad, int accumulate,
                        float drop_p, uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
+/* K7 kd_t  distillation at a temperature: the teacher is given by its LOGITS t_logits [B][R] (fp32, the layout of Wh's rows: what
+ * nbest_stc_heads_logits returns for the teacher) and both models are softened by 1 / T (Hinton et al., 2015).  With u = z / T:
+ *   p_T = sigmoid(u_t) ; s_T = softmax over a head's columns of u ; f_T = p_T * s_T  (f_T = p_T for a single-bottom top)
+ *   soft_T = T^2 * [ BCE_sum(f_T^student, f_T^teacher) + BCE_sum(p_T^student, p_T^teacher)
+ *                    + (1 / n_heads) sum_k sum_j -s_T^teacher_kj log(s_T^student_kj + 1e-12) ]
+ * with the -100 clamps on the logs and the 1e-12 guards of K7 kd, on the tempered values; the teacher's tempered scores are
+ * formed inside the kernel.  top / bott / final and loss_parts[0..2] are the T = 1 quantities of nbest_stc_heads;
+ *   loss_parts[3] = soft_T (T^2 included) ; d(logits) = (1 - alpha) d_hard + alpha d_soft_T, d_soft_T = d(soft_T)/d(student logits)
+ * (the K7 kd expressions on the tempered scores, times T).  Same two launches, workspace and dropout bits as nbest_stc_heads;
+ * fixed-order sums.  0 <= alpha <= 1, temperature finite and > 0; t_logits may be null only when alpha == 0, which then is
+ * nbest_stc_heads itself (loss_parts[3] = 0).                                                                                  */
+int nbest_stc_heads_kd_t(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                         const nbest_label_space* ls, const float* labels, const float* t_logits, float alpha,
+                         float temperature, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls,
+                         float* dWh, float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p,
+                         uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
+/* K7 logits  the logits of the heads, an inference quantity (no dropout):
+ *   logits[b][r] = bh[r] + sum_h Wh[r][h] * float(hidden[b * cls_stride + h])      fp32 [B][R], r in the order of Wh's rows
+ * in the arithmetic of nbest_stc_heads's logits stage (a wave per row, lanes strided over h, fma, fixed-order wave sum, + bh), so
+ * these are the numbers its scores are made from at dropout 0.  hidden fp32 or bf16.  One launch, no workspace, no atomics.     */
+int nbest_stc_heads_logits(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                           const nbest_label_space* ls, float* logits, int B, int H, int dtype, nbest_stream_t stream);
 /* Backward of the heads for ARBITRARY upstream gradients dtop [B][n_top], dbott [B][R - n_top], dfin [B][n_bottom] (fp32) - what
  * torch autograd hands to the heads when the reference's loop calls total_loss.backward() on a loss it built itself
  * (/root/reference/n_best_asr_bert.py:255-264; nbest_amd.model's autograd bridge).  `ws` must be the workspace of the

@@ -18,6 +18,7 @@ local WordPiece vocabulary (``--vocab``; default: the words of memory.pt).  Addi
 import argparse
 import contextlib
 import json
+import math
 import os
 import random
 import sys
@@ -161,6 +162,11 @@ def parse_arguments(argv=None):
                    help="with --distill_from: the teacher's number of encoder layers (default: the family's, whatever "
                         "--encoder_layers says)")
     g.add_argument("--distill_alpha", type=float, default=0.5, metavar="A", help="with --distill_from: weight of the soft loss, 0 <= A <= 1")
+    g.add_argument("--distill_temperature", type=float, default=None, metavar="T",
+                   help="with --distill_from: distil from the teacher's LOGITS at temperature T (finite, > 0): both models' logits are "
+                        "divided by T inside the heads kernel and the soft loss is T^2 x the three terms on the tempered scores "
+                        "(Hinton et al., 2015).  Given, even as 1.0, the logits path runs (nbest_stc_heads_kd_t) and exp_dir gains "
+                        "__kdT_<T>; not given, the teacher's probabilities are the targets, as without the flag")
     g.add_argument("--distill_init_layers", default=None, metavar="i0,i1,...",
                    help="with --distill_from: initialise student layer k from teacher layer i_k and copy the teacher's embeddings "
                         "and heads (one index per student layer, each below the teacher's depth); replaces --init_checkpoint")
@@ -168,7 +174,11 @@ def parse_arguments(argv=None):
     if opt.distill_from is None:
         if opt.distill_teacher_layers is not None or opt.distill_init_layers is not None:
             ap.error("--distill_teacher_layers / --distill_init_layers describe the teacher of --distill_from: pass --distill_from PATH too")
+        if opt.distill_temperature is not None:
+            ap.error("--distill_temperature softens the teacher of --distill_from: pass --distill_from PATH too")
     else:
+        if opt.distill_temperature is not None and not (opt.distill_temperature > 0.0 and math.isfinite(opt.distill_temperature)):
+            ap.error("--distill_temperature %s: must be a finite number > 0" % opt.distill_temperature)
         if not 0.0 <= opt.distill_alpha <= 1.0:
             ap.error("--distill_alpha %s: must be in [0, 1]" % opt.distill_alpha)
         for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
@@ -254,6 +264,8 @@ def exp_dir(opt):
         parts.append("ema_%s" % opt.ema_decay)
     if getattr(opt, "distill_from", None) is not None:
         parts.append("kd_%s" % opt.distill_alpha)
+        if getattr(opt, "distill_temperature", None) is not None:
+            parts.append("kdT_%s" % opt.distill_temperature)
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -475,8 +487,10 @@ def main(argv=None):
     t_start = time.time()
     log.info("Training starts at %s" % time.asctime(time.localtime(t_start)))
     if teacher is not None:
-        log.info("Distillation: teacher %s (%d layers), alpha %s; gradient of (1 - alpha) * hard + alpha * soft, Loss below is the hard loss"
-                 % (opt.distill_from, teacher.cfg.num_hidden_layers, opt.distill_alpha))
+        log.info("Distillation: teacher %s (%d layers), alpha %s%s; gradient of (1 - alpha) * hard + alpha * soft, Loss below is the hard loss"
+                 % (opt.distill_from, teacher.cfg.num_hidden_layers, opt.distill_alpha,
+                    "" if opt.distill_temperature is None else ", temperature %s (teacher logits, soft = T^2 x the tempered terms)"
+                    % opt.distill_temperature))
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)

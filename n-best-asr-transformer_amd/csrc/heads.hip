@@ -72,11 +72,19 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
 // the one-hot class.  Its sum goes to sample_loss[4 b + 3]; d(logits) = (1 - alpha) d_hard + alpha d_soft (dz is linear in the
 // upstream gradient, so the two are blended per logit).  Every hard statement is the plain instantiation's; the soft ones sit
 // under `if constexpr (KD)`, so the plain instantiation computes what it always did.
+//
+// KD_T (nbest_stc_heads_kd_t, distillation at a temperature): the teacher comes as its LOGITS t_logits [B][R]; its row is staged in LDS
+// next to the student's.  Both rows are softened by 1 / T and the soft statements of KD run on the tempered scores p_T = sigmoid(z_t / T),
+// s_T = softmax(z / T), f_T = p_T s_T of the two models; loss = T^2 x that, d(logits) = T x that (T^2 of the loss x 1 / T of du / dz).
+// The teacher's per-head max and the two tempered sums ride in the student's passes over the columns (independent shuffle chains:
+// the kernel is latency-bound); the student's tempered max is max(z) / T.  Hard statements, scores and dropout bits as plain.
+enum { kPlain = 0, kKd = 1, kKdT = 2 };
 struct KdArgs {
-  const float* t_top;   // [B][n_top]
+  const float* t_top;   // [B][n_top]        (kKdT: t_logits [B][R])
   const float* t_bott;  // [B][R - n_top]
   const float* t_fin;   // [B][n_bottom]
   float alpha;
+  float temperature;    // kKdT only
 };
 
 __device__ __forceinline__ float bce_term(float p, float y) {
@@ -84,7 +92,7 @@ __device__ __forceinline__ float bce_term(float p, float y) {
 }
 
 constexpr int kFwdThreads = 512;
-template <typename T, bool KD>
+template <typename T, int MODE>
 __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restrict__ hidden, int64_t cls_stride, const float* __restrict__ Wh,
                                                                  const float* __restrict__ bh, const float* __restrict__ labels,
                                                                  const int32_t* __restrict__ bottom_off, const int32_t* __restrict__ bottom_ids,
@@ -93,7 +101,8 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
                                                                  float* __restrict__ bott, float* __restrict__ fin, float* __restrict__ dz,
                                                                  float* __restrict__ sample_loss, uint32_t* __restrict__ mw,
                                                                  int32_t* __restrict__ lay_row, DropCfg drop, KdArgs kd) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3] (KD: | soft [waves])
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3] (KD: | soft [waves]) (KD_T: | teacher logits [R])
+  constexpr bool KD = MODE == kKd, KDT = MODE == kKdT;
   const int b = blockIdx.x, B = gridDim.x, W = (H + 31) >> 5;
   float* zs = xs + H;
   int32_t* lay_s = (int32_t*)(zs + R);
@@ -105,6 +114,9 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
     xs[h] = v;
     cls_out[(int64_t)b * H + h] = v;
   }
+  float* tzs = lsum + 4 * (blockDim.x >> 6);               // KD_T: the teacher's row of logits
+  if constexpr (KDT)
+    for (int r = threadIdx.x; r < R; r += blockDim.x) tzs[r] = kd.t_top[(int64_t)b * R + r];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     const int l = layer_of_row(r, head_row, n_top, nullptr);
@@ -135,6 +147,8 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
   const float* tfin = KD ? kd.t_fin + (int64_t)b * n_bottom : nullptr;
   const float* tbot = KD ? kd.t_bott + (int64_t)b * (R - n_top) : nullptr;
   const float wh = 1.f - kd.alpha, wsft = kd.alpha;
+  const float invT = KDT ? 1.0f / kd.temperature : 1.f;     // KD_T: u = z / T of both models
+  const float wsT = KDT ? kd.alpha * kd.temperature : 0.f;  // KD_T: alpha x T, the weight of d(soft / T^2) / du in dz
   for (int t = wave; t < n_top; t += nw) {                  // a wave per top label (lanes parallelise the head columns)
     const int o0 = bottom_off[t], nk = bottom_off[t + 1] - o0, hr = head_row[t];
     const float zt = z[t];
@@ -142,6 +156,11 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
     float dpt = 0.f;  // d(loss)/d(top score)
     float ytop = 0.f;
     float dpt_s = 0.f;  // KD: d(soft loss)/d(top score)
+    float ptT = 0.f, qT = 0.f;                              // KD_T: the tempered top scores of the student and the teacher
+    if constexpr (KDT) {
+      ptT = 1.0f / (1.0f + __expf(-zt * invT));
+      qT = 1.0f / (1.0f + __expf(-tzs[t] * invT));
+    }
     if (hr < 0) {
       const int bi = bottom_ids[o0];                        // single bottom label: final = top score
       const float yy = y[bi];
@@ -156,14 +175,32 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
         if (lane == 0) l_soft += bce_term(pt, tf);
         dpt_s += (pt - tf) / fmaxf(pt * (1.f - pt), 1e-12f);
       }
+      if constexpr (KDT) {                                  // final = top score, of both models
+        if (lane == 0) l_soft += bce_term(ptT, qT);
+        dpt_s += (ptT - qT) / fmaxf(ptT * (1.f - ptT), 1e-12f);
+      }
     } else {
       float mx = -INFINITY;                                 // softmax head over nk columns (nk may exceed 64: strided)
-      for (int j = lane; j < nk; j += 64) mx = fmaxf(mx, z[hr + j]);
+      float tmx = -INFINITY;                                // KD_T: the teacher's max, in the same pass
+      for (int j = lane; j < nk; j += 64) {
+        mx = fmaxf(mx, z[hr + j]);
+        if constexpr (KDT) tmx = fmaxf(tmx, tzs[hr + j]);
+      }
       mx = wave_max(mx);
+      if constexpr (KDT) tmx = wave_max(tmx);
       float se = 0.f;
-      for (int j = lane; j < nk; j += 64) se += __expf(z[hr + j] - mx);
+      float seT = 0.f, teT = 0.f;                           // KD_T: sums of exp((z - max) / T), student and teacher (max(z / T) = max(z) / T)
+      for (int j = lane; j < nk; j += 64) {
+        se += __expf(z[hr + j] - mx);
+        if constexpr (KDT) {
+          seT += __expf((z[hr + j] - mx) * invT);
+          teT += __expf((tzs[hr + j] - tmx) * invT);
+        }
+      }
       se = wave_sum(se);
+      if constexpr (KDT) wave_sum2(seT, teT);
       const float inv = 1.0f / se;
+      const float invsT = KDT ? 1.0f / seT : 0.f, invtT = KDT ? 1.0f / teT : 0.f;
       int idx = nk - 1;                                     // class index: the active bottom label, else the last column (NONE)
       float ysum = 0.f;
       for (int j = lane; j < nk; j += 64) {
@@ -198,12 +235,25 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           dot_s += dss * s;
           dtop_s += gs * s;
         }
+        if constexpr (KDT) {                                // the KD statements on the tempered scores
+          const float sT = __expf((z[hr + j] - mx) * invT) * invsT, tb = __expf((tzs[hr + j] - tmx) * invT) * invtT;
+          const float fT = ptT * sT, tf = qT * tb;
+          l_soft += bce_term(fT, tf);
+          const float gs = (fT - tf) / fmaxf(fT * (1.f - fT), 1e-12f);
+          const float dss = gs * ptT - tb / ((sT + 1e-12f) * (float)n_heads);
+          dot_s += dss * sT;
+          dtop_s += gs * sT;
+        }
       }
       dot = wave_sum(dot);
       dpt += wave_sum(dtop_acc);
       if constexpr (KD) {
         dot_s = wave_sum(dot_s);
         dpt_s += wave_sum(dtop_s);
+      }
+      if constexpr (KDT) {
+        wave_sum2(dot_s, dtop_s);
+        dpt_s += dtop_s;
       }
       l_bot += wave_sum(lb) * (lane == 0 ? 1.f : 0.f);
       for (int j = lane; j < nk; j += 64) {
@@ -224,6 +274,14 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           l_soft += -tb * logf(s + 1e-12f) / (float)n_heads;
           // alpha = 0 gives the plain kernel's bits because the soft term is finite (|gs|, tb / (s + 1e-12) <= 1e12): 1 * x + 0 * y = x
           dz[(int64_t)b * R + hr + j] = wh * (s * (ds - dot)) + wsft * (s * (dss - dot_s));
+        } else if constexpr (KDT) {
+          const float sT = __expf((z[hr + j] - mx) * invT) * invsT, tb = __expf((tzs[hr + j] - tmx) * invT) * invtT;
+          const float fT = ptT * sT, tf = qT * tb;
+          const float gs = (fT - tf) / fmaxf(fT * (1.f - fT), 1e-12f);
+          const float dss = gs * ptT - tb / ((sT + 1e-12f) * (float)n_heads);
+          l_soft += -tb * logf(sT + 1e-12f) / (float)n_heads;
+          // alpha = 0 gives the plain kernel's bits: the soft term is finite, as in KD
+          dz[(int64_t)b * R + hr + j] = wh * (s * (ds - dot)) + wsT * (sT * (dss - dot_s));
         } else {
           dz[(int64_t)b * R + hr + j] = s * (ds - dot);
         }
@@ -236,15 +294,20 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
       if (lane == 0) l_soft += bce_term(pt, tt);
       dpt_s += (pt - tt) / fmaxf(pt * (1.f - pt), 1e-12f);
     }
+    if constexpr (KDT) {
+      if (lane == 0) l_soft += bce_term(ptT, qT);
+      dpt_s += (ptT - qT) / fmaxf(ptT * (1.f - ptT), 1e-12f);
+    }
     if (lane == 0) {
       top[(int64_t)b * n_top + t] = pt;
       if constexpr (KD) dz[(int64_t)b * R + t] = wh * (dpt * pt * (1.f - pt)) + wsft * (dpt_s * pt * (1.f - pt));
+      else if constexpr (KDT) dz[(int64_t)b * R + t] = wh * (dpt * pt * (1.f - pt)) + wsT * (dpt_s * ptT * (1.f - ptT));
       else dz[(int64_t)b * R + t] = dpt * pt * (1.f - pt);
     }
   }
   l_ce = wave_sum(l_ce);
   if (lane == 0) { lsum[3 * wave] = l_bot; lsum[3 * wave + 1] = l_top; lsum[3 * wave + 2] = l_ce; }
-  if constexpr (KD) {
+  if constexpr (KD || KDT) {
     l_soft = wave_sum(l_soft);
     if (lane == 0) lsum[3 * nw + wave] = l_soft;
   }
@@ -256,8 +319,9 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
   }
   if (threadIdx.x == 3) {
     float v = 0.f;
-    if constexpr (KD)
+    if constexpr (KD || KDT)
       for (int w = 0; w < nw; ++w) v += lsum[3 * nw + w];
+    if constexpr (KDT) v *= kd.temperature * kd.temperature;
     sample_loss[4 * b + 3] = v;
   }
 }
@@ -445,7 +509,8 @@ extern "C" size_t nbest_heads_ws_bytes(int B, int R, int H) {
 }
 
 namespace {
-// the two launches of nbest_stc_heads / nbest_stc_heads_kd (kd: the teacher's arrays and alpha, or nullptr for the plain kernel)
+// the two launches of nbest_stc_heads / nbest_stc_heads_kd / nbest_stc_heads_kd_t (kd: the teacher's arrays and alpha, or nullptr for
+// the plain kernel; kd->temperature > 0 selects the logits form, whose t_top is t_logits [B][R])
 int heads_launch(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh, const nbest_label_space* ls,
                  const float* labels, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls, float* dWh,
                  float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed,
@@ -472,14 +537,20 @@ int heads_launch(const void* hidden, int64_t cls_stride, const float* Wh, const 
   const int n_heads = R - n_bottom;
   NB_CHECK(n_heads > 0, NBEST_ERR_SHAPE, "stc_heads: label space has no multi-value head");
   const int n_lay = n_heads + 1;
-  const size_t smemF = ((size_t)H + 2 * (size_t)R) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)(kd ? 4 : 3) * (kFwdThreads / 64) * sizeof(float);
-  const KdArgs ka = kd ? *kd : KdArgs{nullptr, nullptr, nullptr, 0.f};
+  const int mode = !kd ? kPlain : kd->temperature > 0.f ? kKdT : kKd;
+  // kKdT: the soft partials as kKd, then the teacher's row of R logits (heads_fwd_kernel finds it at lsum + 4 floats per wave)
+  const size_t smemF = ((size_t)H + 2 * (size_t)R) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)(kd ? 4 : 3) * (kFwdThreads / 64) * sizeof(float) +
+                       (mode == kKdT ? (size_t)R * sizeof(float) : 0);
+  const KdArgs ka = kd ? *kd : KdArgs{nullptr, nullptr, nullptr, 0.f, 0.f};
 #define NB_HEADS_FWD(TT, KD)                                                                                                          \
   heads_fwd_kernel<TT, KD><<<B, kFwdThreads, smemF, st>>>((const TT*)hidden, cls_stride, Wh, bh, labels, ls->bottom_off, ls->bottom_ids,  \
                                                           ls->head_row, n_top, n_bottom, R, H, n_heads, n_lay, cls, top, bott,            \
                                                           final_scores, dz, sloss, mw, lay_row, d, ka)
-  if (dtype == NBEST_F32) { if (kd) NB_HEADS_FWD(float, true); else NB_HEADS_FWD(float, false); }
-  else if (dtype == NBEST_BF16) { if (kd) NB_HEADS_FWD(bf16, true); else NB_HEADS_FWD(bf16, false); }
+  if (dtype == NBEST_F32) {
+    if (mode == kKdT) NB_HEADS_FWD(float, kKdT); else if (mode == kKd) NB_HEADS_FWD(float, kKd); else NB_HEADS_FWD(float, kPlain);
+  } else if (dtype == NBEST_BF16) {
+    if (mode == kKdT) NB_HEADS_FWD(bf16, kKdT); else if (mode == kKd) NB_HEADS_FWD(bf16, kKd); else NB_HEADS_FWD(bf16, kPlain);
+  }
   else NB_CHECK(false, NBEST_ERR_DTYPE, "stc_heads: bad dtype %d", dtype);
 #undef NB_HEADS_FWD
   NB_LAUNCH_CHECK();
@@ -519,9 +590,68 @@ extern "C" int nbest_stc_heads_kd(const void* hidden, int64_t cls_stride, const 
   if (!t_top)       // alpha = 0 without a teacher: nothing soft to compute, the plain kernel (loss_parts[3] = 0)
     return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
                         need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, nullptr);
-  const KdArgs kd{t_top, t_bott, t_final, alpha};
+  const KdArgs kd{t_top, t_bott, t_final, alpha, 0.f};
   return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
                       need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, &kd);
+}
+
+// Distillation at a temperature: the teacher's LOGITS as the second set of targets, both models softened by 1 / T (heads_fwd_kernel<T, kKdT>).
+extern "C" int nbest_stc_heads_kd_t(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                                    const nbest_label_space* ls, const float* labels, const float* t_logits, float alpha,
+                                    float temperature, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls,
+                                    float* dWh, float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p,
+                                    uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  NB_CHECK(alpha >= 0.f && alpha <= 1.f, NBEST_ERR_ARG, "stc_heads_kd_t: alpha %g outside [0, 1]", (double)alpha);
+  NB_CHECK(temperature > 0.f && temperature < INFINITY, NBEST_ERR_ARG, "stc_heads_kd_t: temperature %g must be finite and > 0",
+           (double)temperature);
+  NB_CHECK(alpha == 0.f || t_logits, NBEST_ERR_ARG, "stc_heads_kd_t: null teacher logits with alpha != 0");
+  if (!t_logits)    // alpha = 0 without a teacher: nothing soft to compute, the plain kernel (loss_parts[3] = 0)
+    return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
+                        need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, nullptr);
+  const KdArgs kd{t_logits, nullptr, nullptr, alpha, temperature};
+  return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
+                      need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, &kd);
+}
+
+namespace {
+// The logits stage of heads_fwd_kernel on its own, dropout off: one block per sample, the CLS row in LDS, a wave per head row, lanes
+// strided over h, fmaf, wave_sum, + bh[r] - the same arithmetic in the same order, so these are the numbers its scores are made from.
+constexpr int kLogitsThreads = 512;
+template <typename T>
+__global__ __launch_bounds__(kLogitsThreads) void heads_logits_kernel(const T* __restrict__ hidden, int64_t cls_stride,
+                                                                       const float* __restrict__ Wh, const float* __restrict__ bh, int R,
+                                                                       int H, float* __restrict__ logits) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H]
+  const int b = blockIdx.x;
+  const T* x = hidden + (int64_t)b * cls_stride;
+  for (int h = threadIdx.x; h < H; h += blockDim.x) xs[h] = to_f<T>(x[h]);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  __syncthreads();
+  for (int r = wave; r < R; r += nw) {
+    const float* w = Wh + (int64_t)r * H;
+    float s = 0.f;
+#pragma unroll 4
+    for (int h = lane; h < H; h += 64) s = fmaf(w[h], xs[h], s);
+    s = wave_sum(s);
+    if (lane == 0) logits[(int64_t)b * R + r] = s + bh[r];
+  }
+}
+}  // namespace
+
+extern "C" int nbest_stc_heads_logits(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                                      const nbest_label_space* ls, float* logits, int B, int H, int dtype, nbest_stream_t stream) {
+  NB_CHECK(hidden && Wh && bh && ls && logits && B > 0 && H > 0, NBEST_ERR_ARG, "stc_heads_logits: null pointer");
+  NB_CHECK(dtype == NBEST_F32 || dtype == NBEST_BF16, NBEST_ERR_DTYPE, "stc_heads_logits: bad dtype %d", dtype);
+  const int R = ls->n_rows, n_top = ls->n_top;
+  NB_CHECK(R > n_top && n_top > 0 && R <= 4096 && H <= 2048, NBEST_ERR_SHAPE, "stc_heads_logits: bad label space");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t smem = (size_t)H * sizeof(float);
+  if (dtype == NBEST_F32)
+    heads_logits_kernel<float><<<B, kLogitsThreads, smem, st>>>((const float*)hidden, cls_stride, Wh, bh, R, H, logits);
+  else
+    heads_logits_kernel<bf16><<<B, kLogitsThreads, smem, st>>>((const bf16*)hidden, cls_stride, Wh, bh, R, H, logits);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
 }
 
 // Backward of the heads for arbitrary upstream gradients (autograd bridge; hipabi.stc_heads_vjp): `ws` is the workspace a

@@ -19,7 +19,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
     "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
-    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd",
+    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd", "nbest_stc_heads_kd_t", "nbest_stc_heads_logits",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
@@ -150,6 +150,8 @@ def lib():
         L.nbest_colsum.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, sz, vp]
         L.nbest_stc_heads.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
         L.nbest_stc_heads_kd.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 4 + [f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
+        L.nbest_stc_heads_kd_t.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 2 + [f32, f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
+        L.nbest_stc_heads_logits.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC), vp, i32, i32, i32, vp]
         L.nbest_stc_heads_vjp.argtypes = [vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_cls_mse.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp]
         L.nbest_cls_grad_scatter.argtypes = [vp, vp, i32, i32, i32, i32, vp]
@@ -779,7 +781,7 @@ def stc_heads_vjp(Wh, dls, top, bott, dtop, dbott, dfin, B, H, dWh, dbh, ws, acc
 def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
                     teacher=None):
     """the outputs, gradient buffers and workspace of one heads call, then nbest_stc_heads or - ``teacher`` = (t_top, t_bott,
-    t_final, alpha) - nbest_stc_heads_kd"""
+    t_final, alpha) - nbest_stc_heads_kd, or - ``teacher`` = (t_logits, alpha, temperature) - nbest_stc_heads_kd_t"""
     dev = Wh.device
     R, nt, nb = dls.n_rows, dls.labels.n_top, dls.labels.n_bottom
     f = dict(dtype=torch.float32, device=dev)
@@ -795,6 +797,9 @@ def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, 
             int(accumulate), drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr())
     if teacher is None:
         check(lib().nbest_stc_heads(*head, *tail), "stc_heads")
+    elif len(teacher) == 3:
+        t_logits, alpha, temperature = teacher
+        check(lib().nbest_stc_heads_kd_t(*head, ptr(t_logits), float(alpha), float(temperature), *tail), "stc_heads_kd_t")
     else:
         t_top, t_bott, t_final, alpha = teacher
         check(lib().nbest_stc_heads_kd(*head, ptr(t_top), ptr(t_bott), ptr(t_final), float(alpha), *tail), "stc_heads_kd")
@@ -821,6 +826,32 @@ def stc_heads_kd(hidden, cls_stride, Wh, bh, dls, labels_f, t_top, t_bott, t_fin
                              % (name, B, n, dev, t.dtype, tuple(t.shape), t.device))
     return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
                            teacher=(t_top, t_bott, t_final, alpha))
+
+
+def stc_heads_kd_t(hidden, cls_stride, Wh, bh, dls, labels_f, t_logits, alpha, temperature, B, H, need_grad=True, accumulate=False,
+                   drop_p=0.0, seed=0, drop_stream=0, dWh=None, dbh=None, ws=None):
+    """stc_heads with a teacher's LOGITS (fp32 [B, R], another model's stc_heads_logits / predict(return_logits=True)) as soft
+    targets at a temperature: both models' logits are divided by ``temperature`` inside the kernel, loss[3] = T^2 x the soft loss
+    of the tempered scores, the gradients are those of (1 - alpha) * hard + alpha * that (nbest_stc_heads_kd_t).  The 7-tuple of
+    stc_heads_kd; top / bott / final and loss[:3] are the T = 1 quantities"""
+    dev = Wh.device
+    R = dls.n_rows
+    if t_logits is not None and (t_logits.dtype != torch.float32 or t_logits.device != dev or tuple(t_logits.shape) != (B, R)
+                                 or not t_logits.is_contiguous()):
+        raise ValueError("stc_heads_kd_t: t_logits must be a contiguous fp32 [%d, %d] tensor on %s (got %s %s on %s)"
+                         % (B, R, dev, t_logits.dtype, tuple(t_logits.shape), t_logits.device))
+    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
+                           teacher=(t_logits, alpha, temperature))
+
+
+def stc_heads_logits(hidden, cls_stride, Wh, bh, dls, B, H):
+    """the logits of the heads on the CLS rows ``hidden[b * cls_stride : +H]`` (fp32 or bf16), no dropout: fp32 [B, R] in the order
+    of Wh's rows (the top classifier, then the softmax heads in head order) - the numbers stc_heads makes its scores from
+    (nbest_stc_heads_logits, one launch)"""
+    logits = torch.empty(B, dls.n_rows, dtype=torch.float32, device=Wh.device)
+    check(lib().nbest_stc_heads_logits(ptr(hidden), cls_stride, ptr(Wh), ptr(bh), C.byref(dls.c), ptr(logits), B, H,
+                                       dtype_code(hidden.dtype), stream_ptr()), "stc_heads_logits")
+    return logits
 
 
 def stc_decode(top, bott, dls, out=None):

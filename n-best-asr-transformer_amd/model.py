@@ -15,6 +15,7 @@ gradients in the flat arena ``arena.g`` (also visible as ``param.grad`` views).
 """
 import collections
 import ctypes as C
+import math
 import os
 
 import torch
@@ -175,14 +176,27 @@ class _STCBridge(torch.autograd.Function):
 
 
 def _check_distill(distill, B, dls):
-    """forward_backward's ``distill`` argument -> dict(top, bott, final, alpha) with a float alpha in [0, 1]; refused before anything
-    is enqueued"""
-    if not isinstance(distill, dict) or set(distill) != {"top", "bott", "final", "alpha"}:
+    """forward_backward's ``distill`` argument -> dict(top, bott, final, alpha) or dict(logits, alpha, temperature) with a float alpha
+    in [0, 1] (and a finite float temperature > 0); exactly these two key sets pass, everything else is refused before anything is
+    enqueued"""
+    if not isinstance(distill, dict) or set(distill) not in ({"top", "bott", "final", "alpha"}, {"logits", "alpha", "temperature"}):
         raise ValueError("nbest_amd: distill must be dict(top=, bott=, final=, alpha=) (a teacher's predict() scores and the weight "
-                         "of the soft loss)")
+                         "of the soft loss) or dict(logits=, alpha=, temperature=) (its predict(return_logits=True) logits)")
     alpha = float(distill["alpha"])
     if not 0.0 <= alpha <= 1.0:
         raise ValueError("nbest_amd: distill alpha %r: must be in [0, 1]" % (distill["alpha"],))
+    if "logits" in distill:
+        try:
+            T = float(distill["temperature"])
+        except (TypeError, ValueError):
+            T = float("nan")
+        if not (T > 0.0 and math.isfinite(T)):
+            raise ValueError("nbest_amd: distill temperature %r: must be a finite number > 0" % (distill["temperature"],))
+        t = distill["logits"]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (B, dls.n_rows):
+            raise ValueError("nbest_amd: distill['logits'] must be an fp32 device tensor of shape [%d, %d] (the teacher's "
+                             "predict(return_logits=True)['logits'])" % (B, dls.n_rows))
+        return dict(logits=t.contiguous(), alpha=alpha, temperature=T)
     widths = dict(top=dls.labels.n_top, bott=dls.n_rows - dls.labels.n_top, final=dls.labels.n_bottom)
     for k in ("top", "bott", "final"):
         t = distill[k]
@@ -527,12 +541,18 @@ class NBestSTCModel(nn.Module):
 
     def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None, distill=None):
         """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch.
-        ``distill``: forward_backward's teacher scores - the same two launches through nbest_stc_heads_kd"""
+        ``distill``: forward_backward's teacher scores (or logits and a temperature) - the same two launches through
+        nbest_stc_heads_kd (nbest_stc_heads_kd_t)"""
         B, H = hidden.shape[0] // S, self.cfg.hidden_size
         Wh, bh = self.arena.heads_wb()
         dWh, dbh = self.arena.heads_grad_wb()
         if labels_f is None:
             labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
+        if distill is not None and "logits" in distill:
+            return hb.stc_heads_kd_t(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["logits"], distill["alpha"],
+                                     distill["temperature"], B, H, need_grad=need_grad, accumulate=accumulate,
+                                     drop_p=self.dropout if train else 0.0, seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh,
+                                     ws=ws)
         if distill is not None:
             return hb.stc_heads_kd(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["top"], distill["bott"],
                                    distill["final"], distill["alpha"], B, H, need_grad=need_grad, accumulate=accumulate,
@@ -632,7 +652,11 @@ class NBestSTCModel(nn.Module):
         same utterances - fp32 device tensors in ``predict``'s shapes - and 0 <= alpha <= 1.  The heads of the ASR pass then run
         nbest_stc_heads_kd: ``loss_parts[3]`` is the soft loss (the three terms with the teacher's scores in place of the labels,
         unscaled) and the gradients left in ``arena.g`` are those of (1 - alpha) * hard + alpha * soft (+ MSE, unweighted).  With
-        ``add_l2_loss`` too, loss_parts[3] stays the soft loss and the MSE is returned as ``mse``.  Same launches as without."""
+        ``add_l2_loss`` too, loss_parts[3] stays the soft loss and the MSE is returned as ``mse``.  Same launches as without.
+        ``distill`` = dict(logits=, alpha=, temperature=): the same at a temperature T (finite, > 0).  logits is the teacher's
+        ``predict(return_logits=True)["logits"]``, fp32 [B, R]; the heads run nbest_stc_heads_kd_t, which divides both models'
+        logits by T: ``loss_parts[3]`` is T^2 x the soft loss of the tempered scores and enters the gradient with weight alpha.
+        The returned top / bott / final and the hard terms are the T = 1 quantities."""
         if distill is not None:
             distill = _check_distill(distill, input_ids.shape[0], self.dls)
         plan = None
@@ -668,11 +692,14 @@ class NBestSTCModel(nn.Module):
         return out
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
-    def predict(self, input_ids, seg_ids=None, return_attns=False):
+    def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False):
         """Scores and decoded labels of one batch through nbest_encoder_infer: no activation stash, no dropout (in either
         mode), the heads on the compact CLS rows.  Returns dict(top, bott, final, cls [B, H] compute dtype, pred int32 [B, n_top]).
         ``return_attns``: also ``cls_attn``, fp32 [L, B, heads, S] - the CLS row's attention probabilities of every layer
         (nbest_encoder_infer_attn); the other outputs are the same bits as without it.
+        ``return_logits``: also ``logits``, fp32 [B, R] - the logits of the heads in the order of the head matrix's rows (the top
+        classifier, then the softmax heads in head order), from nbest_stc_heads_logits on the same CLS rows: one launch after the
+        heads call, which is unchanged; without the flag nothing new is enqueued.
         Touches no training state: stashes, gradients, optimizer moments, step_counter and the fp8 amax histories stay as they
         are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it)."""
         cfg = self.cfg
@@ -699,6 +726,8 @@ class NBestSTCModel(nn.Module):
         out = dict(top=top, bott=bott, final=fin, cls=cls, pred=self.decode(top, bott))
         if return_attns:
             out["cls_attn"] = cls_attn
+        if return_logits:
+            out["logits"] = hb.stc_heads_logits(cls, H, Wh, bh, self.dls, B, H)
         return out
 
     # ---- integrated-gradients attribution (forward + input-gradient backward, no parameter gradient) ------------------------

@@ -312,13 +312,17 @@ def student_state_from_teacher(sd, layers):
     return out
 
 
-def teacher_scores(teacher, ids, seg, alpha):
+def teacher_scores(teacher, ids, seg, alpha, temperature=None):
     """forward_backward's ``distill`` argument from ``teacher.predict`` on the batch: enqueued on the current stream ahead of the
-    student's step, no host synchronisation; the teacher is put into eval mode and nothing of it is stepped"""
+    student's step, no host synchronisation; the teacher is put into eval mode and nothing of it is stepped.  With a
+    ``temperature`` the teacher's logits (``predict(return_logits=True)``) in the logits form dict(logits, alpha, temperature);
+    without one its probabilities dict(top, bott, final, alpha)"""
     if teacher.training:
         teacher.eval()
     with torch.no_grad():
-        t = teacher.predict(ids, seg_ids=seg)
+        t = teacher.predict(ids, seg_ids=seg, return_logits=temperature is not None)
+    if temperature is not None:
+        return dict(logits=t["logits"], alpha=float(alpha), temperature=float(temperature))
     return dict(top=t["top"], bott=t["bott"], final=t["final"], alpha=float(alpha))
 
 
@@ -334,11 +338,12 @@ def hard_loss_parts(out):
 
 
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
-               distill_alpha=0.5):
+               distill_alpha=0.5, distill_temperature=None):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
     ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
-    the step (forward_backward's ``distill``), weighted ``distill_alpha``; ``loss_parts[3]`` is then the soft loss.
+    the step (forward_backward's ``distill``), weighted ``distill_alpha``; ``loss_parts[3]`` is then the soft loss.  With a
+    ``distill_temperature`` T the teacher's logits are the targets and both models are softened by 1 / T (the logits form).
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
@@ -346,7 +351,7 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     if teacher is not None:
         if world > 1:
             raise RuntimeError("nbest_amd: distillation under data parallelism is not built (world size %d)" % world)
-        distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha)
+        distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha, distill_temperature)
     chunks = reducer.chunks if reducer is not None else None
     b_local = batch["ids"].shape[0]
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
@@ -754,6 +759,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     # (n_best_asr_bert.py:273-275); BertAdam and Adam have none
     sched = getattr(opt.optimizer, "scheduler", None)
     teacher, alpha = getattr(opt, "teacher", None), getattr(opt, "distill_alpha", 0.5)      # --distill_from
+    temperature = getattr(opt, "distill_temperature", None)                                 # --distill_temperature
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -773,7 +779,8 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             continue
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
-                             global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha)
+                             global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha,
+                             distill_temperature=temperature)
             if sched is not None:
                 sched.step()
         else:
@@ -781,7 +788,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
-                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha))
+                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha, temperature))
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)

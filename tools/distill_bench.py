@@ -2,11 +2,13 @@
 """What distillation costs per step, and what the kd instantiation of the heads kernel costs beside the plain one.
 
 Step: train_step at the bench shape (bert-base student of 6 layers, bf16, B 256, S 128, n-best 5, BertAdam, dropout on: hidden 0.1,
-attention 0.1, heads 0.3) without a teacher and with a 12-layer bf16 teacher (teacher.predict ahead of every step), alternately in
-one process on the same seeded batches, timed with device events: median over the rounds, min..max as the spread.
+attention 0.1, heads 0.3) without a teacher, with a 12-layer bf16 teacher (teacher.predict ahead of every step) and with that
+teacher at temperature 2 (its logits: one more launch in predict, the kd_t heads kernel in the step), alternately in one process on
+the same seeded batches, timed with device events: median over the rounds, min..max as the spread.
 
-Kernel: hipabi.stc_heads against hipabi.stc_heads_kd (alpha 0.5) on B 256 CLS rows of H 768, dropout 0.3, need_grad: the two
-launches of each (forward + backward), many calls between two events, alternately.
+Kernel: hipabi.stc_heads against hipabi.stc_heads_kd (alpha 0.5) and hipabi.stc_heads_kd_t (alpha 0.5, T 2) on B 256 CLS rows of
+H 768, dropout 0.3, need_grad: the two launches of each (forward + backward), many calls between two events, alternately; and
+hipabi.stc_heads_logits (one launch) in the same protocol.
 
     python tools/distill_bench.py [--rounds 9] [--iters 10] [--out profiles/distill_bench.txt]"""
 import argparse
@@ -77,6 +79,7 @@ def main():
         batches.append({k: torch.from_numpy(v).cuda() for k, v in bt.items()})
     legs = {"no teacher": lambda i: train_step(student, optim, batches[i % 2]),
             "teacher": lambda i: train_step(student, optim, batches[i % 2], teacher=teacher, distill_alpha=0.5),
+            "teacher, T = 2": lambda i: train_step(student, optim, batches[i % 2], teacher=teacher, distill_alpha=0.5, distill_temperature=2.0),
             "teacher.predict": lambda i: teacher.predict(batches[i % 2]["ids"], seg_ids=batches[i % 2]["seg"])}
     for fn in legs.values():                   # warm-up: buffers sized, kernels loaded, clocks up
         for i in range(5):
@@ -95,6 +98,8 @@ def main():
                                                      max(times[leg]), B / med * 1e3))
     m0, m1, mp = (statistics.median(times[k]) for k in ("no teacher", "teacher", "teacher.predict"))
     say("the teacher adds %.3f ms per step (%.1f %%); its predict alone takes %.3f ms" % (m1 - m0, 100 * (m1 - m0) / m0, mp))
+    mt = statistics.median(times["teacher, T = 2"])
+    say("the temperature adds %.3f ms to the step with a teacher (%.2f %%)" % (mt - m1, 100 * (mt - m1) / m1))
 
     # ---- the heads kernel alone ----------------------------------------------------------------------------------------------------
     H = scfg.hidden_size
@@ -105,11 +110,13 @@ def main():
     Wh, bh = student.arena.heads_wb()
     y = (torch.rand(B, nb, generator=gen, device="cuda") < 0.02).float()
     with torch.no_grad():
-        t = teacher.predict(batches[0]["ids"], seg_ids=batches[0]["seg"])
+        t = teacher.predict(batches[0]["ids"], seg_ids=batches[0]["seg"], return_logits=True)
     dWh, dbh = torch.zeros(R, H, device="cuda"), torch.zeros(R, device="cuda")
     kw = dict(need_grad=True, drop_p=0.3, seed=5, drop_stream=900, dWh=dWh, dbh=dbh, ws=hb.heads_ws(B, R, H, "cuda"))
     klegs = {"stc_heads": lambda i: hb.stc_heads(hidden, H, Wh, bh, dls, y, B, H, **kw),
-             "stc_heads_kd": lambda i: hb.stc_heads_kd(hidden, H, Wh, bh, dls, y, t["top"], t["bott"], t["final"], 0.5, B, H, **kw)}
+             "stc_heads_kd": lambda i: hb.stc_heads_kd(hidden, H, Wh, bh, dls, y, t["top"], t["bott"], t["final"], 0.5, B, H, **kw),
+             "stc_heads_kd_t (T = 2)": lambda i: hb.stc_heads_kd_t(hidden, H, Wh, bh, dls, y, t["logits"], 0.5, 2.0, B, H, **kw),
+             "stc_heads_logits (one launch)": lambda i: hb.stc_heads_logits(hidden, H, Wh, bh, dls, B, H)}
     for fn in klegs.values():
         for i in range(20):
             fn(i)
@@ -124,11 +131,13 @@ def main():
         for leg, fn in klegs.items():
             ktimes[leg].append(timed(fn, 200, blocker) * 1e3)
     say("")
-    say("K7, B %d, H %d, R %d, bf16 CLS rows, dropout 0.3, forward + backward launches, queued behind ~ 20 ms of GEMMs so that the "
+    say("K7, B %d, H %d, R %d, bf16 CLS rows, dropout 0.3, forward + backward launches (stc_heads_logits: its one launch, no dropout), queued behind ~ 20 ms of GEMMs so that the "
         "events bracket device time; %d rounds x 200 calls, alternating" % (B, H, R, a.rounds))
     say("%-34s %10s %20s" % ("call", "us/call", "spread us"))
     for leg in klegs:
         say("%-34s %10.2f %9.2f..%-10.2f" % (leg, statistics.median(ktimes[leg]), min(ktimes[leg]), max(ktimes[leg])))
+    k0, k1, k2 = (statistics.median(ktimes[k]) for k in ("stc_heads", "stc_heads_kd", "stc_heads_kd_t (T = 2)"))
+    say("stc_heads_kd - stc_heads %+.2f us; stc_heads_kd_t - stc_heads_kd %+.2f us" % (k1 - k0, k2 - k1))
     if a.out:
         with open(a.out, "w") as fp:
             fp.write("\n".join(lines) + "\n")
