@@ -442,6 +442,27 @@ int nbest_stc_heads_kd_t(const void* hidden, int64_t cls_stride, const float* Wh
                          float temperature, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls,
                          float* dWh, float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p,
                          uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
+/* K7 rdrop  R-Drop (Liang et al., 2021): the batch has B2 = 2 P rows, rows b and b' = b + P (0 <= b < P) are twins - one utterance
+ * under two sets of dropout bits (the hashes are keyed on the position in the batch, so the twins' masks are independent).  With z, z'
+ * the twins' head logits, p = sigmoid(z_t) the top scores and s = softmax over a multi-bottom head's columns, the pair's consistency
+ * term is the symmetric KL of the model's own factorisation (n_top Bernoullis + one categorical per head, averaged over n_heads as CE):
+ *   R(b, b') = sum_t 1/2 (p_t - p'_t)(z_t - z'_t) + (1 / n_heads) sum_k 1/2 sum_j (s_kj - s'_kj)(z_kj - z'_kj)
+ *            = 1/2 [KL(P || P') + KL(P' || P)]     (no logarithm, no clamp, no 1e-12; no term on final)
+ * and its gradient w.r.t. a row's own logits
+ *   top t:            1/2 [ p_t (1 - p_t)(z_t - z'_t) + (p_t - p'_t) ]
+ *   head k, column i: (1 / n_heads) 1/2 [ (s_i - s'_i) + s_i ( (z_i - z'_i) - sum_j s_j (z_j - z'_j) ) ].
+ * Optimised: sum over the 2 P rows of the hard loss + alpha * sum over the P pairs of R, so
+ *   top / bott / final, loss_parts[0..2] : those of nbest_stc_heads on the B2 rows, bit for bit
+ *   loss_parts[3] = sum over the pairs of R (unscaled by alpha; each row of a pair contributes R / 2)
+ *   d(logits) = d_hard + alpha * dR/d(own logits)      (alpha = 0: the bits of nbest_stc_heads; equal twins, dropout off: dR = 0 exactly)
+ * The block of row b forms its twin's logits itself (the twin's CLS row and mask words in LDS, the arithmetic and order of its own), so
+ * no grid-wide synchronisation, the same two launches, workspace and dropout bits as nbest_stc_heads; fixed-order sums.
+ * alpha finite and >= 0; B2 even.  The trailing arguments are those of nbest_stc_heads.                                             */
+int nbest_stc_heads_rdrop(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                          const nbest_label_space* ls, const float* labels, float alpha, float* top, float* bott,
+                          float* final_scores, float* loss_parts, float* dcls, float* dWh, float* dbh, int B2, int H, int dtype,
+                          int need_grad, int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream, void* ws,
+                          size_t ws_bytes, nbest_stream_t stream);
 /* K7 logits  the logits of the heads, an inference quantity (no dropout):
  *   logits[b][r] = bh[r] + sum_h Wh[r][h] * float(hidden[b * cls_stride + h])      fp32 [B][R], r in the order of Wh's rows
  * in the arithmetic of nbest_stc_heads's logits stage (a wave per row, lanes strided over h, fma, fixed-order wave sum, + bh), so

@@ -170,7 +170,27 @@ def parse_arguments(argv=None):
     g.add_argument("--distill_init_layers", default=None, metavar="i0,i1,...",
                    help="with --distill_from: initialise student layer k from teacher layer i_k and copy the teacher's embeddings "
                         "and heads (one index per student layer, each below the teacher's depth); replaces --init_checkpoint")
+    g.add_argument("--rdrop_alpha", type=float, default=None, metavar="A",
+                   help="R-Drop (Liang et al., 2021): every training step runs each utterance twice in one batch of 2 x batchSize rows "
+                        "(the dropout hashes are keyed on the position in the batch, so the two copies get independent masks) and adds "
+                        "A x the symmetric KL between the two copies' outputs to the hard loss of both (nbest_stc_heads_rdrop); A finite "
+                        "and > 0.  The [Train] line's Loss is half the hard loss of the 2 x batchSize rows and its F1 that of the first "
+                        "copies; exp_dir gains __rdrop_<A>.  A training flag, one GPU; needs --dropout or --bert_dropout > 0; not with "
+                        "--distill_from")
     opt = ap.parse_args(argv)
+    if opt.rdrop_alpha is not None:
+        if not (opt.rdrop_alpha > 0.0 and math.isfinite(opt.rdrop_alpha)):
+            ap.error("--rdrop_alpha %s: must be a finite number > 0" % opt.rdrop_alpha)
+        for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--rdrop_alpha is a training flag: %s reads model.pt from the directory named without it" % flag)
+        if opt.distill_from is not None:
+            ap.error("--rdrop_alpha together with --distill_from is not built (one soft term per step)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--rdrop_alpha runs on one GPU: R-Drop under data parallelism is not built (world size %s)" % os.environ["WORLD_SIZE"])
+        if opt.dropout == 0 and opt.bert_dropout == 0:
+            ap.error("--rdrop_alpha needs dropout: with --dropout 0 and --bert_dropout 0 the two copies of an utterance are identical "
+                     "and the consistency term is zero")
     if opt.distill_from is None:
         if opt.distill_teacher_layers is not None or opt.distill_init_layers is not None:
             ap.error("--distill_teacher_layers / --distill_init_layers describe the teacher of --distill_from: pass --distill_from PATH too")
@@ -266,6 +286,8 @@ def exp_dir(opt):
         parts.append("kd_%s" % opt.distill_alpha)
         if getattr(opt, "distill_temperature", None) is not None:
             parts.append("kdT_%s" % opt.distill_temperature)
+    if getattr(opt, "rdrop_alpha", None) is not None:
+        parts.append("rdrop_%s" % opt.rdrop_alpha)
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -491,6 +513,9 @@ def main(argv=None):
                  % (opt.distill_from, teacher.cfg.num_hidden_layers, opt.distill_alpha,
                     "" if opt.distill_temperature is None else ", temperature %s (teacher logits, soft = T^2 x the tempered terms)"
                     % opt.distill_temperature))
+    if opt.rdrop_alpha is not None:
+        log.info("R-Drop: alpha %s; every utterance twice per step under independent dropout bits, gradient of the hard loss of both "
+                 "copies + alpha * their symmetric KL, Loss below is half the hard loss of the doubled batch" % opt.rdrop_alpha)
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)

@@ -78,7 +78,16 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
 // s_T = softmax(z / T), f_T = p_T s_T of the two models; loss = T^2 x that, d(logits) = T x that (T^2 of the loss x 1 / T of du / dz).
 // The teacher's per-head max and the two tempered sums ride in the student's passes over the columns (independent shuffle chains:
 // the kernel is latency-bound); the student's tempered max is max(z) / T.  Hard statements, scores and dropout bits as plain.
-enum { kPlain = 0, kKd = 1, kKdT = 2 };
+//
+// RDROP (nbest_stc_heads_rdrop, R-Drop): rows b and b + B / 2 of the batch are twins (one utterance under two sets of dropout bits).  The
+// block of row b also stages its twin's CLS row and the twin's mask words of the n_lay layers, and forms the twin's R logits in the logits
+// loop with its own arithmetic in its own order (the twin's block computes the same bits for them); they sit where KD_T keeps the
+// teacher's row.  The pair's consistency term is the symmetric KL of the model's factorisation, in its logarithm-free form
+//   R = sum_t 1/2 (p_t - p'_t)(z_t - z'_t) + (1 / n_heads) sum_k 1/2 sum_j (s_kj - s'_kj)(z_kj - z'_kj)
+// (no term on final); each block of a pair writes R / 2 into sample_loss[4 b + 3] and dz = dz_hard + alpha dR/dz(own row).  The twin's max and
+// exp-sum ride in the row's own passes, as KD_T's teacher.  The differences of scores are formed under fp contract(off): equal twins give
+// dR/dz = 0 exactly, alpha = 0 the plain kernel's bits.
+enum { kPlain = 0, kKd = 1, kKdT = 2, kRDrop = 3 };
 struct KdArgs {
   const float* t_top;   // [B][n_top]        (kKdT: t_logits [B][R])
   const float* t_bott;  // [B][R - n_top]
@@ -86,6 +95,12 @@ struct KdArgs {
   float alpha;
   float temperature;    // kKdT only
 };
+
+// a - b that never fuses with a product feeding it (the device default contracts a * b - c into an fma; e * inv - e * inv must be 0)
+__device__ __forceinline__ float sub_exact(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 
 __device__ __forceinline__ float bce_term(float p, float y) {
   return -(y * fmaxf(logf(p), -100.f) + (1.f - y) * fmaxf(logf(1.f - p), -100.f));
@@ -101,8 +116,8 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
                                                                  float* __restrict__ bott, float* __restrict__ fin, float* __restrict__ dz,
                                                                  float* __restrict__ sample_loss, uint32_t* __restrict__ mw,
                                                                  int32_t* __restrict__ lay_row, DropCfg drop, KdArgs kd) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3] (KD: | soft [waves]) (KD_T: | teacher logits [R])
-  constexpr bool KD = MODE == kKd, KDT = MODE == kKdT;
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [H] | logits [R] | layer of row [R] | mask words [n_lay][W] | loss partials [waves][3] (KD: | soft [waves]) (KD_T: | teacher logits [R]) (RDROP: | twin logits [R] | twin CLS [H] | twin mask words [n_lay][W])
+  constexpr bool KD = MODE == kKd, KDT = MODE == kKdT, RD = MODE == kRDrop;
   const int b = blockIdx.x, B = gridDim.x, W = (H + 31) >> 5;
   float* zs = xs + H;
   int32_t* lay_s = (int32_t*)(zs + R);
@@ -117,6 +132,15 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
   float* tzs = lsum + 4 * (blockDim.x >> 6);               // KD_T: the teacher's row of logits
   if constexpr (KDT)
     for (int r = threadIdx.x; r < R; r += blockDim.x) tzs[r] = kd.t_top[(int64_t)b * R + r];
+  float* xt = tzs + R;                                      // RDROP: the twin's CLS row and mask words
+  uint32_t* mkt = (uint32_t*)(xt + H);
+  if constexpr (RD) {
+    const int bt = b < (B >> 1) ? b + (B >> 1) : b - (B >> 1);
+    const T* x2 = hidden + (int64_t)bt * cls_stride;
+    for (int h = threadIdx.x; h < H; h += blockDim.x) xt[h] = to_f<T>(x2[h]);
+    if (drop.thr16)
+      for (int lay = 0; lay < n_lay; ++lay) heads_mask_words(drop, lay, bt, B, H, W, mkt + lay * W, nullptr);
+  }
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     const int l = layer_of_row(r, head_row, n_top, nullptr);
@@ -130,6 +154,28 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
     const float* w = Wh + (int64_t)r * H;
     const uint32_t* mrow = mk + lay_s[r] * W;
     float s = 0.f;
+    if constexpr (RD) {                                     // the twin's logit next to the row's own: one read of the weights
+      const uint32_t* mrow2 = mkt + lay_s[r] * W;
+      float s2 = 0.f;
+#pragma unroll 4
+      for (int h = lane; h < H; h += 64) {
+        float xv = xs[h], xv2 = xt[h];
+        if (drop.thr16) {
+          xv = ((mrow[h >> 5] >> (h & 31)) & 1u) ? xv * drop.scale : 0.f;
+          xv2 = ((mrow2[h >> 5] >> (h & 31)) & 1u) ? xv2 * drop.scale : 0.f;
+        }
+        const float wv = w[h];
+        s = fmaf(wv, xv, s);
+        s2 = fmaf(wv, xv2, s2);
+      }
+      s = wave_sum(s);
+      s2 = wave_sum(s2);
+      if (lane == 0) {
+        zs[r] = s + bh[r];
+        tzs[r] = s2 + bh[r];
+      }
+      continue;
+    }
 #pragma unroll 4
     for (int h = lane; h < H; h += 64) {
       float xv = xs[h];
@@ -161,6 +207,11 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
       ptT = 1.0f / (1.0f + __expf(-zt * invT));
       qT = 1.0f / (1.0f + __expf(-tzs[t] * invT));
     }
+    float ptw = 0.f, dzt = 0.f;                             // RDROP: the twin's top score, z_t - z'_t
+    if constexpr (RD) {
+      ptw = 1.0f / (1.0f + __expf(-tzs[t]));
+      dzt = zt - tzs[t];
+    }
     if (hr < 0) {
       const int bi = bottom_ids[o0];                        // single bottom label: final = top score
       const float yy = y[bi];
@@ -184,10 +235,10 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
       float tmx = -INFINITY;                                // KD_T: the teacher's max, in the same pass
       for (int j = lane; j < nk; j += 64) {
         mx = fmaxf(mx, z[hr + j]);
-        if constexpr (KDT) tmx = fmaxf(tmx, tzs[hr + j]);
+        if constexpr (KDT || RD) tmx = fmaxf(tmx, tzs[hr + j]);
       }
       mx = wave_max(mx);
-      if constexpr (KDT) tmx = wave_max(tmx);
+      if constexpr (KDT || RD) tmx = wave_max(tmx);
       float se = 0.f;
       float seT = 0.f, teT = 0.f;                           // KD_T: sums of exp((z - max) / T), student and teacher (max(z / T) = max(z) / T)
       for (int j = lane; j < nk; j += 64) {
@@ -196,11 +247,14 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           seT += __expf((z[hr + j] - mx) * invT);
           teT += __expf((tzs[hr + j] - tmx) * invT);
         }
+        if constexpr (RD) teT += __expf(tzs[hr + j] - tmx);  // RDROP: the twin's sum, in the row's own order
       }
       se = wave_sum(se);
       if constexpr (KDT) wave_sum2(seT, teT);
+      if constexpr (RD) teT = wave_sum(teT);
       const float inv = 1.0f / se;
-      const float invsT = KDT ? 1.0f / seT : 0.f, invtT = KDT ? 1.0f / teT : 0.f;
+      const float invsT = KDT ? 1.0f / seT : 0.f, invtT = (KDT || RD) ? 1.0f / teT : 0.f;
+      const float wr = 0.5f / (float)n_heads;               // RDROP: the weight of a head's term
       int idx = nk - 1;                                     // class index: the active bottom label, else the last column (NONE)
       float ysum = 0.f;
       for (int j = lane; j < nk; j += 64) {
@@ -244,7 +298,13 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           dot_s += dss * sT;
           dtop_s += gs * sT;
         }
+        if constexpr (RD) {                                 // 1/2 (s - s')(z - z') and sum_j s_j (z_j - z'_j)
+          const float sw = __expf(tzs[hr + j] - tmx) * invtT, dzz = z[hr + j] - tzs[hr + j];
+          l_soft += wr * (sub_exact(s, sw) * dzz);
+          dot_s += s * dzz;
+        }
       }
+      if constexpr (RD) dot_s = wave_sum(dot_s);
       dot = wave_sum(dot);
       dpt += wave_sum(dtop_acc);
       if constexpr (KD) {
@@ -282,6 +342,11 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
           l_soft += -tb * logf(sT + 1e-12f) / (float)n_heads;
           // alpha = 0 gives the plain kernel's bits: the soft term is finite, as in KD
           dz[(int64_t)b * R + hr + j] = wh * (s * (ds - dot)) + wsT * (sT * (dss - dot_s));
+        } else if constexpr (RD) {
+          const float sw = __expf(tzs[hr + j] - tmx) * invtT, dzz = z[hr + j] - tzs[hr + j];
+          const float dr = wr * (sub_exact(s, sw) + s * (dzz - dot_s));
+          // alpha = 0 gives the plain kernel's bits (dr is finite: x + 0 * y = x), equal twins give dr = 0
+          dz[(int64_t)b * R + hr + j] = s * (ds - dot) + kd.alpha * dr;
         } else {
           dz[(int64_t)b * R + hr + j] = s * (ds - dot);
         }
@@ -298,16 +363,19 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
       if (lane == 0) l_soft += bce_term(ptT, qT);
       dpt_s += (ptT - qT) / fmaxf(ptT * (1.f - ptT), 1e-12f);
     }
+    if constexpr (RD)
+      if (lane == 0) l_soft += 0.5f * ((pt - ptw) * dzt);
     if (lane == 0) {
       top[(int64_t)b * n_top + t] = pt;
       if constexpr (KD) dz[(int64_t)b * R + t] = wh * (dpt * pt * (1.f - pt)) + wsft * (dpt_s * pt * (1.f - pt));
       else if constexpr (KDT) dz[(int64_t)b * R + t] = wh * (dpt * pt * (1.f - pt)) + wsT * (dpt_s * ptT * (1.f - ptT));
+      else if constexpr (RD) dz[(int64_t)b * R + t] = dpt * pt * (1.f - pt) + kd.alpha * (0.5f * (pt * (1.f - pt) * dzt + (pt - ptw)));
       else dz[(int64_t)b * R + t] = dpt * pt * (1.f - pt);
     }
   }
   l_ce = wave_sum(l_ce);
   if (lane == 0) { lsum[3 * wave] = l_bot; lsum[3 * wave + 1] = l_top; lsum[3 * wave + 2] = l_ce; }
-  if constexpr (KD || KDT) {
+  if constexpr (KD || KDT || RD) {
     l_soft = wave_sum(l_soft);
     if (lane == 0) lsum[3 * nw + wave] = l_soft;
   }
@@ -319,9 +387,10 @@ __global__ __launch_bounds__(kFwdThreads) void heads_fwd_kernel(const T* __restr
   }
   if (threadIdx.x == 3) {
     float v = 0.f;
-    if constexpr (KD || KDT)
+    if constexpr (KD || KDT || RD)
       for (int w = 0; w < nw; ++w) v += lsum[3 * nw + w];
     if constexpr (KDT) v *= kd.temperature * kd.temperature;
+    if constexpr (RD) v *= 0.5f;                             // each block of a pair carries half of the pair's term
     sample_loss[4 * b + 3] = v;
   }
 }
@@ -510,11 +579,12 @@ extern "C" size_t nbest_heads_ws_bytes(int B, int R, int H) {
 
 namespace {
 // the two launches of nbest_stc_heads / nbest_stc_heads_kd / nbest_stc_heads_kd_t (kd: the teacher's arrays and alpha, or nullptr for
-// the plain kernel; kd->temperature > 0 selects the logits form, whose t_top is t_logits [B][R])
+// the plain kernel; kd->temperature > 0 selects the logits form, whose t_top is t_logits [B][R]; rdrop: kd carries alpha alone and rows
+// b / b + B / 2 are twins)
 int heads_launch(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh, const nbest_label_space* ls,
                  const float* labels, float* top, float* bott, float* final_scores, float* loss_parts, float* dcls, float* dWh,
                  float* dbh, int B, int H, int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed,
-                 uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream, const KdArgs* kd) {
+                 uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream, const KdArgs* kd, bool rdrop = false) {
   NB_CHECK(hidden && Wh && bh && ls && labels && top && bott && final_scores && loss_parts && ws && B > 0 && H > 0,
            NBEST_ERR_ARG, "stc_heads: null pointer");
   NB_CHECK(!need_grad || (dcls && dWh && dbh), NBEST_ERR_ARG, "stc_heads: need_grad without gradient buffers");
@@ -537,19 +607,22 @@ int heads_launch(const void* hidden, int64_t cls_stride, const float* Wh, const 
   const int n_heads = R - n_bottom;
   NB_CHECK(n_heads > 0, NBEST_ERR_SHAPE, "stc_heads: label space has no multi-value head");
   const int n_lay = n_heads + 1;
-  const int mode = !kd ? kPlain : kd->temperature > 0.f ? kKdT : kKd;
+  const int mode = !kd ? kPlain : rdrop ? kRDrop : kd->temperature > 0.f ? kKdT : kKd;
   // kKdT: the soft partials as kKd, then the teacher's row of R logits (heads_fwd_kernel finds it at lsum + 4 floats per wave)
   const size_t smemF = ((size_t)H + 2 * (size_t)R) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) + (size_t)(kd ? 4 : 3) * (kFwdThreads / 64) * sizeof(float) +
-                       (mode == kKdT ? (size_t)R * sizeof(float) : 0);
+                       (mode == kKdT ? (size_t)R * sizeof(float) : 0) +
+                       // kRDrop: the twin's logits where kKdT keeps the teacher's, then the twin's CLS row and its mask words
+                       (mode == kRDrop ? ((size_t)R + H) * sizeof(float) + (size_t)n_lay * ((H + 31) / 32) * sizeof(uint32_t) : 0);
+  NB_CHECK(mode != kRDrop || smemF <= (size_t)64 * 1024, NBEST_ERR_SHAPE, "stc_heads_rdrop: %zu bytes of LDS per block exceed 64 KB", smemF);
   const KdArgs ka = kd ? *kd : KdArgs{nullptr, nullptr, nullptr, 0.f, 0.f};
 #define NB_HEADS_FWD(TT, KD)                                                                                                          \
   heads_fwd_kernel<TT, KD><<<B, kFwdThreads, smemF, st>>>((const TT*)hidden, cls_stride, Wh, bh, labels, ls->bottom_off, ls->bottom_ids,  \
                                                           ls->head_row, n_top, n_bottom, R, H, n_heads, n_lay, cls, top, bott,            \
                                                           final_scores, dz, sloss, mw, lay_row, d, ka)
   if (dtype == NBEST_F32) {
-    if (mode == kKdT) NB_HEADS_FWD(float, kKdT); else if (mode == kKd) NB_HEADS_FWD(float, kKd); else NB_HEADS_FWD(float, kPlain);
+    if (mode == kRDrop) NB_HEADS_FWD(float, kRDrop); else if (mode == kKdT) NB_HEADS_FWD(float, kKdT); else if (mode == kKd) NB_HEADS_FWD(float, kKd); else NB_HEADS_FWD(float, kPlain);
   } else if (dtype == NBEST_BF16) {
-    if (mode == kKdT) NB_HEADS_FWD(bf16, kKdT); else if (mode == kKd) NB_HEADS_FWD(bf16, kKd); else NB_HEADS_FWD(bf16, kPlain);
+    if (mode == kRDrop) NB_HEADS_FWD(bf16, kRDrop); else if (mode == kKdT) NB_HEADS_FWD(bf16, kKdT); else if (mode == kKd) NB_HEADS_FWD(bf16, kKd); else NB_HEADS_FWD(bf16, kPlain);
   }
   else NB_CHECK(false, NBEST_ERR_DTYPE, "stc_heads: bad dtype %d", dtype);
 #undef NB_HEADS_FWD
@@ -611,6 +684,19 @@ extern "C" int nbest_stc_heads_kd_t(const void* hidden, int64_t cls_stride, cons
   const KdArgs kd{t_logits, nullptr, nullptr, alpha, temperature};
   return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B, H, dtype,
                       need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, &kd);
+}
+
+// R-Drop: rows b and b + B2 / 2 are twins; the symmetric KL between their outputs enters the loss with weight alpha (heads_fwd_kernel<T, kRDrop>).
+extern "C" int nbest_stc_heads_rdrop(const void* hidden, int64_t cls_stride, const float* Wh, const float* bh,
+                                     const nbest_label_space* ls, const float* labels, float alpha, float* top, float* bott,
+                                     float* final_scores, float* loss_parts, float* dcls, float* dWh, float* dbh, int B2, int H,
+                                     int dtype, int need_grad, int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream,
+                                     void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  NB_CHECK(alpha >= 0.f && alpha < INFINITY, NBEST_ERR_ARG, "stc_heads_rdrop: alpha %g must be finite and >= 0", (double)alpha);
+  NB_CHECK(B2 > 0 && (B2 & 1) == 0, NBEST_ERR_SHAPE, "stc_heads_rdrop: B2 = %d must be even (rows b and b + B2 / 2 are twins)", B2);
+  const KdArgs kd{nullptr, nullptr, nullptr, alpha, 0.f};
+  return heads_launch(hidden, cls_stride, Wh, bh, ls, labels, top, bott, final_scores, loss_parts, dcls, dWh, dbh, B2, H, dtype,
+                      need_grad, accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream, &kd, true);
 }
 
 namespace {

@@ -19,7 +19,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F3
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
     "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
-    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd", "nbest_stc_heads_kd_t", "nbest_stc_heads_logits",
+    "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd", "nbest_stc_heads_kd_t", "nbest_stc_heads_logits", "nbest_stc_heads_rdrop",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
@@ -151,6 +151,7 @@ def lib():
         L.nbest_stc_heads.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
         L.nbest_stc_heads_kd.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 4 + [f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
         L.nbest_stc_heads_kd_t.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC)] + [vp] * 2 + [f32, f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
+        L.nbest_stc_heads_rdrop.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC), vp, f32] + [vp] * 7 + [i32] * 5 + [f32, u64, u32, vp, sz, vp]
         L.nbest_stc_heads_logits.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC), vp, i32, i32, i32, vp]
         L.nbest_stc_heads_vjp.argtypes = [vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_cls_mse.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp]
@@ -781,7 +782,8 @@ def stc_heads_vjp(Wh, dls, top, bott, dtop, dbott, dfin, B, H, dWh, dbh, ws, acc
 def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
                     teacher=None):
     """the outputs, gradient buffers and workspace of one heads call, then nbest_stc_heads or - ``teacher`` = (t_top, t_bott,
-    t_final, alpha) - nbest_stc_heads_kd, or - ``teacher`` = (t_logits, alpha, temperature) - nbest_stc_heads_kd_t"""
+    t_final, alpha) - nbest_stc_heads_kd, or - ``teacher`` = (t_logits, alpha, temperature) - nbest_stc_heads_kd_t, or - ``teacher`` =
+    (alpha,), no teacher at all: the rows' twins - nbest_stc_heads_rdrop"""
     dev = Wh.device
     R, nt, nb = dls.n_rows, dls.labels.n_top, dls.labels.n_bottom
     f = dict(dtype=torch.float32, device=dev)
@@ -797,6 +799,8 @@ def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, 
             int(accumulate), drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr())
     if teacher is None:
         check(lib().nbest_stc_heads(*head, *tail), "stc_heads")
+    elif len(teacher) == 1:
+        check(lib().nbest_stc_heads_rdrop(*head, float(teacher[0]), *tail), "stc_heads_rdrop")
     elif len(teacher) == 3:
         t_logits, alpha, temperature = teacher
         check(lib().nbest_stc_heads_kd_t(*head, ptr(t_logits), float(alpha), float(temperature), *tail), "stc_heads_kd_t")
@@ -842,6 +846,15 @@ def stc_heads_kd_t(hidden, cls_stride, Wh, bh, dls, labels_f, t_logits, alpha, t
                          % (B, R, dev, t_logits.dtype, tuple(t_logits.shape), t_logits.device))
     return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
                            teacher=(t_logits, alpha, temperature))
+
+
+def stc_heads_rdrop(hidden, cls_stride, Wh, bh, dls, labels_f, alpha, B2, H, need_grad=True, accumulate=False, drop_p=0.0, seed=0,
+                    drop_stream=0, dWh=None, dbh=None, ws=None):
+    """stc_heads on a batch of ``B2`` = 2 P rows whose rows b and b + P are twins (R-Drop): loss[3] = the sum over the pairs of the
+    symmetric KL between the twins' outputs (unscaled), the gradients are those of the hard loss of all B2 rows + alpha * that
+    (nbest_stc_heads_rdrop).  The 7-tuple of stc_heads; top / bott / final and loss[:3] are its bits"""
+    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B2, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
+                           teacher=(alpha,))
 
 
 def stc_heads_logits(hidden, cls_stride, Wh, bh, dls, B, H):

@@ -206,6 +206,24 @@ def _check_distill(distill, B, dls):
     return dict(top=distill["top"].contiguous(), bott=distill["bott"].contiguous(), final=distill["final"].contiguous(), alpha=alpha)
 
 
+def _check_rdrop(rdrop, B, distill=None):
+    """forward_backward's ``rdrop`` argument -> dict(alpha) with a finite float alpha >= 0; the batch of ``B`` rows must be even (rows b
+    and b + B / 2 are twins) and carry no ``distill``; refused before anything is enqueued"""
+    if not isinstance(rdrop, dict) or set(rdrop) != {"alpha"}:
+        raise ValueError("nbest_amd: rdrop must be dict(alpha=) (the weight of the twins' consistency term)")
+    if distill is not None:
+        raise ValueError("nbest_amd: rdrop together with distill is not built (one soft term per step: loss_parts[3] carries it)")
+    try:
+        alpha = float(rdrop["alpha"])
+    except (TypeError, ValueError):
+        alpha = float("nan")
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise ValueError("nbest_amd: rdrop alpha %r: must be a finite number >= 0" % (rdrop["alpha"],))
+    if B < 2 or B % 2:
+        raise ValueError("nbest_amd: rdrop needs a batch of 2 P rows (rows b and b + P are twins), got %d rows" % B)
+    return dict(alpha=alpha)
+
+
 def _require_trainable(plan):
     if plan is not None and not plan.trainable:
         raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
@@ -539,15 +557,20 @@ class NBestSTCModel(nn.Module):
             if on_chunk_done is not None:
                 on_chunk_done(lo, hi)
 
-    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None, distill=None):
+    def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None, distill=None, rdrop=None):
         """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch.
         ``distill``: forward_backward's teacher scores (or logits and a temperature) - the same two launches through
-        nbest_stc_heads_kd (nbest_stc_heads_kd_t)"""
+        nbest_stc_heads_kd (nbest_stc_heads_kd_t).  ``rdrop``: forward_backward's dict(alpha) - the same two launches through
+        nbest_stc_heads_rdrop"""
         B, H = hidden.shape[0] // S, self.cfg.hidden_size
         Wh, bh = self.arena.heads_wb()
         dWh, dbh = self.arena.heads_grad_wb()
         if labels_f is None:
             labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
+        if rdrop is not None:
+            return hb.stc_heads_rdrop(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), rdrop["alpha"], B, H, need_grad=need_grad,
+                                      accumulate=accumulate, drop_p=self.dropout if train else 0.0, seed=self._step_seed(),
+                                      drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
         if distill is not None and "logits" in distill:
             return hb.stc_heads_kd_t(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["logits"], distill["alpha"],
                                      distill["temperature"], B, H, need_grad=need_grad, accumulate=accumulate,
@@ -563,7 +586,7 @@ class NBestSTCModel(nn.Module):
                             seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
-                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None):
+                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None, rdrop=None):
         """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
         ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs).
         ``after_asr(record)``: called right after the ASR pass, before any other pass can touch a stash."""
@@ -572,7 +595,7 @@ class NBestSTCModel(nn.Module):
             after_asr(ra)
         rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan)
         r = rt if from_transcript else ra
-        return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws, distill)
+        return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws, distill, rdrop)
 
     def _bottoms_dict(self, bott):
         out, col = {}, 0
@@ -638,7 +661,7 @@ class NBestSTCModel(nn.Module):
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,
-                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None):
+                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None, rdrop=None):
         """Returns dict(top, bott, final, loss_parts[4] (device), asr_cls, trans_cls).  Gradients of the sum
         BCE(final) + BCE(top) + mean-CE (+ MSE) are left in ``arena.g``.  The transcript pass runs only
         when its output is used (--add_l2_loss); the reference computes and discards it otherwise (Q4).
@@ -656,7 +679,15 @@ class NBestSTCModel(nn.Module):
         ``distill`` = dict(logits=, alpha=, temperature=): the same at a temperature T (finite, > 0).  logits is the teacher's
         ``predict(return_logits=True)["logits"]``, fp32 [B, R]; the heads run nbest_stc_heads_kd_t, which divides both models'
         logits by T: ``loss_parts[3]`` is T^2 x the soft loss of the tempered scores and enters the gradient with weight alpha.
-        The returned top / bott / final and the hard terms are the T = 1 quantities."""
+        The returned top / bott / final and the hard terms are the T = 1 quantities.
+        ``rdrop`` = dict(alpha=): R-Drop.  The batch handed in has 2 P rows and rows b / b + P are a pair (the same holds for
+        ``labels_f``, ``seg_ids`` and the transcript tensors, which work as for any batch); the twins are usually two copies of an
+        utterance, which the position-keyed dropout hashes run under independent masks, but need not be.  The heads of the ASR pass
+        run nbest_stc_heads_rdrop: ``loss_parts[3]`` is the sum over the P pairs of the symmetric KL between the twins' outputs
+        (unscaled) and the gradients left in ``arena.g`` are those of the hard loss of all 2 P rows + alpha * that (+ MSE).  alpha
+        finite and >= 0; not together with ``distill``.  With ``add_l2_loss`` the MSE comes back as ``mse``.  Same launches as without."""
+        if rdrop is not None:
+            rdrop = _check_rdrop(rdrop, input_ids.shape[0], distill)
         if distill is not None:
             distill = _check_distill(distill, input_ids.shape[0], self.dls)
         plan = None
@@ -666,13 +697,13 @@ class NBestSTCModel(nn.Module):
             _require_trainable(plan)
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
             input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
-            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan, distill=distill)
+            need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan, distill=distill, rdrop=rdrop)
         B, H = ra.ps.B, self.cfg.hidden_size
         dt = mse = None
         if rt is not None:
             dt = torch.empty(B, H, dtype=torch.float32, device=self.device) if need_grad else None
             mse = hb.cls_mse(ra.hidden, ra.ps.S * H, rt.hidden, rt.ps.S * H, B, H, dcls, dt, grad_scale=mse_grad_scale)
-            if distill is None:
+            if distill is None and rdrop is None:
                 loss[3:4].copy_(mse)
         if need_grad and encoder_grad_scale != 1.0:
             dcls.mul_(encoder_grad_scale)
@@ -687,7 +718,7 @@ class NBestSTCModel(nn.Module):
                 self._backward_pass(ra, dcls, accumulate=accumulate, chunks=chunks, on_chunk_done=on_chunk_done)
         self._end_of_step(need_grad)
         out = dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
-        if distill is not None and mse is not None:
+        if (distill is not None or rdrop is not None) and mse is not None:
             out["mse"] = mse
         return out
 

@@ -337,15 +337,50 @@ def hard_loss_parts(out):
     return lp
 
 
+def rdrop_batch(batch):
+    """the batch of an R-Drop step: every tensor of ``batch`` (ids, seg, labels, tids, tseg) repeated along dimension 0, so that rows
+    b and b + P hold the same utterance (forward_backward's ``rdrop`` pairs them; the dropout hashes are keyed on the position in the
+    batch, so the two copies run under independent masks).  ``tok_perm`` / ``ttok_perm`` are rebuilt for the doubled ids - token
+    indices sorted stably by word id, ties in ascending token index, nbest_embed_ln_bwd's contract - by hipabi.word_perm on the
+    tensors' device (a sort on the current stream, no host synchronisation).  Everything else (``word_rows``) passes through."""
+    out = dict(batch)
+    for k in ("ids", "seg", "labels", "tids", "tseg"):
+        if batch.get(k) is not None:
+            out[k] = torch.cat([batch[k], batch[k]], dim=0)
+    for k, src in (("tok_perm", "ids"), ("ttok_perm", "tids")):
+        if batch.get(src) is not None:
+            out[k] = hb.word_perm(out[src])
+    return out
+
+
+def rdrop_hard_loss_parts(out):
+    """the record of an R-Drop step for the [Train] line: half the hard parts of its 2 P rows (+ the MSE of --add_l2_loss, a mean
+    already), so that Loss compares with a run without the flag; slot 3's consistency term is left out, as the soft loss is"""
+    lp = hard_loss_parts(out)
+    lp[:3].mul_(0.5)
+    return lp
+
+
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
-               distill_alpha=0.5, distill_temperature=None):
+               distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
     ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
     the step (forward_backward's ``distill``), weighted ``distill_alpha``; ``loss_parts[3]`` is then the soft loss.  With a
     ``distill_temperature`` T the teacher's logits are the targets and both models are softened by 1 / T (the logits form).
+    ``rdrop_alpha``: R-Drop - the step runs on ``rdrop_batch(batch)`` (every utterance twice, 2 P rows) and adds alpha x the symmetric
+    KL between the twins' outputs (forward_backward's ``rdrop``); the returned tensors have 2 P rows, ``loss_parts[3]`` is the
+    consistency sum.  Not with a ``teacher``; data parallelism is not built.
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
+    b_local = batch["ids"].shape[0]
+    rdrop = None
+    if rdrop_alpha is not None:
+        if teacher is not None:
+            raise ValueError("nbest_amd: rdrop_alpha together with a teacher is not built (one soft term per step)")
+        if world > 1:
+            raise RuntimeError("nbest_amd: rdrop under data parallelism is not built (world size %d)" % world)
+        batch, rdrop = rdrop_batch(batch), dict(alpha=float(rdrop_alpha))
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
     distill = None
     if teacher is not None:
@@ -353,7 +388,6 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
             raise RuntimeError("nbest_amd: distillation under data parallelism is not built (world size %d)" % world)
         distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha, distill_temperature)
     chunks = reducer.chunks if reducer is not None else None
-    b_local = batch["ids"].shape[0]
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
     # B_local rows, so after the SUM all-reduce the term needs the weight B_local / B_global (= 1/world for equal shards)
     mse_scale = b_local / float(global_batch) if global_batch else 1.0 / world
@@ -363,7 +397,7 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
                                  trans_seg_ids=batch.get("tseg"), add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale,
                                  chunks=chunks, on_chunk_done=reducer.layers_ready if reducer is not None else None,
-                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill)
+                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop)
     if reducer is not None:
         reducer.wait_layers()
         optimizer.step_main()             # runs while the embedding tables' all-reduce is still in flight
@@ -760,6 +794,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     sched = getattr(opt.optimizer, "scheduler", None)
     teacher, alpha = getattr(opt, "teacher", None), getattr(opt, "distill_alpha", 0.5)      # --distill_from
     temperature = getattr(opt, "distill_temperature", None)                                 # --distill_temperature
+    rdrop_alpha = getattr(opt, "rdrop_alpha", None)                                         # --rdrop_alpha
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -780,15 +815,20 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
                              global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha,
-                             distill_temperature=temperature)
+                             distill_temperature=temperature, rdrop_alpha=rdrop_alpha)
             if sched is not None:
                 sched.step()
         else:
+            if rdrop_alpha is not None:
+                if teacher is not None or world > 1:
+                    raise RuntimeError("nbest_amd: rdrop with a teacher or under data parallelism is not built")
+                b = rdrop_batch(b)
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
-                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha, temperature))
+                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha, temperature),
+                                         rdrop=None if rdrop_alpha is None else dict(alpha=float(rdrop_alpha)))
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)
@@ -798,7 +838,12 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                 opt.optimizer.step()
                 if sched is not None:
                     sched.step()
-        losses.append((out["loss_parts"] if teacher is None else hard_loss_parts(out), len(mine), len(lists[bi])))
+        if rdrop_alpha is not None:
+            # the record: half the hard parts of the 2 P rows; the metrics: the first copy of every utterance
+            losses.append((rdrop_hard_loss_parts(out), len(mine), len(lists[bi])))
+            out = dict(top=out["top"][:len(mine)], bott=out["bott"][:len(mine)])
+        else:
+            losses.append((out["loss_parts"] if teacher is None else hard_loss_parts(out), len(mine), len(lists[bi])))
         pipe.push(out, [split.labels[j] for j in mine])
     counts, _ = pipe.finish()
     return _finish(losses, counts, model.device, len(lists))
