@@ -4,6 +4,7 @@ PyTorch is used only for device memory and streams: every wrapper passes ``tenso
 the current HIP stream handle.  There is NO fallback: if the library is missing or an entry point
 fails, a RuntimeError is raised (the product path must never silently run on the CPU).
 """
+import collections
 import ctypes as C
 import os
 
@@ -779,11 +780,14 @@ def stc_heads_vjp(Wh, dls, top, bott, dtop, dbott, dfin, B, H, dWh, dbh, ws, acc
     return dcls
 
 
+# the soft term of a heads call: kind "kd" (tensors: t_top, t_bott, t_final), "kd_t" (tensors: t_logits; a temperature) or "rdrop"
+SoftTerm = collections.namedtuple("SoftTerm", "kind alpha temperature tensors", defaults=(None, ()))
+
+
 def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
-                    teacher=None):
-    """the outputs, gradient buffers and workspace of one heads call, then nbest_stc_heads or - ``teacher`` = (t_top, t_bott,
-    t_final, alpha) - nbest_stc_heads_kd, or - ``teacher`` = (t_logits, alpha, temperature) - nbest_stc_heads_kd_t, or - ``teacher`` =
-    (alpha,), no teacher at all: the rows' twins - nbest_stc_heads_rdrop"""
+                    soft=None):
+    """the outputs, gradient buffers and workspace of one heads call, then nbest_stc_heads or - ``soft``: a SoftTerm -
+    nbest_stc_heads_<soft.kind>"""
     dev = Wh.device
     R, nt, nb = dls.n_rows, dls.labels.n_top, dls.labels.n_bottom
     f = dict(dtype=torch.float32, device=dev)
@@ -794,25 +798,22 @@ def _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, 
         dWh, dbh = torch.zeros(R, H, **f), torch.zeros(R, **f)
     if ws is None:
         ws = _ws(lib().nbest_heads_ws_bytes(B, R, H), dev)
-    head = (ptr(hidden), cls_stride, ptr(Wh), ptr(bh), C.byref(dls.c), ptr(labels_f))
-    tail = (ptr(top), ptr(bott), ptr(fin), ptr(loss), ptr(dcls), ptr(dWh), ptr(dbh), B, H, dtype_code(hidden.dtype), int(need_grad),
-            int(accumulate), drop_p, seed, drop_stream, ptr(ws), ws.numel(), stream_ptr())
-    if teacher is None:
-        check(lib().nbest_stc_heads(*head, *tail), "stc_heads")
-    elif len(teacher) == 1:
-        check(lib().nbest_stc_heads_rdrop(*head, float(teacher[0]), *tail), "stc_heads_rdrop")
-    elif len(teacher) == 3:
-        t_logits, alpha, temperature = teacher
-        check(lib().nbest_stc_heads_kd_t(*head, ptr(t_logits), float(alpha), float(temperature), *tail), "stc_heads_kd_t")
-    else:
-        t_top, t_bott, t_final, alpha = teacher
-        check(lib().nbest_stc_heads_kd(*head, ptr(t_top), ptr(t_bott), ptr(t_final), float(alpha), *tail), "stc_heads_kd")
+    name, extra = "stc_heads", ()
+    if soft is not None:
+        name = "stc_heads_" + soft.kind
+        extra = tuple(ptr(t) for t in soft.tensors) + (float(soft.alpha),) + (() if soft.temperature is None else (float(soft.temperature),))
+    check(getattr(lib(), "nbest_" + name)(
+        ptr(hidden), cls_stride, ptr(Wh), ptr(bh), C.byref(dls.c), ptr(labels_f), *extra, ptr(top), ptr(bott), ptr(fin), ptr(loss),
+        ptr(dcls), ptr(dWh), ptr(dbh), B, H, dtype_code(hidden.dtype), int(need_grad), int(accumulate), drop_p, seed, drop_stream,
+        ptr(ws), ws.numel(), stream_ptr()), name)
     return top, bott, fin, loss, dcls, dWh, dbh
 
 
 def stc_heads(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad=True, accumulate=False, drop_p=0.0, seed=0,
-              drop_stream=0, dWh=None, dbh=None, ws=None):
-    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws)
+              drop_stream=0, dWh=None, dbh=None, ws=None, soft=None):
+    """``soft``: a SoftTerm whose tensors the caller has checked (model._heads); the wrappers below check theirs"""
+    return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
+                           soft)
 
 
 def stc_heads_kd(hidden, cls_stride, Wh, bh, dls, labels_f, t_top, t_bott, t_final, alpha, B, H, need_grad=True, accumulate=False,
@@ -829,7 +830,7 @@ def stc_heads_kd(hidden, cls_stride, Wh, bh, dls, labels_f, t_top, t_bott, t_fin
             raise ValueError("stc_heads_kd: %s must be a contiguous fp32 [%d, %d] tensor on %s (got %s %s on %s)"
                              % (name, B, n, dev, t.dtype, tuple(t.shape), t.device))
     return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
-                           teacher=(t_top, t_bott, t_final, alpha))
+                           soft=SoftTerm("kd", alpha, None, (t_top, t_bott, t_final)))
 
 
 def stc_heads_kd_t(hidden, cls_stride, Wh, bh, dls, labels_f, t_logits, alpha, temperature, B, H, need_grad=True, accumulate=False,
@@ -845,7 +846,7 @@ def stc_heads_kd_t(hidden, cls_stride, Wh, bh, dls, labels_f, t_logits, alpha, t
         raise ValueError("stc_heads_kd_t: t_logits must be a contiguous fp32 [%d, %d] tensor on %s (got %s %s on %s)"
                          % (B, R, dev, t_logits.dtype, tuple(t_logits.shape), t_logits.device))
     return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
-                           teacher=(t_logits, alpha, temperature))
+                           soft=SoftTerm("kd_t", alpha, temperature, (t_logits,)))
 
 
 def stc_heads_rdrop(hidden, cls_stride, Wh, bh, dls, labels_f, alpha, B2, H, need_grad=True, accumulate=False, drop_p=0.0, seed=0,
@@ -854,7 +855,7 @@ def stc_heads_rdrop(hidden, cls_stride, Wh, bh, dls, labels_f, alpha, B2, H, nee
     symmetric KL between the twins' outputs (unscaled), the gradients are those of the hard loss of all B2 rows + alpha * that
     (nbest_stc_heads_rdrop).  The 7-tuple of stc_heads; top / bott / final and loss[:3] are its bits"""
     return _stc_heads_call(hidden, cls_stride, Wh, bh, dls, labels_f, B2, H, need_grad, accumulate, drop_p, seed, drop_stream, dWh, dbh, ws,
-                           teacher=(alpha,))
+                           soft=SoftTerm("rdrop", alpha))
 
 
 def stc_heads_logits(hidden, cls_stride, Wh, bh, dls, B, H):

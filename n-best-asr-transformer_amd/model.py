@@ -559,31 +559,23 @@ class NBestSTCModel(nn.Module):
 
     def _heads(self, hidden, S, labels_f, need_grad, train, accumulate=False, ws=None, distill=None, rdrop=None):
         """``ws``: a private heads workspace (the autograd bridge keeps it for stc_heads_vjp); None = the shared scratch.
-        ``distill``: forward_backward's teacher scores (or logits and a temperature) - the same two launches through
-        nbest_stc_heads_kd (nbest_stc_heads_kd_t).  ``rdrop``: forward_backward's dict(alpha) - the same two launches through
-        nbest_stc_heads_rdrop"""
+        ``distill`` / ``rdrop``: forward_backward's checked arguments - the same two launches through nbest_stc_heads_kd,
+        nbest_stc_heads_kd_t or nbest_stc_heads_rdrop (one hb.SoftTerm says which)"""
         B, H = hidden.shape[0] // S, self.cfg.hidden_size
         Wh, bh = self.arena.heads_wb()
         dWh, dbh = self.arena.heads_grad_wb()
         if labels_f is None:
             labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
+        soft = None
         if rdrop is not None:
-            return hb.stc_heads_rdrop(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), rdrop["alpha"], B, H, need_grad=need_grad,
-                                      accumulate=accumulate, drop_p=self.dropout if train else 0.0, seed=self._step_seed(),
-                                      drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
-        if distill is not None and "logits" in distill:
-            return hb.stc_heads_kd_t(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["logits"], distill["alpha"],
-                                     distill["temperature"], B, H, need_grad=need_grad, accumulate=accumulate,
-                                     drop_p=self.dropout if train else 0.0, seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh,
-                                     ws=ws)
-        if distill is not None:
-            return hb.stc_heads_kd(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), distill["top"], distill["bott"],
-                                   distill["final"], distill["alpha"], B, H, need_grad=need_grad, accumulate=accumulate,
-                                   drop_p=self.dropout if train else 0.0, seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh,
-                                   ws=ws)
+            soft = hb.SoftTerm("rdrop", rdrop["alpha"])
+        elif distill is not None and "logits" in distill:
+            soft = hb.SoftTerm("kd_t", distill["alpha"], distill["temperature"], (distill["logits"],))
+        elif distill is not None:
+            soft = hb.SoftTerm("kd", distill["alpha"], None, (distill["top"], distill["bott"], distill["final"]))
         return hb.stc_heads(hidden, S * H, Wh, bh, self.dls, labels_f.contiguous(), B, H, need_grad=need_grad,
                             accumulate=accumulate, drop_p=self.dropout if train else 0.0,
-                            seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws)
+                            seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws, soft=soft)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
                           accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None, rdrop=None):

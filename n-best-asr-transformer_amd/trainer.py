@@ -361,6 +361,24 @@ def rdrop_hard_loss_parts(out):
     return lp
 
 
+def soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids=True):
+    """(batch, distill, rdrop) of one forward_backward call: under ``rdrop_alpha`` the doubled batch and dict(alpha); with a
+    ``teacher`` its scores of the batch (teacher_scores).  One soft term per step, and neither is built under data parallelism."""
+    distill = rdrop = None
+    if rdrop_alpha is not None:
+        if teacher is not None:
+            raise ValueError("nbest_amd: rdrop_alpha together with a teacher is not built (one soft term per step)")
+        if world > 1:
+            raise RuntimeError("nbest_amd: rdrop under data parallelism is not built (world size %d)" % world)
+        batch, rdrop = rdrop_batch(batch), dict(alpha=float(rdrop_alpha))
+    if teacher is not None:
+        if world > 1:
+            raise RuntimeError("nbest_amd: distillation under data parallelism is not built (world size %d)" % world)
+        seg = batch.get("seg") if add_segment_ids else None
+        distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha, distill_temperature)
+    return batch, distill, rdrop
+
+
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
                distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
@@ -374,19 +392,8 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
     b_local = batch["ids"].shape[0]
-    rdrop = None
-    if rdrop_alpha is not None:
-        if teacher is not None:
-            raise ValueError("nbest_amd: rdrop_alpha together with a teacher is not built (one soft term per step)")
-        if world > 1:
-            raise RuntimeError("nbest_amd: rdrop under data parallelism is not built (world size %d)" % world)
-        batch, rdrop = rdrop_batch(batch), dict(alpha=float(rdrop_alpha))
+    batch, distill, rdrop = soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids)
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
-    distill = None
-    if teacher is not None:
-        if world > 1:
-            raise RuntimeError("nbest_amd: distillation under data parallelism is not built (world size %d)" % world)
-        distill = teacher_scores(teacher, batch["ids"], seg, distill_alpha, distill_temperature)
     chunks = reducer.chunks if reducer is not None else None
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
     # B_local rows, so after the SUM all-reduce the term needs the weight B_local / B_global (= 1/world for equal shards)
@@ -819,16 +826,12 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             if sched is not None:
                 sched.step()
         else:
-            if rdrop_alpha is not None:
-                if teacher is not None or world > 1:
-                    raise RuntimeError("nbest_amd: rdrop with a teacher or under data parallelism is not built")
-                b = rdrop_batch(b)
+            b, distill, rdrop = soft_term_args(teacher, alpha, temperature, rdrop_alpha, b, world, opt.add_segment_ids)
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
-                                         distill=None if teacher is None else teacher_scores(teacher, b["ids"], seg, alpha, temperature),
-                                         rdrop=None if rdrop_alpha is None else dict(alpha=float(rdrop_alpha)))
+                                         distill=distill, rdrop=rdrop)
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)
