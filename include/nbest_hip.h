@@ -686,7 +686,26 @@ typedef struct nbest_encoder_desc {
   const uint32_t* aamax_prev;
   uint32_t* aamax_new;
   int32_t fp8_act;
-  int32_t pad4;
+  /* (in the slot that was padding: zero = every entry point enqueues exactly the launches it did without the field, and the size
+   * of the struct is unchanged)
+   * cls_top != 0: the top layer (L - 1) is trained on the CLS rows only.  Everything that reads the final hidden state reads row 0
+   * of each utterance, so the backward's dhidden is zero outside those B rows and, of the top layer, only the K and V rows of the
+   * other positions can reach the result.  nbest_encoder_forward then runs the top layer's QKV projection over all B S rows as
+   * before and everything after it on B rows: a one-query attention per (utterance, head), attention-out, LayerNorm, FFN and
+   * LayerNorm, with the dropout decisions the full-width kernels take for rows b S.  The B output rows go to rows b S of the final
+   * hidden state; ITS OTHER ROWS ARE NOT WRITTEN.  The compact intermediates occupy the first B rows of the top layer's stash
+   * regions (the LayerNorm output rows B .. 2 B - 1 of r2 on their way to the hidden state); its lse and keep words are not
+   * written.  nbest_encoder_backward with layer_end == L reads dhidden at rows b S only, runs the top layer's LayerNorm backwards,
+   * FFN and attention-out dgrads on B rows, forms the gradients of Wo, W1 and W2 as plain launches over K = B token rows (they
+   * honour accumulate and wgrad_skip_host and are not part of the grouped / window queue), recomputes the B heads softmax rows in a
+   * one-query attention backward that writes the layer's dQ|dK|dV in full (dQ zero outside the CLS rows), and runs the QKV dgrad
+   * and weight gradient unchanged.  Event pairs (wgrad_events): as many as without the flag; the top layer's bracket its small
+   * launches.  Same results up to summation order (fp32) / one more rounding of the B rows (bf16); bit-reproducible run to run.
+   * Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward (w8), head_gate, base_ids / alpha, no_param_grad and S < 2.
+   * first_trainable == L (nothing stashed, no backward) is accepted: the forward runs the top layer on the CLS rows of the frozen
+   * layers' scratch, so the final CLS rows are the bits a trainable top layer gives.  The backward must see the value the forward of
+   * its stash saw.  nbest_encoder_infer* ignore the field; nbest_encoder_act_view refuses the top layer of such a stash.           */
+  int32_t cls_top;
   /* optional frozen parameters (zero = everything trainable).  first_trainable = K in [0, L]: nothing of the embeddings or of layers
    * [0, K) is trainable - nbest_encoder_forward runs those layers on scratch in `ws` (which it then needs: nbest_encoder_ws_bytes)
    * with the same dropout streams, stashes nothing of them (nbest_encoder_act_bytes covers X[K..L] and layers K..L-1 only) and, in

@@ -1239,10 +1239,14 @@ static void launch_fwd(const bf16* qkv, const uint8_t* mask, bf16* ctx, float* l
 // PROBS (nbest_attention_cls_probs): the same scores, max and sum, then the fp32 probabilities of the row go to
 // probs[bh * ldp + j] and P.V is skipped - unrounded in both dtypes, 0 on masked keys (a fully masked row: all 0).
 // =================================================================================================
-template <typename T, bool PROBS>
+// DROP (the training forward's top layer, desc.cls_top): attention dropout with the keep decisions the full kernels take for query 0 of
+// the utterance - element (bh S + 0) S + key of the layer's stream; bf16 rounds the dropped, rescaled probability once, as they do.
+// `drop` is the last argument and is not read without DROP: the instantiations of the inference keep their instructions.
+template <typename T, bool PROBS, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kv, int64_t ldkv,
                                                            const uint8_t* __restrict__ mask, T* __restrict__ ctx, int64_t ldctx, int S,
-                                                           int heads, int H, float scale, float* __restrict__ probs, int64_t ldp) {
+                                                           int heads, int H, float scale, float* __restrict__ probs, int64_t ldp,
+                                                           DropCfg drop) {
   constexpr bool kF32 = sizeof(T) == 4;
   constexpr int VEC = 16 / (int)sizeof(T);   // elements per 16-byte load
   constexpr int LPK = 64 / VEC;              // lanes per 64-wide head row: 8 (bf16) / 16 (fp32)
@@ -1309,9 +1313,19 @@ __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__
     }
     return;
   }
-  for (int j = tid; j < S; j += 256) {
-    const float v = sc[j];
-    sc[j] = kF32 ? (v == -INFINITY ? 0.f : expf(v - lse)) : (float)(bf16)(ex(v) * inv);
+  if constexpr (DROP) {
+    const float ids = inv * drop.scale;
+    for (int j = tid; j < S; j += 256) {
+      const float v = sc[j];
+      const bool keep = nb_keep(drop, (uint32_t)((bh * S) * S + j));
+      if constexpr (kF32) sc[j] = (v == -INFINITY || !keep) ? 0.f : expf(v - lse) * drop.scale;
+      else sc[j] = keep ? (float)(bf16)(ex(v) * ids) : 0.f;
+    }
+  } else {
+    for (int j = tid; j < S; j += 256) {
+      const float v = sc[j];
+      sc[j] = kF32 ? (v == -INFINITY ? 0.f : expf(v - lse)) : (float)(bf16)(ex(v) * inv);
+    }
   }
   __syncthreads();
   // ---- P.V: partial rows per key group, then a fixed-order sum over the groups ----
@@ -1336,6 +1350,146 @@ __global__ __launch_bounds__(256) void attn_cls_fwd_kernel(const T* __restrict__
     T* op = ctx + (int64_t)b * ldctx + h * 64 + tid;
     if constexpr (kF32) *op = acc;
     else *op = (bf16)acc;
+  }
+}
+
+// =================================================================================================
+// CLS-query backward (training, desc.cls_top): the backward of attn_cls_fwd_kernel<T, false, DROP> for one (utterance, head).  Nothing
+// of the forward is kept but the compact context: the softmax row is recomputed from q and K, the dropout decisions are hashed again
+// (element (bh S + 0) S + key).  With dO the [64] gradient of the CLS context, delta = dO . ctx, p the probabilities, pt the dropped
+// and rescaled ones, dp_j = keep_j scale_drop (dO . v_j), ds_j = p_j (dp_j - delta) scale:
+//   dV_j = pt_j dO,   dK_j = ds_j q,   dQ_0 = sum_j ds_j k_j,   dQ_i = 0 for i > 0
+// - every element of the head's 3 x 64 columns of dqkv [S][3H] is written exactly once (masked keys: zero), so the caller needs no
+// memset, and the column sums of dQ | dK | dV over the S rows go to colpart [B][3H] in a fixed order (no atomics).
+// =================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void attn_cls_bwd_kernel(const T* __restrict__ qkv, const uint8_t* __restrict__ mask,
+                                                           const T* __restrict__ ctx, const T* __restrict__ dctx, T* __restrict__ dqkv,
+                                                           float* __restrict__ colpart, int S, int heads, int H, float scale, DropCfg drop) {
+  constexpr bool kF32 = sizeof(T) == 4;
+  constexpr int VEC = 16 / (int)sizeof(T);
+  constexpr int LPK = 64 / VEC;
+  constexpr int KPP = 256 / LPK;
+  __shared__ float sp[512];    // scores, then ds
+  __shared__ float spt[512];   // dO . v, then pt
+  __shared__ float qs[64], dos[64];
+  __shared__ float part[3][KPP][65];   // dQ_0 | column sums of dK | of dV, per key group
+  __shared__ float red[9];
+  const int tid = threadIdx.x, sub = tid % LPK, kg = tid / LPK, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+  const int64_t ld = 3 * (int64_t)H;
+  const T* base = qkv + (int64_t)b * S * ld + h * 64;   // q = row 0; K at + H, V at + 2 H of every row
+  T* dbase = dqkv + (int64_t)b * S * ld + h * 64;
+  const uint8_t* mk = mask + (int64_t)b * S;
+  auto load = [](const T* p, float* v) {
+    if constexpr (kF32) {
+      const f32x4 x = *(const f32x4*)p;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = x[e];
+    } else {
+      const bf16x8 x = __builtin_bit_cast(bf16x8, *(const i32x4*)p);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
+    }
+  };
+  auto store = [](T* p, const float* v) {
+    if constexpr (kF32) {
+      f32x4 x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = v[e];
+      *(f32x4*)p = x;
+    } else {
+      bf16x8 x;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = (bf16)v[e];
+      *(i32x4*)p = __builtin_bit_cast(i32x4, x);
+    }
+  };
+  if (wave == 0) {
+    const float qv = (float)base[lane], dv = (float)dctx[(int64_t)b * H + h * 64 + lane];
+    qs[lane] = qv; dos[lane] = dv;
+    const float dl = wave_sum(dv * (float)ctx[(int64_t)b * H + h * 64 + lane]);
+    if (lane == 0) red[8] = dl;
+  }
+  __syncthreads();
+  // ---- scores and dO . v: one lane per key, sequential over d ----
+  float mloc = -INFINITY;
+  for (int j = tid; j < S; j += 256) {
+    const T* kp = base + (int64_t)j * ld + H;
+    float d = 0.f, dv = 0.f;
+#pragma unroll
+    for (int c = 0; c < 64; c += VEC) {
+      float kr[VEC], vr[VEC];
+      load(kp + c, kr);
+      load(kp + H + c, vr);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) { d = fmaf(qs[c + e], kr[e], d); dv = fmaf(dos[c + e], vr[e], dv); }
+    }
+    const float sv = mk[j] ? d * scale : -INFINITY;
+    sp[j] = sv; spt[j] = dv;
+    mloc = fmaxf(mloc, sv);
+  }
+  mloc = wave_max(mloc);
+  if (lane == 0) red[wave] = mloc;
+  __syncthreads();
+  const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float mxs = (mx == -INFINITY) ? 0.f : mx;
+  auto ex = [&](float v) { return kF32 ? expf(v - mxs) : __expf(v - mxs); };
+  float sum = 0.f;
+  for (int j = tid; j < S; j += 256) sum += ex(sp[j]);
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  const float lse = mxs + logf(sum), inv = 1.0f / sum, delta = red[8];
+  for (int j = tid; j < S; j += 256) {
+    const float v = sp[j];
+    const float p = (v == -INFINITY) ? 0.f : (kF32 ? expf(v - lse) : ex(v) * inv);
+    float ks = 1.f;
+    if (drop.thr16) ks = nb_keep(drop, (uint32_t)((bh * S) * S + j)) ? drop.scale : 0.f;
+    // bf16: pt and ds are rounded to bf16 where the full kernels round them (they are MFMA operands there: P^T for dV, dS for dK and dQ)
+    const float ds = p * (spt[j] * ks - delta) * scale;
+    sp[j] = kF32 ? ds : (float)(bf16)ds;
+    spt[j] = kF32 ? p * ks : (float)(bf16)(p * ks);
+  }
+  __syncthreads();
+  // ---- dK, dV and the zero rows of dQ; partial dQ_0 and column sums per key group ----
+  float dq[VEC], ck[VEC], cv[VEC], zero[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) dq[e] = ck[e] = cv[e] = zero[e] = 0.f;
+  for (int j = kg; j < S; j += KPP) {
+    const float ds = sp[j], pt = spt[j];
+    float kr[VEC], ok[VEC], ov[VEC];
+    load(base + (int64_t)j * ld + H + sub * VEC, kr);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      ok[e] = ds * qs[sub * VEC + e];
+      ov[e] = pt * dos[sub * VEC + e];
+      dq[e] = fmaf(ds, kr[e], dq[e]);
+      ck[e] += ok[e]; cv[e] += ov[e];
+    }
+    T* row = dbase + (int64_t)j * ld + sub * VEC;
+    if (j > 0) store(row, zero);
+    store(row + H, ok);
+    store(row + 2 * H, ov);
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    part[0][kg][sub * VEC + e] = dq[e];
+    part[1][kg][sub * VEC + e] = ck[e];
+    part[2][kg][sub * VEC + e] = cv[e];
+  }
+  __syncthreads();
+  if (tid < 192) {
+    const int which = tid >> 6;   // wave-uniform
+    float acc = 0.f;
+#pragma unroll
+    for (int g = 0; g < KPP; ++g) acc += part[which][g][lane];
+    if (which == 0) {
+      if constexpr (kF32) dbase[lane] = acc;
+      else dbase[lane] = (bf16)acc;
+    }
+    if (colpart) colpart[(int64_t)b * 3 * H + which * H + h * 64 + lane] = acc;
   }
 }
 
@@ -1516,7 +1670,8 @@ extern "C" int nbest_attention_fwd(const void* qkv, const uint8_t* key_mask, voi
 }
 
 int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
-                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
+                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream, float drop_p,
+                                     uint64_t seed, uint32_t drop_stream) {
   NB_CHECK(q && kv && key_mask && ctx, NBEST_ERR_ARG, "attention_cls_fwd: null pointer");
   NB_CHECK(B > 0 && S > 0 && heads > 0, NBEST_ERR_SHAPE, "attention_cls_fwd: bad shape");
   NB_CHECK(d == 64, NBEST_ERR_SHAPE, "attention_cls_fwd: head dimension %d not supported (64 only)", d);
@@ -1529,19 +1684,56 @@ int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv,
   NB_CHECK(((uintptr_t)q & 15) == 0 && ((uintptr_t)kv & 15) == 0, NBEST_ERR_ALIGN, "attention_cls_fwd: q and kv must be 16-byte aligned");
   const float scale = 1.0f / sqrtf((float)d);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == NBEST_F32)
+  const DropCfg dc = make_drop(drop_p, seed, drop_stream);
+  if (dc.thr16) {   // the keep decisions of query 0 in the full kernels' counter stream
+    if (int e = check_common("attention_cls_fwd", B, S, heads, d, dtype)) return e;
+    if (dtype == NBEST_F32)
+      attn_cls_fwd_kernel<float, false, true><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, (float*)ctx,
+                                                                         ldctx, S, heads, H, scale, nullptr, 0, dc);
+    else
+      attn_cls_fwd_kernel<bf16, false, true><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, (bf16*)ctx,
+                                                                        ldctx, S, heads, H, scale, nullptr, 0, dc);
+  } else if (dtype == NBEST_F32)
     attn_cls_fwd_kernel<float, false><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, (float*)ctx, ldctx, S,
-                                                                 heads, H, scale, nullptr, 0);
+                                                                 heads, H, scale, nullptr, 0, DropCfg{});
   else
     attn_cls_fwd_kernel<bf16, false><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, (bf16*)ctx, ldctx, S,
-                                                                heads, H, scale, nullptr, 0);
+                                                                heads, H, scale, nullptr, 0, DropCfg{});
   NB_LAUNCH_CHECK();
   return NBEST_OK;
 }
 
 extern "C" int nbest_attention_cls_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
                                        int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream) {
-  return nbest_attention_cls_fwd_internal(q, ldq, kv, ldkv, key_mask, ctx, ldctx, B, S, heads, d, dtype, stream);
+  return nbest_attention_cls_fwd_internal(q, ldq, kv, ldkv, key_mask, ctx, ldctx, B, S, heads, d, dtype, stream, 0.f, 0, 0);
+}
+
+// The backward of the one-query attention (training, desc.cls_top): qkv [B S][3H] as the forward read it, ctx / dctx [B][H] the compact
+// CLS context and its gradient.  Writes dqkv [B S][3H] in full and, with dbias, the QKV bias gradient through the partial rows [B][3H]
+// in `ws` (summed by the fixed-order finalize, as nbest_internal_attention_bwd8).
+int nbest_internal_attention_cls_bwd(const void* qkv, const uint8_t* key_mask, const void* ctx, const void* dctx, void* dqkv, float* dbias,
+                                     int accumulate, void* ws, size_t ws_bytes, int B, int S, int heads, int d, int dtype, float drop_p,
+                                     uint64_t seed, uint32_t drop_stream, nbest_stream_t stream) {
+  NB_CHECK(qkv && key_mask && ctx && dctx && dqkv, NBEST_ERR_ARG, "attention_cls_bwd: null pointer");
+  if (int e = check_common("attention_cls_bwd", B, S, heads, d, dtype)) return e;
+  NB_CHECK(S <= 512, NBEST_ERR_SHAPE, "attention_cls_bwd: S=%d > 512", S);
+  const int H = heads * d;
+  NB_CHECK(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0 && ((uintptr_t)dctx & 15) == 0,
+           NBEST_ERR_ALIGN, "attention_cls_bwd: pointers must be 16-byte aligned");
+  NB_CHECK(!dbias || (ws && ws_bytes >= (size_t)B * 3 * H * sizeof(float)), NBEST_ERR_WORKSPACE, "attention_cls_bwd: workspace too small");
+  const float scale = 1.0f / sqrtf((float)d);
+  const DropCfg dc = make_drop(drop_p, seed, drop_stream);
+  float* colpart = dbias ? (float*)ws : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == NBEST_F32)
+    attn_cls_bwd_kernel<float><<<B * heads, 256, 0, st>>>((const float*)qkv, key_mask, (const float*)ctx, (const float*)dctx, (float*)dqkv,
+                                                          colpart, S, heads, H, scale, dc);
+  else
+    attn_cls_bwd_kernel<bf16><<<B * heads, 256, 0, st>>>((const bf16*)qkv, key_mask, (const bf16*)ctx, (const bf16*)dctx, (bf16*)dqkv,
+                                                         colpart, S, heads, H, scale, dc);
+  NB_LAUNCH_CHECK();
+  if (dbias) return nbest_internal_partial_rows_sum(colpart, B, 3 * H, dbias, accumulate, st);
+  return NBEST_OK;
 }
 
 extern "C" int nbest_attention_probs(const void* qkv, const uint8_t* key_mask, const float* lse, float* probs, int B, int S, int heads,
@@ -1583,10 +1775,10 @@ int nbest_internal_attention_cls_probs(const void* q, int64_t ldq, const void* k
   hipStream_t st = (hipStream_t)stream;
   if (dtype == NBEST_F32)
     attn_cls_fwd_kernel<float, true><<<B * heads, 256, 0, st>>>((const float*)q, ldq, (const float*)kv, ldkv, key_mask, nullptr, 0, S,
-                                                                heads, H, scale, probs, ldp);
+                                                                heads, H, scale, probs, ldp, DropCfg{});
   else
     attn_cls_fwd_kernel<bf16, true><<<B * heads, 256, 0, st>>>((const bf16*)q, ldq, (const bf16*)kv, ldkv, key_mask, nullptr, 0, S,
-                                                               heads, H, scale, probs, ldp);
+                                                               heads, H, scale, probs, ldp, DropCfg{});
   NB_LAUNCH_CHECK();
   return NBEST_OK;
 }

@@ -269,6 +269,8 @@ static WsLayout ws_layout(const nbest_encoder_desc* d, const Sizes& z, const Wgr
   w.red_bytes = std::max(w.red_bytes, al((size_t)((M + 127) / 128) * 2 * d->F * sizeof(float)));   // fused column sums of the dU GEMM
   w.red = take(o, 4 * w.red_bytes);     // four regions: the partial rows of a layer's four producers live until its one finalize
   w.slab_bytes = al(max_splitk_bytes(d, M));
+  // desc.cls_top: the top layer's gradients over K = B rows (whatever the flag says: it is set per call, the workspace is sized once)
+  w.slab_bytes = std::max(w.slab_bytes, al(max_splitk_bytes(d, d->B)));
   w.slab = take(o, w.slab_bytes);
   w.emb_bytes = al(nbest_embed_bwd_ws_bytes(M, d->H));
   w.emb = take(o, w.emb_bytes);
@@ -323,6 +325,31 @@ static int check_desc(const nbest_encoder_desc* d) {
   NB_CHECK(!d->head_gate || d->first_trainable == 0, NBEST_ERR_ARG, "encoder: head_gate needs first_trainable == 0 (got %d)", d->first_trainable);
   NB_CHECK(!d->head_gate_grad || d->head_gate, NBEST_ERR_ARG, "encoder: head_gate_grad without head_gate");
   return NBEST_OK;
+}
+
+// desc.cls_top (the top layer on the CLS rows only; include/nbest_hip.h): what the training entry points refuse it with.  The inference
+// entry points ignore the field and do not come here.
+static int check_cls_top(const nbest_encoder_desc* d) {
+  if (!d->cls_top) return NBEST_OK;
+  NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder: cls_top is not supported with the fp8 forward / backward (desc.w8)");
+  NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder: cls_top is not supported with head_gate (the gate runs on the full-width context)");
+  NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder: cls_top is not supported with interpolated embeddings (base_ids / alpha)");
+  NB_CHECK(!d->no_param_grad, NBEST_ERR_ARG, "encoder: cls_top is not supported with no_param_grad");
+  // (first_trainable == L is NOT refused: the forward then runs the top layer on the CLS rows of the frozen layers' scratch, and the heads of
+  // an all-frozen encoder see the bits they see above a trainable one - tests/test_freeze_gpu.py holds their gradients to bit equality)
+  NB_CHECK(d->S >= 2, NBEST_ERR_SHAPE, "encoder: cls_top needs S >= 2 (got %d)", d->S);
+  return NBEST_OK;
+}
+static bool cls_layer_of(const nbest_encoder_desc* d, int l) { return d->cls_top && l == d->L - 1; }
+
+// The flags of the grouped / window queue of a backward call that ends at layer_end: desc.wgrad_skip_host (NULL: none), plus - cls_top,
+// layer_end == L - the top layer's attention-out, FFN-up and FFN-down gradients, which are plain launches over the B CLS rows.
+static std::vector<uint8_t> queue_skip(const nbest_encoder_desc* d, int layer_end) {
+  std::vector<uint8_t> s((size_t)4 * d->L, 0);
+  if (d->wgrad_skip_host) std::copy(d->wgrad_skip_host, d->wgrad_skip_host + (size_t)4 * d->L, s.begin());
+  if (d->cls_top && layer_end == d->L)
+    for (int j = 1; j < 4; ++j) s[(size_t)4 * (d->L - 1) + j] = 1;
+  return s;
 }
 
 struct Ptrs {
@@ -528,16 +555,62 @@ static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const
   return NBEST_OK;
 }
 
+// The top layer with desc.cls_top: the QKV projection over all M rows as layer_forward, everything after it on the B CLS rows (row 0 of
+// each utterance).  The compact tensors are the first B rows of the layer's stash regions; rows B .. 2B-1 of r2 are scratch (the GEMM
+// outputs ahead of the dropout, then the LayerNorm output on its way to rows b S of xout).  Dropout: the attention kernel hashes
+// query 0's counters; the hidden dropout follows the GEMMs (bias-only epilogue) in a small kernel that hashes row b S of the
+// full-width tensor (nbest_internal_rows_drop_res) - the GEMM kernels are untouched.  Weights are read unpacked.
+static int layer_forward_cls(const Fwd& c, int l, const void* xin, void* xout, const LayerBufs& b) {
+  const nbest_encoder_desc* d = c.d;
+  const nbest_layer_offsets& o = d->layers_host[l];
+  const Ptrs& P = c.g.W;
+  const nbest_stream_t stream = c.g.stream;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d->H, F = d->F, dt = d->dtype, t = 4 * l;
+  const int64_t B = d->B, SH = (int64_t)d->S * H;
+  const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
+  const bool hdrop = d->hidden_drop > 0.f;
+  void* tmp = (char*)b.r2 + (size_t)B * H * P.esz;
+  const GemmOp wqkv = {xin, nullptr, t + 0, o.wqkv, t + 0, b.qkv, 3 * H, H, NBEST_EPI_BIAS, P.P(o.bqkv)};
+  RUN(layer_gemm(c.g, wqkv));
+  // q = row 0 of each utterance (ldq = S 3H), K | V = the second and third thirds of every row -> ctx [B][H]
+  RUN(nbest_attention_cls_fwd_internal(b.qkv, SH * 3, (const char*)b.qkv + H * P.esz, 3 * H, c.key_mask, b.ctx, H, d->B, d->S, d->heads, 64, dt,
+                                       stream, d->attn_drop, d->seed, s0 + 0));
+  // a GEMM of the B rows + bias, dropout and the residual rows R (row stride ldr) -> out [B][N]
+  auto dense_drop_res = [&](const void* A, int64_t w_off, const float* bias, int64_t N, int64_t K, const void* R, int64_t ldr, uint32_t ds,
+                            void* out) -> int {
+    nbest_gemm_args g = gemm_nt(dt, A, P.W(w_off), hdrop ? tmp : out, B, N, K);
+    g.bias = bias;
+    if (hdrop) {
+      g.epilogue = NBEST_EPI_BIAS;
+      RUN(nbest_gemm(&g, stream));
+      return nbest_internal_rows_drop_res(tmp, N, R, ldr, out, N, B, (int)N, d->S, dt, d->hidden_drop, d->seed, ds, st);
+    }
+    g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.R = R; g.ldr = ldr;
+    return nbest_gemm(&g, stream);
+  };
+  RUN(dense_drop_res(b.ctx, o.wo, P.P(o.bo), H, H, xin, SH, s0 + 1, b.r1));
+  RUN(nbest_internal_layernorm_fwd8(b.r1, P.P(o.ln1_g), P.P(o.ln1_b), b.x1, nullptr, b.st1, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
+  nbest_gemm_args g = gemm_nt(dt, b.x1, P.W(o.w1), b.hact, B, F, H);
+  g.epilogue = NBEST_EPI_BIAS_GELU; g.bias = P.P(o.b1); g.U = b.u; g.ldu = F;
+  RUN(nbest_gemm(&g, stream));
+  RUN(dense_drop_res(b.hact, o.w2, P.P(o.b2), H, F, b.x1, H, s0 + 2, b.r2));
+  RUN(nbest_internal_layernorm_fwd8(b.r2, P.P(o.ln2_g), P.P(o.ln2_b), tmp, nullptr, b.st2, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
+  return nbest_internal_rows_drop_res(tmp, H, nullptr, 0, xout, SH, B, H, 1, dt, 0.f, 0, 0, st);   // -> rows b S of the hidden state
+}
+
 }  // namespace
 
 extern "C" size_t nbest_encoder_act_bytes(const nbest_encoder_desc* d) { return d ? act_layout(d, sizes(d)).total : 0; }
 
 extern "C" int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, int layer, void** qkv, float** lse) {
   RUN(check_desc(d));
+  RUN(check_cls_top(d));
   NB_CHECK(act && qkv && lse, NBEST_ERR_ARG, "encoder_act_view: null pointer");
   NB_CHECK(0 <= layer && layer < d->L, NBEST_ERR_ARG, "encoder_act_view: layer %d outside [0, L=%d)", layer, d->L);
   const ActLayout a = act_layout(d, sizes(d));
   NB_CHECK(layer >= a.K, NBEST_ERR_ARG, "encoder_act_view: layer %d < first_trainable %d (frozen layers are not stashed)", layer, a.K);
+  NB_CHECK(!cls_layer_of(d, layer), NBEST_ERR_ARG, "encoder_act_view: layer %d of a cls_top stash has no lse (its attention ran on the CLS rows only)", layer);
   const LayerBufs b = stashed_layer(d, a, act, layer);
   *qkv = b.qkv; *lse = b.lse;
   return NBEST_OK;
@@ -559,10 +632,12 @@ extern "C" int nbest_encoder_wgrad_plan(const nbest_encoder_desc* d, int layer_b
   NB_CHECK(d && d->B > 0 && d->S > 0 && d->L > 0 && d->H > 0 && d->F > 0, NBEST_ERR_ARG, "encoder_wgrad_plan: bad descriptor");
   NB_CHECK(first_trainable(d) <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_wgrad_plan: bad layer range");
   NB_CHECK(out || cap <= 0, NBEST_ERR_ARG, "encoder_wgrad_plan: null pointer");
+  RUN(check_cls_top(d));
   const WgradMode wm = wgrad_mode(d);
   std::vector<int32_t> v = {wm.mode, wm.gl + wm.sets, -1, 0};
   if (wm.sets > 0) {
-    const WinPlan wp = window_plan(d, layer_begin, layer_end, d->wgrad_skip_host, d->no_param_grad != 0, true, wm.sets);
+    const std::vector<uint8_t> qskip = queue_skip(d, layer_end);
+    const WinPlan wp = window_plan(d, layer_begin, layer_end, qskip.data(), d->no_param_grad != 0, true, wm.sets);
     v[2] = wp.peel_layer; v[3] = (int32_t)wp.launches.size();
     for (const WinLaunch& w : wp.launches) {
       v.insert(v.end(), {w.after_layer, w.tiles, w.n});
@@ -577,6 +652,7 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
                                      const int64_t* seg, const int64_t* pos, const uint8_t* key_mask, void* act, size_t act_bytes,
                                      void* ws, size_t ws_bytes, void** hidden_out, nbest_stream_t stream) {
   RUN(check_desc(d));
+  RUN(check_cls_top(d));
   NB_CHECK(wts && prm && ids && pos && key_mask && act, NBEST_ERR_ARG, "encoder_forward: null pointer");
   const Sizes z = sizes(d);
   const ActLayout a = act_layout(d, z);
@@ -607,7 +683,8 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
                            (hipStream_t)stream));
   for (int l = 0; l < d->L; ++l) {
     uint8_t* x8_next = (l + 1 < d->L) ? bufs(l + 1).x8 : nullptr;   // the last LayerNorm's copy has no reader
-    RUN(layer_forward(c, l, X(l), X(l + 1), bufs(l), x8_next, nullptr));
+    if (cls_layer_of(d, l)) RUN(layer_forward_cls(c, l, X(l), X(l + 1), bufs(l)));
+    else RUN(layer_forward(c, l, X(l), X(l + 1), bufs(l), x8_next, nullptr));
   }
   if (hidden_out) *hidden_out = X(d->L);
   return NBEST_OK;
@@ -628,6 +705,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
                                       void* act, size_t act_bytes, void* dhidden, void* ws, size_t ws_bytes, int accumulate,
                                       int layer_begin, int layer_end, int with_embeddings, nbest_stream_t stream) {
   RUN(check_desc(d));
+  RUN(check_cls_top(d));
   NB_CHECK(0 <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_backward: bad layer range");
   // no_param_grad: dhidden only (attribution) - no weight-gradient GEMM, no bias / LayerNorm-parameter gradient, grad may be NULL
   const bool npg = d->no_param_grad != 0;
@@ -659,7 +737,10 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   auto G = [&](int64_t off) { return grad + off; };
   auto GP = [&](int64_t off) -> float* { return npg ? nullptr : grad + off; };   // a bias / LayerNorm-parameter gradient (none: no_param_grad)
   // frozen matrices (desc.wgrad_skip_host[4 l + {0: QKV, 1: attention-out, 2: FFN-up, 3: FFN-down}]): no weight-gradient GEMM
-  auto skip = [&](int l, int j) -> bool { return npg || (d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]); };
+  // (cls_top: also the top layer's three gradients over the CLS rows, which are plain launches of their own - frozen: the caller's flags alone)
+  const std::vector<uint8_t> qskip = queue_skip(d, layer_end);
+  auto skip = [&](int l, int j) -> bool { return npg || qskip[4 * l + j]; };
+  auto frozen = [&](int l, int j) -> bool { return npg || (d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]); };
   void* dA = dhidden; void* dR = W + w.dR;
   const bool hdrop = d->hidden_drop > 0.f;
   void* dRd = hdrop ? (void*)(W + w.dRd) : dR;
@@ -732,7 +813,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   // attention-out, FFN-up, FFN-down, the higher layer first.  A layer left without a partner (odd range; plan mode) issues its
   // split-K launches back to back instead.  One event pair per layer (include/nbest_hip.h, wgrad_events).
   nbest_gemm_args pend[8];
-  int n_pend = 0;
+  int n_pend = 0, cls_pair = 0;   // cls_pair: the group's first layer (desc.cls_top) has recorded its pair already
   // Windows: the gradients of a layer wait in the queue of window_plan; its launches go out at the end of the layer that completes them,
   // the peeled pair and the remainder at the end of the range's lowest layer.  One event pair per layer of the range: a pair brackets each
   // window launch (the peeled pair launch inside the pair of the window next to it), the pairs left over are recorded back to back at
@@ -741,7 +822,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   WinPlan wp;
   std::vector<nbest_gemm_args> wargs;   // [4 (layer_end - 1 - l) + j]
   if (window) {
-    wp = window_plan(d, layer_begin, layer_end, d->wgrad_skip_host, npg, true, wm.sets);
+    wp = window_plan(d, layer_begin, layer_end, qskip.data(), npg, true, wm.sets);
     wargs.resize((size_t)4 * nl);
   }
   size_t wi = 0;            // next launch of wp
@@ -768,52 +849,120 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       dRd2 = W + w.gset[gpos][0]; dBigL = W + w.gset[gpos][1]; dRd1 = W + w.gset[gpos][2]; dqkvL = W + w.gset[gpos][3];
       if (!hdrop) { dR2 = dRd2; dR1 = dRd1; }
     }
+    // desc.cls_top, top layer: everything but dqkv is [B][.], the CLS rows - two compact buffers in each of the shared dR, dRd and dB1
+    // regions (S >= 2), one in dctx and dBig; the gradients of Wo, W1 and W2 read them and the first B rows of the stash regions
+    const bool cls = cls_layer_of(d, l);
+    if (cls) {
+      const size_t bh = (size_t)d->B * H * z.esz;   // (a multiple of 128 bytes: H % 64 == 0)
+      dR2 = W + w.dR; dR1 = W + w.dB1 + bh; dBigL = dBig;
+      dRd2 = hdrop ? (void*)(W + w.dRd) : dR2; dRd1 = hdrop ? (void*)(W + w.dRd + bh) : dR1;
+    }
     const WGrad wg[4] = {{dqkvL, X(l), dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0},
                          {dRd1, b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},
                          {dBigL, b.x1, dBig8, b.x18, o.w1, F, H, t + 1, t + 2},
                          {dRd2, b.hact, dRd8, b.h8, o.w2, H, F, t + 0, t + 3}};
+    // cls: gradient j (1: attention-out, 2: FFN-up, 3: FFN-down) of the top layer over its K = B token rows, one plain launch
+    auto cls_wgrad = [&](int j) -> int {
+      if (frozen(l, j)) return NBEST_OK;
+      nbest_gemm_args g = wgrad_args(dt, wg[j].rows, wg[j].cols, d->B);
+      g.A = wg[j].dY; g.B = wg[j].X; g.C = G(wg[j].w_off); g.accumulate = accumulate;
+      g.ws = slab; g.ws_bytes = w.slab_bytes;
+      return nbest_gemm(&g, stream);
+    };
+    auto cls_wgrads = [&]() -> int {
+      RUN(cls_wgrad(3));
+      RUN(cls_wgrad(2));
+      return cls_wgrad(1);
+    };
     if (!npg) nbest_internal_rowred_batch_begin();    // the layer's four bias / LayerNorm-parameter reductions: one finalize launch at its end
-    // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
-    // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
-    RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), dR2, (hdrop && !f8b) ? dRd2 : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H,
-                                      dt, accumulate, d->hidden_drop, d->seed, s0 + 2, red, w.red_bytes, stream, fg(dRd8, t + 0)));   // partial rows: region 0
-    // FFN-down: dgrad fused with GELU' -> dU ; wgrad
-    // (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
-    GemmOp dw2 = {dRd2, dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : dBigL, F, H, NBEST_EPI_DGELU};
-    dw2.U = b.u; dw2.colsum = GP(o.b1); dw2.C8 = dBig8; dw2.c_idx = t + 1;
-    RUN(layer_gemm(dg, dw2));
-    if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBigL, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
-    if (!deferred) RUN(wgrad(l, wg, 3, -1));
-    // FFN-up: dgrad + residual gradient ; wgrad
-    GemmOp dw1 = {dBigL, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
-    dw1.R = dR2;
-    RUN(layer_gemm(dg, dw1));
-    if (!deferred) RUN(wgrad(l, wg, 2, -1));
-    // LN1 backward
-    RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, (hdrop && !f8b) ? dRd1 : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
-                                      dt, accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, t + 2)));
-    // attention output projection: dgrad ; wgrad
-    const GemmOp dwo = {dRd1, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
-    RUN(layer_gemm(dg, dwo));
-    // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
-    if (!paired && !deferred) RUN(wgrad(l, wg, 1, -1));
-    // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
-    // (per utterance), and scaled by the gate it is the gradient the attention backward takes
-    if (d->head_gate)
-      RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads,
-                              d->head_gate_grad ? d->head_gate_grad + (int64_t)l * d->B * d->heads : nullptr, d->B, d->S, d->heads, 64, dt, stream));
-    // attention backward -> dqkv ; QKV bias gradient
-    RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkvL, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
-                                      d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, t + 3), b.keep));
-    // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad (with the attention-out gradient when paired)
-    if (input_grad) {
-      GemmOp dwqkv = {dqkvL, dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
-      dwqkv.R = dR1;
-      RUN(layer_gemm(dg, dwqkv));
+    if (cls) {
+      const int64_t Bn = d->B, SH = (int64_t)d->S * H;
+      const size_t bh = (size_t)Bn * H * z.esz, half = w.red_bytes / 2;
+      void* dAc = W + w.dR + bh;   // the CLS rows of dhidden
+      GemmPass dgc = dg;           // the dgrads of the B rows: weights read unpacked
+      dgc.M = Bn; dgc.packed = nullptr;
+      const Fp8Grad nof8 = {nullptr, nullptr, nullptr};
+      RUN(nbest_internal_rows_drop_res(dA, SH, nullptr, 0, dAc, H, Bn, H, 1, dt, 0.f, 0, 0, st));
+      // LayerNorm backwards without dropout; the dense branch's mask (the decisions of rows b S) and the bias gradient under it follow
+      // in a small kernel and a fixed-order column sum (partial rows: the upper half of the LayerNorm's region)
+      RUN(nbest_internal_layernorm_bwd8(dAc, b.r2, b.st2, P.P(o.ln2_g), dR2, nullptr, G(o.ln2_g), G(o.ln2_b), hdrop ? nullptr : G(o.b2), Bn, H, dt,
+                                        accumulate, 0.f, 0, 0, red, half, stream, nof8));
+      if (hdrop) {
+        RUN(nbest_internal_rows_drop_res(dR2, H, nullptr, 0, dRd2, H, Bn, H, d->S, dt, d->hidden_drop, d->seed, s0 + 2, st));
+        RUN(nbest_colsum(dRd2, G(o.b2), Bn, H, H, dt, accumulate, (char*)red + half, half, stream));
+      }
+      GemmOp dw2 = {dRd2, nullptr, t + 0, o.w2, t + 3, dBigL, F, H, NBEST_EPI_DGELU};
+      dw2.U = b.u; dw2.colsum = G(o.b1);
+      RUN(layer_gemm(dgc, dw2));
+      GemmOp dw1 = {dBigL, nullptr, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
+      dw1.R = dR2;
+      RUN(layer_gemm(dgc, dw1));
+      RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, nullptr, G(o.ln1_g), G(o.ln1_b), hdrop ? nullptr : G(o.bo), Bn, H, dt,
+                                        accumulate, 0.f, 0, 0, red2, half, stream, nof8));
+      if (hdrop) {
+        RUN(nbest_internal_rows_drop_res(dR1, H, nullptr, 0, dRd1, H, Bn, H, d->S, dt, d->hidden_drop, d->seed, s0 + 1, st));
+        RUN(nbest_colsum(dRd1, G(o.bo), Bn, H, H, dt, accumulate, (char*)red2 + half, half, stream));
+      }
+      const GemmOp dwo = {dRd1, nullptr, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
+      RUN(layer_gemm(dgc, dwo));
+      // one-query attention backward: the layer's dQ|dK|dV in full (dQ zero outside the CLS rows) ; QKV bias gradient
+      RUN(nbest_internal_attention_cls_bwd(b.qkv, key_mask, b.ctx, dctx, dqkvL, G(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S, d->heads, 64,
+                                           dt, d->attn_drop, d->seed, s0 + 0, stream));
+      // QKV dgrad as ever, its residual gradient zero outside the CLS rows (dctx [M][H] is free again)
+      if (input_grad) {
+        NB_CHECK(hipMemsetAsync(dctx, 0, (size_t)M * H * z.esz, st) == hipSuccess, NBEST_ERR_LAUNCH, "encoder_backward: memset failed");
+        RUN(nbest_internal_rows_drop_res(dR1, H, nullptr, 0, dctx, SH, Bn, H, 1, dt, 0.f, 0, 0, st));
+        GemmOp dwqkv = {dqkvL, nullptr, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
+        dwqkv.R = dctx;
+        RUN(layer_gemm(dg, dwqkv));
+      }
+    } else {
+      // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
+      // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
+      RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), dR2, (hdrop && !f8b) ? dRd2 : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H,
+                                        dt, accumulate, d->hidden_drop, d->seed, s0 + 2, red, w.red_bytes, stream, fg(dRd8, t + 0)));   // partial rows: region 0
+      // FFN-down: dgrad fused with GELU' -> dU ; wgrad
+      // (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
+      GemmOp dw2 = {dRd2, dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : dBigL, F, H, NBEST_EPI_DGELU};
+      dw2.U = b.u; dw2.colsum = GP(o.b1); dw2.C8 = dBig8; dw2.c_idx = t + 1;
+      RUN(layer_gemm(dg, dw2));
+      if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBigL, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
+      if (!deferred) RUN(wgrad(l, wg, 3, -1));
+      // FFN-up: dgrad + residual gradient ; wgrad
+      GemmOp dw1 = {dBigL, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
+      dw1.R = dR2;
+      RUN(layer_gemm(dg, dw1));
+      if (!deferred) RUN(wgrad(l, wg, 2, -1));
+      // LN1 backward
+      RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, (hdrop && !f8b) ? dRd1 : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
+                                        dt, accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, t + 2)));
+      // attention output projection: dgrad ; wgrad
+      const GemmOp dwo = {dRd1, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
+      RUN(layer_gemm(dg, dwo));
+      // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
+      if (!paired && !deferred) RUN(wgrad(l, wg, 1, -1));
+      // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
+      // (per utterance), and scaled by the gate it is the gradient the attention backward takes
+      if (d->head_gate)
+        RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads,
+                                d->head_gate_grad ? d->head_gate_grad + (int64_t)l * d->B * d->heads : nullptr, d->B, d->S, d->heads, 64, dt, stream));
+      // attention backward -> dqkv ; QKV bias gradient
+      RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkvL, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
+                                        d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, t + 3), b.keep));
+      // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad (with the attention-out gradient when paired)
+      if (input_grad) {
+        GemmOp dwqkv = {dqkvL, dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
+        dwqkv.R = dR1;
+        RUN(layer_gemm(dg, dwqkv));
+      }
     }
     if (window) {
       for (int j = 0; j < 4; ++j)
         if (!skip(l, j)) wargs[(size_t)4 * (layer_end - 1 - l) + j] = wgrad_args_of(wg + j);
+      if (cls) {   // the top layer's small launches open its pair
+        pair_begin();
+        RUN(cls_wgrads());
+      }
       if (l == wp.peel_layer) {
         pair_begin();   // today's split-K launches of the two: one launch where the pair fits it
         if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
@@ -834,10 +983,19 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       pair_end();   // (a peeled pair with no window after it)
       if (l == layer_begin)
         for (; pairs_used < nl; ++pairs_used) { stamp(0); stamp(1); }
+    } else if (!grouped && cls) {   // the layer's 3 or 4 pairs, in today's order, around its own launches
+      stamp(0); RUN(cls_wgrad(3)); stamp(1);
+      stamp(0); RUN(cls_wgrad(2)); stamp(1);
+      if (!paired) { stamp(0); RUN(cls_wgrad(1)); stamp(1); }
+      stamp(0);
+      if (paired) RUN(cls_wgrad(1));
+      RUN(wgrad_launch(l, wg, 0, -1));
+      stamp(1);
     } else if (!grouped) {
       RUN(wgrad(l, wg, 0, paired ? 1 : -1));
     } else if (group_ends && gpos + 1 < gl && d->wgrad_group != NBEST_WGRAD_GROUP_ALWAYS) {   // no partner: today's launches, one event pair
       stamp(0);
+      if (cls) RUN(cls_wgrads());
       RUN(wgrad_launch(l, wg, 3, -1));
       RUN(wgrad_launch(l, wg, 2, -1));
       if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
@@ -846,12 +1004,19 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     } else {
       for (int j = 0; j < 4; ++j)
         if (!skip(l, j)) pend[n_pend++] = wgrad_args_of(wg + j);
+      if (cls && !group_ends) {   // the top layer's own pair brackets its small launches; its QKV gradient waits for the group
+        stamp(0);
+        RUN(cls_wgrads());
+        stamp(1);
+        cls_pair = 1;
+      }
       if (group_ends) {
         stamp(0);
+        if (cls) RUN(cls_wgrads());
         if (n_pend) RUN(nbest_wgrad_group(pend, n_pend, stream));
         stamp(1);
-        for (int i = 0; i < gpos; ++i) { stamp(0); stamp(1); }
-        n_pend = 0;
+        for (int i = 0; i < gpos - cls_pair; ++i) { stamp(0); stamp(1); }
+        n_pend = 0; cls_pair = 0;
       }
     }
     if (!npg) RUN(nbest_internal_rowred_batch_flush(st));
@@ -944,7 +1109,7 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   g.lda = SH; g.epilogue = NBEST_EPI_BIAS; g.bias = P.P(o.bqkv);
   RUN(nbest_gemm(&g, stream));
   if (cls_attn) RUN(nbest_internal_attention_cls_probs(q, H, kv, 2 * H, key_mask, probs(l), d->S, d->B, d->S, d->heads, 64, dt, stream));
-  RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream));
+  RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream, 0.f, 0, 0));
   if (d->head_gate) RUN(nbest_head_gate_fwd(cctx, H, cctx, H, d->head_gate + (int64_t)l * d->heads, B, d->heads, 64, dt, stream));
   g = gemm_nt(dt, cctx, P.W(o.wo), cr, B, H, H);
   g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.bias = P.P(o.bo); g.R = xin; g.ldr = SH;        // residual: the CLS rows

@@ -22,6 +22,8 @@ int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* st
                                   size_t ws_bytes, nbest_stream_t stream, Fp8Grad f8);
 // out[N] (+)= the sum of the nrows partial rows part[nrows][N] (fused column sums of the GEMM and attention epilogues)
 int nbest_internal_partial_rows_sum(const float* part, int nrows, int N, float* out, int accumulate, hipStream_t st);
+int nbest_internal_rows_drop_res(const void* x, int64_t ldx, const void* R, int64_t ldr, void* y, int64_t ldy, int64_t rows, int N,
+                                 int64_t row_mul, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, hipStream_t st);
 void nbest_internal_rowred_batch_begin();
 void nbest_internal_rowred_batch_abort();
 int nbest_internal_rowred_batch_flush(hipStream_t st);
@@ -36,7 +38,11 @@ int nbest_internal_attention_bwd8(const void* qkv, const uint8_t* key_mask, cons
                                   const uint32_t* keep);
 size_t nbest_internal_attention_keep_bytes(int B, int S, int heads);
 int nbest_attention_cls_fwd_internal(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, void* ctx,
-                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
+                                     int64_t ldctx, int B, int S, int heads, int d, int dtype, nbest_stream_t stream, float drop_p,
+                                     uint64_t seed, uint32_t drop_stream);
+int nbest_internal_attention_cls_bwd(const void* qkv, const uint8_t* key_mask, const void* ctx, const void* dctx, void* dqkv, float* dbias,
+                                     int accumulate, void* ws, size_t ws_bytes, int B, int S, int heads, int d, int dtype, float drop_p,
+                                     uint64_t seed, uint32_t drop_stream, nbest_stream_t stream);
 int nbest_internal_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
                                        int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 

@@ -1499,6 +1499,49 @@ extern "C" int nbest_cls_grad_scatter(const float* dcls, void* dhidden, int B, i
   return NBEST_OK;
 }
 
+// ---- the CLS rows of the top layer (nbest_encoder_desc::cls_top) ----------------------------------------------------------------
+// y[r][c] = drop(x[r][c]) + R[r][c] over `rows` rows of N columns with row strides ldx, ldy, ldr (R == NULL: no residual).  The
+// dropout decision of element (r, c) is the one the full-width kernels take for row r * row_mul of an [.][N] tensor - counter
+// (r row_mul) N + c - so a compact [B][N] buffer of the CLS rows (row_mul = S) drops what the GEMM epilogue and the LayerNorm backward
+// drop at rows b S.  drop_p == 0: a strided row copy (gather / scatter of the CLS rows).  One thread per element pair.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void rows_drop_res_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ R, int64_t ldr,
+                                                            T* __restrict__ y, int64_t ldy, int64_t rows, int N, int64_t row_mul,
+                                                            DropCfg drop) {
+  const int half = N >> 1;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * half) return;
+  const int64_t r = i / half;
+  const int c = (int)(i - r * half) * 2;
+  float v0 = (float)x[r * ldx + c], v1 = (float)x[r * ldx + c + 1];
+  if (drop.thr16) {
+    const uint32_t k = nb_keep2(drop, (uint32_t)(r * row_mul * N + c));
+    v0 = (k & 1u) ? v0 * drop.scale : 0.f;
+    v1 = (k & 2u) ? v1 * drop.scale : 0.f;
+  }
+  if (R) { v0 += (float)R[r * ldr + c]; v1 += (float)R[r * ldr + c + 1]; }
+  y[r * ldy + c] = (T)v0;
+  y[r * ldy + c + 1] = (T)v1;
+}
+}  // namespace
+
+int nbest_internal_rows_drop_res(const void* x, int64_t ldx, const void* R, int64_t ldr, void* y, int64_t ldy, int64_t rows, int N,
+                                 int64_t row_mul, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, hipStream_t st) {
+  NB_CHECK(x && y && rows > 0 && N > 0 && N % 2 == 0 && ldx >= N && ldy >= N && (!R || ldr >= N), NBEST_ERR_ARG, "rows_drop_res: bad arguments");
+  const DropCfg d = make_drop(drop_p, seed, drop_stream);
+  NB_CHECK(d.thr16 == 0 || rows * row_mul * N < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "rows_drop_res: dropout counter overflow");
+  const int64_t n = rows * (N >> 1);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (dtype == NBEST_F32)
+    rows_drop_res_kernel<float><<<grid, 256, 0, st>>>((const float*)x, ldx, (const float*)R, ldr, (float*)y, ldy, rows, N, row_mul, d);
+  else if (dtype == NBEST_BF16)
+    rows_drop_res_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)x, ldx, (const bf16*)R, ldr, (bf16*)y, ldy, rows, N, row_mul, d);
+  else NB_CHECK(false, NBEST_ERR_DTYPE, "rows_drop_res: bad dtype %d", dtype);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
 extern "C" int nbest_cast_f32_to_bf16(const float* src, void* dst, int64_t n, nbest_stream_t stream) {
   NB_CHECK(src && dst && n >= 0, NBEST_ERR_ARG, "cast: bad arguments");
   if (n == 0) return NBEST_OK;

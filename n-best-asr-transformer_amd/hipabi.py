@@ -90,7 +90,7 @@ class EncoderDesc(C.Structure):
                 ("w8", C.c_void_p), ("w8_inv_scale", C.c_void_p), ("w8t", C.c_void_p), ("gamax_prev", C.c_void_p),
                 ("gamax_new", C.c_void_p), ("fp8_bwd", C.c_int32), ("pad2", C.c_int32),
                 ("wpk", C.c_void_p), ("wpkt", C.c_void_p), ("w8p", C.c_void_p), ("w8tp", C.c_void_p),
-                ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("pad4", C.c_int32),
+                ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("cls_top", C.c_int32),
                 ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p),
                 ("head_gate", C.c_void_p), ("head_gate_grad", C.c_void_p),
                 ("base_ids", C.c_void_p), ("alpha", C.c_void_p), ("no_param_grad", C.c_int32), ("pad5", C.c_int32)]

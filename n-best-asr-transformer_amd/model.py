@@ -116,10 +116,11 @@ class _Pass:
         self.B, self.S = B, S
 
 
-class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen plan")):
+class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen plan cls_top")):
     """one call's encoder pass: its _Pass, slot, (ids, seg, pos, mask), token permutation (None: sorted on the device when the
-    backward asks), hidden states [B*S, H] (a view into the slot's stash), the generation of that stash it wrote and the
-    FreezePlan it ran with (None: everything trainable, full stash)"""
+    backward asks), hidden states [B*S, H] (a view into the slot's stash), the generation of that stash it wrote, the
+    FreezePlan it ran with (None: everything trainable, full stash) and whether its top layer ran on the CLS rows only (then
+    only rows b S of ``hidden`` are written, and the backward must run with the same descriptor flag)"""
     __slots__ = ()
 
     @property
@@ -240,7 +241,10 @@ class NBestSTCModel(nn.Module):
         # weight gradients without K-splits (nbest_encoder_desc.wgrad_group, hipabi.WGRAD_GROUP_*): the library's plan decides, never (every
         # layer's split-K launches), two layers per launch wherever the shapes allow, or rolling windows of 256 tiles across the layers
         self.wgrad_group = int(wgrad_group)
-        self.arena = ParamArena(cfg, labels, self.device, compute_dtype)
+        # training passes run the top layer on the CLS rows only (nbest_encoder_desc.cls_top): nothing downstream reads another row
+        # of the final hidden state.  False: the full-width top layer (what the passes _cls_top_ok excludes run anyway)
+        self.cls_top = True
+        self.arena =ParamArena(cfg, labels, self.device, compute_dtype)
         # "fp8w" (BASELINE configs[4]): forward GEMMs on the block-scaled fp8 MFMA from an e4m3 copy of the weights; the
         # master weights, the backward and everything between the GEMMs stay as in the bf16 path
         self.fp8_forward = bool(fp8_forward)
@@ -458,7 +462,7 @@ class NBestSTCModel(nn.Module):
             seg = seg.contiguous()
         return ids, seg, pos, mask
 
-    def _encode(self, slot, ids, seg, train, perm=None, plan=None):
+    def _encode(self, slot, ids, seg, train, perm=None, plan=None, full_top=False):
         """one encoder pass through the C-ABI into the slot's stash; returns its _PassRecord.
         ``perm``: the pass's tokens sorted by word id (hipabi.word_perm; host-built by the data loaders) - only the backward
         reads it; None = sorted on the device when a backward pass asks for it.  ``plan``: the FreezePlan of a pass a backward
@@ -472,6 +476,7 @@ class NBestSTCModel(nn.Module):
         d.seed = self._step_seed()
         self._set_head_gate(d)
         self._set_weights(d, "forward")
+        d.cls_top = int(not full_top and self._cls_top_ok(train, S, plan))
         act, ws = self._stash[slot][:ps.act_bytes], self._ws
         out = C.c_void_p()
         hb.check(hb.lib().nbest_encoder_forward(C.byref(d), hb.ptr(self.arena.weights), hb.ptr(self.arena.p), hb.ptr(ids),
@@ -482,7 +487,13 @@ class NBestSTCModel(nn.Module):
         M, H = B * S, self.cfg.hidden_size
         esz = 2 if self.compute_dtype == torch.bfloat16 else 4
         hidden = act[off:off + M * H * esz].view(self.compute_dtype).view(M, H)
-        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot], plan)
+        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot], plan, bool(d.cls_top))
+
+    def _cls_top_ok(self, train, S, plan):
+        """a training pass runs its top layer on the CLS rows (``self.cls_top``) unless the library refuses the combination: the fp8
+        modes, a head mask.  Whatever is frozen (``plan``): an all-frozen encoder gives its heads the CLS rows a trainable one gives.
+        Eval passes keep the full-width layer: ``return_attns`` reads its lse from the stash."""
+        return self.cls_top and train and S >= 2 and not self.fp8_forward and self._head_mask is None
 
     def _packed_bf16_ok(self):
         """the packed bf16 weight copies (arena.wpk / wpkt) exist and are current: they are refreshed with the bf16 transposed
@@ -532,6 +543,7 @@ class NBestSTCModel(nn.Module):
         ps, d = rec.ps, rec.ps.desc
         B, S, H = ps.B, ps.S, self.cfg.hidden_size
         self._set_weights(d, "backward")
+        d.cls_top = int(rec.cls_top)              # as the forward that wrote this stash
         # gradient w.r.t. the final hidden states [B*S, H] (zero except the CLS rows), in a grow-only buffer like the stash
         dh = self._grow(vars(self), "_dh", B * S * H, self.compute_dtype)[:B * S * H].view(B * S, H)
         dh = hb.cls_grad_scatter(dcls, B, S, H, self.compute_dtype, out=dh)
@@ -578,14 +590,15 @@ class NBestSTCModel(nn.Module):
                             seed=self._step_seed(), drop_stream=900, dWh=dWh, dbh=dbh, ws=ws, soft=soft)
 
     def _passes_and_heads(self, ids, seg, trans_ids, trans_seg, train, from_transcript=False, labels_f=None, need_grad=False,
-                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None, rdrop=None):
+                          accumulate=False, perm=None, trans_perm=None, ws=None, plan=None, after_asr=None, distill=None, rdrop=None,
+                          full_top=False):
         """the ASR pass, the transcript pass when ``trans_ids`` is given, then the heads on the CLS rows of the one
         ``from_transcript`` picks.  Returns (ASR record, transcript record or None, the stc_heads outputs).
         ``after_asr(record)``: called right after the ASR pass, before any other pass can touch a stash."""
-        ra = self._encode(0, ids, seg, train, perm, plan)
+        ra = self._encode(0, ids, seg, train, perm, plan, full_top)
         if after_asr is not None:
             after_asr(ra)
-        rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan)
+        rt = None if trans_ids is None else self._encode(1, trans_ids, trans_seg, train, trans_perm, plan, full_top)
         r = rt if from_transcript else ra
         return ra, rt, self._heads(r.hidden, r.ps.S, labels_f, need_grad, train, accumulate, ws, distill, rdrop)
 
@@ -626,7 +639,7 @@ class NBestSTCModel(nn.Module):
         after = (lambda rec: attns.extend(self._attention_maps(rec))) if return_attns else None
         ra, rt, (top, bott, fin, _, _, _, _) = self._passes_and_heads(input_ids, seg_ids, trans_input_ids, trans_seg_ids, self.training,
                                                                       from_transcript=classifier_input_type == "transcript",
-                                                                      after_asr=after)
+                                                                      after_asr=after, full_top=return_attns)
         self._end_of_step(False, advance=False)
         trans_cls = None if rt is None else rt.cls.float()
         if return_attns:
