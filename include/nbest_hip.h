@@ -503,10 +503,14 @@ int nbest_stream_stamp(int32_t* flag, int32_t value, nbest_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * K9  multi-tensor BertAdam over flat arenas
  * replaces BertAdam.step (/root/reference/models/optimization.py:237-302) with the per-parameter
- * grouping of /root/reference/n_best_asr_bert.py:540-561: per tensor g *= min(1, 1/(||g||+1e-6));
- * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; u = m/(sqrt(v)+eps) [+ wd p]; p -= lr*lr_mult * u,
- * lr_mult = warmup-linear schedule value for this step (optimization.py:162-171; one scalar: every
- * tensor that receives gradients shares the same step count).
+ * grouping of the reference's n_best_asr_bert.py:540-561: per tensor c = min(1, max_grad_norm/(||g||+1e-6))
+ * (1 if max_grad_norm <= 0), g' = c g; m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; u = m/(sqrt(v)+eps)
+ * [+ wd p if wd > 0]; p -= lr*lr_mult * u, lr_mult = warmup-linear schedule value for this step
+ * (optimization.py:162-171; one scalar: every tensor that receives gradients shares the same step count).
+ * The clipped gradient g' lives in registers only: the arena g is READ, never written (the reference
+ * scales p.grad in place; nothing reads it between the step and the next zero_grad).  b1 and b2 are
+ * doubles: the kernels use (float)b and (float)(1 - b), the values torch's kernels receive from the
+ * reference's Python floats (1.f - 0.999f would be 1.29e-5 below 0.001f).
  * The arenas p, g, m, v are fp32; tensors are described by device descriptors ordered by offset.
  * block_start[t] = sum_{u<t} ceil(numel[u] / nbest_bertadam_chunk()); n_blocks = that sum over all
  * tensors.  If p_lowp != NULL the updated parameters are also written as bf16 at the same element
@@ -520,8 +524,8 @@ typedef struct nbest_tensor_desc {
   int32_t block_start;
 } nbest_tensor_desc;
 int nbest_bertadam_chunk(void);
-int nbest_bertadam_step(float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
-                        int n_tensors, int n_blocks, float lr_mult, float b1, float b2, float eps,
+int nbest_bertadam_step(float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                        int n_tensors, int n_blocks, float lr_mult, double b1, double b2, float eps,
                         float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* The same step in two halves over a range of blocks [blk_lo, blk_hi) (new functionality: the optimizer sharded over data-parallel
  * ranks).  norms: partial[blk] = sum of squares of block blk's gradient elements, for the blocks of the range (the caller zeroes
@@ -531,7 +535,7 @@ int nbest_bertadam_norms(const float* g, const nbest_tensor_desc* descs, int n_t
                          float* partial, nbest_stream_t stream);
 int nbest_bertadam_update(float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                           int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* partial, float* coef,
-                          float lr_mult, float b1, float b2, float eps, float max_grad_norm, nbest_stream_t stream);
+                          float lr_mult, double b1, double b2, float eps, float max_grad_norm, nbest_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * K9b  torch Adam / HF AdamW over the same arenas and descriptors, under ONE global-norm clip
  * (the reference's n_best_asr_bert.py:266-277,551-569, --optim_choice adam | adamw):
@@ -548,13 +552,15 @@ int nbest_bertadam_update(float* p, const float* g, float* m, float* v, void* p_
  * all tables back to back in one vector of n_partial floats (zeroed and SUM-all-reduced over the ranks when the optimizer is
  * sharded).  nbest_adam_clip_coef reduces it in a fixed order (fp64) into clip[0] = c, clip[1] = total norm (device memory:
  * no host synchronisation); nbest_adam_update then updates blocks [blk_lo, blk_hi) of one table, reading clip[0].
- * nbest_adam_step = norms + clip coefficient + update of one table; ws: >= (n_blocks + 2) floats.                       */
+ * nbest_adam_step = norms + clip coefficient + update of one table; ws: >= (n_blocks + 2) floats.  g is read, never written.
+ * A mode that is neither of the two, bc1 <= 0 or bc2_sqrt <= 0, a range outside 0 <= blk_lo <= blk_hi <= n_blocks: NBEST_ERR_ARG; a
+ * short ws: NBEST_ERR_WORKSPACE; either way nothing is enqueued (the step forms check before their first launch), as in K9.        */
 enum { NBEST_ADAM_L2 = 0, NBEST_ADAMW = 1 };
 int nbest_adam_clip_coef(const float* partial, int n_partial, float max_grad_norm, float* clip, nbest_stream_t stream);
 int nbest_adam_update(int mode, float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                       int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* clip, float lr_mult, float bc1,
                       float bc2_sqrt, double b1, double b2, float eps, nbest_stream_t stream);
-int nbest_adam_step(int mode, float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+int nbest_adam_step(int mode, float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                     int n_tensors, int n_blocks, float lr_mult, float bc1, float bc2_sqrt, double b1, double b2, float eps,
                     float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* ---------------------------------------------------------------------------------------------

@@ -64,11 +64,13 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__
   }
 }
 
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float coef, float b1, float b2, float eps,
-                                      float lr, float wd) {
+// ob1 / ob2 = 1 - b1 / 1 - b2 rounded from double, the values torch's add_(1 - beta1, grad) / addcmul_(1 - beta2, ...) receive from the
+// reference's Python floats (optimization.py:275-276): 1.f - 0.999f is 1.29e-5 below 0.001f, and v would be that much too small
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float coef, float b1, float b2, float ob1, float ob2,
+                                      float eps, float lr, float wd) {
   g *= coef;
-  m = m * b1 + (1.f - b1) * g;
-  v = v * b2 + (1.f - b2) * g * g;
+  m = m * b1 + ob1 * g;
+  v = v * b2 + ob2 * g * g;
   float u = m / (sqrtf(v) + eps);
   if (wd > 0.f) u += wd * p;
   p -= lr * u;
@@ -77,8 +79,8 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
 __global__ __launch_bounds__(256) void bertadam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, bf16* __restrict__ plow,
                                                        const nbest_tensor_desc* __restrict__ descs, int n_tensors,
-                                                       const float* __restrict__ coef, float lr_mult, float b1, float b2, float eps,
-                                                       int blk_off) {
+                                                       const float* __restrict__ coef, float lr_mult, float b1, float b2, float ob1, float ob2,
+                                                       float eps, int blk_off) {
   const int blk = blockIdx.x + blk_off;
   const int t = find_tensor(descs, n_tensors, blk);
   const nbest_tensor_desc d = descs[t];
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(256) void bertadam_kernel(float* __restrict__ p, co
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float p1 = pp[e], m1 = mm[e], v1e = vv[e];
-        adam1(p1, gg[e], m1, v1e, cf, b1, b2, eps, lr, d.wd);
+        adam1(p1, gg[e], m1, v1e, cf, b1, b2, ob1, ob2, eps, lr, d.wd);
         pp[e] = p1; mm[e] = m1; vv[e] = v1e;
       }
       *(f32x4*)(p + base + i) = pp;
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(256) void bertadam_kernel(float* __restrict__ p, co
   }
   for (int64_t i = v1 + threadIdx.x; i < c1; i += 256) {
     float pp = p[base + i], mm = m[base + i], vv = v[base + i];
-    adam1(pp, g[base + i], mm, vv, cf, b1, b2, eps, lr, d.wd);
+    adam1(pp, g[base + i], mm, vv, cf, b1, b2, ob1, ob2, eps, lr, d.wd);
     p[base + i] = pp; m[base + i] = mm; v[base + i] = vv;
     if (plow) plow[base + i] = (bf16)pp;
   }
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256) void global_clip_kernel(const float* __restric
 // ADAM_L2 (torch.optim.Adam): g = c g + wd p; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
 //                             p -= (lr / bc1) * m / (sqrt(v) / bc2s + eps)
 // ADAMW (HF AdamW, correct_bias=False): g = c g; m = b1 m + (1-b1) g; v = ...; p -= lr * m / (sqrt(v) + eps); p -= lr wd p
-// ob1 / ob2 = 1 - b1 / 1 - b2 rounded from double, as torch passes them (1 - 0.999f would be 1.3e-5 off)
+// ob1 / ob2: as in adam1
 template <int MODE>
 __device__ __forceinline__ void adam_mode1(float& p, float g, float& m, float& v, float c, float b1, float b2, float ob1, float ob2,
                                            float eps, float lr, float wd, float bc2s) {
@@ -325,20 +327,21 @@ extern "C" int nbest_bertadam_norms(const float* g, const nbest_tensor_desc* des
 
 extern "C" int nbest_bertadam_update(float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                                      int n_tensors, int n_blocks, int blk_lo, int blk_hi, const float* partial, float* coef,
-                                     float lr_mult, float b1, float b2, float eps, float max_grad_norm, nbest_stream_t stream) {
+                                     float lr_mult, double b1, double b2, float eps, float max_grad_norm, nbest_stream_t stream) {
   NB_CHECK(p && g && m && v && descs && partial && coef && n_tensors > 0 && 0 <= blk_lo && blk_lo <= blk_hi && blk_hi <= n_blocks,
            NBEST_ERR_ARG, "bertadam_update: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   clip_coef_kernel<<<n_tensors, 64, 0, st>>>(partial, descs, n_tensors, n_blocks, max_grad_norm, coef);
   NB_LAUNCH_CHECK();
   if (blk_hi == blk_lo) return NBEST_OK;
-  bertadam_kernel<<<blk_hi - blk_lo, 256, 0, st>>>(p, g, m, v, (bf16*)p_lowp, descs, n_tensors, coef, lr_mult, b1, b2, eps, blk_lo);
+  bertadam_kernel<<<blk_hi - blk_lo, 256, 0, st>>>(p, g, m, v, (bf16*)p_lowp, descs, n_tensors, coef, lr_mult, (float)b1, (float)b2,
+                                                   (float)(1.0 - b1), (float)(1.0 - b2), eps, blk_lo);
   NB_LAUNCH_CHECK();
   return NBEST_OK;
 }
 
-extern "C" int nbest_bertadam_step(float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
-                                   int n_tensors, int n_blocks, float lr_mult, float b1, float b2, float eps, float max_grad_norm,
+extern "C" int nbest_bertadam_step(float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+                                   int n_tensors, int n_blocks, float lr_mult, double b1, double b2, float eps, float max_grad_norm,
                                    void* ws, size_t ws_bytes, nbest_stream_t stream) {
   NB_CHECK(p && g && m && v && descs && ws && n_tensors > 0 && n_blocks > 0, NBEST_ERR_ARG, "bertadam: null pointer");
   NB_CHECK(ws_bytes >= ((size_t)n_blocks + n_tensors) * sizeof(float), NBEST_ERR_WORKSPACE, "bertadam: workspace too small");
@@ -375,10 +378,12 @@ extern "C" int nbest_adam_update(int mode, float* p, const float* g, float* m, f
   return NBEST_OK;
 }
 
-extern "C" int nbest_adam_step(int mode, float* p, float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
+extern "C" int nbest_adam_step(int mode, float* p, const float* g, float* m, float* v, void* p_lowp, const nbest_tensor_desc* descs,
                                int n_tensors, int n_blocks, float lr_mult, float bc1, float bc2_sqrt, double b1, double b2, float eps,
                                float max_grad_norm, void* ws, size_t ws_bytes, nbest_stream_t stream) {
   NB_CHECK(p && g && m && v && descs && ws && n_tensors > 0 && n_blocks > 0, NBEST_ERR_ARG, "adam_step: null pointer");
+  // what nbest_adam_update would refuse is refused before the norms are launched: a failed call leaves ws as it was
+  NB_CHECK((mode == NBEST_ADAM_L2 || mode == NBEST_ADAMW) && bc1 > 0.f && bc2_sqrt > 0.f, NBEST_ERR_ARG, "adam_step: bad arguments");
   NB_CHECK(ws_bytes >= ((size_t)n_blocks + 2) * sizeof(float), NBEST_ERR_WORKSPACE, "adam_step: workspace too small");
   float* partial = (float*)ws;
   float* clip = partial + n_blocks;

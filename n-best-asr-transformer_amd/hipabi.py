@@ -160,11 +160,11 @@ def lib():
         L.nbest_stc_decode.argtypes = [vp, vp, C.POINTER(LabelSpaceC), vp, vp, i32, vp]
         L.nbest_stream_stamp.argtypes = [vp, i32, vp]
         L.nbest_fp8_amax_fold.argtypes = [vp, vp, i32, vp]
-        L.nbest_bertadam_step.argtypes = [vp] * 6 + [i32, i32, f32, f32, f32, f32, f32, vp, sz, vp]
+        f64 = C.c_double                  # b1, b2 of every optimizer: the library forms (float)b and (float)(1 - b) itself
+        L.nbest_bertadam_step.argtypes = [vp] * 6 + [i32, i32, f32, f64, f64, f32, f32, vp, sz, vp]
         L.nbest_bertadam_norms.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-        L.nbest_bertadam_update.argtypes = [vp] * 6 + [i32, i32, i32, i32, vp, vp, f32, f32, f32, f32, f32, vp]
+        L.nbest_bertadam_update.argtypes = [vp] * 6 + [i32, i32, i32, i32, vp, vp, f32, f64, f64, f32, f32, vp]
         L.nbest_adam_clip_coef.argtypes = [vp, i32, f32, vp, vp]
-        f64 = C.c_double
         L.nbest_adam_update.argtypes = [i32] + [vp] * 6 + [i32, i32, i32, i32, vp, f32, f32, f32, f64, f64, f32, vp]
         L.nbest_adam_step.argtypes = [i32] + [vp] * 6 + [i32, i32, f32, f32, f32, f64, f64, f32, f32, vp, sz, vp]
         L.nbest_ema_update.argtypes = [vp, vp, vp, i32, i32, f32, vp]
