@@ -73,6 +73,38 @@ int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const int64_t* po
                        int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
                        uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
 size_t nbest_embed_bwd_ws_bytes(int64_t M, int64_t H);
+/* Adversarial training on the word embeddings, the fast gradient method (new functionality: the reference has none; Miyato et al.,
+ * ICLR 2017).  With delta fp32 [M][H] (device), row m of the embedding sum becomes
+ *   e'[m,:] = ((word[ids[m]] + delta[m,:]) + type[seg[m]]) + ptab[pos[m]]
+ * in fp32 from the stored table rows, in this order in the forward and in the backward's recomputation of x_hat; a zero delta row gives
+ * the bits of the plain row.
+ * nbest_embed_ln_fwd_adv: nbest_embed_ln_fwd on e' (the same kernel, one more instantiation); stats are those of e'.
+ * nbest_embed_ln_bwd_adv: nbest_embed_ln_bwd for a forward that ran on e' (stats from it).  delta is a constant: it gets no gradient.
+ *   perm, determinism, accumulate / tables_accumulate and the fallback layouts as documented there; same workspace.
+ * nbest_embed_adv_delta forms delta from dout [B*S][H] (dtype) = the gradient w.r.t. the embedding LayerNorm output of a CLEAN pass
+ * (what nbest_encoder_backward leaves in dhidden after layer_begin = 0) in two launches:
+ *   1. one wave per token: g[m,:] = ((d gamma) - mean(d gamma) - x_hat mean(d gamma x_hat)) rstd, d = dout[m,:] under the forward's
+ *      keep bits and scale (drop_p, seed, drop_stream: the pass's hidden_drop, seed and drop_stream_base; element index m H + c), mean,
+ *      rstd and x_hat recomputed from the clean row - equal to the forward's statistics to rounding; g[m,:] = 0 exactly where
+ *      key_mask[m] == 0.  g goes to delta (fp32), its sum of squares per row to the workspace.
+ *   2. per utterance b: n_b = sqrt(sum of the S row values in ascending t) -> norm[b] (fp32 [B]); delta[m,:] = g[m,:] (epsilon / n_b)
+ *      in place; n_b zero or not finite: every delta row of the utterance is exactly 0.
+ * No atomics, fixed summation order: bit-reproducible.  epsilon finite, >= 0.  ws >= nbest_embed_adv_ws_bytes(B, S).               */
+int nbest_embed_ln_fwd_adv(const int64_t* ids, const int64_t* seg, const int64_t* pos, const void* word, const void* type,
+                           const void* ptab, const float* gamma, const float* beta, const float* delta, void* out, float* stats,
+                           int64_t M, int H, float eps, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
+                           nbest_stream_t stream);
+int nbest_embed_ln_bwd_adv(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
+                           const void* type, const void* ptab, const float* gamma, const float* stats, const float* delta,
+                           const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,
+                           float* dbeta, int B, int S, int H, int n_types, int dtype, int64_t word_pad_id,
+                           int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
+                           uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream);
+size_t nbest_embed_adv_ws_bytes(int B, int S);
+int nbest_embed_adv_delta(const int64_t* ids, const int64_t* seg, const int64_t* pos, const uint8_t* key_mask, const void* word,
+                          const void* type, const void* ptab, const float* gamma, const void* dout, float* delta, float* norm,
+                          int B, int S, int H, float eps, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
+                          float epsilon, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* Integrated gradients (new functionality: the reference has no attribution; Sundararajan et al., 2017).
  * Interpolated forward: nbest_embed_ln_fwd with the word row of token m of sequence b = m / S moved along the path from the
  * baseline id base_ids[m] to ids[m] (int64 [B*S] each; alpha fp32 [B], device):
@@ -722,6 +754,12 @@ typedef struct nbest_encoder_desc {
    * written.  Bias and LayerNorm gradients are always written (except with no_param_grad below).                               */
   int32_t first_trainable;
   int32_t no_input_grad;
+  /* optional adversarial perturbation of the word rows (FGM; nbest_embed_adv_delta): fp32 [B*S][H], device memory, set per call like
+   * `seed`.  Non-NULL: nbest_encoder_forward's embedding is nbest_embed_ln_fwd_adv and nbest_encoder_backward(with_embeddings) runs
+   * nbest_embed_ln_bwd_adv - the backward must see the pointer (and the values) its stash's forward saw.  Everything above the
+   * embedding is unchanged, cls_top included.  NULL: today's launches.  Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward
+   * (w8), base_ids / alpha and first_trainable > 0; nbest_encoder_infer* refuse it.                                              */
+  const float* emb_delta;
   const uint8_t* wgrad_skip_host;
   /* optional head gates (NULL = none: every entry point then enqueues exactly the launches it did without these fields; the two
    * pointers sit here, ahead of the attribution fields, which stay the descriptor's last).

@@ -177,7 +177,31 @@ def parse_arguments(argv=None):
                         "and > 0.  The [Train] line's Loss is half the hard loss of the 2 x batchSize rows and its F1 that of the first "
                         "copies; exp_dir gains __rdrop_<A>.  A training flag, one GPU; needs --dropout or --bert_dropout > 0; not with "
                         "--distill_from")
+    g.add_argument("--adv_epsilon", type=float, default=None, metavar="E",
+                   help="FGM adversarial training on the word embeddings (Miyato et al., 2017): every training step runs the ASR pass a "
+                        "second time with each utterance's word embeddings moved by E (L2 norm) along the gradient of the step's loss "
+                        "(nbest_embed_adv_delta, nbest_encoder_desc.emb_delta), under the same dropout bits, and the optimizer steps once on "
+                        "the sum of both passes' gradients; E finite and > 0.  The [Train] line's Loss and F1 are the clean pass's; exp_dir "
+                        "gains __fgm_<E>.  A training flag, one GPU; not with --distill_from, --rdrop_alpha, --dtype fp8w, "
+                        "--freeze_embeddings or --freeze_layers K > 0")
     opt = ap.parse_args(argv)
+    if opt.adv_epsilon is not None:
+        if not (opt.adv_epsilon > 0.0 and math.isfinite(opt.adv_epsilon)):
+            ap.error("--adv_epsilon %s: must be a finite number > 0" % opt.adv_epsilon)
+        for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--adv_epsilon is a training flag: %s reads model.pt from the directory named without it" % flag)
+        if opt.distill_from is not None:
+            ap.error("--adv_epsilon together with --distill_from is not built (the adversarial pass has the hard terms only)")
+        if opt.rdrop_alpha is not None:
+            ap.error("--adv_epsilon together with --rdrop_alpha is not built (the adversarial pass has the hard terms only)")
+        if opt.dtype == "fp8w":
+            ap.error("--adv_epsilon together with --dtype fp8w is not built (the fp8 forward has no perturbed embedding)")
+        if opt.freeze_embeddings or opt.freeze_layers > 0:
+            ap.error("--adv_epsilon needs trainable embeddings: not with --freeze_embeddings or --freeze_layers K > 0 (the perturbation "
+                     "is formed from the gradient w.r.t. the word embeddings)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--adv_epsilon runs on one GPU: FGM under data parallelism is not built (world size %s)" % os.environ["WORLD_SIZE"])
     if opt.rdrop_alpha is not None:
         if not (opt.rdrop_alpha > 0.0 and math.isfinite(opt.rdrop_alpha)):
             ap.error("--rdrop_alpha %s: must be a finite number > 0" % opt.rdrop_alpha)
@@ -288,6 +312,8 @@ def exp_dir(opt):
             parts.append("kdT_%s" % opt.distill_temperature)
     if getattr(opt, "rdrop_alpha", None) is not None:
         parts.append("rdrop_%s" % opt.rdrop_alpha)
+    if getattr(opt, "adv_epsilon", None) is not None:
+        parts.append("fgm_%s" % opt.adv_epsilon)
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -516,6 +542,10 @@ def main(argv=None):
     if opt.rdrop_alpha is not None:
         log.info("R-Drop: alpha %s; every utterance twice per step under independent dropout bits, gradient of the hard loss of both "
                  "copies + alpha * their symmetric KL, Loss below is half the hard loss of the doubled batch" % opt.rdrop_alpha)
+    if opt.adv_epsilon is not None:
+        log.info("FGM: epsilon %s; every step runs the ASR pass again on word embeddings moved by epsilon (L2 norm per utterance) along "
+                 "the loss gradient, same dropout bits, one optimizer step on the sum of both gradients, Loss and F1 below are the clean "
+                 "pass's" % opt.adv_epsilon)
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)

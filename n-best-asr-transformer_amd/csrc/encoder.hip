@@ -324,6 +324,11 @@ static int check_desc(const nbest_encoder_desc* d) {
   NB_CHECK(!d->head_gate || !d->w8, NBEST_ERR_ARG, "encoder: head_gate is not supported with the fp8 forward (desc.w8)");
   NB_CHECK(!d->head_gate || d->first_trainable == 0, NBEST_ERR_ARG, "encoder: head_gate needs first_trainable == 0 (got %d)", d->first_trainable);
   NB_CHECK(!d->head_gate_grad || d->head_gate, NBEST_ERR_ARG, "encoder: head_gate_grad without head_gate");
+  // adversarial perturbation of the word rows (desc.emb_delta): the embedding kernels' _adv entry points, bf16 / fp32 forward, full stash
+  NB_CHECK(!d->emb_delta || !d->w8, NBEST_ERR_ARG, "encoder: emb_delta is not supported with the fp8 forward (desc.w8)");
+  NB_CHECK(!d->emb_delta || (!d->base_ids && !d->alpha), NBEST_ERR_ARG, "encoder: emb_delta is not supported with interpolated embeddings (base_ids / alpha)");
+  NB_CHECK(!d->emb_delta || d->first_trainable == 0, NBEST_ERR_ARG, "encoder: emb_delta needs first_trainable == 0 (got %d): the perturbation "
+           "is formed from the gradient w.r.t. trainable embeddings", d->first_trainable);
   return NBEST_OK;
 }
 
@@ -677,6 +682,10 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
     RUN(nbest_embed_ln_fwd_interp(ids, d->base_ids, d->alpha, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos),
                                   P.P(d->off_emb_ln_g), P.P(d->off_emb_ln_b), X(0), emb_stats, d->B, d->S, H, d->ln_eps, dt,
                                   d->hidden_drop, d->seed, d->drop_stream_base, (hipStream_t)stream));
+  else if (d->emb_delta)   // FGM: the word rows moved by desc.emb_delta
+    RUN(nbest_embed_ln_fwd_adv(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
+                               P.P(d->off_emb_ln_b), d->emb_delta, X(0), emb_stats, z.M, H, d->ln_eps, dt, d->hidden_drop, d->seed,
+                               d->drop_stream_base, (hipStream_t)stream));
   else
     RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
                            P.P(d->off_emb_ln_b), X(0), emb_stats, z.M, H, d->ln_eps, dt, d->hidden_drop, d->seed, d->drop_stream_base,
@@ -1028,10 +1037,16 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
     if (e == hipSuccess) e = hipMemsetAsync(G(d->off_type), 0, (size_t)d->n_types * H * sizeof(float), st);
     NB_CHECK(e == hipSuccess, NBEST_ERR_LAUNCH, "encoder_backward: memset failed: %s", hipGetErrorString(e));
   }
-  RUN(nbest_embed_ln_bwd(ids, seg, pos, d->word_perm, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
-                         (const float*)(A + a.emb_stats), dA, G(d->off_word), G(d->off_type), G(d->off_pos), G(d->off_emb_ln_g),
-                         G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, dt, d->word_pad_id, d->pos_pad_id, accumulate, accumulate,
-                         d->hidden_drop, d->seed, d->drop_stream_base, W + w.emb, w.emb_bytes, stream));
+  if (d->emb_delta)   // the stash's forward ran on the perturbed word rows: x_hat is recomputed from them (delta gets no gradient)
+    RUN(nbest_embed_ln_bwd_adv(ids, seg, pos, d->word_perm, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
+                               (const float*)(A + a.emb_stats), d->emb_delta, dA, G(d->off_word), G(d->off_type), G(d->off_pos),
+                               G(d->off_emb_ln_g), G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, dt, d->word_pad_id, d->pos_pad_id,
+                               accumulate, accumulate, d->hidden_drop, d->seed, d->drop_stream_base, W + w.emb, w.emb_bytes, stream));
+  else
+    RUN(nbest_embed_ln_bwd(ids, seg, pos, d->word_perm, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
+                           (const float*)(A + a.emb_stats), dA, G(d->off_word), G(d->off_type), G(d->off_pos), G(d->off_emb_ln_g),
+                           G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, dt, d->word_pad_id, d->pos_pad_id, accumulate, accumulate,
+                           d->hidden_drop, d->seed, d->drop_stream_base, W + w.emb, w.emb_bytes, stream));
   return NBEST_OK;
 }
 
@@ -1080,6 +1095,7 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");
   NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder_infer: interpolated embeddings (desc.base_ids / alpha) are not supported; "
                                                      "run nbest_encoder_forward");
+  NB_CHECK(!d->emb_delta, NBEST_ERR_ARG, "encoder_infer: perturbed embeddings (desc.emb_delta) are not supported; run nbest_encoder_forward");
   NB_CHECK(wts && prm && ids && pos && key_mask && ws && cls_out, NBEST_ERR_ARG, "encoder_infer: null pointer");
   const Sizes z = sizes(d);
   const InferLayout w = infer_layout(z);

@@ -461,14 +461,17 @@ __device__ __forceinline__ void emb_row_stats(const f32x4* v, float s, int lane,
 
 // INTERP (nbest_embed_ln_fwd_interp): the word part of row m is emb_lerp4(word[ids[m]], word[base_ids[m]], alpha[m / S]); one kernel
 // for both, so that an alpha = 1 row runs the plain forward's instructions
-template <typename T, int VPL, bool INTERP = false>
+// ADV (nbest_embed_ln_fwd_adv): the word part of row m is word[ids[m]] + delta[m] (fp32 [M][H]), added before the token-type row - the
+// order emb_tok_grad<ADV> recomputes; a zero delta row leaves the word row's bits
+template <typename T, int VPL, bool INTERP = false, bool ADV = false>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seg,
                                                         const int64_t* __restrict__ pos, const T* __restrict__ word,
                                                         const T* __restrict__ type, const T* __restrict__ ptab,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         T* __restrict__ out, float* __restrict__ stats, int64_t M, int H,
                                                         float eps, DropCfg drop, const int64_t* __restrict__ base_ids = nullptr,
-                                                        const float* __restrict__ alpha = nullptr, int S = 1) {
+                                                        const float* __restrict__ alpha = nullptr, int S = 1,
+                                                        const float* __restrict__ delta = nullptr) {
   const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6, nvec = H >> 2;
   const float invH = 1.0f / (float)H;
   for (int64_t row = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * wpb) {
@@ -485,6 +488,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
       if (c < nvec) {
         if constexpr (INTERP)
           v[i] = (emb_lerp4(Vec4<T>::load(wr + 4 * c), Vec4<T>::load(br + 4 * c), a) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
+        else if constexpr (ADV)
+          v[i] = ((Vec4<T>::load(wr + 4 * c) + *(const f32x4*)(delta + row * H + 4 * c)) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
         else
           v[i] = (Vec4<T>::load(wr + 4 * c) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
         s += sum4(v[i]);
@@ -614,6 +619,122 @@ __global__ __launch_bounds__(256) void embed_attrib_kernel(const int64_t* __rest
   }
 }
 
+// FGM perturbation (nbest_embed_adv_delta), launch 1.  One wave per token row m: g_m = the embedding LayerNorm backward of the
+// dropout-masked dout[m] (the formula of emb_tok_grad, mean and rstd recomputed from the clean row with emb_row_stats, as the
+// attribution kernel does) goes to delta[m] in fp32, its sum of squares to rowsq[m].  Rows with key_mask[m] == 0: exact zeros, no table
+// or statistics work.  The next row's dout is in flight while this one is reduced.  No LDS, no atomics.
+template <typename T, int VPL>
+__global__ __launch_bounds__(256) void embed_adv_grad_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seg,
+                                                             const int64_t* __restrict__ pos, const uint8_t* __restrict__ key_mask,
+                                                             const T* __restrict__ word, const T* __restrict__ type,
+                                                             const T* __restrict__ ptab, const float* __restrict__ gamma,
+                                                             const T* __restrict__ dout, float* __restrict__ delta,
+                                                             float* __restrict__ rowsq, int64_t M, int H, float eps, DropCfg drop) {
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6, nvec = H >> 2;
+  const float invH = 1.0f / (float)H;
+  const int64_t stride = (int64_t)gridDim.x * wpb;
+  int64_t row = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
+  if (row >= M) return;
+  f32x4 gm[VPL];
+  typename Vec4<T>::raw_t nd[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nvec) { gm[i] = *(const f32x4*)(gamma + 4 * c); nd[i] = Vec4<T>::raw_load(dout + row * H + 4 * c); }
+    else gm[i] = f32x4{0, 0, 0, 0};
+  }
+  for (; row < M; row += stride) {
+    typename Vec4<T>::raw_t cd[VPL];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) cd[i] = nd[i];
+    if (row + stride < M) {
+      const T* nr = dout + (row + stride) * H;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) nd[i] = Vec4<T>::raw_load(nr + 4 * c);
+      }
+    }
+    float* gr = delta + row * H;
+    if (key_mask[row] == 0) {   // wave-uniform: a masked token is not perturbed
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) *(f32x4*)(gr + 4 * c) = f32x4{0, 0, 0, 0};
+      }
+      if (lane == 0) rowsq[row] = 0.f;
+      continue;
+    }
+    const T* wr = word + ids[row] * H;
+    const T* tr = type + (seg ? seg[row] : 0) * H;
+    const T* pr = ptab + pos[row] * H;
+    f32x4 v[VPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nvec) {
+        v[i] = (Vec4<T>::load(wr + 4 * c) + Vec4<T>::load(tr + 4 * c)) + Vec4<T>::load(pr + 4 * c);
+        s += sum4(v[i]);
+      } else v[i] = f32x4{0, 0, 0, 0};
+    }
+    float mean, rstd;
+    emb_row_stats<VPL>(v, s, lane, nvec, invH, eps, mean, rstd);
+    f32x4 xh[VPL], g[VPL];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nvec) {
+        xh[i] = (v[i] - mean) * rstd;
+        f32x4 d = Vec4<T>::cvt(cd[i]);
+        if (drop.thr16) {
+          const uint32_t k = nb_keep4(drop, (uint32_t)(row * H + 4 * c));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) d[e] = (k >> e & 1) ? d[e] * drop.scale : 0.f;
+        }
+        g[i] = d * gm[i];
+        s1 += sum4(g[i]);
+        s2 += sum4(g[i] * xh[i]);
+      } else {
+        xh[i] = g[i] = f32x4{0, 0, 0, 0};
+      }
+    }
+    wave_sum2(s1, s2);
+    s1 *= invH; s2 *= invH;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nvec) {
+        const f32x4 o = (g[i] - s1 - xh[i] * s2) * rstd;
+        *(f32x4*)(gr + 4 * c) = o;
+        q += sum4(o * o);
+      }
+    }
+    q = wave_sum(q);
+    if (lane == 0) rowsq[row] = q;
+  }
+}
+
+// launch 2, grid (Y, B): every block of utterance b forms n_b = sqrt(rowsq[b S] + rowsq[b S + 1] + ...) itself, in ascending t (the
+// same S additions in every block and on every run), and scales its slice of the utterance's S H values in place by epsilon / n_b;
+// n_b zero or not finite: exact zeros.  Block (0, b) writes norm[b].
+__global__ __launch_bounds__(256) void embed_adv_scale_kernel(float* __restrict__ delta, const float* __restrict__ rowsq,
+                                                              float* __restrict__ norm, int S, int H, float epsilon) {
+  const int b = blockIdx.y;
+  float q = 0.f;
+  for (int t = 0; t < S; ++t) q += rowsq[(int64_t)b * S + t];
+  const float n = sqrtf(q);
+  const bool ok = n > 0.f && n <= 3.4028234e38f;   // false for 0, NaN and infinity
+  const float sc = ok ? epsilon / n : 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm[b] = n;
+  const int64_t nv = (int64_t)S * (H >> 2);
+  f32x4* p = (f32x4*)(delta + (int64_t)b * S * H);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x)
+    p[i] = ok ? p[i] * sc : f32x4{0, 0, 0, 0};
+}
+
 // Embedding backward, deterministic (round 4; rounds 1-3 summed the word table with fp32 atomics: 150 us at the atomic rate and
 // a step that was not bit-reproducible).  LayerNorm backward per token gives de = o (fp32, registers only); five kernels:
 //   embed_bwd_colkey_kernel  one block per sequence position j: the column's key colkey[j] = the position key of its first
@@ -663,17 +784,29 @@ __device__ __forceinline__ void emb_tok_load(EmbTok<T, VPL>& r, int64_t row, int
   }
   r.mean = stats[2 * row]; r.rstd = stats[2 * row + 1];
 }
+// ADV (nbest_embed_ln_bwd_adv): the forward added delta[row] (fp32) to the word row, so the recomputed x_hat does too.  The row travels
+// beside EmbTok, in an array only the ADV instantiations declare with VPL entries: the plain ones keep their loads and registers.
+template <int VPL, bool FULL>
+__device__ __forceinline__ void emb_tok_delta(f32x4* dl, int64_t row, const float* __restrict__ delta, int H, int lane, int nvec) {
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int c = lane + 64 * i;
+    if (FULL || c < nvec) dl[i] = *(const f32x4*)(delta + row * H + 4 * c);
+  }
+}
 // o = d(embedding sum) of the token; d / xh = dropout-masked upstream gradient and the normalised row (LayerNorm-parameter sums)
-template <typename T, int VPL, bool FULL>
+template <typename T, int VPL, bool FULL, bool ADV = false>
 __device__ __forceinline__ void emb_tok_grad(const EmbTok<T, VPL>& r, int64_t row, const f32x4* gm, f32x4* o, f32x4* d, f32x4* xh, int H,
-                                             int lane, int nvec, float invH, const DropCfg& drop) {
+                                             int lane, int nvec, float invH, const DropCfg& drop, const f32x4* dl = nullptr) {
   f32x4 g[VPL];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = lane + 64 * i;
     if (FULL || c < nvec) {
-      const f32x4 e = (Vec4<T>::cvt(r.w[i]) + Vec4<T>::cvt(r.t[i])) + Vec4<T>::cvt(r.p[i]);
+      f32x4 e;
+      if constexpr (ADV) e = ((Vec4<T>::cvt(r.w[i]) + dl[i]) + Vec4<T>::cvt(r.t[i])) + Vec4<T>::cvt(r.p[i]);
+      else e = (Vec4<T>::cvt(r.w[i]) + Vec4<T>::cvt(r.t[i])) + Vec4<T>::cvt(r.p[i]);
       xh[i] = (e - r.mean) * r.rstd;
       d[i] = Vec4<T>::cvt(r.d[i]);
       if (drop.thr16) {
@@ -730,7 +863,7 @@ __global__ __launch_bounds__(256) void embed_bwd_colkey_kernel(const int64_t* __
   if (threadIdx.x == 0) { colkey[j] = key; mixed[j] = mix; }
 }
 
-template <typename T, int VPL, bool FULL>
+template <typename T, int VPL, bool FULL, bool ADV = false>
 __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seg,
                                                             const int64_t* __restrict__ pos, const T* __restrict__ word,
                                                             const T* __restrict__ type, const T* __restrict__ ptab,
@@ -738,7 +871,8 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
                                                             const T* __restrict__ dout, float* __restrict__ dtype_tab,
                                                             float* __restrict__ dptab, float* __restrict__ part, int* __restrict__ fixlist,
                                                             const int64_t* __restrict__ colkey, const int* __restrict__ mixed,
-                                                            int* __restrict__ shared, int B, int S, int H, int64_t pos_pad_id, DropCfg drop) {
+                                                            int* __restrict__ shared, int B, int S, int H, int64_t pos_pad_id, DropCfg drop,
+                                                            const float* __restrict__ delta = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float acc[];  // [5][H] column sums (dgamma, dbeta, position, type 0, type 1)
   // (readfirstlane: the wave index is uniform, but only this tells the compiler - otherwise every token index below is a
   // "divergent" value and each readlane becomes a waterfall loop)
@@ -777,10 +911,12 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
     // groups of kEmbGroupPos tokens: all their rows are requested before the first is reduced
     for (int g0 = 0; g0 < n; g0 += kEmbGroupPos) {
       EmbTok<T, VPL> r[kEmbGroupPos];
+      f32x4 dl[ADV ? kEmbGroupPos : 1][ADV ? VPL : 1];
 #pragma unroll
       for (int u = 0; u < kEmbGroupPos; ++u) {
         const int k = (g0 + u < n) ? g0 + u : n - 1;
         emb_tok_load<T, VPL, FULL>(r[u], bc(lrow, k), bc(lid, k), bc(lsv, k), bc(lkey, k), word, type, ptab, stats, dout, H, lane, nvec);
+        if constexpr (ADV) emb_tok_delta<VPL, FULL>(dl[u], bc(lrow, k), delta, H, lane, nvec);
       }
 #pragma unroll
       for (int u = 0; u < kEmbGroupPos; ++u) {
@@ -788,7 +924,8 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
         if (k >= n) break;
         const int64_t row = bc(lrow, k), key = bc(lkey, k), sv = bc(lsv, k);
         f32x4 o[VPL], d[VPL], xh[VPL];
-        emb_tok_grad<T, VPL, FULL>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop);
+        if constexpr (ADV) emb_tok_grad<T, VPL, FULL, true>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop, dl[u]);
+        else emb_tok_grad<T, VPL, FULL>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop);
         const bool own_key = (key == key0), t_is0 = (sv == 0), t_is1 = (sv == 1);   // wave-uniform
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
@@ -886,14 +1023,15 @@ __device__ __forceinline__ int64_t emb_sid(const int32_t* __restrict__ perm, con
   return i < 0 ? -2 : (i >= M ? -3 : ids[perm[i]]);
 }
 
-template <typename T, int VPL, bool FULL>
+template <typename T, int VPL, bool FULL, bool ADV = false>
 __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const int32_t* __restrict__ perm, const int64_t* __restrict__ ids,
                                                              const int64_t* __restrict__ seg, const int64_t* __restrict__ pos,
                                                              const T* __restrict__ word, const T* __restrict__ type,
                                                              const T* __restrict__ ptab, const float* __restrict__ gamma,
                                                              const float* __restrict__ stats, const T* __restrict__ dout,
                                                              float* __restrict__ dword, float* __restrict__ wpart, int* __restrict__ fixlist,
-                                                             int64_t M, int H, int tpc, int64_t word_pad_id, int accumulate, DropCfg drop) {
+                                                             int64_t M, int H, int tpc, int64_t word_pad_id, int accumulate, DropCfg drop,
+                                                             const float* __restrict__ delta = nullptr) {
   const int lane = threadIdx.x & 63, nvec = H >> 2;
   const int64_t c = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: see the pos kernel
   const int64_t i0 = c * tpc;
@@ -924,10 +1062,12 @@ __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const int32_t* __re
   int64_t run_id = -5;
   for (int g0 = 1; g0 <= n; g0 += kEmbGroupWord) {               // groups of kEmbGroupWord tokens: every row requested before the first is reduced
     EmbTok<T, VPL> r[kEmbGroupWord];
+    f32x4 dl[ADV ? kEmbGroupWord : 1][ADV ? VPL : 1];
 #pragma unroll
     for (int u = 0; u < kEmbGroupWord; ++u) {
       const int k = (g0 + u <= n) ? g0 + u : n;
       emb_tok_load<T, VPL, FULL>(r[u], bc(lrow, k), bc(lid, k), bc(lsv, k), bc(lkey, k), word, type, ptab, stats, dout, H, lane, nvec);
+      if constexpr (ADV) emb_tok_delta<VPL, FULL>(dl[u], bc(lrow, k), delta, H, lane, nvec);
     }
 #pragma unroll
     for (int u = 0; u < kEmbGroupWord; ++u) {
@@ -942,7 +1082,8 @@ __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const int32_t* __re
         for (int i = 0; i < VPL; ++i) acc[i] = f32x4{0, 0, 0, 0};
       }
       f32x4 o[VPL], d[VPL], xh[VPL];
-      emb_tok_grad<T, VPL, FULL>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop);
+      if constexpr (ADV) emb_tok_grad<T, VPL, FULL, true>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop, dl[u]);
+      else emb_tok_grad<T, VPL, FULL>(r[u], row, gm, o, d, xh, H, lane, nvec, invH, drop);
 #pragma unroll
       for (int i = 0; i < VPL; ++i) acc[i] += o[i];
       const int64_t id_next = bc(lid, k + 1);                // k = n: the id after the chunk
@@ -1377,6 +1518,64 @@ extern "C" int nbest_embed_ln_fwd_interp(const int64_t* ids, const int64_t* base
   return NBEST_OK;
 }
 
+extern "C" int nbest_embed_ln_fwd_adv(const int64_t* ids, const int64_t* seg, const int64_t* pos, const void* word, const void* type,
+                                      const void* ptab, const float* gamma, const float* beta, const float* delta, void* out, float* stats,
+                                      int64_t M, int H, float eps, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
+                                      nbest_stream_t stream) {
+  if (int e = check_h(H)) return e;
+  NB_CHECK(ids && pos && word && type && ptab && gamma && beta && delta && out && stats && M > 0, NBEST_ERR_ARG, "embed_ln_fwd_adv: null pointer");
+  NB_CHECK(M * (int64_t)H < (int64_t)1 << 32, NBEST_ERR_SHAPE, "embed_ln_fwd_adv: M*H must fit 32 bits (dropout counter)");
+  hipStream_t st = (hipStream_t)stream;
+  const DropCfg d = make_drop(drop_p, seed, drop_stream);
+  const int grid = grid_rows(M, 4);
+  if (dtype == NBEST_F32) {
+    DISPATCH_VPL(H, (embed_fwd_kernel<float, VPL, false, true><<<grid, 256, 0, st>>>(ids, seg, pos, (const float*)word, (const float*)type, (const float*)ptab,
+                                                                                     gamma, beta, (float*)out, stats, M, H, eps, d, nullptr, nullptr, 1, delta)));
+  } else if (dtype == NBEST_BF16) {
+    DISPATCH_VPL(H, (embed_fwd_kernel<bf16, VPL, false, true><<<grid, 256, 0, st>>>(ids, seg, pos, (const bf16*)word, (const bf16*)type, (const bf16*)ptab,
+                                                                                    gamma, beta, (bf16*)out, stats, M, H, eps, d, nullptr, nullptr, 1, delta)));
+  } else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_ln_fwd_adv: bad dtype %d", dtype);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
+extern "C" size_t nbest_embed_adv_ws_bytes(int B, int S) { return (size_t)(B > 0 ? B : 0) * (size_t)(S > 0 ? S : 0) * sizeof(float); }
+
+extern "C" int nbest_embed_adv_delta(const int64_t* ids, const int64_t* seg, const int64_t* pos, const uint8_t* key_mask, const void* word,
+                                     const void* type, const void* ptab, const float* gamma, const void* dout, float* delta, float* norm,
+                                     int B, int S, int H, float eps, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream,
+                                     float epsilon, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  if (int e = check_h(H)) return e;
+  NB_CHECK(ids && pos && key_mask && word && type && ptab && gamma && dout && delta && norm && ws, NBEST_ERR_ARG, "embed_adv_delta: null pointer");
+  NB_CHECK(B > 0 && S > 0, NBEST_ERR_SHAPE, "embed_adv_delta: B=%d, S=%d must be positive", B, S);
+  NB_CHECK(epsilon >= 0.f && epsilon <= 3.4028234e38f, NBEST_ERR_ARG, "embed_adv_delta: epsilon %g must be finite and >= 0", (double)epsilon);
+  NB_CHECK(ws_bytes >= nbest_embed_adv_ws_bytes(B, S), NBEST_ERR_WORKSPACE, "embed_adv_delta: workspace too small");
+  const int64_t M = (int64_t)B * S;
+  const DropCfg d = make_drop(drop_p, seed, drop_stream);
+  NB_CHECK(M * (int64_t)H < (int64_t)1 << 32 || d.thr16 == 0, NBEST_ERR_SHAPE, "embed_adv_delta: dropout counter overflow");
+  hipStream_t st = (hipStream_t)stream;
+  float* rowsq = (float*)ws;
+  const int grid = grid_rows(M, 4);
+  if (dtype == NBEST_F32) {
+    DISPATCH_VPL(H, (embed_adv_grad_kernel<float, VPL><<<grid, 256, 0, st>>>(ids, seg, pos, key_mask, (const float*)word, (const float*)type,
+                                                                             (const float*)ptab, gamma, (const float*)dout, delta, rowsq, M, H, eps, d)));
+  } else if (dtype == NBEST_BF16) {
+    DISPATCH_VPL(H, (embed_adv_grad_kernel<bf16, VPL><<<grid, 256, 0, st>>>(ids, seg, pos, key_mask, (const bf16*)word, (const bf16*)type,
+                                                                            (const bf16*)ptab, gamma, (const bf16*)dout, delta, rowsq, M, H, eps, d)));
+  } else NB_CHECK(false, NBEST_ERR_DTYPE, "embed_adv_delta: bad dtype %d", dtype);
+  NB_LAUNCH_CHECK();
+  // blocks per utterance: enough that B x Y covers the chip a few times over, each with at least one float4 per thread
+  const int64_t nv = (int64_t)S * (H >> 2);
+  int Y = (int)((nv + 255) / 256);
+  const int want = (2048 + B - 1) / B;
+  if (Y > want) Y = want;
+  if (Y < 1) Y = 1;
+  NB_CHECK(B <= 65535, NBEST_ERR_SHAPE, "embed_adv_delta: B = %d exceeds the grid's y extent", B);
+  embed_adv_scale_kernel<<<dim3(Y, B), 256, 0, st>>>(delta, rowsq, norm, S, H, epsilon);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
+
 extern "C" int nbest_embed_attrib(const int64_t* ids, const int64_t* base_ids, const float* alpha, const int64_t* seg, const int64_t* pos,
                                   const void* word, const void* type, const void* ptab, const float* gamma, const void* dhidden,
                                   float* attr, int pairs, int m, int S, int H, float eps, int dtype, nbest_stream_t stream) {
@@ -1399,12 +1598,13 @@ extern "C" int nbest_embed_attrib(const int64_t* ids, const int64_t* base_ids, c
   return NBEST_OK;
 }
 
-extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
-                                  const void* type, const void* ptab, const float* gamma, const float* stats,
-                                  const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,
-                                  float* dbeta, int B, int S, int H, int n_types, int dtype, int64_t word_pad_id,
-                                  int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
-                                  uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+// delta != NULL (nbest_embed_ln_bwd_adv): the ADV instantiations of the two token kernels, which recompute x_hat from the perturbed row
+static int embed_ln_bwd_impl(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
+                             const void* type, const void* ptab, const float* gamma, const float* stats,
+                             const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,
+                             float* dbeta, int B, int S, int H, int n_types, int dtype, int64_t word_pad_id,
+                             int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
+                             uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream, const float* delta) {
   if (int e = check_h(H)) return e;
   const int64_t M = (int64_t)B * S;
   NB_CHECK(ids && pos && word && type && ptab && gamma && stats && dout && dword && dtype_tab && dptab && dgamma && dbeta && ws && M > 0,
@@ -1430,18 +1630,18 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
   const int64_t chunks = (M + kEmbTpc - 1) / kEmbTpc;
   const unsigned wgrid = (unsigned)((chunks + 3) / 4);
   int* fixlist = (int*)(wpart + (size_t)chunks * 2 * H);
-#define NB_EMB_BWD2(TT, FULL)                                                                                                   \
-  DISPATCH_VPL(H, ((void)hipFuncSetAttribute((const void*)embed_bwd_pos_kernel<TT, VPL, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), \
-                   embed_bwd_pos_kernel<TT, VPL, FULL><<<grid, 256, smem, st>>>(ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, gamma, \
+#define NB_EMB_BWD2(TT, FULL, ADV)                                                                                              \
+  DISPATCH_VPL(H, ((void)hipFuncSetAttribute((const void*)embed_bwd_pos_kernel<TT, VPL, FULL, ADV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), \
+                   embed_bwd_pos_kernel<TT, VPL, FULL, ADV><<<grid, 256, smem, st>>>(ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, gamma, \
                                                                                  stats, (const TT*)dout, dtype_tab, dptab, part, fixlist, colkey, mixed, \
-                                                                                 shared, B, S, H, pos_pad_id, d), \
-                   embed_bwd_word_kernel<TT, VPL, FULL><<<wgrid, 256, 0, st>>>(perm, ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, \
+                                                                                 shared, B, S, H, pos_pad_id, d, delta), \
+                   embed_bwd_word_kernel<TT, VPL, FULL, ADV><<<wgrid, 256, 0, st>>>(perm, ids, seg, pos, (const TT*)word, (const TT*)type, (const TT*)ptab, \
                                                                                 gamma, stats, (const TT*)dout, dword, wpart, fixlist, M, H,  \
-                                                                                kEmbTpc, word_pad_id, tables_accumulate, d)))
-#define NB_EMB_BWD(TT)                                   \
-  do {                                                   \
-    if (H % 256 == 0 && H <= 1024) NB_EMB_BWD2(TT, true); \
-    else NB_EMB_BWD2(TT, false);                         \
+                                                                                kEmbTpc, word_pad_id, tables_accumulate, d, delta)))
+#define NB_EMB_BWD(TT)                                                                  \
+  do {                                                                                  \
+    if (H % 256 == 0 && H <= 1024) { if (delta) NB_EMB_BWD2(TT, true, true); else NB_EMB_BWD2(TT, true, false); } \
+    else { if (delta) NB_EMB_BWD2(TT, false, true); else NB_EMB_BWD2(TT, false, false); } \
   } while (0)
   embed_bwd_colkey_kernel<<<S, 256, 0, st>>>(seg, pos, B, S, H, pos_pad_id, tables_accumulate, colkey, mixed, dptab, dtype_tab);
   if (dtype == NBEST_F32) NB_EMB_BWD(float);
@@ -1456,6 +1656,29 @@ extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const 
                                                                                              dtype_tab, dptab, accumulate, tables_accumulate);
   NB_LAUNCH_CHECK();
   return NBEST_OK;
+}
+
+extern "C" int nbest_embed_ln_bwd(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
+                                  const void* type, const void* ptab, const float* gamma, const float* stats,
+                                  const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,
+                                  float* dbeta, int B, int S, int H, int n_types, int dtype, int64_t word_pad_id,
+                                  int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
+                                  uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  return embed_ln_bwd_impl(ids, seg, pos, perm, word, type, ptab, gamma, stats, dout, dword, dtype_tab, dptab, dgamma, dbeta, B, S, H, n_types,
+                           dtype, word_pad_id, pos_pad_id, accumulate, tables_accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream,
+                           nullptr);
+}
+
+extern "C" int nbest_embed_ln_bwd_adv(const int64_t* ids, const int64_t* seg, const int64_t* pos, const int32_t* perm, const void* word,
+                                      const void* type, const void* ptab, const float* gamma, const float* stats, const float* delta,
+                                      const void* dout, float* dword, float* dtype_tab, float* dptab, float* dgamma,
+                                      float* dbeta, int B, int S, int H, int n_types, int dtype, int64_t word_pad_id,
+                                      int64_t pos_pad_id, int accumulate, int tables_accumulate, float drop_p, uint64_t seed,
+                                      uint32_t drop_stream, void* ws, size_t ws_bytes, nbest_stream_t stream) {
+  NB_CHECK(delta, NBEST_ERR_ARG, "embed_ln_bwd_adv: null delta (call nbest_embed_ln_bwd)");
+  return embed_ln_bwd_impl(ids, seg, pos, perm, word, type, ptab, gamma, stats, dout, dword, dtype_tab, dptab, dgamma, dbeta, B, S, H, n_types,
+                           dtype, word_pad_id, pos_pad_id, accumulate, tables_accumulate, drop_p, seed, drop_stream, ws, ws_bytes, stream,
+                           delta);
 }
 
 extern "C" int nbest_rows_gather(const float* table, const int64_t* rows, int64_t n_rows, int64_t cap, int64_t* ids_out,

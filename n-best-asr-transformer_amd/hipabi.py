@@ -29,6 +29,7 @@ EXPORTS = [
     "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
     "nbest_embed_ln_fwd_interp", "nbest_embed_attrib",
     "nbest_head_gate_fwd", "nbest_head_gate_bwd",
+    "nbest_embed_ln_fwd_adv", "nbest_embed_ln_bwd_adv", "nbest_embed_adv_ws_bytes", "nbest_embed_adv_delta",
 ]
 
 
@@ -91,7 +92,7 @@ class EncoderDesc(C.Structure):
                 ("gamax_new", C.c_void_p), ("fp8_bwd", C.c_int32), ("pad2", C.c_int32),
                 ("wpk", C.c_void_p), ("wpkt", C.c_void_p), ("w8p", C.c_void_p), ("w8tp", C.c_void_p),
                 ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("cls_top", C.c_int32),
-                ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("wgrad_skip_host", C.c_void_p),
+                ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("emb_delta", C.c_void_p), ("wgrad_skip_host", C.c_void_p),
                 ("head_gate", C.c_void_p), ("head_gate_grad", C.c_void_p),
                 ("base_ids", C.c_void_p), ("alpha", C.c_void_p), ("no_param_grad", C.c_int32), ("pad5", C.c_int32)]
     # nbest_encoder_desc.wgrad_group (WGRAD_GROUP_*): the descriptor's last field, in the slot that was padding
@@ -113,7 +114,7 @@ def lib():
             if not hasattr(L, name):
                 raise RuntimeError("nbest_amd: %s does not export %s" % (LIB_PATH, name))
         for name in ("nbest_embed_bwd_ws_bytes", "nbest_gemm_ws_bytes", "nbest_wgrad_pair_ws_bytes", "nbest_rowred_ws_bytes", "nbest_heads_ws_bytes",
-                     "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes",
+                     "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_embed_adv_ws_bytes",
                      "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.nbest_embed_bwd_ws_bytes.argtypes = [C.c_int64, C.c_int64]
@@ -138,6 +139,10 @@ def lib():
         L.nbest_embed_ln_bwd.argtypes = [vp] * 15 + [i32, i32, i32, i32, i32, i64, i64, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_embed_ln_fwd_interp.argtypes = [vp] * 12 + [i32, i32, i32, f32, i32, f32, u64, u32, vp]
         L.nbest_embed_attrib.argtypes = [vp] * 11 + [i32, i32, i32, i32, f32, i32, vp]
+        L.nbest_embed_ln_fwd_adv.argtypes = [vp] * 11 + [i64, i32, f32, i32, f32, u64, u32, vp]
+        L.nbest_embed_ln_bwd_adv.argtypes = [vp] * 16 + [i32, i32, i32, i32, i32, i64, i64, i32, i32, f32, u64, u32, vp, sz, vp]
+        L.nbest_embed_adv_ws_bytes.argtypes = [i32, i32]
+        L.nbest_embed_adv_delta.argtypes = [vp] * 11 + [i32, i32, i32, f32, i32, f32, u64, u32, f32, vp, sz, vp]
         L.nbest_head_gate_fwd.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp]
         L.nbest_head_gate_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         L.nbest_attention_fwd.argtypes = [vp] * 4 + [i32] * 5 + [f32, u64, u32, vp]
@@ -669,10 +674,17 @@ def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0
     return dqkv
 
 
-def embed_ln_fwd(ids, seg, pos, word, type_tab, ptab, gamma, beta, eps, drop_p=0.0, seed=0, drop_stream=0):
+def embed_ln_fwd(ids, seg, pos, word, type_tab, ptab, gamma, beta, eps, drop_p=0.0, seed=0, drop_stream=0, delta=None):
+    """``delta`` (fp32 [B*S, H]): nbest_embed_ln_fwd_adv, the word rows moved by it"""
     M, H = ids.numel(), word.shape[1]
     out = torch.empty(M, H, dtype=word.dtype, device=word.device)
     stats = torch.empty(M, 2, dtype=torch.float32, device=word.device)
+    if delta is not None:
+        _check_delta(delta, M, H)
+        check(lib().nbest_embed_ln_fwd_adv(ptr(ids), ptr(seg), ptr(pos), ptr(word), ptr(type_tab), ptr(ptab), ptr(gamma), ptr(beta),
+                                           ptr(delta), ptr(out), ptr(stats), M, H, eps, dtype_code(word.dtype), drop_p, seed, drop_stream,
+                                           stream_ptr()), "embed_ln_fwd_adv")
+        return out, stats
     check(lib().nbest_embed_ln_fwd(ptr(ids), ptr(seg), ptr(pos), ptr(word), ptr(type_tab), ptr(ptab), ptr(gamma), ptr(beta),
                                    ptr(out), ptr(stats), M, H, eps, dtype_code(word.dtype), drop_p, seed, drop_stream,
                                    stream_ptr()), "embed_ln_fwd")
@@ -702,6 +714,29 @@ def embed_attrib(ids, base_ids, alpha, seg, pos, word, type_tab, ptab, gamma, dh
     return attr
 
 
+def _check_delta(delta, M, H):
+    if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != M * H:
+        raise ValueError("nbest_amd: delta must be a contiguous fp32 tensor of [%d, %d] elements" % (M, H))
+
+
+def embed_adv_delta(ids, seg, pos, key_mask, word, type_tab, ptab, gamma, dout, B, S, eps, epsilon, drop_p=0.0, seed=0, drop_stream=0,
+                    out=None, norm=None, ws=None):
+    """nbest_embed_adv_delta -> (delta fp32 [B*S, H], norm fp32 [B]): the FGM perturbation of the word rows from ``dout``, the gradient
+    w.r.t. the embedding LayerNorm output of the clean pass (its drop_p / seed / drop_stream): the per-token LayerNorm backward scaled
+    per utterance to an L2 norm of ``epsilon``; norm[b] is the gradient's norm before scaling.  ``out`` / ``norm`` / ``ws``: buffers to
+    write into (None: allocated)."""
+    H = word.shape[1]
+    delta = torch.empty(B * S, H, dtype=torch.float32, device=word.device) if out is None else out
+    _check_delta(delta, B * S, H)
+    norm = torch.empty(B, dtype=torch.float32, device=word.device) if norm is None else norm
+    if ws is None:
+        ws = _ws(lib().nbest_embed_adv_ws_bytes(B, S), word.device)
+    check(lib().nbest_embed_adv_delta(ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(word), ptr(type_tab), ptr(ptab), ptr(gamma), ptr(dout),
+                                      ptr(delta), ptr(norm), B, S, H, eps, dtype_code(word.dtype), drop_p, seed, drop_stream, float(epsilon),
+                                      ptr(ws), ws.numel(), stream_ptr()), "embed_adv_delta")
+    return delta, norm
+
+
 def word_perm(ids):
     """token indices sorted by word id, ties in token order (int32 [B*S]): the index the deterministic embedding backward
     reduces over.  The data loaders build it on the host next to ids (trainer.EncodedSplit.host_batch, bench.py); this is the
@@ -710,11 +745,29 @@ def word_perm(ids):
 
 
 def embed_ln_bwd(ids, seg, pos, word, type_tab, ptab, gamma, stats, dout, B, S, word_pad_id=-1, pos_pad_id=-1, drop_p=0.0,
-                 seed=0, drop_stream=0, perm=None, accumulate_into=None):
-    """accumulate_into = (dword, dtype_tab, dptab, dgamma, dbeta): add to these (tables_accumulate = accumulate = 1)"""
+                 seed=0, drop_stream=0, perm=None, accumulate_into=None, delta=None):
+    """accumulate_into = (dword, dtype_tab, dptab, dgamma, dbeta): add to these (tables_accumulate = accumulate = 1)
+    ``delta`` (fp32 [B*S, H]): nbest_embed_ln_bwd_adv, for a forward that ran with it (``stats`` are that forward's)"""
     H = word.shape[1]
     if perm is None:
         perm = word_perm(ids)
+    if delta is not None:
+        _check_delta(delta, B * S, H)
+        dev, acc = word.device, accumulate_into is not None
+        if acc:
+            dword, dtype_tab, dptab, dg, db = accumulate_into
+        else:
+            dword = torch.zeros(word.shape, dtype=torch.float32, device=dev)
+            dtype_tab = torch.zeros(type_tab.shape, dtype=torch.float32, device=dev)
+            dptab = torch.zeros(ptab.shape, dtype=torch.float32, device=dev)
+            dg = torch.zeros(H, dtype=torch.float32, device=dev)
+            db = torch.zeros_like(dg)
+        ws = _ws(lib().nbest_embed_bwd_ws_bytes(B * S, H), dev)
+        check(lib().nbest_embed_ln_bwd_adv(ptr(ids), ptr(seg), ptr(pos), ptr(perm), ptr(word), ptr(type_tab), ptr(ptab), ptr(gamma), ptr(stats),
+                                           ptr(delta), ptr(dout), ptr(dword), ptr(dtype_tab), ptr(dptab), ptr(dg), ptr(db), B, S, H,
+                                           type_tab.shape[0], dtype_code(word.dtype), word_pad_id, pos_pad_id, int(acc), int(acc), drop_p, seed,
+                                           drop_stream, ptr(ws), ws.numel(), stream_ptr()), "embed_ln_bwd_adv")
+        return dword, dtype_tab, dptab, dg, db
     if accumulate_into is not None:
         dword, dtype_tab, dptab, dg, db = accumulate_into
         ws = _ws(lib().nbest_embed_bwd_ws_bytes(B * S, H), word.device)

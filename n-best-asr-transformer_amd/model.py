@@ -225,6 +225,26 @@ def _check_rdrop(rdrop, B, distill=None):
     return dict(alpha=alpha)
 
 
+def _check_adv(adv, need_grad=True, distill=None, rdrop=None):
+    """forward_backward's ``adv`` argument -> dict(epsilon) with a finite float epsilon >= 0; it needs the backward (``need_grad``) and
+    carries no ``distill`` and no ``rdrop``; refused before anything is enqueued"""
+    if not isinstance(adv, dict) or set(adv) != {"epsilon"}:
+        raise ValueError("nbest_amd: adv must be dict(epsilon=) (the L2 norm of the perturbation of each utterance's word embeddings)")
+    if not need_grad:
+        raise ValueError("nbest_amd: adv with need_grad=False: the perturbation is formed from the backward's input gradient")
+    if distill is not None:
+        raise ValueError("nbest_amd: adv together with distill is not built (the adversarial pass has the hard terms only)")
+    if rdrop is not None:
+        raise ValueError("nbest_amd: adv together with rdrop is not built (the adversarial pass has the hard terms only)")
+    try:
+        eps = float(adv["epsilon"])
+    except (TypeError, ValueError):
+        eps = float("nan")
+    if not (eps >= 0.0 and math.isfinite(eps)):
+        raise ValueError("nbest_amd: adv epsilon %r: must be a finite number >= 0" % (adv["epsilon"],))
+    return dict(epsilon=eps)
+
+
 def _require_trainable(plan):
     if plan is not None and not plan.trainable:
         raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
@@ -283,6 +303,8 @@ class NBestSTCModel(nn.Module):
         self._stash_gen = collections.Counter()    # slot -> generation of its stash: moves on whenever a pass is handed the stash
         self._ws = None                    # grow-only workspace of the encoder passes
         self._dh = None                    # grow-only scratch of the backward's input gradient
+        self._adv_delta = None             # grow-only fp32 perturbation of the word rows (forward_backward(adv=))
+        self._adv_ws = None                # ... and the row sums of squares nbest_embed_adv_delta leaves between its launches
         self._infer_ws = None              # grow-only workspace of predict() (nbest_encoder_infer)
         self._anchor = None                # autograd bridge: a leaf that makes the outputs of forward() require grad
         self._head_mask = None             # set_head_mask: fp32 [L, heads] on the device (not a parameter, not in state_dict)
@@ -666,7 +688,8 @@ class NBestSTCModel(nn.Module):
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,
-                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None, rdrop=None):
+                         accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None, rdrop=None,
+                         adv=None):
         """Returns dict(top, bott, final, loss_parts[4] (device), asr_cls, trans_cls).  Gradients of the sum
         BCE(final) + BCE(top) + mean-CE (+ MSE) are left in ``arena.g``.  The transcript pass runs only
         when its output is used (--add_l2_loss); the reference computes and discards it otherwise (Q4).
@@ -690,7 +713,24 @@ class NBestSTCModel(nn.Module):
         utterance, which the position-keyed dropout hashes run under independent masks, but need not be.  The heads of the ASR pass
         run nbest_stc_heads_rdrop: ``loss_parts[3]`` is the sum over the P pairs of the symmetric KL between the twins' outputs
         (unscaled) and the gradients left in ``arena.g`` are those of the hard loss of all 2 P rows + alpha * that (+ MSE).  alpha
-        finite and >= 0; not together with ``distill``.  With ``add_l2_loss`` the MSE comes back as ``mse``.  Same launches as without."""
+        finite and >= 0; not together with ``distill``.  With ``add_l2_loss`` the MSE comes back as ``mse``.  Same launches as without.
+        ``adv`` = dict(epsilon=): adversarial training on the word embeddings, the fast gradient method (Miyato et al., 2017).  The
+        clean step runs first, exactly as without the argument (with the caller's ``accumulate``).  Its ASR backward leaves the
+        gradient of the step's whole loss (MSE term included) w.r.t. the embedding LayerNorm output; nbest_embed_adv_delta turns it
+        into the gradient g w.r.t. each token's word embedding and into delta = epsilon g / ||g||, the norm taken per utterance over
+        its non-padding tokens (an utterance whose norm is zero or not finite gets delta = 0).  The ASR pass then runs again with
+        delta added to the word rows (nbest_encoder_desc.emb_delta), the heads with the hard terms only, and its backward ADDS its
+        parameter gradients: ``arena.g`` holds those of L(x) + L(x + delta), delta a constant.  No transcript pass and no MSE term in
+        the second pass.  ``step_counter`` does not move between the two passes, so both run under the SAME dropout bits (encoder
+        and heads): the perturbation is adversarial for exactly the network instance that produced the gradient.  The dict gains
+        ``adv_loss_parts`` (fp32 [4], device: the perturbed pass's three hard terms, slot 3 zero) and ``adv_norm`` (fp32 [B]: ||g||
+        per utterance); everything else returned is the clean pass's.  epsilon finite and >= 0 (0 runs the second pass with a zero
+        delta).  Needs ``need_grad``, trainable embeddings, no head mask, no fp8 model; not together with ``distill`` or ``rdrop``.
+        No host synchronisation; about twice the launches of the plain step plus three."""
+        if adv is not None:
+            adv = _check_adv(adv, need_grad, distill, rdrop)
+            if self.fp8_forward:
+                raise RuntimeError("nbest_amd: adv on an fp8w model is not built (the fp8 forward has no perturbed embedding)")
         if rdrop is not None:
             rdrop = _check_rdrop(rdrop, input_ids.shape[0], distill)
         if distill is not None:
@@ -700,6 +740,9 @@ class NBestSTCModel(nn.Module):
             self._refuse_training_under_mask("forward_backward(need_grad=True)")
             plan = self._training_plan()
             _require_trainable(plan)
+            if adv is not None and (plan.first_trainable > 0 or not plan.with_embeddings):
+                raise RuntimeError("nbest_amd: adv needs trainable embeddings (the perturbation is formed from the gradient w.r.t. "
+                                   "the word embeddings, which a backward over frozen embeddings does not form)")
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
             input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
             need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan, distill=distill, rdrop=rdrop)
@@ -721,11 +764,46 @@ class NBestSTCModel(nn.Module):
                 self._backward_pass(ra, dcls, accumulate=True, chunks=chunks, on_chunk_done=on_chunk_done)
             else:
                 self._backward_pass(ra, dcls, accumulate=accumulate, chunks=chunks, on_chunk_done=on_chunk_done)
+        adv_out = None
+        if adv is not None:
+            adv_out = self._adversarial_pass(ra, labels_f, adv["epsilon"], plan, chunks, on_chunk_done, encoder_grad_scale)
         self._end_of_step(need_grad)
         out = dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
+        if adv_out is not None:
+            out["adv_loss_parts"], out["adv_norm"] = adv_out
         if (distill is not None or rdrop is not None) and mse is not None:
             out["mse"] = mse
         return out
+
+    def _adversarial_pass(self, ra, labels_f, epsilon, plan, chunks=None, on_chunk_done=None, encoder_grad_scale=1.0):
+        """the second half of an FGM step (forward_backward(adv=)): the clean ASR pass ``ra`` has run its backward, so ``self._dh``
+        holds the gradient w.r.t. its embedding LayerNorm output.  Forms delta, runs the ASR pass again on the perturbed word rows
+        (slot 0: the clean stash is finished with) and adds its gradients to ``arena.g``.  Same step seed, same dropout bits.
+        Returns (adv_loss_parts, adv_norm).  Nothing here waits for the device."""
+        a, cfg = self.arena, self.cfg
+        B, S, H = ra.ps.B, ra.ps.S, cfg.hidden_size
+        ids, seg, pos, mask = ra.inputs
+        d = ra.ps.desc
+        pre = "bert_encoder.embeddings."
+        word, ttab, ptab = (a.view(a.weights, pre + n) for n in ("word_embeddings.weight", "token_type_embeddings.weight", "position_embeddings.weight"))
+        gamma = a.view(a.p, pre + "LayerNorm.weight")
+        dh = self._dh[:B * S * H].view(B * S, H)
+        delta = self._grow(vars(self), "_adv_delta", B * S * H, torch.float32)[:B * S * H].view(B * S, H)
+        ws = self._grow(vars(self), "_adv_ws", hb.lib().nbest_embed_adv_ws_bytes(B, S))
+        norm = torch.empty(B, dtype=torch.float32, device=self.device)
+        hb.embed_adv_delta(ids, seg, pos, mask, word, ttab, ptab, gamma, dh, B, S, cfg.layer_norm_eps, epsilon, drop_p=d.hidden_drop,
+                           seed=d.seed, drop_stream=d.drop_stream_base, out=delta, norm=norm, ws=ws)
+        perm = ra.perm if ra.perm is not None else hb.word_perm(ids)
+        d.emb_delta = delta.data_ptr()
+        try:                                                 # whatever raises, the cached descriptor keeps no pointer of this call
+            rb = self._encode(0, ids, seg, self.training, perm, plan)
+            _, _, _, adv_loss, dcls, _, _ = self._heads(rb.hidden, S, labels_f, True, self.training, accumulate=True)
+            if encoder_grad_scale != 1.0:
+                dcls.mul_(encoder_grad_scale)
+            self._backward_pass(rb, dcls, accumulate=True, chunks=chunks, on_chunk_done=on_chunk_done)
+        finally:
+            d.emb_delta = None
+        return adv_loss, norm
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
     def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False):

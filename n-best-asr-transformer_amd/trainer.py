@@ -379,8 +379,21 @@ def soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, bat
     return batch, distill, rdrop
 
 
+def adv_args(adv_epsilon, teacher, rdrop_alpha, world):
+    """forward_backward's ``adv`` of one call under ``adv_epsilon`` (None: none).  FGM carries no soft term and is not built under
+    data parallelism."""
+    if adv_epsilon is None:
+        return None
+    if teacher is not None or rdrop_alpha is not None:
+        raise ValueError("nbest_amd: adv_epsilon together with a teacher or rdrop_alpha is not built (the adversarial pass has the "
+                         "hard terms only)")
+    if world > 1:
+        raise RuntimeError("nbest_amd: adv_epsilon under data parallelism is not built (world size %d)" % world)
+    return dict(epsilon=float(adv_epsilon))
+
+
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
-               distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None):
+               distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None, adv_epsilon=None):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
     ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
@@ -389,12 +402,19 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     ``rdrop_alpha``: R-Drop - the step runs on ``rdrop_batch(batch)`` (every utterance twice, 2 P rows) and adds alpha x the symmetric
     KL between the twins' outputs (forward_backward's ``rdrop``); the returned tensors have 2 P rows, ``loss_parts[3]`` is the
     consistency sum.  Not with a ``teacher``; data parallelism is not built.
+    ``adv_epsilon``: FGM adversarial training on the word embeddings (forward_backward's ``adv``): the step runs the ASR pass a
+    second time on embeddings moved by epsilon along the normalised gradient and the optimizer steps ONCE on the sum of both passes'
+    gradients; the returned scores and ``loss_parts`` are the clean pass's, ``adv_loss_parts`` / ``adv_norm`` come on top.  Not with a
+    ``teacher`` or ``rdrop_alpha``; data parallelism is not built.
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
     b_local = batch["ids"].shape[0]
+    adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
     batch, distill, rdrop = soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids)
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
-    chunks = reducer.chunks if reducer is not None else None
+    # (FGM: the second pass adds to every gradient, so nothing is ready before the call returns - one world-size-1 exchange at the end)
+    overlap = reducer is not None and adv is None
+    chunks = reducer.chunks if overlap else None
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
     # B_local rows, so after the SUM all-reduce the term needs the weight B_local / B_global (= 1/world for equal shards)
     mse_scale = b_local / float(global_batch) if global_batch else 1.0 / world
@@ -403,9 +423,13 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
         reducer.set_step_tokens(batch["ids"], batch.get("tids") if add_l2_loss else None, rows=batch.get("word_rows"))
     out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
                                  trans_seg_ids=batch.get("tseg"), add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale,
-                                 chunks=chunks, on_chunk_done=reducer.layers_ready if reducer is not None else None,
-                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop)
-    if reducer is not None:
+                                 chunks=chunks, on_chunk_done=reducer.layers_ready if overlap else None,
+                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop,
+                                 adv=adv)
+    if reducer is not None and not overlap:
+        reducer.reduce_all()
+        optimizer.step()
+    elif reducer is not None:
         reducer.wait_layers()
         optimizer.step_main()             # runs while the embedding tables' all-reduce is still in flight
         reducer.wait()
@@ -802,6 +826,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     teacher, alpha = getattr(opt, "teacher", None), getattr(opt, "distill_alpha", 0.5)      # --distill_from
     temperature = getattr(opt, "distill_temperature", None)                                 # --distill_temperature
     rdrop_alpha = getattr(opt, "rdrop_alpha", None)                                         # --rdrop_alpha
+    adv_epsilon = getattr(opt, "adv_epsilon", None)                                         # --adv_epsilon
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -822,16 +847,17 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
                              global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha,
-                             distill_temperature=temperature, rdrop_alpha=rdrop_alpha)
+                             distill_temperature=temperature, rdrop_alpha=rdrop_alpha, adv_epsilon=adv_epsilon)
             if sched is not None:
                 sched.step()
         else:
+            adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
             b, distill, rdrop = soft_term_args(teacher, alpha, temperature, rdrop_alpha, b, world, opt.add_segment_ids)
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
-                                         distill=distill, rdrop=rdrop)
+                                         distill=distill, rdrop=rdrop, adv=adv)
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)
