@@ -703,7 +703,10 @@ typedef struct nbest_encoder_desc {
   const uint32_t* gamax_prev;
   uint32_t* gamax_new;
   int32_t fp8_bwd;
-  int32_t pad2;
+  /* (in the slot that was padding: no offset and no size changes)
+   * head_gate_stash != 0 (needs head_gate): training under a head mask, see head_gate below.  Zero = no gated-context stash (the
+   * behaviour without the field). */
+  int32_t head_gate_stash;
   /* optional (bf16): the weight arena packed by nbest_pack_weights for the forward GEMMs (wpk: matrices as stored, [out][in]) and for
    * the dgrad GEMMs (wpkt: packed from the TRANSPOSED copy wts_t), at the arena's element offsets; NULL = the GEMMs read wts / wts_t */
   const void* wpk;
@@ -739,7 +742,8 @@ typedef struct nbest_encoder_desc {
    * one-query attention backward that writes the layer's dQ|dK|dV in full (dQ zero outside the CLS rows), and runs the QKV dgrad
    * and weight gradient unchanged.  Event pairs (wgrad_events): as many as without the flag; the top layer's bracket its small
    * launches.  Same results up to summation order (fp32) / one more rounding of the B rows (bf16); bit-reproducible run to run.
-   * Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward (w8), head_gate, base_ids / alpha, no_param_grad and S < 2.
+   * Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward (w8), head_gate without head_gate_stash, base_ids / alpha,
+   * no_param_grad and S < 2.
    * first_trainable == L (nothing stashed, no backward) is accepted: the forward runs the top layer on the CLS rows of the frozen
    * layers' scratch, so the final CLS rows are the bits a trainable top layer gives.  The backward must see the value the forward of
    * its stash saw.  nbest_encoder_infer* ignore the field; nbest_encoder_act_view refuses the top layer of such a stash.           */
@@ -772,7 +776,20 @@ typedef struct nbest_encoder_desc {
    * the layers of [layer_begin, layer_end) (overwritten; other layers untouched).
    * Refused (NBEST_ERR_ARG, nothing enqueued): head_gate with the fp8 forward (w8) or with first_trainable > 0, head_gate_grad
    * without head_gate, and a backward with head_gate but without no_param_grad (the attention-output weight gradient would need
-   * the gated context, which is not kept).                                                                                       */
+   * the gated context, which is not kept) - all of this without head_gate_stash.
+   * head_gate_stash != 0 (the field after fp8_bwd) keeps the gated context too, so that parameters can be trained under the gates:
+   * the activation stash gains one region gctx [M][H] of the dtype per stashed layer, after everything else (the offsets of every
+   * other region, and nbest_encoder_act_view, are unchanged; nbest_encoder_act_bytes grows by (L - first_trainable) [M][H] regions,
+   * nbest_encoder_ws_bytes does not change).  The forward of a stashed layer writes the gated copy to gctx (not to the workspace)
+   * and the attention-output GEMM reads it; ctx stays un-gated for the attention backward.  A frozen layer (l < first_trainable)
+   * gates its scratch context in place, so first_trainable > 0 (up to L) is accepted; the cls_top layer gates its B compact rows
+   * into the first B rows of gctx, so cls_top is accepted.  nbest_encoder_backward runs with parameter gradients: the
+   * attention-output weight gradient reads gctx (plain, paired, grouped, window and cls_top launches alike - the stash outlives the
+   * deferred ones), and nbest_head_gate_bwd scales dctx by the gate ahead of the attention backward (cls_top layer: over the B
+   * compact rows, S = 1).  The weights of a head with gate 0 get exactly zero gradients (its Wo columns, its Q / K / V rows and
+   * biases).  The backward must see the flag its stash's forward saw.  Refused with head_gate_stash (NBEST_ERR_ARG, nothing
+   * enqueued): head_gate == NULL, the fp8 forward (w8), emb_delta, base_ids / alpha, no_param_grad and head_gate_grad.
+   * nbest_encoder_infer* ignore head_gate_stash.                                                                                 */
   const float* head_gate;
   float* head_gate_grad;
   /* optional interpolated embeddings (integrated gradients): base_ids int64 [B*S] and alpha fp32 [B], device memory, set per call

@@ -86,6 +86,12 @@ def parse_arguments(argv=None):
     g.add_argument("--head_mask", default=None, metavar="FILE",
                    help="gate the attention heads (HF's head_mask) for --testing, --predict and --head_importance: a JSON list of L rows "
                         "of `heads` numbers, 0 = head pruned, 1 = kept (any float scales the head's output).  Not for a training run")
+    g.add_argument("--train_head_mask", default=None, metavar="FILE",
+                   help="train under a head mask (the format of --head_mask; usually the pruned_mask of --head_importance --prune_heads, "
+                        "with --init_checkpoint): the fine-tune that recovers what pruning lost (Michel et al., 2019).  Every step and "
+                        "every epoch's evaluation run under the mask; model.pt keeps the full tensors, the mask is not in it - evaluate "
+                        "with --testing --head_mask FILE.  The experiment directory gains __hm_<digest of the mask>.  A training flag, one "
+                        "GPU; not with --head_mask, --dtype fp8w or --adv_epsilon")
     g.add_argument("--head_importance", default=None, metavar="PATH",
                    help="score every attention head on the --valid_file split with <exp_dir>/model.pt (Michel et al., 2019: the mean "
                         "over utterances of |d loss / d head gate|) and write one JSON object to PATH: importance and normalized "
@@ -287,6 +293,25 @@ def parse_arguments(argv=None):
             ap.error("--head_mask applies to --testing, --predict and --head_importance; training under a head mask is not built")
         if not os.path.isfile(opt.head_mask):
             ap.error("--head_mask %s: no such file" % opt.head_mask)
+    if opt.train_head_mask is not None:
+        for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--train_head_mask is a training flag: %s runs under --head_mask FILE, on the directory named without it" % flag)
+        if opt.head_mask is not None:
+            ap.error("--train_head_mask together with --head_mask: a training run takes its mask from --train_head_mask alone")
+        if opt.dtype == "fp8w":
+            ap.error("--train_head_mask together with --dtype fp8w is not built (the fp8 forward has no gated context)")
+        if opt.adv_epsilon is not None:
+            ap.error("--train_head_mask together with --adv_epsilon is not built (FGM under a head mask)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--train_head_mask runs on one GPU: training under a head mask under data parallelism is not built (world size %s)"
+                     % os.environ["WORLD_SIZE"])
+        if not os.path.isfile(opt.train_head_mask):
+            ap.error("--train_head_mask %s: no such file" % opt.train_head_mask)
+        try:
+            trainer.head_mask_file_digest(opt.train_head_mask)
+        except ValueError as e:
+            ap.error("--train_head_mask: %s" % e)
     opt.gpu_index = 0 if opt.deviceId == 0 else opt.deviceId - 1            # n_best_asr_bert.py:116-126 (0: auto -> first GPU)
     # gradient accumulation exactly as the reference derives it (n_best_asr_bert.py:522): 4 micro-batches of batchSize / 4
     # per optimizer step when --n_layers 12 is passed (the shipped script never passes it -> 1)
@@ -314,6 +339,8 @@ def exp_dir(opt):
         parts.append("rdrop_%s" % opt.rdrop_alpha)
     if getattr(opt, "adv_epsilon", None) is not None:
         parts.append("fgm_%s" % opt.adv_epsilon)
+    if getattr(opt, "train_head_mask", None) is not None:                                # last: the mask's digest, not the file's name
+        parts.append("hm_%s" % trainer.head_mask_file_digest(opt.train_head_mask))
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
 
 
@@ -445,6 +472,14 @@ def main(argv=None):
     frozen = freeze_parameters(model, opt.freeze_embeddings, opt.freeze_layers)
     n_params = sum(s.numel for s in model.arena.slots if s.name not in frozen)
     n_bert = sum(s.numel for s in model.arena.slots if "bert_encoder" in s.name and s.name not in frozen)
+    # (the weights are in place: --init_checkpoint is the usual companion; a mask of the wrong shape exits before a directory is made)
+    train_mask = None
+    if opt.train_head_mask is not None:                    # after the weights are in place (--init_checkpoint is the usual companion)
+        try:
+            train_mask = trainer.read_head_mask(opt.train_head_mask, cfg.num_hidden_layers, cfg.num_attention_heads)
+        except ValueError as e:
+            raise SystemExit("--train_head_mask: %s" % e)
+        model.set_head_mask(train_mask, trainable=True)    # every step and every epoch's evaluation below run under it
     opt.exp_dir = exp_dir(opt)
     if rank == 0:
         os.makedirs(opt.exp_dir, exist_ok=True)
@@ -546,12 +581,21 @@ def main(argv=None):
         log.info("FGM: epsilon %s; every step runs the ASR pass again on word embeddings moved by epsilon (L2 norm per utterance) along "
                  "the loss gradient, same dropout bits, one optimizer step on the sum of both gradients, Loss and F1 below are the clean "
                  "pass's" % opt.adv_epsilon)
+    if train_mask is not None:
+        log.info("Head mask: %s (digest %s), heads kept per layer %s of %d; every step and every evaluation run under it, a pruned "
+                 "head's weights get a zero gradient, model.pt keeps the full tensors (evaluate with --testing --head_mask)"
+                 % (opt.train_head_mask, trainer.head_mask_digest(train_mask), [sum(1 for x in r if x != 0.0) for r in train_mask],
+                    cfg.num_attention_heads))
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)
     first_epoch, last = 0, os.path.join(opt.exp_dir, "last.pt")
     if opt.resume and os.path.exists(last):
         ck = torch.load(last, map_location="cpu", weights_only=True)           # written by this program: tensors + numbers
+        if ck.get("head_mask") != train_mask:
+            said = lambda m: "without a head mask" if m is None else "under the head mask %s" % trainer.head_mask_digest(m)
+            raise SystemExit("--resume from %s: the checkpoint was trained %s, this run trains %s; resume with the --train_head_mask "
+                             "it was started with" % (last, said(ck.get("head_mask")), said(train_mask)))
         model.load_reference_state(ck["model"])
         try:
             opt.optimizer.load_state_dict(ck["optimizer"])
@@ -596,7 +640,8 @@ def main(argv=None):
             opt.optimizer.gather_master()           # all ranks (collectives); master and moments are whole everywhere afterwards
             if rank == 0:                           # ... so the state dicts are built AFTER the gather, on rank 0 only
                 torch.save(dict(model={k: v.detach().cpu() for k, v in model.state_dict().items()},
-                                optimizer=opt.optimizer.state_dict(gather=False), best=best, epoch=ep, dropout_step=model.step_counter),
+                                optimizer=opt.optimizer.state_dict(gather=False), best=best, epoch=ep, dropout_step=model.step_counter,
+                                **({} if train_mask is None else dict(head_mask=train_mask))),
                            last + ".tmp")
                 os.replace(last + ".tmp", last)
         if opt.stop_after_epoch is not None and ep >= opt.stop_after_epoch:

@@ -18,6 +18,9 @@
 //   Layers 0..K-1 are not stashed: their forward runs on fz plus the backward's layer-gradient buffers, which are idle
 //   during a forward (frozen_layer).
 // Head gates (desc.head_gate): the forward's gated copy of a layer's ctx borrows dctx; the stash keeps the un-gated ctx.
+//   desc.head_gate_stash (training under the gates): the stash ends with gctx [M][H] T per layer K..L-1, the gated copy - the X operand
+//   of the attention-output weight gradient, which a deferred (grouped / window) launch reads long after dctx is reused.  ctx stays
+//   un-gated (the attention backward's O); a frozen layer gates its scratch ctx in place; dctx is not borrowed.
 // Inference workspace: infer_layout, below.
 #include <algorithm>
 #include <vector>
@@ -54,11 +57,15 @@ struct ActLayout {
   size_t o_qkv, o_ctx, o_lse, o_r1, o_st1, o_x1, o_u, o_hact, o_r2, o_st2;
   size_t o_x8, o_ctx8, o_x18, o_h8;   // fp8 forward ("fp8w"): e4m3 copies of the four GEMM inputs of the layer, kept for the fp8 weight gradients
   size_t o_keep, keep_bytes;          // bf16, S <= 256: attention-dropout keep words of the layer (forward -> backward)
+  size_t gctx, gctx_stride;           // desc.head_gate_stash: the gated contexts [L - K][M][H], after every layer block (else 0 bytes)
   size_t total;
   int K;                              // first stashed layer (desc.first_trainable)
 };
 
 static int first_trainable(const nbest_encoder_desc* d) { return d->first_trainable < 0 ? 0 : (d->first_trainable > d->L ? d->L : d->first_trainable); }
+
+// training under head gates: the gated context of every stashed layer is kept (include/nbest_hip.h, head_gate)
+static bool gate_stashed(const nbest_encoder_desc* d) { return d->head_gate && d->head_gate_stash; }
 
 static ActLayout act_layout(const nbest_encoder_desc* d, const Sizes& z) {
   ActLayout a;
@@ -79,7 +86,10 @@ static ActLayout act_layout(const nbest_encoder_desc* d, const Sizes& z) {
     a.o_x8 = take(p, z.MH8); a.o_ctx8 = take(p, z.MH8); a.o_x18 = take(p, z.MH8); a.o_h8 = take(p, z.MF8);
   }
   a.layer_stride = p;
-  a.total = o + (size_t)(d->L - a.K) * p;
+  o += (size_t)(d->L - a.K) * p;
+  a.gctx = take(o, gate_stashed(d) ? (size_t)(d->L - a.K) * z.MH : 0);   // last: every other offset is what it is without it
+  a.gctx_stride = z.MH;
+  a.total = o;
   return a;
 }
 
@@ -302,7 +312,8 @@ static bool fp8_backward_active(const nbest_encoder_desc* d) {
   return fp8_forward_active(d) && d->fp8_bwd && d->w8t && d->gamax_prev && d->gamax_new;   // reads the forward's e4m3 activation copies
 }
 
-static int check_desc(const nbest_encoder_desc* d) {
+// train: a training entry point (the inference ones ignore head_gate_stash, as they ignore cls_top)
+static int check_desc(const nbest_encoder_desc* d, bool train = true) {
   NB_CHECK(d && d->layers_host, NBEST_ERR_ARG, "encoder: null descriptor");
   NB_CHECK(d->dtype == NBEST_F32 || d->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "encoder: bad dtype %d", d->dtype);
   NB_CHECK(d->B > 0 && d->S > 0 && d->L > 0 && d->heads > 0, NBEST_ERR_SHAPE, "encoder: bad shape");
@@ -319,10 +330,19 @@ static int check_desc(const nbest_encoder_desc* d) {
   NB_CHECK(0 <= d->first_trainable && d->first_trainable <= d->L, NBEST_ERR_ARG, "encoder: first_trainable %d outside [0, L=%d]",
            d->first_trainable, d->L);
   NB_CHECK(!d->base_ids == !d->alpha, NBEST_ERR_ARG, "encoder: interpolated embeddings need both base_ids and alpha (or neither)");
-  // head gates (desc.head_gate): the gated context is a scratch copy the bf16 / fp32 attention-output GEMM reads - the fp8 forward's
-  // e4m3 copy of ctx comes out of the attention kernel, and a frozen layer's forward already lives in that scratch
+  // head_gate_stash: the gated context is kept in the stash, parameters train under the gates (frozen layers gate in place)
+  if (train && d->head_gate_stash) {
+    NB_CHECK(d->head_gate, NBEST_ERR_ARG, "encoder: head_gate_stash without head_gate");
+    NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder: head_gate_stash is not supported with the fp8 forward (desc.w8)");
+    NB_CHECK(!d->emb_delta, NBEST_ERR_ARG, "encoder: head_gate_stash is not supported with perturbed embeddings (emb_delta)");
+    NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder: head_gate_stash is not supported with interpolated embeddings (base_ids / alpha)");
+    NB_CHECK(!d->no_param_grad, NBEST_ERR_ARG, "encoder: head_gate_stash is not supported with no_param_grad (it exists for the parameter gradients)");
+    NB_CHECK(!d->head_gate_grad, NBEST_ERR_ARG, "encoder: head_gate_stash is not supported with head_gate_grad");
+  }
+  // head gates (desc.head_gate) without it: the gated context is a scratch copy the bf16 / fp32 attention-output GEMM reads - the fp8
+  // forward's e4m3 copy of ctx comes out of the attention kernel, and a frozen layer's forward already lives in that scratch
   NB_CHECK(!d->head_gate || !d->w8, NBEST_ERR_ARG, "encoder: head_gate is not supported with the fp8 forward (desc.w8)");
-  NB_CHECK(!d->head_gate || d->first_trainable == 0, NBEST_ERR_ARG, "encoder: head_gate needs first_trainable == 0 (got %d)", d->first_trainable);
+  NB_CHECK(!d->head_gate || d->first_trainable == 0 || (train && d->head_gate_stash), NBEST_ERR_ARG, "encoder: head_gate needs first_trainable == 0 (got %d) or head_gate_stash", d->first_trainable);
   NB_CHECK(!d->head_gate_grad || d->head_gate, NBEST_ERR_ARG, "encoder: head_gate_grad without head_gate");
   // adversarial perturbation of the word rows (desc.emb_delta): the embedding kernels' _adv entry points, bf16 / fp32 forward, full stash
   NB_CHECK(!d->emb_delta || !d->w8, NBEST_ERR_ARG, "encoder: emb_delta is not supported with the fp8 forward (desc.w8)");
@@ -337,7 +357,8 @@ static int check_desc(const nbest_encoder_desc* d) {
 static int check_cls_top(const nbest_encoder_desc* d) {
   if (!d->cls_top) return NBEST_OK;
   NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder: cls_top is not supported with the fp8 forward / backward (desc.w8)");
-  NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder: cls_top is not supported with head_gate (the gate runs on the full-width context)");
+  NB_CHECK(!d->head_gate || d->head_gate_stash, NBEST_ERR_ARG, "encoder: cls_top is not supported with head_gate (the gate runs on the "
+           "full-width context) unless head_gate_stash keeps the gated rows");
   NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder: cls_top is not supported with interpolated embeddings (base_ids / alpha)");
   NB_CHECK(!d->no_param_grad, NBEST_ERR_ARG, "encoder: cls_top is not supported with no_param_grad");
   // (first_trainable == L is NOT refused: the forward then runs the top layer on the CLS rows of the frozen layers' scratch, and the heads of
@@ -449,6 +470,7 @@ static int layer_gemm(const GemmPass& c, const GemmOp& o) {
 // outside the fp8 forward.
 struct LayerBufs {
   void *qkv, *ctx, *r1, *x1, *u, *hact, *r2;
+  void* gctx;   // head gates: where the gated context goes and what the attention-output GEMM reads; NULL: ctx is gated in place
   float *lse, *st1, *st2;
   uint32_t* keep;
   uint8_t *x8, *ctx8, *x18, *h8;
@@ -468,6 +490,7 @@ static LayerBufs stashed_layer(const nbest_encoder_desc* d, const ActLayout& a, 
     b.x8 = (uint8_t*)(Lb + a.o_x8); b.ctx8 = (uint8_t*)(Lb + a.o_ctx8);
     b.x18 = (uint8_t*)(Lb + a.o_x18); b.h8 = (uint8_t*)(Lb + a.o_h8);
   }
+  if (gate_stashed(d)) b.gctx = (char*)act + a.gctx + (size_t)(l - a.K) * a.gctx_stride;
   return b;
 }
 
@@ -492,8 +515,6 @@ struct Fwd {
   GemmPass g;   // g.fp8: the four GEMMs of a layer on the block-scaled fp8 MFMA, their A operands the e4m3 copies x8 | ctx8 | x18 | h8
   const uint8_t* key_mask;
   bool arec;    // record the activation amax of this pass (fp8, or the calibration pass: fp8 mode without an activation history)
-  // head gates (desc.head_gate): where a layer's gated context goes - [M][H] scratch, or NULL: in place (nothing reads the un-gated one)
-  void* gated_ctx;
   // delayed scale of activation idx = 4 l + {x, ctx, x1, gelu} and the slot block its producer records this pass's amax in (fp8 pass)
   const uint32_t* AP(int idx) const { return g.fp8 ? d->aamax_prev + idx : nullptr; }
   uint32_t* AN(int idx) const { return (g.fp8 && arec) ? d->aamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS : nullptr; }
@@ -508,7 +529,7 @@ static Fwd make_fwd(const nbest_encoder_desc* d, const void* wts, const float* p
                     nbest_stream_t stream) {
   const GemmPass g = {d->dtype, z.M, stream, d->seed, Ptrs{(const char*)wts, prm, z.esz}, d->wpk, false, fp8_forward_active(d),
                       d->w8, d->w8p, d->w8_inv_scale, d->aamax_prev, d->aamax_new, nullptr, 0, 0};
-  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16, nullptr};
+  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16};
 }
 
 // Layer l over all M rows: xin -> xout through the buffers `b`.  x8_next: where the last LayerNorm leaves the e4m3 copy of xout for
@@ -536,7 +557,7 @@ static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const
   RUN(c.calib(b.ctx, M * H, t + 1));
   const void* ctx = b.ctx;   // what the attention-output GEMM reads: the context, or its gated copy
   if (d->head_gate) {
-    void* gated = c.gated_ctx ? c.gated_ctx : b.ctx;
+    void* gated = b.gctx ? b.gctx : b.ctx;
     RUN(nbest_head_gate_fwd(b.ctx, H, gated, H, d->head_gate + (int64_t)l * d->heads, M, d->heads, 64, dt, stream));
     ctx = gated;
   }
@@ -594,7 +615,13 @@ static int layer_forward_cls(const Fwd& c, int l, const void* xin, void* xout, c
     g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.R = R; g.ldr = ldr;
     return nbest_gemm(&g, stream);
   };
-  RUN(dense_drop_res(b.ctx, o.wo, P.P(o.bo), H, H, xin, SH, s0 + 1, b.r1));
+  const void* ctx = b.ctx;   // head gates (head_gate_stash): the B compact rows gated into gctx (a frozen top layer: in place)
+  if (d->head_gate) {
+    void* gated = b.gctx ? b.gctx : b.ctx;
+    RUN(nbest_head_gate_fwd(b.ctx, H, gated, H, d->head_gate + (int64_t)l * d->heads, B, d->heads, 64, dt, stream));
+    ctx = gated;
+  }
+  RUN(dense_drop_res(ctx, o.wo, P.P(o.bo), H, H, xin, SH, s0 + 1, b.r1));
   RUN(nbest_internal_layernorm_fwd8(b.r1, P.P(o.ln1_g), P.P(o.ln1_b), b.x1, nullptr, b.st1, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
   nbest_gemm_args g = gemm_nt(dt, b.x1, P.W(o.w1), b.hact, B, F, H);
   g.epilogue = NBEST_EPI_BIAS_GELU; g.bias = P.P(o.b1); g.U = b.u; g.ldu = F;
@@ -665,17 +692,22 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
   const WsLayout wl = ws_layout(d, z, wgrad_mode(d));
   const int FT = a.K;   // layers 0..FT-1 are frozen: run on scratch in ws, nothing of them stashed
-  if (c.g.fp8 || FT > 0 || d->head_gate)
+  const bool gscratch = d->head_gate && !gate_stashed(d);
+  if (c.g.fp8 || FT > 0 || gscratch)
     NB_CHECK(ws && ws_bytes >= wl.total, NBEST_ERR_WORKSPACE, "encoder_forward(%s): workspace too small (%zu < %zu)",
-             FT > 0 ? "first_trainable > 0" : d->head_gate ? "head_gate" : "fp8", ws_bytes, wl.total);
+             FT > 0 ? "first_trainable > 0" : gscratch ? "head_gate" : "fp8", ws_bytes, wl.total);
   // head gates: the stash keeps the un-gated context (the backward's operand); the gated copy lives in the backward's dctx buffer,
-  // idle during a forward (first_trainable == 0: no frozen layer borrows it)
-  if (d->head_gate) c.gated_ctx = (char*)ws + wl.dctx;
+  // idle during a forward (first_trainable == 0: no frozen layer borrows it).  head_gate_stash: the stashed layers' gctx instead
+  // (stashed_layer), a frozen layer in place
   const Ptrs& P = c.g.W;
   char *A = (char*)act, *W = (char*)ws;
   const int H = d->H, dt = d->dtype;
   auto X = [&](int l) { return l >= FT ? (void*)(A + a.X + (size_t)(l - FT) * z.MH) : (void*)(W + ((l & 1) ? wl.fz_x1 : wl.fz_x0)); };
-  auto bufs = [&](int l) { return l >= FT ? stashed_layer(d, a, act, l) : frozen_layer(d, wl, z, ws); };
+  auto bufs = [&](int l) {
+    LayerBufs b = l >= FT ? stashed_layer(d, a, act, l) : frozen_layer(d, wl, z, ws);
+    if (gscratch) b.gctx = W + wl.dctx;
+    return b;
+  };
 
   float* emb_stats = (float*)(FT > 0 ? W + wl.fz_emb_stats : A + a.emb_stats);
   if (d->base_ids)   // integrated gradients: the word rows at the path points alpha (desc.base_ids / alpha)
@@ -721,8 +753,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   NB_CHECK(!npg || (!with_embeddings && d->first_trainable == 0 && !d->no_input_grad && !d->w8), NBEST_ERR_ARG,
            "encoder_backward: no_param_grad refuses with_embeddings (%d), first_trainable > 0 (%d), no_input_grad (%d) and the fp8 "
            "forward (w8): it forms the input gradient only, of a full stash", with_embeddings, d->first_trainable, d->no_input_grad);
-  NB_CHECK(!d->head_gate || npg, NBEST_ERR_ARG, "encoder_backward: head_gate needs no_param_grad (the attention-output weight gradient would "
-           "need the gated context, which the forward does not keep)");
+  NB_CHECK(!d->head_gate || npg || d->head_gate_stash, NBEST_ERR_ARG, "encoder_backward: head_gate needs no_param_grad (the attention-output weight gradient would "
+           "need the gated context, which the forward keeps only with head_gate_stash)");
   NB_CHECK(wts && prm && (grad || npg) && ids && pos && key_mask && act && dhidden && ws, NBEST_ERR_ARG, "encoder_backward: null pointer");
   NB_CHECK(!with_embeddings || d->word_perm, NBEST_ERR_ARG, "encoder_backward: desc.word_perm (stable argsort of this pass's ids) is required");
   NB_CHECK(layer_begin >= d->first_trainable, NBEST_ERR_ARG, "encoder_backward: layer_begin %d < first_trainable %d (those layers are not stashed)",
@@ -867,7 +899,7 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       dRd2 = hdrop ? (void*)(W + w.dRd) : dR2; dRd1 = hdrop ? (void*)(W + w.dRd + bh) : dR1;
     }
     const WGrad wg[4] = {{dqkvL, X(l), dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0},
-                         {dRd1, b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},
+                         {dRd1, b.gctx ? b.gctx : b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},   // (head_gate_stash: the gated context)
                          {dBigL, b.x1, dBig8, b.x18, o.w1, F, H, t + 1, t + 2},
                          {dRd2, b.hact, dRd8, b.h8, o.w2, H, F, t + 0, t + 3}};
     // cls: gradient j (1: attention-out, 2: FFN-up, 3: FFN-down) of the top layer over its K = B token rows, one plain launch
@@ -914,6 +946,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
       }
       const GemmOp dwo = {dRd1, nullptr, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
       RUN(layer_gemm(dgc, dwo));
+      if (d->head_gate)   // (head_gate_stash) the B compact rows: dctx scaled by the gate, the attention backward takes the un-gated ctx
+        RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads, nullptr, d->B, 1, d->heads, 64, dt, stream));
       // one-query attention backward: the layer's dQ|dK|dV in full (dQ zero outside the CLS rows) ; QKV bias gradient
       RUN(nbest_internal_attention_cls_bwd(b.qkv, key_mask, b.ctx, dctx, dqkvL, G(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S, d->heads, 64,
                                            dt, d->attn_drop, d->seed, s0 + 0, stream));
@@ -1089,7 +1123,7 @@ extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { re
 extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                                         const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
                                         float* cls_attn, nbest_stream_t stream) {
-  RUN(check_desc(d));
+  RUN(check_desc(d, false));
   NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
            "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
   NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");

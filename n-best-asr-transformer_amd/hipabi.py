@@ -89,7 +89,7 @@ class EncoderDesc(C.Structure):
                 ("layers_host", C.POINTER(LayerOffsets)), ("seed", C.c_uint64), ("drop_stream_base", C.c_uint32),
                 ("wgrad_events_n", C.c_int32), ("wgrad_events", C.POINTER(C.c_void_p)),
                 ("w8", C.c_void_p), ("w8_inv_scale", C.c_void_p), ("w8t", C.c_void_p), ("gamax_prev", C.c_void_p),
-                ("gamax_new", C.c_void_p), ("fp8_bwd", C.c_int32), ("pad2", C.c_int32),
+                ("gamax_new", C.c_void_p), ("fp8_bwd", C.c_int32), ("head_gate_stash", C.c_int32),
                 ("wpk", C.c_void_p), ("wpkt", C.c_void_p), ("w8p", C.c_void_p), ("w8tp", C.c_void_p),
                 ("word_perm", C.c_void_p), ("aamax_prev", C.c_void_p), ("aamax_new", C.c_void_p), ("fp8_act", C.c_int32), ("cls_top", C.c_int32),
                 ("first_trainable", C.c_int32), ("no_input_grad", C.c_int32), ("emb_delta", C.c_void_p), ("wgrad_skip_host", C.c_void_p),

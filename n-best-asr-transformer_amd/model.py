@@ -87,9 +87,10 @@ def freeze_plan(model):
 class _Pass:
     """descriptor of one encoder pass shape (B, S); the activation stash it writes belongs to the slot.  Slots 0 / 1 are the
     training path's ASR / transcript passes; a named slot ("infer") is a forward-only inference descriptor without fp8 fields.
-    ``first_trainable``: layers below it run without a stash (FreezePlan)."""
+    ``first_trainable``: layers below it run without a stash (FreezePlan).  ``gate_stash``: the stash also keeps every layer's
+    gated context (nbest_encoder_desc.head_gate_stash: a trainable head mask) - it is sized with the flag set."""
 
-    def __init__(self, model, B, S, slot, first_trainable=0):
+    def __init__(self, model, B, S, slot, first_trainable=0, gate_stash=False):
         a, cfg = model.arena, model.cfg
         train = isinstance(slot, int)
         d = hb.EncoderDesc()
@@ -112,15 +113,19 @@ class _Pass:
         if model.fp8_forward and train:    # set before the stash is sized: the fp8 mode keeps e4m3 copies of the GEMM inputs per layer
             d.w8, d.w8_inv_scale = a.w8.data_ptr(), a.w8_inv_scale.data_ptr()
         self.desc = d
+        self.gate_stash = bool(gate_stash)
+        if gate_stash:                     # the layout follows the flag only with a gate set (the pointer is set anew by every call)
+            d.head_gate_stash, d.head_gate = 1, model.head_mask.data_ptr()
         self.act_bytes = hb.lib().nbest_encoder_act_bytes(C.byref(d))
         self.B, self.S = B, S
 
 
-class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen plan cls_top")):
+class _PassRecord(collections.namedtuple("_PassRecord", "ps slot inputs perm hidden gen plan cls_top gate_stash")):
     """one call's encoder pass: its _Pass, slot, (ids, seg, pos, mask), token permutation (None: sorted on the device when the
     backward asks), hidden states [B*S, H] (a view into the slot's stash), the generation of that stash it wrote, the
     FreezePlan it ran with (None: everything trainable, full stash) and whether its top layer ran on the CLS rows only (then
-    only rows b S of ``hidden`` are written, and the backward must run with the same descriptor flag)"""
+    only rows b S of ``hidden`` are written, and the backward must run with the same descriptor flag), and whether the stash keeps
+    the gated contexts (head_gate_stash: the same holds)"""
     __slots__ = ()
 
     @property
@@ -375,32 +380,60 @@ class NBestSTCModel(nn.Module):
         return missing
 
     # ---- head mask (HF's head_mask) ---------------------------------------------------------------
+    _head_mask_trainable = False           # set_head_mask(trainable=True): forward_backward(need_grad=True) runs under the mask
     @property
     def head_mask(self):
         """the mask set_head_mask installed (fp32 [L, heads] on the device), or None"""
         return self._head_mask
 
-    def set_head_mask(self, mask):
+    @property
+    def head_mask_trainable(self):
+        """True while the mask in force was installed with ``set_head_mask(mask, trainable=True)``"""
+        return self._head_mask_trainable
+
+    def set_head_mask(self, mask, trainable=False):
         """Gate the attention heads, as ``BertModel.forward(head_mask=)``: ``mask`` [L, heads] of any floats (0 prunes head h of
         layer l, 1 is the identity) multiplies each head's attention context after dropout and P.V, before the attention-output
         projection; None removes it.  Held on the device, not part of ``state_dict``.  While set it applies to the eval / no_grad
         ``forward``, ``forward_backward(need_grad=False)`` (what eval_epoch runs), ``predict``, ``attribute`` and ``head_gate_grad``;
-        the attention maps (``return_attns``, ``cls_attn``) stay the un-gated probabilities.  Training under a mask is not built:
+        the attention maps (``return_attns``, ``cls_attn``) stay the un-gated probabilities.  Without ``trainable``,
         ``forward_backward(need_grad=True)`` and the autograd-bridge forward raise, and so does the stash forward of an fp8w model
-        (its ``predict`` / ``attribute`` run the bf16 copy and work).  Without a mask every pass enqueues what it always did."""
+        (its ``predict`` / ``attribute`` run the bf16 copy and work).  Without a mask every pass enqueues what it always did.
+        ``trainable=True`` (needs a mask): ``forward_backward(need_grad=True)`` - and with it ``train_step`` - runs under the mask:
+        the fine-tune of a pruned model (Michel et al., 2019).  Every stash pass, eval passes included, then keeps each layer's gated
+        context next to the un-gated one (nbest_encoder_desc.head_gate_stash; one more [B S, H] tensor per stashed layer), the
+        attention-output weight gradient reads it, and the gradient entering the attention backward is scaled by the gate; the
+        scores of an eval pass are the bits of the same mask set without the flag.  The weights of a head with gate 0 get exactly
+        zero gradients.  Frozen parameters (FreezePlan: frozen layers gate in place), ``accumulate``, ``chunks``, ``add_l2_loss``
+        (the transcript pass runs under the same mask), ``distill=`` and ``rdrop=`` (they change the heads call and the batch only)
+        and the top layer on the CLS rows (``cls_top``) work as without a mask.  Still refused: the autograd-bridge forward, an
+        fp8w model, ``adv=``, and data parallelism (``train_step``).  ``head_gate_grad``, ``attribute`` and ``predict`` run their own
+        descriptors as before."""
         if mask is None:
-            self._head_mask = None
+            if trainable:
+                raise ValueError("nbest_amd set_head_mask: trainable=True needs a mask (got None)")
+            self._head_mask, self._head_mask_trainable = None, False
             return
         L, heads = self.cfg.num_hidden_layers, self.cfg.num_attention_heads
         m = torch.as_tensor(mask)
         if tuple(m.shape) != (L, heads):
             raise ValueError("nbest_amd set_head_mask: the mask must be [L=%d, heads=%d] (got %s)" % (L, heads, list(m.shape)))
         self._head_mask = m.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        self._head_mask_trainable = bool(trainable)
 
-    def _refuse_training_under_mask(self, what):
-        if self._head_mask is not None:
+    def _refuse_training_under_mask(self, what, bridge=False):
+        if self._head_mask is None:
+            return
+        if not self._head_mask_trainable:
             raise RuntimeError("nbest_amd: %s with a head mask set: training under a head mask is not built (the attention-output "
-                               "weight gradient needs the gated context); call set_head_mask(None) first" % what)
+                               "weight gradient needs the gated context); call set_head_mask(None) first, or set the mask with "
+                               "trainable=True and train through forward_backward" % what)
+        if bridge:
+            raise RuntimeError("nbest_amd: %s with a trainable head mask set: training under a head mask runs through "
+                               "forward_backward / train_step only" % what)
+        if self.fp8_forward:
+            raise RuntimeError("nbest_amd: %s with a trainable head mask on an fp8w model is not built (the fp8 forward has no "
+                               "gated context)" % what)
 
     def _set_head_gate(self, d, grad=None):
         """the head-gate fields of descriptor ``d`` for this call: the mask in force (None: no gate, today's launches)"""
@@ -408,12 +441,14 @@ class NBestSTCModel(nn.Module):
         d.head_gate_grad = None if grad is None else grad.data_ptr()
 
     def _desc(self, B, S, slot, first_trainable=0):
-        """the (cached) descriptor of a pass shape; allocates nothing"""
-        key = (B, S, slot, first_trainable)
+        """the (cached) descriptor of a pass shape; allocates nothing.  A training-path pass (integer slot) under a trainable head
+        mask is a descriptor of its own: its stash is larger (head_gate_stash)"""
+        gate_stash = self._head_mask_trainable and isinstance(slot, int)
+        key = (B, S, slot, first_trainable, gate_stash)
         if key not in self._passes:
             if len(self._passes) >= 4096:
                 self._passes.clear()
-            self._passes[key] = _Pass(self, B, S, slot, first_trainable)
+            self._passes[key] = _Pass(self, B, S, slot, first_trainable, gate_stash)
         return self._passes[key]
 
     def _training_plan(self):
@@ -497,6 +532,9 @@ class NBestSTCModel(nn.Module):
         d.attn_drop = self.cfg.attention_probs_dropout_prob if train else 0.0
         d.seed = self._step_seed()
         self._set_head_gate(d)
+        # a trainable mask: every stash forward keeps the gated contexts.  (_desc keys the cached descriptors on the flag and _Pass
+        # sets it, so this, the record's field and the backward's restore repeat ps.gate_stash: stated per call like cls_top)
+        d.head_gate_stash = int(ps.gate_stash)
         self._set_weights(d, "forward")
         d.cls_top = int(not full_top and self._cls_top_ok(train, S, plan))
         act, ws = self._stash[slot][:ps.act_bytes], self._ws
@@ -509,13 +547,13 @@ class NBestSTCModel(nn.Module):
         M, H = B * S, self.cfg.hidden_size
         esz = 2 if self.compute_dtype == torch.bfloat16 else 4
         hidden = act[off:off + M * H * esz].view(self.compute_dtype).view(M, H)
-        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot], plan, bool(d.cls_top))
+        return _PassRecord(ps, slot, inputs, perm, hidden, self._stash_gen[slot], plan, bool(d.cls_top), ps.gate_stash)
 
     def _cls_top_ok(self, train, S, plan):
         """a training pass runs its top layer on the CLS rows (``self.cls_top``) unless the library refuses the combination: the fp8
-        modes, a head mask.  Whatever is frozen (``plan``): an all-frozen encoder gives its heads the CLS rows a trainable one gives.
+        modes, a head mask that is not trainable.  Whatever is frozen (``plan``): an all-frozen encoder gives its heads the CLS rows a trainable one gives.
         Eval passes keep the full-width layer: ``return_attns`` reads its lse from the stash."""
-        return self.cls_top and train and S >= 2 and not self.fp8_forward and self._head_mask is None
+        return self.cls_top and train and S >= 2 and not self.fp8_forward and (self._head_mask is None or self._head_mask_trainable)
 
     def _packed_bf16_ok(self):
         """the packed bf16 weight copies (arena.wpk / wpkt) exist and are current: they are refreshed with the bf16 transposed
@@ -566,6 +604,7 @@ class NBestSTCModel(nn.Module):
         B, S, H = ps.B, ps.S, self.cfg.hidden_size
         self._set_weights(d, "backward")
         d.cls_top = int(rec.cls_top)              # as the forward that wrote this stash
+        d.head_gate_stash = int(rec.gate_stash)   # likewise
         # gradient w.r.t. the final hidden states [B*S, H] (zero except the CLS rows), in a grow-only buffer like the stash
         dh = self._grow(vars(self), "_dh", B * S * H, self.compute_dtype)[:B * S * H].view(B * S, H)
         dh = hb.cls_grad_scatter(dcls, B, S, H, self.compute_dtype, out=dh)
@@ -646,7 +685,7 @@ class NBestSTCModel(nn.Module):
             if return_attns:
                 raise RuntimeError("nbest_amd: return_attns=True: attention maps are an eval / predict output - call model.eval() "
                                    "or run the forward under torch.no_grad() (a training forward has no post-dropout maps)")
-            self._refuse_training_under_mask("the training forward (autograd bridge)")
+            self._refuse_training_under_mask("the training forward (autograd bridge)", bridge=True)
             if self._anchor is None:
                 self._anchor = torch.zeros(1, device=self.device, requires_grad=True)    # what makes the outputs require grad
             top, bott, fin, asr_cls, trans_cls = _STCBridge.apply(self._anchor, self, input_ids.contiguous(),
@@ -729,6 +768,8 @@ class NBestSTCModel(nn.Module):
         No host synchronisation; about twice the launches of the plain step plus three."""
         if adv is not None:
             adv = _check_adv(adv, need_grad, distill, rdrop)
+            if self._head_mask is not None:
+                raise RuntimeError("nbest_amd: adv with a head mask set is not built (FGM under a head mask, trainable or not)")
             if self.fp8_forward:
                 raise RuntimeError("nbest_amd: adv on an fp8w model is not built (the fp8 forward has no perturbed embedding)")
         if rdrop is not None:

@@ -12,6 +12,7 @@ chunk's gradients are complete their slice of the flat gradient arena is all-red
 (RCCL on its own stream over xGMI; 6 chunks of 2 layers for bert-base) while the remaining backward - ending with the embedding backward -
 keeps the compute stream busy.  Per-tensor clipping + BertAdam run after the last reduce.
 """
+import hashlib
 import json
 import os
 import re
@@ -406,8 +407,12 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     second time on embeddings moved by epsilon along the normalised gradient and the optimizer steps ONCE on the sum of both passes'
     gradients; the returned scores and ``loss_parts`` are the clean pass's, ``adv_loss_parts`` / ``adv_norm`` come on top.  Not with a
     ``teacher`` or ``rdrop_alpha``; data parallelism is not built.
+    A model under a trainable head mask (``set_head_mask(mask, trainable=True)``) steps as any other on one GPU; data parallelism is
+    not built (refused before anything is enqueued).
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
+    if world > 1 and getattr(model, "head_mask_trainable", False):
+        raise RuntimeError("nbest_amd: training under a head mask under data parallelism is not built (world size %d)" % world)
     b_local = batch["ids"].shape[0]
     adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
     batch, distill, rdrop = soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids)
@@ -1023,6 +1028,21 @@ def read_head_mask(path, L, heads):
     if not all(num(x) and x == x and abs(x) != float("inf") for r in rows for x in r):
         raise ValueError("head mask %s: every entry must be a finite number" % path)
     return [[float(x) for x in r] for r in rows]
+
+
+def head_mask_digest(rows):
+    """the name a mask goes by in an experiment directory (--train_head_mask): the first 8 hex digits of the SHA-1 of its entries as
+    little-endian fp32, row-major"""
+    return hashlib.sha1(np.asarray(rows, dtype="<f4").tobytes()).hexdigest()[:8]
+
+
+def head_mask_file_digest(path):
+    """head_mask_digest of a mask file, before the encoder's shape is known (the shape is read_head_mask's to check)"""
+    try:
+        with open(path) as fp:
+            return head_mask_digest(json.load(fp))
+    except (OSError, ValueError, TypeError) as e:
+        raise ValueError("head mask %s: %s" % (path, e))
 
 
 def head_importance_table(grads):
