@@ -626,6 +626,47 @@ typedef struct nbest_matrix_desc {
  * slots: uint32 [n_tensors][NBEST_AMAX_TENSOR_WORDS], zero-initialised by the caller once. */
 #define NBEST_AMAX_TENSOR_WORDS 1024
 int nbest_fp8_amax_fold(void* slots, void* out, int32_t n_tensors, nbest_stream_t stream);
+/* The fp8 PRODUCERS on their own: the kernels that write, next to their bf16 output, the e4m3 copy a later fp8 GEMM reads, and record
+ * the amax the next pass scales by.  nbest_encoder_forward / _backward are their only other callers; these entries forward their
+ * arguments to the same internal functions (no kernel and no dispatch of their own) so that the contract below can be tested
+ * kernel by kernel.  With every extra argument NULL each one IS its plain entry (nbest_layernorm_fwd, ...): same launch, same bits.
+ *   amax_prev: ONE device word, the float bits of the amax the tensor had in the previous pass (what nbest_fp8_amax_fold wrote).
+ *     The copy is e4m3(v * s), saturating at +-448, round to nearest even, with s = 2^floor(log2(T / amax_prev)), the exponent
+ *     clamped to +-100; T = 224 for the forward activations (layernorm_fwd, attention_fwd, cast), T = 56 for the gradients
+ *     (layernorm_bwd, attention_bwd).  s = 1 for a NULL pointer and for a zero, denormal (< 2^-100) or non-finite amax.
+ *   amax_new: a slot block of NBEST_AMAX_TENSOR_WORDS words (above): every workgroup RAISES one of the 16 words 64 k, k < 16 (picked
+ *     by its block index), to the float bits of max |v| over its elements - never lowered; the other 1008 words are not touched.
+ *   v, the value that is scaled, rounded and measured:
+ *     layernorm_fwd, attention_fwd, attention_bwd, cast: the STORED bf16 value (y, ctx, dqkv, src) - the bytes are what a cast of
+ *       the bf16 output gives, the recorded amax is max |bf16 output| exactly.
+ *     layernorm_bwd: the fp32 value BEFORE its bf16 rounding - dx, or under dropout dx_drop = dx . keep . scale (a dropped element
+ *       gives byte 0x00 and does not count in the amax).  bf16 rounding is monotone, so bf16(recorded amax) = max |bf16 output|.
+ *   What each one records without a copy (out8 / y8 / ctx8 NULL, amax_new given - the calibration pass): attention_fwd,
+ *   attention_bwd and layernorm_bwd record the same amax as with the copy; layernorm_fwd records NOTHING without y8 (the encoder
+ *   calibrates that tensor with nbest_amax_bf16).
+ *   layernorm_bwd writes its copy only where it records: out8 or amax_prev without amax_new is NBEST_ERR_ARG.
+ *   bf16 only, and for the LayerNorms H in {256, 512, 768, 1024} only (the fast kernels): ANY of the copy, amax_prev and amax_new
+ *   with fp32 or another H is NBEST_ERR_SHAPE, in all four entries.
+ *   attention_bwd: dqkv may be NULL when out8 is given (only the copy is written).  layernorm_bwd under dropout: dx_drop may be
+ *   NULL when out8 (and so amax_new) is given.  keep: as nbest_attention_fwd_keep / _bwd_keep (NULL: none).
+ *   nbest_cast_bf16_to_fp8_scaled: the cast with a history (n % 8 == 0, else NBEST_ERR_ARG).  nbest_amax_bf16: slots raised by
+ *   max |x| of a bf16 tensor (n % 8 == 0; the calibration pass of tensors whose producer is a bf16 kernel).                       */
+int nbest_layernorm_fwd_fp8(const void* x, const float* gamma, const float* beta, void* y, void* y8, float* stats, int64_t M, int H,
+                            float eps, int dtype, const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream);
+int nbest_layernorm_bwd_fp8(const void* dy, const void* x, const float* stats, const float* gamma, void* dx, void* dx_drop,
+                            float* dgamma, float* dbeta, float* dbias, int64_t M, int H, int dtype, int accumulate, float drop_p,
+                            uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, void* out8, const uint32_t* amax_prev,
+                            uint32_t* amax_new, nbest_stream_t stream);
+int nbest_attention_fwd_fp8(const void* qkv, const uint8_t* key_mask, void* ctx, void* ctx8, float* lse, int B, int S, int heads,
+                            int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, void* keep,
+                            const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream);
+int nbest_attention_bwd_fp8(const void* qkv, const uint8_t* key_mask, const void* ctx, const void* dctx, const float* lse,
+                            void* dqkv, float* dbias, int accumulate, void* ws, size_t ws_bytes, int B, int S, int heads, int d,
+                            int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, const void* keep, void* out8,
+                            const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream);
+int nbest_cast_bf16_to_fp8_scaled(const void* src, void* dst, int64_t n, const uint32_t* amax_prev, uint32_t* amax_new,
+                                  nbest_stream_t stream);
+int nbest_amax_bf16(const void* x, int64_t n, uint32_t* amax_new, nbest_stream_t stream);
 /* e4m3 copy of the weight matrices (same element offsets, ONE byte per element) from the fp32 master, one scale per
  * matrix: w8 = e4m3(w * 2^floor(log2(224 / max|w|))); inv_scale[i] = 1 / scale of matrix i (device, [n_matrices]).
  * w8t (optional): the same e4m3 values written transposed ([cols][rows] at the matrix' offset; n_tiles = 64x64 tiles over all

@@ -1875,3 +1875,24 @@ extern "C" int nbest_attention_bwd_keep(const void* qkv, const uint8_t* key_mask
   return nbest_internal_attention_bwd8(qkv, key_mask, ctx, dctx, lse, dqkv, dbias, accumulate, ws, ws_bytes, B, S, heads, d, dtype, drop_p,
                                        seed, drop_stream, stream, Fp8Grad{nullptr, nullptr, nullptr}, ok ? (const uint32_t*)keep : nullptr);
 }
+
+// The fp8 producers on their own (include/nbest_hip.h): the arguments nbest_encoder_forward / _backward pass, forwarded unchanged.
+// The fp32 kernels have no fp8 outputs and would ignore them: refused here.
+extern "C" int nbest_attention_fwd_fp8(const void* qkv, const uint8_t* key_mask, void* ctx, void* ctx8, float* lse, int B, int S, int heads,
+                                       int d, int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, void* keep,
+                                       const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream) {
+  NB_CHECK(!(ctx8 || amax_prev || amax_new) || dtype == NBEST_BF16, NBEST_ERR_SHAPE, "attention_fwd_fp8: the fp8 copy needs bf16");
+  const bool ok = keep && dtype == NBEST_BF16 && nbest_internal_attention_keep_bytes(B, S, heads) > 0;
+  return nbest_internal_attention_fwd8(qkv, key_mask, ctx, ctx8, lse, B, S, heads, d, dtype, drop_p, seed, drop_stream, stream,
+                                       ok ? (uint32_t*)keep : nullptr, amax_prev, amax_new);
+}
+extern "C" int nbest_attention_bwd_fp8(const void* qkv, const uint8_t* key_mask, const void* ctx, const void* dctx, const float* lse,
+                                       void* dqkv, float* dbias, int accumulate, void* ws, size_t ws_bytes, int B, int S, int heads, int d,
+                                       int dtype, float drop_p, uint64_t seed, uint32_t drop_stream, const void* keep, void* out8,
+                                       const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream) {
+  NB_CHECK(!(out8 || amax_prev || amax_new) || dtype == NBEST_BF16, NBEST_ERR_SHAPE, "attention_bwd_fp8: the fp8 copy needs bf16");
+  const bool ok = keep && dtype == NBEST_BF16 && nbest_internal_attention_keep_bytes(B, S, heads) > 0;
+  return nbest_internal_attention_bwd8(qkv, key_mask, ctx, dctx, lse, dqkv, dbias, accumulate, ws, ws_bytes, B, S, heads, d, dtype, drop_p,
+                                       seed, drop_stream, stream, Fp8Grad{(uint8_t*)out8, amax_prev, amax_new},
+                                       ok ? (const uint32_t*)keep : nullptr);
+}

@@ -887,6 +887,15 @@ int nbest_internal_cast_bf16_to_fp8(const void* src, void* dst, int64_t n, const
 extern "C" int nbest_cast_bf16_to_fp8(const void* src, void* dst, int64_t n, nbest_stream_t stream) {
   return nbest_internal_cast_bf16_to_fp8(src, dst, n, nullptr, nullptr, (hipStream_t)stream);
 }
+// the cast with a history and the amax of a bf16 tensor on their own (include/nbest_hip.h), as nbest_encoder_forward / _backward call them
+extern "C" int nbest_cast_bf16_to_fp8_scaled(const void* src, void* dst, int64_t n, const uint32_t* amax_prev, uint32_t* amax_new,
+                                             nbest_stream_t stream) {
+  return nbest_internal_cast_bf16_to_fp8(src, dst, n, amax_prev, amax_new, (hipStream_t)stream);
+}
+extern "C" int nbest_amax_bf16(const void* x, int64_t n, uint32_t* amax_new, nbest_stream_t stream) {
+  NB_CHECK(x && amax_new && n > 0 && n % 8 == 0, NBEST_ERR_ARG, "amax_bf16: bad arguments");   // (the kernel reads eight elements at a time)
+  return nbest_internal_amax_bf16(x, n, amax_new, (hipStream_t)stream);
+}
 
 extern "C" int nbest_quantize_weights_fp8(const float* master, void* w8, void* w8t, const nbest_matrix_desc* descs, int n_matrices,
                                           int n_tiles, float* inv_scale, void* ws, size_t ws_bytes, nbest_stream_t stream) {

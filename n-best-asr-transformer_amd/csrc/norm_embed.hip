@@ -1334,7 +1334,8 @@ extern "C" size_t nbest_embed_bwd_ws_bytes(int64_t M, int64_t H) {
          (size_t)chunks * 2 * H * sizeof(float) + (size_t)(chunks + 4) * sizeof(int);
 }
 
-// y8 != NULL (bf16, H % 256 == 0, H <= 1024 only): also write the e4m3 copy of y that the next fp8 forward GEMM reads
+// y8 != NULL (bf16, H % 256 == 0, H <= 1024 only): also write the e4m3 copy of y that the next fp8 forward GEMM reads; a_new is
+// recorded into only together with y8 (a calibration pass measures y with nbest_internal_amax_bf16)
 int nbest_internal_layernorm_fwd8(const void* x, const float* gamma, const float* beta, void* y, void* y8, float* stats,
                                   int64_t M, int H, float eps, int dtype, nbest_stream_t stream, const uint32_t* a_prev, uint32_t* a_new) {
   if (int e = check_h(H)) return e;
@@ -1364,13 +1365,20 @@ extern "C" int nbest_layernorm_fwd(const void* x, const float* gamma, const floa
   return nbest_internal_layernorm_fwd8(x, gamma, beta, y, nullptr, stats, M, H, eps, dtype, stream, nullptr, nullptr);
 }
 
-// f8 (bf16 fast path only): e4m3 copy + amax of the gradient the dense-layer GEMMs read (dx_drop under dropout, else dx)
+// f8 (bf16 fast path only): e4m3 copy + amax of the gradient the dense-layer GEMMs read (dx_drop under dropout, else dx).  Both are
+// taken from the fp32 value BEFORE its bf16 rounding (the attention and LayerNorm-forward producers round the stored bf16 value): the
+// byte is e4m3(fp32 . s), a dropped element is byte 0, and bf16(recorded amax) = max |bf16 tensor|.  The kernel writes the copy
+// only where it records, so out8 or amax_prev without amax_new is refused.  Pinned by tests/test_fp8_producers_gpu.py.
 int nbest_internal_layernorm_bwd8(const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
                                   void* dx_drop, float* dgamma, float* dbeta, float* dbias, int64_t M, int H, int dtype,
                                   int accumulate, float drop_p, uint64_t seed, uint32_t drop_stream, void* ws,
                                   size_t ws_bytes, nbest_stream_t stream, Fp8Grad f8) {
   if (int e = check_h(H)) return e;
-  NB_CHECK(!f8.amax_new || (dtype == NBEST_BF16 && H % 256 == 0 && H <= 1024), NBEST_ERR_SHAPE, "layernorm_bwd: fp8 copy needs bf16 and H in {256..1024}");
+  // any fp8 argument needs the fast kernels (the generic ones know none of them, and store dx_drop unconditionally); a copy is written
+  // only by the code that records, so out8 without amax_new would be a silent no-op: refused
+  NB_CHECK(!(f8.out8 || f8.amax_prev || f8.amax_new) || (dtype == NBEST_BF16 && H % 256 == 0 && H <= 1024), NBEST_ERR_SHAPE,
+           "layernorm_bwd: fp8 copy needs bf16 and H in {256..1024}");
+  NB_CHECK(!(f8.out8 || f8.amax_prev) || f8.amax_new, NBEST_ERR_ARG, "layernorm_bwd: the fp8 copy is written only together with the amax record (amax_new)");
   // dgamma == dbeta == dbias == NULL (the no_param_grad backward of nbest_encoder_backward): dx / dx_drop only, no workspace, no finalize
   const bool params = dgamma || dbeta || dbias;
   NB_CHECK(dy && x && stats && gamma && dx && M > 0 && (!params || (dgamma && dbeta && ws)), NBEST_ERR_ARG, "layernorm_bwd: null pointer");
@@ -1456,6 +1464,22 @@ extern "C" int nbest_layernorm_bwd(const void* dy, const void* x, const float* s
                                    size_t ws_bytes, nbest_stream_t stream) {
   return nbest_internal_layernorm_bwd8(dy, x, stats, gamma, dx, dx_drop, dgamma, dbeta, dbias, M, H, dtype, accumulate, drop_p, seed,
                                        drop_stream, ws, ws_bytes, stream, Fp8Grad{nullptr, nullptr, nullptr});
+}
+
+// The fp8 producers on their own (include/nbest_hip.h): the arguments nbest_encoder_forward / _backward pass, forwarded unchanged
+extern "C" int nbest_layernorm_fwd_fp8(const void* x, const float* gamma, const float* beta, void* y, void* y8, float* stats, int64_t M,
+                                       int H, float eps, int dtype, const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream) {
+  // (the kernels without a copy would ignore a history or a slot block: refused like a copy)
+  NB_CHECK(!(y8 || amax_prev || amax_new) || (dtype == NBEST_BF16 && H % 256 == 0 && H <= 1024), NBEST_ERR_SHAPE,
+           "layernorm_fwd_fp8: fp8 copy needs bf16 and H in {256..1024}");
+  return nbest_internal_layernorm_fwd8(x, gamma, beta, y, y8, stats, M, H, eps, dtype, stream, amax_prev, amax_new);
+}
+extern "C" int nbest_layernorm_bwd_fp8(const void* dy, const void* x, const float* stats, const float* gamma, void* dx, void* dx_drop,
+                                       float* dgamma, float* dbeta, float* dbias, int64_t M, int H, int dtype, int accumulate,
+                                       float drop_p, uint64_t seed, uint32_t drop_stream, void* ws, size_t ws_bytes, void* out8,
+                                       const uint32_t* amax_prev, uint32_t* amax_new, nbest_stream_t stream) {
+  return nbest_internal_layernorm_bwd8(dy, x, stats, gamma, dx, dx_drop, dgamma, dbeta, dbias, M, H, dtype, accumulate, drop_p, seed,
+                                       drop_stream, ws, ws_bytes, stream, Fp8Grad{(uint8_t*)out8, amax_prev, amax_new});
 }
 
 extern "C" int nbest_colsum(const void* X, float* out, int64_t M, int64_t N, int64_t ld, int dtype, int accumulate,

@@ -30,6 +30,7 @@ EXPORTS = [
     "nbest_embed_ln_fwd_interp", "nbest_embed_attrib",
     "nbest_head_gate_fwd", "nbest_head_gate_bwd",
     "nbest_embed_ln_fwd_adv", "nbest_embed_ln_bwd_adv", "nbest_embed_adv_ws_bytes", "nbest_embed_adv_delta",
+    "nbest_layernorm_fwd_fp8", "nbest_layernorm_bwd_fp8", "nbest_attention_fwd_fp8", "nbest_attention_bwd_fp8", "nbest_cast_bf16_to_fp8_scaled", "nbest_amax_bf16",
 ]
 
 
@@ -151,6 +152,12 @@ def lib():
         L.nbest_attention_keep_bytes.argtypes = [i32, i32, i32]
         L.nbest_attention_fwd_keep.argtypes = [vp] * 4 + [i32] * 5 + [f32, u64, u32, vp, vp]
         L.nbest_attention_bwd_keep.argtypes = [vp] * 7 + [i32, vp, sz] + [i32] * 5 + [f32, u64, u32, vp, vp]
+        L.nbest_attention_fwd_fp8.argtypes = [vp] * 5 + [i32] * 5 + [f32, u64, u32, vp, vp, vp, vp]
+        L.nbest_attention_bwd_fp8.argtypes = [vp] * 7 + [i32, vp, sz] + [i32] * 5 + [f32, u64, u32, vp, vp, vp, vp, vp]
+        L.nbest_layernorm_fwd_fp8.argtypes = [vp] * 6 + [i64, i32, f32, i32, vp, vp, vp]
+        L.nbest_layernorm_bwd_fp8.argtypes = [vp] * 9 + [i64, i32, i32, i32, f32, u64, u32, vp, sz, vp, vp, vp, vp]
+        L.nbest_cast_bf16_to_fp8_scaled.argtypes = [vp, vp, i64, vp, vp, vp]
+        L.nbest_amax_bf16.argtypes = [vp, i64, vp, vp]
         L.nbest_layernorm_fwd.argtypes = [vp] * 5 + [i64, i32, f32, i32, vp]
         L.nbest_layernorm_bwd.argtypes = [vp] * 9 + [i64, i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_colsum.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, sz, vp]
@@ -672,6 +679,95 @@ def attention_bwd(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0
                                     ws.numel() if ws is not None else 0, B, S, heads, 64, dtype_code(qkv.dtype), drop_p, seed,
                                     drop_stream, stream_ptr()), "attention_bwd")
     return dqkv
+
+
+# ---- the fp8 producers on their own (include/nbest_hip.h, "The fp8 PRODUCERS on their own"; used by the kernel tests) ----
+# amax_prev: a 1-element int32 tensor holding the float bits of last pass's amax, or None (unit scale); amax_slots: an int32 tensor of
+# AMAX_TENSOR_WORDS words the kernel raises its slot words in, or None (nothing recorded).  The e4m3 copies come back as uint8
+# tensors pre-filled with 0x7F, an e4m3 NaN code no producer writes: a byte the kernel skipped shows.
+def _amax_args(amax_prev, amax_slots):
+    if amax_prev is not None and (amax_prev.dtype != torch.int32 or amax_prev.numel() != 1):
+        raise ValueError("nbest_amd: amax_prev must be a 1-element int32 tensor (float bits)")
+    if amax_slots is not None and (amax_slots.dtype != torch.int32 or amax_slots.numel() != AMAX_TENSOR_WORDS or not amax_slots.is_contiguous()):
+        raise ValueError("nbest_amd: amax_slots must be a contiguous int32 tensor of %d words" % AMAX_TENSOR_WORDS)
+    return ptr(amax_prev), ptr(amax_slots)
+
+
+def _e4m3_buffer(shape, device):
+    return torch.full(shape, 0x7F, dtype=torch.uint8, device=device)
+
+
+def layernorm_fwd_fp8(x, gamma, beta, eps, amax_prev=None, amax_slots=None, want8=True):
+    """nbest_layernorm_fwd_fp8 -> (y, stats, y8); ``want8=False``: no copy (y8 None)"""
+    M, H = x.shape
+    y = torch.empty_like(x)
+    stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+    y8 = _e4m3_buffer((M, H), x.device) if want8 else None
+    ap, an = _amax_args(amax_prev, amax_slots)
+    check(lib().nbest_layernorm_fwd_fp8(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(y8), ptr(stats), M, H, eps, dtype_code(x.dtype), ap, an,
+                                        stream_ptr()), "layernorm_fwd_fp8")
+    return y, stats, y8
+
+
+def layernorm_bwd_fp8(dy, x, stats, gamma, want_dbias=True, drop_p=0.0, seed=0, drop_stream=0, want_params=True, amax_prev=None,
+                      amax_slots=None, want8=True, want_dx_drop=True):
+    """nbest_layernorm_bwd_fp8 -> layernorm_bwd's five results + out8 (the copy of dx_drop under dropout, else of dx);
+    ``want8=False``: record only; ``want_dx_drop=False`` (dropout with ``want8``): dx_drop = NULL, only its copy is written"""
+    M, H = x.shape
+    dx = torch.empty_like(x)
+    dxd = torch.empty_like(x) if drop_p > 0 and want_dx_drop else None
+    dg = torch.zeros(H, dtype=torch.float32, device=x.device) if want_params else None
+    db = torch.zeros_like(dg) if want_params else None
+    dbias = torch.zeros_like(dg) if want_params and want_dbias else None
+    ws = _ws(lib().nbest_rowred_ws_bytes(M, H), x.device) if want_params else None
+    out8 = _e4m3_buffer((M, H), x.device) if want8 else None
+    ap, an = _amax_args(amax_prev, amax_slots)
+    check(lib().nbest_layernorm_bwd_fp8(ptr(dy), ptr(x), ptr(stats), ptr(gamma), ptr(dx), ptr(dxd), ptr(dg), ptr(db), ptr(dbias),
+                                        M, H, dtype_code(x.dtype), 0, drop_p, seed, drop_stream, ptr(ws), ws.numel() if ws is not None else 0,
+                                        ptr(out8), ap, an, stream_ptr()), "layernorm_bwd_fp8")
+    return dx, dxd, dg, db, dbias, out8
+
+
+def attention_fwd_fp8(qkv, key_mask, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, want_keep=False, amax_prev=None, amax_slots=None,
+                      want8=True):
+    """nbest_attention_fwd_fp8 -> (ctx, lse, keep, ctx8); keep as attention_fwd(want_keep=...), None without it"""
+    H = heads * 64
+    ctx = torch.empty(B * S, H, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, heads, S, dtype=torch.float32, device=qkv.device)
+    nb = lib().nbest_attention_keep_bytes(B, S, heads) if want_keep and qkv.dtype == torch.bfloat16 else 0
+    keep = torch.zeros(nb // 4, dtype=torch.int32, device=qkv.device) if nb else None
+    ctx8 = _e4m3_buffer((B * S, H), qkv.device) if want8 else None
+    ap, an = _amax_args(amax_prev, amax_slots)
+    check(lib().nbest_attention_fwd_fp8(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(ctx8), ptr(lse), B, S, heads, 64, dtype_code(qkv.dtype),
+                                        drop_p, seed, drop_stream, ptr(keep), ap, an, stream_ptr()), "attention_fwd_fp8")
+    return ctx, lse, keep, ctx8
+
+
+def attention_bwd_fp8(qkv, key_mask, ctx, dctx, lse, B, S, heads, drop_p=0.0, seed=0, drop_stream=0, dbias=None, keep=None,
+                      accumulate=False, amax_prev=None, amax_slots=None, want8=True, want_dqkv=True):
+    """nbest_attention_bwd_fp8 -> (dqkv, out8); ``want_dqkv=False`` (with ``want8``): dqkv = NULL, only the copy is written"""
+    dqkv = torch.empty_like(qkv) if want_dqkv else None
+    ws = _ws(lib().nbest_attention_bwd_ws_bytes(B, S, heads), qkv.device) if dbias is not None else None
+    out8 = _e4m3_buffer(tuple(qkv.shape), qkv.device) if want8 else None
+    ap, an = _amax_args(amax_prev, amax_slots)
+    check(lib().nbest_attention_bwd_fp8(ptr(qkv), ptr(key_mask), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dbias), int(accumulate), ptr(ws),
+                                        ws.numel() if ws is not None else 0, B, S, heads, 64, dtype_code(qkv.dtype), drop_p, seed,
+                                        drop_stream, ptr(keep), ptr(out8), ap, an, stream_ptr()), "attention_bwd_fp8")
+    return dqkv, out8
+
+
+def cast_fp8_scaled(x, amax_prev=None, amax_slots=None):
+    """nbest_cast_bf16_to_fp8_scaled: bf16 -> e4m3 bytes under the delayed scale of ``amax_prev``; max |x| recorded into ``amax_slots``"""
+    out = _e4m3_buffer(tuple(x.shape), x.device)
+    ap, an = _amax_args(amax_prev, amax_slots)
+    check(lib().nbest_cast_bf16_to_fp8_scaled(ptr(x), ptr(out), x.numel(), ap, an, stream_ptr()), "cast_bf16_to_fp8_scaled")
+    return out
+
+
+def amax_bf16(x, amax_slots):
+    """nbest_amax_bf16: raise the slot words of ``amax_slots`` by max |x| of a bf16 tensor"""
+    _, an = _amax_args(None, amax_slots)
+    check(lib().nbest_amax_bf16(ptr(x), x.numel(), an, stream_ptr()), "amax_bf16")
 
 
 def embed_ln_fwd(ids, seg, pos, word, type_tab, ptab, gamma, beta, eps, drop_p=0.0, seed=0, drop_stream=0, delta=None):
