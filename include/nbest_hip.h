@@ -802,7 +802,7 @@ typedef struct nbest_encoder_desc {
   /* optional adversarial perturbation of the word rows (FGM; nbest_embed_adv_delta): fp32 [B*S][H], device memory, set per call like
    * `seed`.  Non-NULL: nbest_encoder_forward's embedding is nbest_embed_ln_fwd_adv and nbest_encoder_backward(with_embeddings) runs
    * nbest_embed_ln_bwd_adv - the backward must see the pointer (and the values) its stash's forward saw.  Everything above the
-   * embedding is unchanged, cls_top included.  NULL: today's launches.  Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward
+   * embedding is unchanged, cls_top included.  NULL: the plain embedding launches.  Refused (NBEST_ERR_ARG, nothing enqueued) with the fp8 forward
    * (w8), base_ids / alpha and first_trainable > 0; nbest_encoder_infer* refuse it.                                              */
   const float* emb_delta;
   const uint8_t* wgrad_skip_host;
@@ -856,7 +856,7 @@ typedef struct nbest_encoder_desc {
    * the highest first, QKV | attention-out | FFN-up | FFN-down within a layer, are a queue of 256 x 256 tiles, and a launch
    * (nbest_wgrad_window) takes the next 256 pending tiles whichever layers they belong to - 1 296 tiles of 12 bert-base layers in 5
    * rounds of the 256 CUs where the grouped launches of 216 take 6.  The rest is flushed at the end of the call (every call leaves
-   * its gradients written).  Where it saves a whole round, the QKV + attention-out pair of the range's lowest layer runs as today's
+   * its gradients written).  Where it saves a whole round, the QKV + attention-out pair of the range's lowest layer runs as mode _NEVER's
    * split-K pair launch instead (bert-base: 1 260 tiles = 256 + 256 + 256 + 256 + 236).  The dY tensors of a layer live until its last
    * tile is launched: N buffer sets in rotation, N from the tile counts (4 at 108 tiles per layer, 2 at 192).  The plan (_PLAN) takes
    * the windows where its launch-cost model predicts at least 5 % less weight-gradient time than the better of the other two.  Window

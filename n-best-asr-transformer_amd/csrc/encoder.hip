@@ -217,7 +217,7 @@ static bool window_shapes_ok(const nbest_encoder_desc* d) {
 }
 // The window schedule of the whole trainable range, nothing skipped, built once: its buffer sets (a shorter range runs a prefix of the
 // same schedule; skipped matrices are covered by the flush rule of window_plan) and its model time (us).  The time is that of ONE call
-// over the whole range: a backward in chunks (the 2-layer chunks of the data-parallel reducer) flushes per call and runs today's
+// over the whole range: a backward in chunks (the 2-layer chunks of the data-parallel reducer) flushes per call and runs mode ALWAYS's
 // 216-tile launches at bert-base tile counts, 256 + 128 tiles per chunk at 192 tiles per layer - the prediction does not hold there.
 struct WindowModel { int sets; double us; };
 static WindowModel window_model(const nbest_encoder_desc* d) {
@@ -259,6 +259,8 @@ static WgradMode wgrad_mode(const nbest_encoder_desc* d) {
   if (2 * tiles > 256 || !wgrad_paired(d, false)) return never;
   return round / 2.0 < 0.95 * today ? WgradMode{NBEST_WGRAD_GROUP_ALWAYS, 2, 0} : never;
 }
+// weight-gradient launches = event pairs (desc.wgrad_events) per layer: one when the gradients are deferred to a grouped or window launch
+static int wgrad_launches_per_layer(const WgradMode& wm, bool paired) { return (wm.gl > 0 || wm.sets > 0) ? 1 : paired ? 3 : 4; }
 // wm: wgrad_mode(d), resolved once by the caller
 static WsLayout ws_layout(const nbest_encoder_desc* d, const Sizes& z, const WgradMode& wm) {
   WsLayout w;
@@ -476,6 +478,9 @@ struct LayerBufs {
   uint8_t *x8, *ctx8, *x18, *h8;
 };
 
+// X[l] of the activation stash, l >= first_trainable: the input of layer l (l = L: the final hidden state)
+static void* stash_x(const ActLayout& a, const Sizes& z, void* act, int l) { return (char*)act + a.X + (size_t)(l - a.K) * z.MH; }
+
 // layer l >= first_trainable: its block of the activation stash (what the forward writes is what the backward reads)
 static LayerBufs stashed_layer(const nbest_encoder_desc* d, const ActLayout& a, void* act, int l) {
   char* Lb = (char*)act + a.layer0 + (size_t)(l - a.K) * a.layer_stride;
@@ -650,9 +655,7 @@ extern "C" int nbest_encoder_act_view(const nbest_encoder_desc* d, void* act, in
 extern "C" size_t nbest_encoder_ws_bytes(const nbest_encoder_desc* d) { return d ? ws_layout(d, sizes(d), wgrad_mode(d)).total : 0; }
 extern "C" int nbest_encoder_wgrad_launches_per_layer(const nbest_encoder_desc* d) {
   if (!d) return 0;
-  const WgradMode wm = wgrad_mode(d);
-  if (wm.gl > 0 || wm.sets > 0) return 1;
-  return wgrad_paired(d, fp8_backward_active(d)) ? 3 : 4;
+  return wgrad_launches_per_layer(wgrad_mode(d), wgrad_paired(d, fp8_backward_active(d)));
 }
 
 // host only, enqueues nothing: the resolved weight-gradient schedule of a backward call over [layer_begin, layer_end) as int32 words
@@ -702,7 +705,7 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
   const Ptrs& P = c.g.W;
   char *A = (char*)act, *W = (char*)ws;
   const int H = d->H, dt = d->dtype;
-  auto X = [&](int l) { return l >= FT ? (void*)(A + a.X + (size_t)(l - FT) * z.MH) : (void*)(W + ((l & 1) ? wl.fz_x1 : wl.fz_x0)); };
+  auto X = [&](int l) { return l >= FT ? stash_x(a, z, act, l) : (void*)(W + ((l & 1) ? wl.fz_x1 : wl.fz_x0)); };
   auto bufs = [&](int l) {
     LayerBufs b = l >= FT ? stashed_layer(d, a, act, l) : frozen_layer(d, wl, z, ws);
     if (gscratch) b.gctx = W + wl.dctx;
@@ -732,13 +735,353 @@ extern "C" int nbest_encoder_forward(const nbest_encoder_desc* d, const void* wt
 }
 
 namespace {
-// one weight gradient of a layer: dW (fp32, at w_off of `grad`) [rows][cols] (+)= dY^T . X over the M tokens
+// ---- one layer backward ------------------------------------------------------------------------------------------------------------
+// what the layers of one backward call share
+struct Bwd {
+  const nbest_encoder_desc* d;
+  // the dgrad GEMMs: B = the transposed weight arena when there is one (both operands k-contiguous), else the forward's as [K][N];
+  // fp8 backward: on the transposed e4m3 weight copy.  Partial rows of the column sums fused into the DGELU one: region 1
+  GemmPass dg;
+  Ptrs P;
+  Sizes z; ActLayout a; WsLayout w;
+  char *act, *ws;
+  const uint8_t* key_mask;
+  float* grad; int accumulate;
+  bool npg;     // no_param_grad: dhidden only (attribution) - no weight-gradient GEMM, no bias / LayerNorm-parameter gradient, grad may be NULL
+  // fp8 dgrads (descriptor: w8t, gamax_prev / gamax_new, fp8_bwd): the gradient amax of every dgrad operand is recorded in every pass
+  // (rec); with a history (f8b) the producers also write e4m3 copies and the four dgrad GEMMs of a layer run in fp8
+  bool f8b, rec, hdrop;
+  void* red(int i) const { return ws + w.red + (size_t)i * w.red_bytes; }   // region i of the column-reduction partials
+  float* G(int64_t off) const { return grad + off; }
+  float* GP(int64_t off) const { return npg ? nullptr : grad + off; }   // a bias / LayerNorm-parameter gradient (none: no_param_grad)
+  uint32_t* GN(int idx) const { return d->gamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS; }   // slot block of gradient tensor idx
+  Fp8Grad fg(uint8_t* out8, int idx) const {
+    if (!rec) return Fp8Grad{nullptr, nullptr, nullptr};
+    return Fp8Grad{f8b ? out8 : nullptr, f8b ? d->gamax_prev + idx : nullptr, GN(idx)};
+  }
+};
+
+static Bwd make_bwd(const nbest_encoder_desc* d, const void* wts, const void* wts_t, const float* prm, float* grad, const uint8_t* key_mask,
+                    void* act, void* ws, const Sizes& z, const ActLayout& a, const WsLayout& w, int accumulate, nbest_stream_t stream) {
+  const bool wt = (wts_t != nullptr), npg = d->no_param_grad != 0, f8b = fp8_backward_active(d);
+  const GemmPass dg = {d->dtype, z.M, stream, 0, Ptrs{(const char*)(wt ? wts_t : wts), prm, z.esz}, wt ? d->wpkt : nullptr, !wt, f8b,
+                       d->w8t, d->w8tp, d->w8_inv_scale, d->gamax_prev, d->gamax_new, (char*)ws + w.red + w.red_bytes, w.red_bytes, accumulate};
+  return Bwd{d, dg, Ptrs{(const char*)wts, prm, z.esz}, z, a, w, (char*)act, (char*)ws, key_mask, grad, accumulate, npg, f8b,
+             !npg && d->gamax_new && d->dtype == NBEST_BF16, d->hidden_drop > 0.f};
+}
+
+// The gradient buffers of one layer.  dR2 / dRd2: residual- and dense-branch gradients out of the LN2 backward, dR1 / dRd1: out of the
+// LN1 backward (one buffer each without hidden dropout); dRd2, dBig, dRd1 and dqkv are the dY operands of the weight gradients.
+struct LayerGrads {
+  void *dR2, *dRd2, *dBig, *dB1, *dR1, *dRd1, *dctx, *dqkv;
+  uint8_t *dqkv8, *dBig8, *dRd8;   // fp8 backward: the e4m3 copies [M][3H], [M][F], [M][H] the fp8 dgrads and weight gradients read
+};
+// set < 0: the shared buffers; else those of buffer set `set` (WsLayout::gset), which the layers of the other sets leave alone while
+// this layer's weight gradients wait.  cls (desc.cls_top, top layer): everything but dqkv is [B][.], the CLS rows - two compact buffers
+// in each of the shared dR, dRd and dB1 regions (S >= 2), one in dctx and dBig.
+static LayerGrads layer_grads(const Bwd& c, int set, bool cls) {
+  char* W = c.ws;
+  const WsLayout& w = c.w;
+  const size_t* s = w.gset[set < 0 ? 0 : set];   // (no sets in the workspace: every row names the shared buffers)
+  LayerGrads g = {};
+  g.dB1 = W + w.dB1; g.dctx = W + w.dctx;
+  g.dRd2 = W + s[0]; g.dBig = W + s[1]; g.dRd1 = W + s[2]; g.dqkv = W + s[3];
+  g.dR2 = g.dR1 = W + w.dR;
+  if (!c.hdrop && set < 0) g.dRd2 = g.dRd1 = g.dR2;
+  if (!c.hdrop && set >= 0) { g.dR2 = g.dRd2; g.dR1 = g.dRd1; }
+  if (cls) {
+    const size_t bh = (size_t)c.d->B * c.d->H * c.z.esz;   // (a multiple of 128 bytes: H % 64 == 0)
+    g.dR2 = W + w.dR; g.dR1 = W + w.dB1 + bh; g.dBig = W + w.dBig;
+    g.dRd2 = c.hdrop ? (void*)(W + w.dRd) : g.dR2; g.dRd1 = c.hdrop ? (void*)(W + w.dRd + bh) : g.dR1;
+  }
+  if (c.f8b) { g.dqkv8 = (uint8_t*)W + w.f8; g.dBig8 = g.dqkv8 + 3 * c.z.MH8; g.dRd8 = g.dBig8 + c.z.MF8; }
+  return g;
+}
+
+// ---- the weight gradients of a backward call: every launch and every event stamp ---------------------------------------------------
+// one weight gradient of a layer: dW (fp32, at w_off of `grad`) [rows][cols] (+)= dY^T . X over the token rows
 struct WGrad {
   const void *dY, *X;
   const uint8_t *dY8, *X8;   // their e4m3 copies (fp8 backward) ...
   int64_t w_off, rows, cols;
   int g_idx, a_idx;          // ... and the indices of their gradient / activation amax
 };
+
+// Every weight-gradient launch and every event stamp (desc.wgrad_events) of one call over the layers [l0, l1), by the resolved mode:
+//   NEVER    ready(j), where the layer routine has gradient j's operands complete: its split-K launch between two stamps - the
+//            attention-out gradient with QKV's as ONE launch when paired.  A skipped gradient launches nothing (its stamps are still
+//            recorded); of a pair with one half skipped the other goes alone.
+//   grouped  layer_end: the gradients of a layer wait for the end of its group (their dY tensors in the buffer set of the layer's position,
+//            their X tensors in the stash, which the backward only reads) and go out as ONE nbest_wgrad_group launch: per layer QKV,
+//            attention-out, FFN-up, FFN-down, the higher layer first.  A layer left without a partner (odd range; the plan's grouping)
+//            issues mode NEVER's launches back to back instead.  One event pair per layer (include/nbest_hip.h, wgrad_events).
+//   windows  layer_end: the queue of window_plan; a launch goes out at the end of the layer that completes it, the peeled pair and the
+//            remainder at the end of the lowest layer.  One event pair per layer of the range: a pair brackets each window launch (the
+//            peeled pair launch inside the pair of the window next to it), the pairs left over are recorded back to back at the end.
+// desc.cls_top: the top layer's attention-out, FFN-up and FFN-down gradients are plain launches over its K = B token rows in every
+// mode (rows), inside the layer's own event pair(s); only its QKV gradient takes part in a group or a window.
+struct WgradSched {
+  const Bwd& c;
+  const WgradMode wm;
+  const bool paired;
+  const int l0, l1;
+  const std::vector<uint8_t> qskip;          // queue_skip: no weight-gradient GEMM for [4 l + {0: QKV, 1: attention-out, 2: FFN-up, 3: FFN-down}]
+  int ev_i;                                  // the next event pair
+  int l = -1; bool cls = false; WGrad wg[4];   // the current layer (begin)
+  nbest_gemm_args pend[8];                   // grouped: the problems of the open group
+  int n_pend = 0, cls_pair = 0;              // cls_pair: the group's first layer (desc.cls_top) has recorded its pair already
+  WinPlan wp;                                // windows: the plan, its next launch, the problems [4 (l1 - 1 - l) + j], the pairs recorded
+  size_t wi = 0; std::vector<nbest_gemm_args> wargs; int pairs_used = 0; bool pair_open = false;
+
+  WgradSched(const Bwd& c_, const WgradMode& wm_, int layer_begin, int layer_end)
+      : c(c_), wm(wm_), paired(wgrad_paired(c_.d, c_.f8b)), l0(layer_begin), l1(layer_end), qskip(queue_skip(c_.d, layer_end)),
+        ev_i(wgrad_launches_per_layer(wm_, paired) * (c_.d->L - layer_end)) {
+    if (wm.sets > 0) {
+      wp = window_plan(c.d, l0, l1, qskip.data(), c.npg, true, wm.sets);
+      wargs.resize((size_t)4 * (l1 - l0));
+    }
+  }
+  bool deferred() const { return wm.gl > 0 || wm.sets > 0; }
+  // the buffer set layer l writes its dY tensors to (-1: the shared buffers): groups are formed from l1 - 1 downwards, gl layers per
+  // nbest_wgrad_group launch; the layers of a window schedule rotate over wm.sets sets
+  int set_of(int layer) const { return deferred() ? (l1 - 1 - layer) % (wm.gl + wm.sets) : -1; }
+  void begin(int layer, const LayerBufs& b, const LayerGrads& g) {
+    const nbest_layer_offsets& o = c.d->layers_host[layer];
+    const int64_t H = c.d->H, F = c.d->F;
+    const int t = 4 * layer;
+    l = layer; cls = cls_layer_of(c.d, layer);
+    wg[0] = {g.dqkv, stash_x(c.a, c.z, c.act, layer), g.dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0};
+    wg[1] = {g.dRd1, b.gctx ? b.gctx : b.ctx, g.dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1};   // (head_gate_stash: the gated context)
+    wg[2] = {g.dBig, b.x1, g.dBig8, b.x18, o.w1, F, H, t + 1, t + 2};
+    wg[3] = {g.dRd2, b.hact, g.dRd8, b.h8, o.w2, H, F, t + 0, t + 3};
+  }
+  int ready(int j) {
+    if (deferred() || (j == 1 && paired)) return NBEST_OK;   // at layer_end / with the QKV gradient
+    stamp(0);
+    if (cls && j == 0 && paired) RUN(rows(1));
+    RUN(cls && j > 0 ? rows(j) : splitk(j, j == 0 && paired ? 1 : -1));
+    stamp(1);
+    return NBEST_OK;
+  }
+  int layer_end() { return wm.sets > 0 ? window_layer_end() : wm.gl > 0 ? group_layer_end() : NBEST_OK; }
+
+ private:
+  bool skip(int j) const { return c.npg || qskip[4 * l + j]; }
+  void stamp(int which) {
+    if (c.d->wgrad_events && 2 * ev_i + which < c.d->wgrad_events_n)
+      (void)hipEventRecord((hipEvent_t)c.d->wgrad_events[2 * ev_i + which], (hipStream_t)c.dg.stream);
+    ev_i += which;
+  }
+  nbest_gemm_args args_of(const WGrad& x, int64_t tokens) const {
+    nbest_gemm_args g = wgrad_args(c.d->dtype, x.rows, x.cols, tokens);
+    g.A = x.dY; g.B = x.X; g.C = c.G(x.w_off); g.accumulate = c.accumulate;
+    return g;
+  }
+  // gradient j of the current layer as its split-K launch, or gradients j and j2 as one paired launch
+  int splitk(int j, int j2 = -1) {
+    const nbest_stream_t stream = c.dg.stream;
+    const int64_t M = c.z.M;
+    void* slab = c.ws + c.w.slab;
+    const WGrad* p = skip(j) ? nullptr : wg + j;
+    const WGrad* q = (j2 >= 0 && !skip(j2)) ? wg + j2 : nullptr;
+    if (!p) { p = q; q = nullptr; }
+    if (p && c.f8b) {
+      const uint32_t *gp = c.d->gamax_prev, *ap = c.d->aamax_prev;
+      if (q)
+        RUN(nbest_wgrad_fp8_pair(p->dY8, p->X8, c.G(p->w_off), p->rows, p->rows, p->cols, p->cols, gp + p->g_idx, ap + p->a_idx, q->dY8, q->X8,
+                                 c.G(q->w_off), q->rows, q->rows, q->cols, q->cols, gp + q->g_idx, ap + q->a_idx, p->cols, M, c.accumulate, slab,
+                                 c.w.slab_bytes, stream));
+      else
+        RUN(nbest_wgrad_fp8(p->dY8, p->X8, c.G(p->w_off), p->rows, p->cols, M, p->rows, p->cols, p->cols, gp + p->g_idx, ap + p->a_idx,
+                            c.accumulate, slab, c.w.slab_bytes, stream));
+    } else if (p) {
+      nbest_gemm_args g1 = args_of(*p, M), g2 = args_of(q ? *q : *p, M);
+      g1.ws = slab; g1.ws_bytes = c.w.slab_bytes;   // (a pair: the slabs of both)
+      RUN(q ? nbest_wgrad_pair(&g1, &g2, stream) : nbest_gemm(&g1, stream));
+    }
+    return NBEST_OK;
+  }
+  // the attention-out and QKV gradients at the end of a layer, as mode NEVER launches them: one launch where the pair fits it
+  int low_pair() { if (!paired) RUN(splitk(1)); return splitk(0, paired ? 1 : -1); }
+  // cls_top layer: gradient j (1: attention-out, 2: FFN-up, 3: FFN-down) over its K = B token rows, one plain launch (the caller's
+  // flags alone decide: the queue's flags name these three as skipped)
+  int rows(int j) {
+    if (c.npg || (c.d->wgrad_skip_host && c.d->wgrad_skip_host[4 * l + j])) return NBEST_OK;
+    nbest_gemm_args g = args_of(wg[j], c.d->B);
+    g.ws = c.ws + c.w.slab; g.ws_bytes = c.w.slab_bytes;
+    return nbest_gemm(&g, c.dg.stream);
+  }
+  int rows_all() { RUN(rows(3)); RUN(rows(2)); return rows(1); }
+  int group_layer_end() {
+    const int gpos = set_of(l);
+    const bool group_ends = gpos == wm.gl - 1 || l == l0;
+    if (group_ends && gpos + 1 < wm.gl && c.d->wgrad_group != NBEST_WGRAD_GROUP_ALWAYS) {   // no partner: mode NEVER's launches, one event pair
+      stamp(0);
+      if (cls) RUN(rows_all());
+      RUN(splitk(3)); RUN(splitk(2)); RUN(low_pair());
+      stamp(1);
+      return NBEST_OK;
+    }
+    for (int j = 0; j < 4; ++j)
+      if (!skip(j)) pend[n_pend++] = args_of(wg[j], c.z.M);
+    if (cls && !group_ends) {   // the top layer's own pair brackets its small launches; its QKV gradient waits for the group
+      stamp(0);
+      RUN(rows_all());
+      stamp(1);
+      cls_pair = 1;
+    }
+    if (group_ends) {
+      stamp(0);
+      if (cls) RUN(rows_all());
+      if (n_pend) RUN(nbest_wgrad_group(pend, n_pend, c.dg.stream));
+      stamp(1);
+      for (int i = 0; i < gpos - cls_pair; ++i) { stamp(0); stamp(1); }
+      n_pend = 0; cls_pair = 0;
+    }
+    return NBEST_OK;
+  }
+  void pair_begin() { if (!pair_open && pairs_used < l1 - l0) { stamp(0); pair_open = true; } }
+  void pair_end() { if (pair_open) { stamp(1); ++pairs_used; pair_open = false; } }
+  int window_layer_end() {
+    for (int j = 0; j < 4; ++j)
+      if (!skip(j)) wargs[(size_t)4 * (l1 - 1 - l) + j] = args_of(wg[j], c.z.M);
+    if (cls) {   // the top layer's small launches open its pair
+      pair_begin();
+      RUN(rows_all());
+    }
+    if (l == wp.peel_layer) {
+      pair_begin();
+      RUN(low_pair());
+    }
+    for (; wi < wp.launches.size() && wp.launches[wi].after_layer == l; ++wi) {
+      const WinLaunch& wl = wp.launches[wi];
+      nbest_gemm_args tab[kWinEntries];
+      int32_t first[kWinEntries], count[kWinEntries];
+      for (int i = 0; i < wl.n; ++i) {
+        tab[i] = wargs[(size_t)4 * (l1 - 1 - wl.e[i].layer) + wl.e[i].j];
+        first[i] = wl.e[i].first; count[i] = wl.e[i].count;
+      }
+      pair_begin();
+      RUN(nbest_wgrad_window(tab, first, count, wl.n, c.dg.stream));
+      pair_end();
+    }
+    pair_end();   // (a peeled pair with no window after it)
+    if (l == l0)
+      for (; pairs_used < l1 - l0; ++pairs_used) { stamp(0); stamp(1); }
+    return NBEST_OK;
+  }
+};
+
+// Layer l over all M rows: dA, the gradient w.r.t. its output, becomes the gradient w.r.t. its input (not formed for layer
+// first_trainable under desc.no_input_grad: it has no reader).  LN2 bwd -> FFN-down dgrad -> FFN-up dgrad -> LN1 bwd -> attention-out
+// dgrad -> head gates -> attention bwd -> QKV dgrad; sched.ready(j) where the operands of weight gradient j are complete - without
+// deferral dRd2 and dRd1 are one buffer, so FFN-down's must be issued before the LN1 backward overwrites it.
+static int layer_backward(const Bwd& c, int l, const LayerBufs& b, const LayerGrads& g, void* dA, WgradSched& sched) {
+  const nbest_encoder_desc* d = c.d;
+  const nbest_layer_offsets& o = d->layers_host[l];
+  const Ptrs& P = c.P;
+  const nbest_stream_t stream = c.dg.stream;
+  const int64_t M = c.z.M;
+  const int H = d->H, F = d->F, dt = d->dtype, t = 4 * l, accumulate = c.accumulate;
+  const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
+  const bool f8b = c.f8b, hdrop = c.hdrop;
+  // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
+  // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
+  RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), g.dR2, (hdrop && !f8b) ? g.dRd2 : nullptr, c.GP(o.ln2_g), c.GP(o.ln2_b),
+                                    c.GP(o.b2), M, H, dt, accumulate, d->hidden_drop, d->seed, s0 + 2, c.red(0), c.w.red_bytes, stream,
+                                    c.fg(g.dRd8, t + 0)));
+  // FFN-down: dgrad fused with GELU' -> dU (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
+  GemmOp dw2 = {g.dRd2, g.dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : g.dBig, F, H, NBEST_EPI_DGELU};
+  dw2.U = b.u; dw2.colsum = c.GP(o.b1); dw2.C8 = g.dBig8; dw2.c_idx = t + 1;
+  RUN(layer_gemm(c.dg, dw2));
+  if (c.rec && !f8b) RUN(nbest_internal_amax_bf16(g.dBig, M * F, c.GN(t + 1), (hipStream_t)stream));   // calibration pass: this producer is a bf16 kernel
+  RUN(sched.ready(3));
+  // FFN-up: dgrad + residual gradient
+  GemmOp dw1 = {g.dBig, g.dBig8, t + 1, o.w1, t + 2, g.dB1, H, F, NBEST_EPI_RES};
+  dw1.R = g.dR2;
+  RUN(layer_gemm(c.dg, dw1));
+  RUN(sched.ready(2));
+  // LN1 backward
+  RUN(nbest_internal_layernorm_bwd8(g.dB1, b.r1, b.st1, P.P(o.ln1_g), g.dR1, (hdrop && !f8b) ? g.dRd1 : nullptr, c.GP(o.ln1_g), c.GP(o.ln1_b),
+                                    c.GP(o.bo), M, H, dt, accumulate, d->hidden_drop, d->seed, s0 + 1, c.red(2), c.w.red_bytes, stream,
+                                    c.fg(g.dRd8, t + 2)));
+  // attention output projection: dgrad
+  const GemmOp dwo = {g.dRd1, g.dRd8, t + 2, o.wo, t + 1, g.dctx, H, H, NBEST_EPI_NONE};
+  RUN(layer_gemm(c.dg, dwo));
+  RUN(sched.ready(1));   // (paired: dRd1 and ctx stay untouched until the next layer's LayerNorm backward - issued with QKV's)
+  // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
+  // (per utterance), and scaled by the gate it is the gradient the attention backward takes
+  if (d->head_gate)
+    RUN(nbest_head_gate_bwd(b.ctx, g.dctx, d->head_gate + (int64_t)l * d->heads,
+                            d->head_gate_grad ? d->head_gate_grad + (int64_t)l * d->B * d->heads : nullptr, d->B, d->S, d->heads, 64, dt, stream));
+  // attention backward -> dqkv ; QKV bias gradient
+  RUN(nbest_internal_attention_bwd8(b.qkv, c.key_mask, b.ctx, g.dctx, b.lse, f8b ? nullptr : g.dqkv, c.GP(o.bqkv), accumulate, c.red(3),
+                                    c.w.red_bytes, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, c.fg(g.dqkv8, t + 3),
+                                    b.keep));
+  // QKV projection: dgrad + residual gradient -> gradient wrt the layer input
+  if (!(d->no_input_grad && l == c.a.K)) {
+    GemmOp dwqkv = {g.dqkv, g.dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
+    dwqkv.R = g.dR1;
+    RUN(layer_gemm(c.dg, dwqkv));
+  }
+  return sched.ready(0);
+}
+
+// The top layer with desc.cls_top (layer_forward_cls): dA is read at the CLS rows only; the LayerNorm backwards, the FFN and
+// attention-out dgrads run on B rows (weights read unpacked), a one-query attention backward writes the layer's dQ|dK|dV in full and the
+// QKV dgrad runs as ever.  The weight gradients read the compact buffers and the first B rows of the stash regions: all four at the end.
+static int layer_backward_cls(const Bwd& c, int l, const LayerBufs& b, const LayerGrads& g, void* dA, WgradSched& sched) {
+  const nbest_encoder_desc* d = c.d;
+  const nbest_layer_offsets& o = d->layers_host[l];
+  const Ptrs& P = c.P;
+  const nbest_stream_t stream = c.dg.stream;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d->H, F = d->F, dt = d->dtype, t = 4 * l, accumulate = c.accumulate;
+  const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
+  const bool hdrop = c.hdrop;
+  const int64_t Bn = d->B, SH = (int64_t)d->S * H;
+  const size_t bh = (size_t)Bn * H * c.z.esz, half = c.w.red_bytes / 2;
+  void* dAc = c.ws + c.w.dR + bh;   // the CLS rows of dhidden
+  GemmPass dgc = c.dg;              // the dgrads of the B rows: weights read unpacked
+  dgc.M = Bn; dgc.packed = nullptr;
+  RUN(nbest_internal_rows_drop_res(dA, SH, nullptr, 0, dAc, H, Bn, H, 1, dt, 0.f, 0, 0, st));
+  // a LayerNorm backward of the B rows (parameters at ln_g, ln_b) without dropout: dR; the dense branch's mask (the decisions of rows b S,
+  // stream ds) -> dRd and the bias gradient under it follow in a small kernel and a fixed-order column sum (partial rows: the upper half
+  // of the LayerNorm's region `red`)
+  auto ln_bwd = [&](const void* dy, const void* x, const float* stats, int64_t ln_g, int64_t ln_b, int64_t bias, void* dR, void* dRd, void* red,
+                    uint32_t ds) -> int {
+    RUN(nbest_internal_layernorm_bwd8(dy, x, stats, P.P(ln_g), dR, nullptr, c.G(ln_g), c.G(ln_b), hdrop ? nullptr : c.G(bias), Bn, H, dt,
+                                      accumulate, 0.f, 0, 0, red, half, stream, Fp8Grad{nullptr, nullptr, nullptr}));
+    if (!hdrop) return NBEST_OK;
+    RUN(nbest_internal_rows_drop_res(dR, H, nullptr, 0, dRd, H, Bn, H, d->S, dt, d->hidden_drop, d->seed, ds, st));
+    return nbest_colsum(dRd, c.G(bias), Bn, H, H, dt, accumulate, (char*)red + half, half, stream);
+  };
+  RUN(ln_bwd(dAc, b.r2, b.st2, o.ln2_g, o.ln2_b, o.b2, g.dR2, g.dRd2, c.red(0), s0 + 2));
+  GemmOp dw2 = {g.dRd2, nullptr, t + 0, o.w2, t + 3, g.dBig, F, H, NBEST_EPI_DGELU};
+  dw2.U = b.u; dw2.colsum = c.G(o.b1);
+  RUN(layer_gemm(dgc, dw2));
+  GemmOp dw1 = {g.dBig, nullptr, t + 1, o.w1, t + 2, g.dB1, H, F, NBEST_EPI_RES};
+  dw1.R = g.dR2;
+  RUN(layer_gemm(dgc, dw1));
+  RUN(ln_bwd(g.dB1, b.r1, b.st1, o.ln1_g, o.ln1_b, o.bo, g.dR1, g.dRd1, c.red(2), s0 + 1));
+  const GemmOp dwo = {g.dRd1, nullptr, t + 2, o.wo, t + 1, g.dctx, H, H, NBEST_EPI_NONE};
+  RUN(layer_gemm(dgc, dwo));
+  if (d->head_gate)   // (head_gate_stash) the B compact rows: dctx scaled by the gate, the attention backward takes the un-gated ctx
+    RUN(nbest_head_gate_bwd(b.ctx, g.dctx, d->head_gate + (int64_t)l * d->heads, nullptr, d->B, 1, d->heads, 64, dt, stream));
+  // one-query attention backward: the layer's dQ|dK|dV in full (dQ zero outside the CLS rows) ; QKV bias gradient
+  RUN(nbest_internal_attention_cls_bwd(b.qkv, c.key_mask, b.ctx, g.dctx, g.dqkv, c.G(o.bqkv), accumulate, c.red(3), c.w.red_bytes, d->B, d->S,
+                                       d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream));
+  // QKV dgrad as ever, its residual gradient zero outside the CLS rows (dctx [M][H] is free again)
+  if (!(d->no_input_grad && l == c.a.K)) {
+    NB_CHECK(hipMemsetAsync(g.dctx, 0, (size_t)c.z.M * H * c.z.esz, st) == hipSuccess, NBEST_ERR_LAUNCH, "encoder_backward: memset failed");
+    RUN(nbest_internal_rows_drop_res(g.dR1, H, nullptr, 0, g.dctx, SH, Bn, H, 1, dt, 0.f, 0, 0, st));
+    GemmOp dwqkv = {g.dqkv, nullptr, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
+    dwqkv.R = g.dctx;
+    RUN(layer_gemm(c.dg, dwqkv));
+  }
+  for (int j = 3; j >= 0; --j) RUN(sched.ready(j));
+  return NBEST_OK;
+}
 }  // namespace
 
 extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* wts, const void* wts_t, const float* prm, float* grad,
@@ -748,7 +1091,6 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
   RUN(check_desc(d));
   RUN(check_cls_top(d));
   NB_CHECK(0 <= layer_begin && layer_begin <= layer_end && layer_end <= d->L, NBEST_ERR_ARG, "encoder_backward: bad layer range");
-  // no_param_grad: dhidden only (attribution) - no weight-gradient GEMM, no bias / LayerNorm-parameter gradient, grad may be NULL
   const bool npg = d->no_param_grad != 0;
   NB_CHECK(!npg || (!with_embeddings && d->first_trainable == 0 && !d->no_input_grad && !d->w8), NBEST_ERR_ARG,
            "encoder_backward: no_param_grad refuses with_embeddings (%d), first_trainable > 0 (%d), no_input_grad (%d) and the fp8 "
@@ -763,324 +1105,46 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
            "encoder_backward: with_embeddings needs first_trainable == 0 and no_input_grad == 0");
   const Sizes z = sizes(d);
   const ActLayout a = act_layout(d, z);
-  const WgradMode wm = wgrad_mode(d);   // once per call: the workspace layout and the launches below follow it
+  const WgradMode wm = wgrad_mode(d);   // once per call: the workspace layout and the weight-gradient schedule follow it
   const WsLayout w = ws_layout(d, z, wm);
   NB_CHECK(act_bytes >= a.total, NBEST_ERR_WORKSPACE, "encoder_backward: activation stash too small");
   NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_backward: workspace too small (%zu < %zu)", ws_bytes, w.total);
-  hipStream_t st = (hipStream_t)stream;
-  const Ptrs P{(const char*)wts, prm, z.esz};
-  const bool wt = (wts_t != nullptr);
-  char *A = (char*)act, *W = (char*)ws;
-  const int64_t M = z.M;
-  const int H = d->H, F = d->F, dt = d->dtype;
-  const int FT = a.K;
-  auto X = [&](int l) { return (void*)(A + a.X + (size_t)(l - FT) * z.MH); };
-  auto G = [&](int64_t off) { return grad + off; };
-  auto GP = [&](int64_t off) -> float* { return npg ? nullptr : grad + off; };   // a bias / LayerNorm-parameter gradient (none: no_param_grad)
-  // frozen matrices (desc.wgrad_skip_host[4 l + {0: QKV, 1: attention-out, 2: FFN-up, 3: FFN-down}]): no weight-gradient GEMM
-  // (cls_top: also the top layer's three gradients over the CLS rows, which are plain launches of their own - frozen: the caller's flags alone)
-  const std::vector<uint8_t> qskip = queue_skip(d, layer_end);
-  auto skip = [&](int l, int j) -> bool { return npg || qskip[4 * l + j]; };
-  auto frozen = [&](int l, int j) -> bool { return npg || (d->wgrad_skip_host && d->wgrad_skip_host[4 * l + j]); };
-  void* dA = dhidden; void* dR = W + w.dR;
-  const bool hdrop = d->hidden_drop > 0.f;
-  void* dRd = hdrop ? (void*)(W + w.dRd) : dR;
-  void* dB1 = W + w.dB1; void* dctx = W + w.dctx; void* dBig = W + w.dBig; void* dqkv = W + w.dqkv;
-  void* red = W + w.red; void* slab = W + w.slab;
-  void* red1 = W + w.red + w.red_bytes; void* red2 = W + w.red + 2 * w.red_bytes; void* red3 = W + w.red + 3 * w.red_bytes;
-  // optional in-step timing of the weight-gradient GEMMs (see nbest_encoder_desc::wgrad_events)
-  const bool f8b = fp8_backward_active(d);
-  const bool paired = wgrad_paired(d, f8b);
-  // grouped weight gradients: gl layers per nbest_wgrad_group launch, groups formed from layer_end - 1 downwards
-  // or in rolling windows of 256 tiles (window_plan): the layers' dY tensors rotate over wm.sets buffer sets
-  const int gl = wm.gl;
-  const bool grouped = gl > 0, window = wm.sets > 0, deferred = grouped || window;
-  int ev_i = (deferred ? 1 : paired ? 3 : 4) * (d->L - layer_end);
-  auto stamp = [&](int which) {
-    if (d->wgrad_events && 2 * ev_i + which < d->wgrad_events_n) (void)hipEventRecord((hipEvent_t)d->wgrad_events[2 * ev_i + which], st);
-    ev_i += which;
-  };
-
-  // fp8 dgrads (descriptor: w8t, gamax_prev / gamax_new, fp8_bwd): the gradient amax of every dgrad operand is recorded in
-  // every pass; with a history (fp8_bwd) the producers also write e4m3 copies and the four dgrad GEMMs of a layer run in fp8
-  const bool rec = !npg && d->gamax_new && dt == NBEST_BF16;
-  uint8_t* dqkv8 = f8b ? (uint8_t*)W + w.f8 : nullptr;   // [M][3H]
-  uint8_t* dBig8 = f8b ? dqkv8 + 3 * z.MH8 : nullptr;    // [M][F]
-  uint8_t* dRd8 = f8b ? dBig8 + z.MF8 : nullptr;         // [M][H]
-  auto GN = [&](int idx) { return d->gamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS; };   // slot block of gradient tensor idx
-  auto fg = [&](uint8_t* out8, int idx) -> Fp8Grad {
-    if (!rec) return Fp8Grad{nullptr, nullptr, nullptr};
-    return Fp8Grad{f8b ? out8 : nullptr, f8b ? d->gamax_prev + idx : nullptr, GN(idx)};
-  };
-  // the dgrad GEMMs: B = the transposed weight arena when there is one (both operands k-contiguous), else the forward's as [K][N];
-  // fp8 backward: on the transposed e4m3 weight copy.  Partial rows of the column sums fused into the DGELU one: region 1
-  const GemmPass dg = {dt, M, stream, 0, Ptrs{(const char*)(wt ? wts_t : wts), prm, z.esz}, wt ? d->wpkt : nullptr, !wt, f8b,
-                       d->w8t, d->w8tp, d->w8_inv_scale, d->gamax_prev, d->gamax_new, red1, w.red_bytes, accumulate};
-  // Weight gradient j of the layer described by wg[4], between its two event stamps, or gradients j and j2 as one paired launch.
-  // A skipped gradient launches nothing (its stamps are still recorded); of a pair with one half skipped the other goes alone.
-  auto wgrad_args_of = [&](const WGrad* x) {
-    nbest_gemm_args g = wgrad_args(dt, x->rows, x->cols, M);
-    g.A = x->dY; g.B = x->X; g.C = G(x->w_off); g.accumulate = accumulate;
-    return g;
-  };
-  auto wgrad_launch = [&](int l, const WGrad* wg, int j, int j2) -> int {
-    const WGrad* p = skip(l, j) ? nullptr : wg + j;
-    const WGrad* q = (j2 >= 0 && !skip(l, j2)) ? wg + j2 : nullptr;
-    if (!p) { p = q; q = nullptr; }
-    if (p && f8b) {
-      const uint32_t *gp = d->gamax_prev, *ap = d->aamax_prev;
-      if (q)
-        RUN(nbest_wgrad_fp8_pair(p->dY8, p->X8, G(p->w_off), p->rows, p->rows, p->cols, p->cols, gp + p->g_idx, ap + p->a_idx, q->dY8, q->X8,
-                                 G(q->w_off), q->rows, q->rows, q->cols, q->cols, gp + q->g_idx, ap + q->a_idx, p->cols, M, accumulate, slab,
-                                 w.slab_bytes, stream));
-      else
-        RUN(nbest_wgrad_fp8(p->dY8, p->X8, G(p->w_off), p->rows, p->cols, M, p->rows, p->cols, p->cols, gp + p->g_idx, ap + p->a_idx,
-                            accumulate, slab, w.slab_bytes, stream));
-    } else if (p) {
-      nbest_gemm_args g1 = wgrad_args_of(p), g2 = wgrad_args_of(q ? q : p);
-      g1.ws = slab; g1.ws_bytes = w.slab_bytes;   // (a pair: the slabs of both)
-      RUN(q ? nbest_wgrad_pair(&g1, &g2, stream) : nbest_gemm(&g1, stream));
-    }
-    return NBEST_OK;
-  };
-  auto wgrad = [&](int l, const WGrad* wg, int j, int j2) -> int {
-    stamp(0);
-    RUN(wgrad_launch(l, wg, j, j2));
-    stamp(1);
-    return NBEST_OK;
-  };
-  // Grouped: the gradients of a layer are deferred to the end of its group (their dY tensors live in the group position's buffer set,
-  // their X tensors in the stash, which the backward only reads) and go out as ONE nbest_wgrad_group launch: per layer QKV,
-  // attention-out, FFN-up, FFN-down, the higher layer first.  A layer left without a partner (odd range; plan mode) issues its
-  // split-K launches back to back instead.  One event pair per layer (include/nbest_hip.h, wgrad_events).
-  nbest_gemm_args pend[8];
-  int n_pend = 0, cls_pair = 0;   // cls_pair: the group's first layer (desc.cls_top) has recorded its pair already
-  // Windows: the gradients of a layer wait in the queue of window_plan; its launches go out at the end of the layer that completes them,
-  // the peeled pair and the remainder at the end of the range's lowest layer.  One event pair per layer of the range: a pair brackets each
-  // window launch (the peeled pair launch inside the pair of the window next to it), the pairs left over are recorded back to back at
-  // the end, so the sum over the range's pairs is the weight-gradient time of the call.
-  const int nl = layer_end - layer_begin;
-  WinPlan wp;
-  std::vector<nbest_gemm_args> wargs;   // [4 (layer_end - 1 - l) + j]
-  if (window) {
-    wp = window_plan(d, layer_begin, layer_end, qskip.data(), npg, true, wm.sets);
-    wargs.resize((size_t)4 * nl);
-  }
-  size_t wi = 0;            // next launch of wp
-  int pairs_used = 0;
-  bool pair_open = false;
-  auto pair_begin = [&] { if (!pair_open && pairs_used < nl) { stamp(0); pair_open = true; } };
-  auto pair_end = [&] { if (pair_open) { stamp(1); ++pairs_used; pair_open = false; } };
+  const Bwd c = make_bwd(d, wts, wts_t, prm, grad, key_mask, act, ws, z, a, w, accumulate, stream);
+  WgradSched sched(c, wm, layer_begin, layer_end);
+  void* dA = dhidden;   // the running gradient w.r.t. the input of the lowest layer processed so far
 
   struct BatchGuard { ~BatchGuard() { nbest_internal_rowred_batch_abort(); } } batch_guard;   // an error return mid-layer must not leave it open
   for (int l = layer_end - 1; l >= layer_begin; --l) {
-    const nbest_layer_offsets& o = d->layers_host[l];
     const LayerBufs b = stashed_layer(d, a, act, l);
-    const bool input_grad = !(d->no_input_grad && l == FT);   // the gradient w.r.t. the input of layer FT has no reader
-    const int t = 4 * l;
-    const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
-    // this layer's gradient buffers: the shared ones, or (grouped) those of its position in the group, which the next layer leaves alone,
-    // or (windows) those of its buffer set, which the next sets - 1 layers leave alone.
-    // dR2 / dRd2: residual- and dense-branch gradients out of the LN2 backward, dR1 / dRd1: out of the LN1 backward (one buffer
-    // without hidden dropout)
-    const int gpos = grouped ? (layer_end - 1 - l) % gl : window ? (layer_end - 1 - l) % wm.sets : 0;
-    const bool group_ends = grouped && (gpos == gl - 1 || l == layer_begin);
-    void *dR2 = dR, *dR1 = dR, *dRd2 = dRd, *dRd1 = dRd, *dBigL = dBig, *dqkvL = dqkv;
-    if (deferred) {
-      dRd2 = W + w.gset[gpos][0]; dBigL = W + w.gset[gpos][1]; dRd1 = W + w.gset[gpos][2]; dqkvL = W + w.gset[gpos][3];
-      if (!hdrop) { dR2 = dRd2; dR1 = dRd1; }
-    }
-    // desc.cls_top, top layer: everything but dqkv is [B][.], the CLS rows - two compact buffers in each of the shared dR, dRd and dB1
-    // regions (S >= 2), one in dctx and dBig; the gradients of Wo, W1 and W2 read them and the first B rows of the stash regions
     const bool cls = cls_layer_of(d, l);
-    if (cls) {
-      const size_t bh = (size_t)d->B * H * z.esz;   // (a multiple of 128 bytes: H % 64 == 0)
-      dR2 = W + w.dR; dR1 = W + w.dB1 + bh; dBigL = dBig;
-      dRd2 = hdrop ? (void*)(W + w.dRd) : dR2; dRd1 = hdrop ? (void*)(W + w.dRd + bh) : dR1;
-    }
-    const WGrad wg[4] = {{dqkvL, X(l), dqkv8, b.x8, o.wqkv, 3 * H, H, t + 3, t + 0},
-                         {dRd1, b.gctx ? b.gctx : b.ctx, dRd8, b.ctx8, o.wo, H, H, t + 2, t + 1},   // (head_gate_stash: the gated context)
-                         {dBigL, b.x1, dBig8, b.x18, o.w1, F, H, t + 1, t + 2},
-                         {dRd2, b.hact, dRd8, b.h8, o.w2, H, F, t + 0, t + 3}};
-    // cls: gradient j (1: attention-out, 2: FFN-up, 3: FFN-down) of the top layer over its K = B token rows, one plain launch
-    auto cls_wgrad = [&](int j) -> int {
-      if (frozen(l, j)) return NBEST_OK;
-      nbest_gemm_args g = wgrad_args(dt, wg[j].rows, wg[j].cols, d->B);
-      g.A = wg[j].dY; g.B = wg[j].X; g.C = G(wg[j].w_off); g.accumulate = accumulate;
-      g.ws = slab; g.ws_bytes = w.slab_bytes;
-      return nbest_gemm(&g, stream);
-    };
-    auto cls_wgrads = [&]() -> int {
-      RUN(cls_wgrad(3));
-      RUN(cls_wgrad(2));
-      return cls_wgrad(1);
-    };
+    const LayerGrads g = layer_grads(c, sched.set_of(l), cls);
+    sched.begin(l, b, g);
     if (!npg) nbest_internal_rowred_batch_begin();    // the layer's four bias / LayerNorm-parameter reductions: one finalize launch at its end
-    if (cls) {
-      const int64_t Bn = d->B, SH = (int64_t)d->S * H;
-      const size_t bh = (size_t)Bn * H * z.esz, half = w.red_bytes / 2;
-      void* dAc = W + w.dR + bh;   // the CLS rows of dhidden
-      GemmPass dgc = dg;           // the dgrads of the B rows: weights read unpacked
-      dgc.M = Bn; dgc.packed = nullptr;
-      const Fp8Grad nof8 = {nullptr, nullptr, nullptr};
-      RUN(nbest_internal_rows_drop_res(dA, SH, nullptr, 0, dAc, H, Bn, H, 1, dt, 0.f, 0, 0, st));
-      // LayerNorm backwards without dropout; the dense branch's mask (the decisions of rows b S) and the bias gradient under it follow
-      // in a small kernel and a fixed-order column sum (partial rows: the upper half of the LayerNorm's region)
-      RUN(nbest_internal_layernorm_bwd8(dAc, b.r2, b.st2, P.P(o.ln2_g), dR2, nullptr, G(o.ln2_g), G(o.ln2_b), hdrop ? nullptr : G(o.b2), Bn, H, dt,
-                                        accumulate, 0.f, 0, 0, red, half, stream, nof8));
-      if (hdrop) {
-        RUN(nbest_internal_rows_drop_res(dR2, H, nullptr, 0, dRd2, H, Bn, H, d->S, dt, d->hidden_drop, d->seed, s0 + 2, st));
-        RUN(nbest_colsum(dRd2, G(o.b2), Bn, H, H, dt, accumulate, (char*)red + half, half, stream));
-      }
-      GemmOp dw2 = {dRd2, nullptr, t + 0, o.w2, t + 3, dBigL, F, H, NBEST_EPI_DGELU};
-      dw2.U = b.u; dw2.colsum = G(o.b1);
-      RUN(layer_gemm(dgc, dw2));
-      GemmOp dw1 = {dBigL, nullptr, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
-      dw1.R = dR2;
-      RUN(layer_gemm(dgc, dw1));
-      RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, nullptr, G(o.ln1_g), G(o.ln1_b), hdrop ? nullptr : G(o.bo), Bn, H, dt,
-                                        accumulate, 0.f, 0, 0, red2, half, stream, nof8));
-      if (hdrop) {
-        RUN(nbest_internal_rows_drop_res(dR1, H, nullptr, 0, dRd1, H, Bn, H, d->S, dt, d->hidden_drop, d->seed, s0 + 1, st));
-        RUN(nbest_colsum(dRd1, G(o.bo), Bn, H, H, dt, accumulate, (char*)red2 + half, half, stream));
-      }
-      const GemmOp dwo = {dRd1, nullptr, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
-      RUN(layer_gemm(dgc, dwo));
-      if (d->head_gate)   // (head_gate_stash) the B compact rows: dctx scaled by the gate, the attention backward takes the un-gated ctx
-        RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads, nullptr, d->B, 1, d->heads, 64, dt, stream));
-      // one-query attention backward: the layer's dQ|dK|dV in full (dQ zero outside the CLS rows) ; QKV bias gradient
-      RUN(nbest_internal_attention_cls_bwd(b.qkv, key_mask, b.ctx, dctx, dqkvL, G(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S, d->heads, 64,
-                                           dt, d->attn_drop, d->seed, s0 + 0, stream));
-      // QKV dgrad as ever, its residual gradient zero outside the CLS rows (dctx [M][H] is free again)
-      if (input_grad) {
-        NB_CHECK(hipMemsetAsync(dctx, 0, (size_t)M * H * z.esz, st) == hipSuccess, NBEST_ERR_LAUNCH, "encoder_backward: memset failed");
-        RUN(nbest_internal_rows_drop_res(dR1, H, nullptr, 0, dctx, SH, Bn, H, 1, dt, 0.f, 0, 0, st));
-        GemmOp dwqkv = {dqkvL, nullptr, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
-        dwqkv.R = dctx;
-        RUN(layer_gemm(dg, dwqkv));
-      }
-    } else {
-      // LN2 backward: dR (residual branch), dRd (dense branch, under the dropout mask), db2
-      // (with fp8 dgrads / wgrads the bf16 forms of dRd, dBig and dqkv have no reader: only their e4m3 copies are written)
-      RUN(nbest_internal_layernorm_bwd8(dA, b.r2, b.st2, P.P(o.ln2_g), dR2, (hdrop && !f8b) ? dRd2 : nullptr, GP(o.ln2_g), GP(o.ln2_b), GP(o.b2), M, H,
-                                        dt, accumulate, d->hidden_drop, d->seed, s0 + 2, red, w.red_bytes, stream, fg(dRd8, t + 0)));   // partial rows: region 0
-      // FFN-down: dgrad fused with GELU' -> dU ; wgrad
-      // (the FFN-up bias gradient = column sums of dU is fused into this epilogue)
-      GemmOp dw2 = {dRd2, dRd8, t + 0, o.w2, t + 3, f8b ? nullptr : dBigL, F, H, NBEST_EPI_DGELU};
-      dw2.U = b.u; dw2.colsum = GP(o.b1); dw2.C8 = dBig8; dw2.c_idx = t + 1;
-      RUN(layer_gemm(dg, dw2));
-      if (rec && !f8b) RUN(nbest_internal_amax_bf16(dBigL, M * F, GN(t + 1), st));   // calibration pass: this producer is a bf16 kernel
-      if (!deferred) RUN(wgrad(l, wg, 3, -1));
-      // FFN-up: dgrad + residual gradient ; wgrad
-      GemmOp dw1 = {dBigL, dBig8, t + 1, o.w1, t + 2, dB1, H, F, NBEST_EPI_RES};
-      dw1.R = dR2;
-      RUN(layer_gemm(dg, dw1));
-      if (!deferred) RUN(wgrad(l, wg, 2, -1));
-      // LN1 backward
-      RUN(nbest_internal_layernorm_bwd8(dB1, b.r1, b.st1, P.P(o.ln1_g), dR1, (hdrop && !f8b) ? dRd1 : nullptr, GP(o.ln1_g), GP(o.ln1_b), GP(o.bo), M, H,
-                                        dt, accumulate, d->hidden_drop, d->seed, s0 + 1, red2, w.red_bytes, stream, fg(dRd8, t + 2)));
-      // attention output projection: dgrad ; wgrad
-      const GemmOp dwo = {dRd1, dRd8, t + 2, o.wo, t + 1, dctx, H, H, NBEST_EPI_NONE};
-      RUN(layer_gemm(dg, dwo));
-      // (paired: this layer's dRd and ctx stay untouched until the next layer's LayerNorm backward - the gradient is issued below, with QKV's)
-      if (!paired && !deferred) RUN(wgrad(l, wg, 1, -1));
-      // head gates: dctx is the gradient w.r.t. the gated context - its product with the stashed un-gated one is the gate's gradient
-      // (per utterance), and scaled by the gate it is the gradient the attention backward takes
-      if (d->head_gate)
-        RUN(nbest_head_gate_bwd(b.ctx, dctx, d->head_gate + (int64_t)l * d->heads,
-                                d->head_gate_grad ? d->head_gate_grad + (int64_t)l * d->B * d->heads : nullptr, d->B, d->S, d->heads, 64, dt, stream));
-      // attention backward -> dqkv ; QKV bias gradient
-      RUN(nbest_internal_attention_bwd8(b.qkv, key_mask, b.ctx, dctx, b.lse, f8b ? nullptr : dqkvL, GP(o.bqkv), accumulate, red3, w.red_bytes, d->B, d->S,
-                                        d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0, stream, fg(dqkv8, t + 3), b.keep));
-      // QKV projection: dgrad + residual gradient -> gradient wrt the layer input ; wgrad (with the attention-out gradient when paired)
-      if (input_grad) {
-        GemmOp dwqkv = {dqkvL, dqkv8, t + 3, o.wqkv, t + 0, dA, H, 3 * H, NBEST_EPI_RES};
-        dwqkv.R = dR1;
-        RUN(layer_gemm(dg, dwqkv));
-      }
-    }
-    if (window) {
-      for (int j = 0; j < 4; ++j)
-        if (!skip(l, j)) wargs[(size_t)4 * (layer_end - 1 - l) + j] = wgrad_args_of(wg + j);
-      if (cls) {   // the top layer's small launches open its pair
-        pair_begin();
-        RUN(cls_wgrads());
-      }
-      if (l == wp.peel_layer) {
-        pair_begin();   // today's split-K launches of the two: one launch where the pair fits it
-        if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
-        RUN(wgrad_launch(l, wg, 0, paired ? 1 : -1));
-      }
-      for (; wi < wp.launches.size() && wp.launches[wi].after_layer == l; ++wi) {
-        const WinLaunch& wl = wp.launches[wi];
-        nbest_gemm_args tab[kWinEntries];
-        int32_t first[kWinEntries], count[kWinEntries];
-        for (int i = 0; i < wl.n; ++i) {
-          tab[i] = wargs[(size_t)4 * (layer_end - 1 - wl.e[i].layer) + wl.e[i].j];
-          first[i] = wl.e[i].first; count[i] = wl.e[i].count;
-        }
-        pair_begin();
-        RUN(nbest_wgrad_window(tab, first, count, wl.n, stream));
-        pair_end();
-      }
-      pair_end();   // (a peeled pair with no window after it)
-      if (l == layer_begin)
-        for (; pairs_used < nl; ++pairs_used) { stamp(0); stamp(1); }
-    } else if (!grouped && cls) {   // the layer's 3 or 4 pairs, in today's order, around its own launches
-      stamp(0); RUN(cls_wgrad(3)); stamp(1);
-      stamp(0); RUN(cls_wgrad(2)); stamp(1);
-      if (!paired) { stamp(0); RUN(cls_wgrad(1)); stamp(1); }
-      stamp(0);
-      if (paired) RUN(cls_wgrad(1));
-      RUN(wgrad_launch(l, wg, 0, -1));
-      stamp(1);
-    } else if (!grouped) {
-      RUN(wgrad(l, wg, 0, paired ? 1 : -1));
-    } else if (group_ends && gpos + 1 < gl && d->wgrad_group != NBEST_WGRAD_GROUP_ALWAYS) {   // no partner: today's launches, one event pair
-      stamp(0);
-      if (cls) RUN(cls_wgrads());
-      RUN(wgrad_launch(l, wg, 3, -1));
-      RUN(wgrad_launch(l, wg, 2, -1));
-      if (!paired) RUN(wgrad_launch(l, wg, 1, -1));
-      RUN(wgrad_launch(l, wg, 0, paired ? 1 : -1));
-      stamp(1);
-    } else {
-      for (int j = 0; j < 4; ++j)
-        if (!skip(l, j)) pend[n_pend++] = wgrad_args_of(wg + j);
-      if (cls && !group_ends) {   // the top layer's own pair brackets its small launches; its QKV gradient waits for the group
-        stamp(0);
-        RUN(cls_wgrads());
-        stamp(1);
-        cls_pair = 1;
-      }
-      if (group_ends) {
-        stamp(0);
-        if (cls) RUN(cls_wgrads());
-        if (n_pend) RUN(nbest_wgrad_group(pend, n_pend, stream));
-        stamp(1);
-        for (int i = 0; i < gpos - cls_pair; ++i) { stamp(0); stamp(1); }
-        n_pend = 0; cls_pair = 0;
-      }
-    }
-    if (!npg) RUN(nbest_internal_rowred_batch_flush(st));
+    RUN(cls ? layer_backward_cls(c, l, b, g, dA, sched) : layer_backward(c, l, b, g, dA, sched));
+    RUN(sched.layer_end());
+    if (!npg) RUN(nbest_internal_rowred_batch_flush((hipStream_t)stream));
   }
   if (!with_embeddings) return NBEST_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Ptrs& P = c.P;
+  const int H = d->H;
   if (!accumulate) {
-    hipError_t e = hipMemsetAsync(G(d->off_word), 0, (size_t)d->vocab * H * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(G(d->off_pos), 0, (size_t)d->max_pos * H * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(G(d->off_type), 0, (size_t)d->n_types * H * sizeof(float), st);
+    hipError_t e = hipMemsetAsync(c.G(d->off_word), 0, (size_t)d->vocab * H * sizeof(float), st);
+    if (e == hipSuccess) e = hipMemsetAsync(c.G(d->off_pos), 0, (size_t)d->max_pos * H * sizeof(float), st);
+    if (e == hipSuccess) e = hipMemsetAsync(c.G(d->off_type), 0, (size_t)d->n_types * H * sizeof(float), st);
     NB_CHECK(e == hipSuccess, NBEST_ERR_LAUNCH, "encoder_backward: memset failed: %s", hipGetErrorString(e));
   }
+  const float* emb_stats = (const float*)(c.act + a.emb_stats);
   if (d->emb_delta)   // the stash's forward ran on the perturbed word rows: x_hat is recomputed from them (delta gets no gradient)
     RUN(nbest_embed_ln_bwd_adv(ids, seg, pos, d->word_perm, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
-                               (const float*)(A + a.emb_stats), d->emb_delta, dA, G(d->off_word), G(d->off_type), G(d->off_pos),
-                               G(d->off_emb_ln_g), G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, dt, d->word_pad_id, d->pos_pad_id,
-                               accumulate, accumulate, d->hidden_drop, d->seed, d->drop_stream_base, W + w.emb, w.emb_bytes, stream));
+                               emb_stats, d->emb_delta, dA, c.G(d->off_word), c.G(d->off_type), c.G(d->off_pos),
+                               c.G(d->off_emb_ln_g), c.G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, d->dtype, d->word_pad_id, d->pos_pad_id,
+                               accumulate, accumulate, d->hidden_drop, d->seed, d->drop_stream_base, c.ws + w.emb, w.emb_bytes, stream));
   else
     RUN(nbest_embed_ln_bwd(ids, seg, pos, d->word_perm, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g),
-                           (const float*)(A + a.emb_stats), dA, G(d->off_word), G(d->off_type), G(d->off_pos), G(d->off_emb_ln_g),
-                           G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, dt, d->word_pad_id, d->pos_pad_id, accumulate, accumulate,
-                           d->hidden_drop, d->seed, d->drop_stream_base, W + w.emb, w.emb_bytes, stream));
+                           emb_stats, dA, c.G(d->off_word), c.G(d->off_type), c.G(d->off_pos), c.G(d->off_emb_ln_g),
+                           c.G(d->off_emb_ln_b), d->B, d->S, H, d->n_types, d->dtype, d->word_pad_id, d->pos_pad_id, accumulate, accumulate,
+                           d->hidden_drop, d->seed, d->drop_stream_base, c.ws + w.emb, w.emb_bytes, stream));
   return NBEST_OK;
 }
 
