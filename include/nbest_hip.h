@@ -515,6 +515,32 @@ int nbest_stc_heads_vjp(const float* Wh, const nbest_label_space* ls, const floa
  * da += grad_scale * 2(a-t)/(B*H); dt = -grad_scale * 2(a-t)/(B*H)  (the transcript branch is NOT detached). */
 int nbest_cls_mse(const void* hidden_a, int64_t stride_a, const void* hidden_t, int64_t stride_t, float* loss,
                   float* da, float* dt, int B, int H, int dtype, float grad_scale, nbest_stream_t stream);
+/* K8c  in-batch contrastive loss between the ASR and the transcript CLS rows (--contrastive_weight; the symmetric InfoNCE of SimCSE /
+ * CLIP; Chang & Chen, Interspeech 2022 for ASR-robust SLU).  a_i / t_i: the rows nbest_cls_mse reads (raw CLS, any row stride, fp32
+ * or bf16), k_i an int64 key, W = weight, T = temperature:
+ *   u_i = a_i / max(||a_i||, 1e-12)     v_i = t_i / max(||t_i||, 1e-12)          (fp32; torch's F.normalize)
+ *   Z_ij = <u_i, v_j> / T               keep(i, j) = (i == j) or (k_i != k_j)     (key NULL: every pair kept)
+ *   lr_i = log sum_{j: keep} exp(Z_ij)  lc_j = log sum_{i: keep} exp(Z_ij)
+ *   L    = 1/2 sum_i [ (lr_i - Z_ii) + (lc_i - Z_ii) ]                            (a SUM over the batch, as the BCE / CE terms)
+ *   G_ij = (W / 2T) [ keep(i, j) (exp(Z_ij - lr_i) + exp(Z_ij - lc_j)) - 2 [i == j] ]
+ *   du_i = sum_j G_ij v_j               dv_j = sum_i G_ij u_i
+ *   da_i = (du_i - <du_i, u_i> u_i) / ||a_i||      dt_j = (dv_j - <dv_j, v_j> v_j) / ||t_j||
+ * Rows with an equal key (utterances whose transcripts are identical) stay out of each other's denominators; B = 1 or all keys
+ * equal give L = 0 and zero gradients exactly.
+ *   out[0] = L (unweighted)   out[1] = number of rows i whose own column is the first maximum of Z_i. over the kept columns
+ *   out[2] = B                out[3] = 0                                           (fp32 [4], overwritten)
+ *   da [B][H] += W dL/da (the dcls the heads call wrote, as for nbest_cls_mse); dt [B][H] overwritten, or added to when
+ *   accumulate_dt (the MSE wrote it first); either may be NULL, both NULL = loss only.  The transcript branch is NOT detached.
+ * fp32 on the vector units throughout: the unit vectors are never rounded to bf16 (at T = 0.05 one bf16 ulp of a cosine is 0.08 in
+ * a logit).  Z is formed once in `ws`, so both softmaxes read the same bits.  Four launches, no atomics, no workgroup waits for
+ * another, fixed-order sums: identical bits run to run.  `ws` (16-byte aligned, nbest_cls_contrast_ws_bytes) is written before it is
+ * read - its contents on entry do not matter.  Checked before the first launch: null hidden_* / out / ws, B <= 0, H <= 0,
+ * B > 4096, temperature not finite or <= 0, weight not finite or < 0 -> NBEST_ERR_ARG; H > 8192 -> NBEST_ERR_SHAPE; a short ws ->
+ * NBEST_ERR_WORKSPACE; a bad dtype -> NBEST_ERR_DTYPE.                                                                            */
+size_t nbest_cls_contrast_ws_bytes(int B, int H);
+int nbest_cls_contrast(const void* hidden_a, int64_t stride_a, const void* hidden_t, int64_t stride_t, const int64_t* key,
+                       float weight, float temperature, float* out, float* da, float* dt, int accumulate_dt, int B, int H,
+                       int dtype, void* ws, size_t ws_bytes, nbest_stream_t stream);
 
 /* scatter a [B][H] fp32 CLS gradient into row 0 of every sequence of dhidden [B*S][H] (all other
  * rows zero): the backward of sequence_output[:, 0, :].                                             */

@@ -190,7 +190,40 @@ def parse_arguments(argv=None):
                         "the sum of both passes' gradients; E finite and > 0.  The [Train] line's Loss and F1 are the clean pass's; exp_dir "
                         "gains __fgm_<E>.  A training flag, one GPU; not with --distill_from, --rdrop_alpha, --dtype fp8w, "
                         "--freeze_embeddings or --freeze_layers K > 0")
+    g.add_argument("--contrastive_weight", type=float, default=None, metavar="W",
+                   help="in-batch contrastive alignment of the n-best list with its transcript (Chang & Chen, 2022; the loss of SimCSE / "
+                        "CLIP): every step runs the transcript pass and adds W x the symmetric InfoNCE between the ASR and the "
+                        "transcript CLS rows to the loss (nbest_cls_contrast) - each utterance's ASR row must pick its own transcript "
+                        "out of the batch's and the other way round; utterances with identical transcripts stay out of each other's "
+                        "denominators.  W finite and > 0, a weight per utterance next to the summed BCE terms.  The [Train] line's Loss "
+                        "stays the hard loss (+ MSE); one more line per epoch carries the term and its alignment-hit rate; exp_dir gains "
+                        "__cl_<W>_<T>.  Under gradient accumulation the negatives are those of the micro-batch.  A training flag, one "
+                        "GPU; not with --adv_epsilon, --dtype fp8w or --train_head_mask")
+    g.add_argument("--contrastive_temperature", type=float, default=None, metavar="T",
+                   help="with --contrastive_weight: the temperature the cosines are divided by; finite and > 0 (default 0.1)")
     opt = ap.parse_args(argv)
+    if opt.contrastive_weight is None:
+        if opt.contrastive_temperature is not None:
+            ap.error("--contrastive_temperature applies to --contrastive_weight only")
+    else:
+        if not (opt.contrastive_weight > 0.0 and math.isfinite(opt.contrastive_weight)):
+            ap.error("--contrastive_weight %s: must be a finite number > 0" % opt.contrastive_weight)
+        if opt.contrastive_temperature is None:
+            opt.contrastive_temperature = 0.1
+        if not (opt.contrastive_temperature > 0.0 and math.isfinite(opt.contrastive_temperature)):
+            ap.error("--contrastive_temperature %s: must be a finite number > 0" % opt.contrastive_temperature)
+        for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--contrastive_weight is a training flag: %s reads model.pt from the directory named without it" % flag)
+        if opt.adv_epsilon is not None:
+            ap.error("--contrastive_weight together with --adv_epsilon is not built (the adversarial pass has the hard terms only)")
+        if opt.dtype == "fp8w":
+            ap.error("--contrastive_weight together with --dtype fp8w is not built (e4m3 noise on the CLS rows is of the size of the "
+                     "cosine differences the term resolves)")
+        if opt.train_head_mask is not None:
+            ap.error("--contrastive_weight together with --train_head_mask is not built (the contrastive term under a head mask)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--contrastive_weight runs on one GPU: negatives across ranks are not built (world size %s)" % os.environ["WORLD_SIZE"])
     if opt.adv_epsilon is not None:
         if not (opt.adv_epsilon > 0.0 and math.isfinite(opt.adv_epsilon)):
             ap.error("--adv_epsilon %s: must be a finite number > 0" % opt.adv_epsilon)
@@ -339,6 +372,8 @@ def exp_dir(opt):
         parts.append("rdrop_%s" % opt.rdrop_alpha)
     if getattr(opt, "adv_epsilon", None) is not None:
         parts.append("fgm_%s" % opt.adv_epsilon)
+    if getattr(opt, "contrastive_weight", None) is not None:
+        parts.append("cl_%s_%s" % (opt.contrastive_weight, opt.contrastive_temperature))
     if getattr(opt, "train_head_mask", None) is not None:                                # last: the mask's digest, not the file's name
         parts.append("hm_%s" % trainer.head_mask_file_digest(opt.train_head_mask))
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
@@ -581,6 +616,10 @@ def main(argv=None):
         log.info("FGM: epsilon %s; every step runs the ASR pass again on word embeddings moved by epsilon (L2 norm per utterance) along "
                  "the loss gradient, same dropout bits, one optimizer step on the sum of both gradients, Loss and F1 below are the clean "
                  "pass's" % opt.adv_epsilon)
+    if opt.contrastive_weight is not None:
+        log.info("Contrastive: weight %s, temperature %s; every step runs the transcript pass and adds weight x the in-batch symmetric "
+                 "InfoNCE between the ASR and the transcript CLS rows (identical transcripts are no negatives), Loss below stays the hard "
+                 "loss (+ MSE)" % (opt.contrastive_weight, opt.contrastive_temperature))
     if train_mask is not None:
         log.info("Head mask: %s (digest %s), heads kept per layer %s of %d; every step and every evaluation run under it, a pruned "
                  "head's weights get a zero gradient, model.pt keeps the full tensors (evaluate with --testing --head_mask)"
@@ -608,6 +647,9 @@ def main(argv=None):
         t0 = time.time()
         loss, (p, r, f), acc = trainer.train_epoch(model, train, opt, memory, epoch=ep)
         log.info("[Train]\tEpoch: %02d\tTime: %.2f\tLoss: %.2f\t(p/r/f): (%.2f/%.2f/%.2f)\tAcc: %.2f" % (ep, time.time() - t0, loss, p, r, f, acc))
+        if opt.contrastive_weight is not None and getattr(opt, "contrast_epoch", None):
+            csum, chits, crows = opt.contrast_epoch[:3]
+            log.info("[Contrast]\tEpoch: %02d\tLoss: %.4f\tAlign: %.2f" % (ep, csum / max(crows, 1.0), 100.0 * chits / max(crows, 1.0)))
         # --ema_decay: the evaluations and the model.pt write run on the averaged weights; the raw ones are back afterwards
         with (opt.optimizer.ema_weights() if opt.ema_decay is not None else contextlib.nullcontext()):
             res = {}

@@ -21,7 +21,7 @@ EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
     "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
     "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd", "nbest_stc_heads_kd_t", "nbest_stc_heads_logits", "nbest_stc_heads_rdrop",
-    "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
+    "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_contrast_ws_bytes", "nbest_cls_contrast", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
     "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
@@ -115,7 +115,7 @@ def lib():
             if not hasattr(L, name):
                 raise RuntimeError("nbest_amd: %s does not export %s" % (LIB_PATH, name))
         for name in ("nbest_embed_bwd_ws_bytes", "nbest_gemm_ws_bytes", "nbest_wgrad_pair_ws_bytes", "nbest_rowred_ws_bytes", "nbest_heads_ws_bytes",
-                     "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_embed_adv_ws_bytes",
+                     "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_embed_adv_ws_bytes", "nbest_cls_contrast_ws_bytes",
                      "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.nbest_embed_bwd_ws_bytes.argtypes = [C.c_int64, C.c_int64]
@@ -168,6 +168,8 @@ def lib():
         L.nbest_stc_heads_logits.argtypes = [vp, i64, vp, vp, C.POINTER(LabelSpaceC), vp, i32, i32, i32, vp]
         L.nbest_stc_heads_vjp.argtypes = [vp, C.POINTER(LabelSpaceC)] + [vp] * 8 + [i32, i32, i32, f32, u64, u32, vp, sz, vp]
         L.nbest_cls_mse.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp]
+        L.nbest_cls_contrast_ws_bytes.argtypes = [i32, i32]
+        L.nbest_cls_contrast.argtypes = [vp, i64, vp, i64, vp, f32, f32, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]
         L.nbest_cls_grad_scatter.argtypes = [vp, vp, i32, i32, i32, i32, vp]
         L.nbest_stc_decode.argtypes = [vp, vp, C.POINTER(LabelSpaceC), vp, vp, i32, vp]
         L.nbest_stream_stamp.argtypes = [vp, i32, vp]
@@ -1051,6 +1053,35 @@ def cls_mse(hidden_a, stride_a, hidden_t, stride_t, B, H, da=None, dt=None, grad
     check(lib().nbest_cls_mse(ptr(hidden_a), stride_a, ptr(hidden_t), stride_t, ptr(loss), ptr(da), ptr(dt), B, H,
                               dtype_code(hidden_a.dtype), grad_scale, stream_ptr()), "cls_mse")
     return loss
+
+
+def cls_contrast_ws_bytes(B, H):
+    return int(lib().nbest_cls_contrast_ws_bytes(B, H))
+
+
+def cls_contrast(hidden_a, stride_a, hidden_t, stride_t, B, H, weight, temperature, keys=None, da=None, dt=None, accumulate_dt=False,
+                 ws=None):
+    """the in-batch contrastive loss between the CLS rows ``hidden_a[b * stride_a : +H]`` (ASR) and ``hidden_t[b * stride_t : +H]``
+    (transcript), fp32 or bf16: returns ``out`` = fp32 [4] (the unweighted loss summed over the batch, the alignment hits, B, 0);
+    ``da`` [B, H] += weight * dL/da, ``dt`` [B, H] = (or += when ``accumulate_dt``) weight * dL/dt; both None = loss only.
+    ``keys``: int64 [B], rows with an equal key stay out of each other's denominators (nbest_cls_contrast)"""
+    dev = hidden_a.device
+    if keys is not None and (keys.dtype != torch.int64 or keys.device != dev or tuple(keys.shape) != (B,) or not keys.is_contiguous()):
+        raise ValueError("cls_contrast: keys must be a contiguous int64 [%d] tensor on %s (got %s %s on %s)"
+                         % (B, dev, keys.dtype, tuple(keys.shape), keys.device))
+    for name, g in (("da", da), ("dt", dt)):
+        if g is not None and (g.dtype != torch.float32 or g.device != dev or g.numel() != B * H or not g.is_contiguous()):
+            raise ValueError("cls_contrast: %s must be a contiguous fp32 [%d, %d] tensor on %s" % (name, B, H, dev))
+    if hidden_t.dtype != hidden_a.dtype:
+        raise ValueError("cls_contrast: hidden_a is %s, hidden_t is %s" % (hidden_a.dtype, hidden_t.dtype))
+    nbytes = cls_contrast_ws_bytes(B, H)
+    if ws is None:
+        ws = _ws(nbytes, dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    check(lib().nbest_cls_contrast(ptr(hidden_a), stride_a, ptr(hidden_t), stride_t, ptr(keys), weight, temperature, ptr(out), ptr(da),
+                                   ptr(dt), int(bool(accumulate_dt)), B, H, dtype_code(hidden_a.dtype), ptr(ws),
+                                   ws.numel() * ws.element_size(), stream_ptr()), "cls_contrast")
+    return out
 
 
 def cls_grad_scatter(dcls, B, S, H, dtype, out=None):

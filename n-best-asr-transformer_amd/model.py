@@ -250,6 +250,39 @@ def _check_adv(adv, need_grad=True, distill=None, rdrop=None):
     return dict(epsilon=eps)
 
 
+def _check_contrast(contrast, B, trans_input_ids=None, adv=None, device=None):
+    """forward_backward's ``contrast`` argument -> dict(weight, temperature, keys): a finite float weight >= 0, a finite float
+    temperature > 0 and keys None or an int64 [B] tensor; it needs the transcript tensors and carries no ``adv``; refused before
+    anything is enqueued"""
+    if not isinstance(contrast, dict) or not {"weight", "temperature"} <= set(contrast) or not set(contrast) <= {"weight", "temperature", "keys"}:
+        raise ValueError("nbest_amd: contrast must be dict(weight=, temperature=, keys=None) (the in-batch ASR / transcript CLS "
+                         "contrastive term)")
+    if adv is not None:
+        raise ValueError("nbest_amd: contrast together with adv is not built (the adversarial pass has the hard terms only)")
+    if trans_input_ids is None:
+        raise ValueError("nbest_amd: contrast needs trans_input_ids (the positives are the transcripts' CLS rows)")
+    vals = {}
+    for name in ("weight", "temperature"):
+        try:
+            vals[name] = float(contrast[name])
+        except (TypeError, ValueError):
+            vals[name] = float("nan")
+    if not (vals["weight"] >= 0.0 and math.isfinite(vals["weight"])):
+        raise ValueError("nbest_amd: contrast weight %r: must be a finite number >= 0" % (contrast["weight"],))
+    if not (vals["temperature"] > 0.0 and math.isfinite(vals["temperature"])):
+        raise ValueError("nbest_amd: contrast temperature %r: must be a finite number > 0" % (contrast["temperature"],))
+    if B > 4096:
+        raise ValueError("nbest_amd: contrast on a batch of %d rows: at most 4096 (the B x B similarity matrix)" % B)
+    keys = contrast.get("keys")
+    if keys is not None:
+        if not torch.is_tensor(keys) or keys.dtype != torch.int64 or tuple(keys.shape) != (B,):
+            raise ValueError("nbest_amd: contrast keys must be an int64 [%d] tensor (trainer.transcript_keys)" % B)
+        if device is not None and keys.device.type != torch.device(device).type:       # ("cuda" names the current device)
+            raise ValueError("nbest_amd: contrast keys are on %s, the model on %s" % (keys.device, device))
+        keys = keys.contiguous()
+    return dict(weight=vals["weight"], temperature=vals["temperature"], keys=keys)
+
+
 def _require_trainable(plan):
     if plan is not None and not plan.trainable:
         raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
@@ -728,7 +761,7 @@ class NBestSTCModel(nn.Module):
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,
                          accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None, rdrop=None,
-                         adv=None):
+                         adv=None, contrast=None):
         """Returns dict(top, bott, final, loss_parts[4] (device), asr_cls, trans_cls).  Gradients of the sum
         BCE(final) + BCE(top) + mean-CE (+ MSE) are left in ``arena.g``.  The transcript pass runs only
         when its output is used (--add_l2_loss); the reference computes and discards it otherwise (Q4).
@@ -765,7 +798,25 @@ class NBestSTCModel(nn.Module):
         ``adv_loss_parts`` (fp32 [4], device: the perturbed pass's three hard terms, slot 3 zero) and ``adv_norm`` (fp32 [B]: ||g||
         per utterance); everything else returned is the clean pass's.  epsilon finite and >= 0 (0 runs the second pass with a zero
         delta).  Needs ``need_grad``, trainable embeddings, no head mask, no fp8 model; not together with ``distill`` or ``rdrop``.
-        No host synchronisation; about twice the launches of the plain step plus three."""
+        No host synchronisation; about twice the launches of the plain step plus three.
+        ``contrast`` = dict(weight=, temperature=, keys=None): the in-batch contrastive term between the ASR and the transcript CLS
+        rows (nbest_cls_contrast: each utterance's ASR row must pick its own transcript's row out of the batch's, and the other way
+        round).  The transcript pass runs (as for ``add_l2_loss``, undetached); after the MSE, if any, the kernel adds weight * dL
+        to the CLS gradients of both passes, so ``arena.g`` holds the gradients of hard (+ MSE) (+ soft) + weight * L.  ``keys``:
+        int64 [B] (trainer.transcript_keys): rows with an equal key - identical transcripts - stay out of each other's
+        denominators; None keeps every pair.  The dict gains ``contrast``, fp32 [4] on the device: L summed over the batch and
+        unweighted, the number of rows whose own transcript is their nearest kept one, B, 0.  ``loss_parts`` is untouched.  The
+        negatives are the rows of THIS call: under gradient accumulation those of the micro-batch.  ``need_grad=False``: the loss
+        only.  weight finite and >= 0, temperature finite and > 0; needs ``trans_input_ids``; not with ``adv``, not on an fp8w model
+        and not under a head mask (not built).  Four launches more than the same step without it, no host synchronisation."""
+        if contrast is not None:
+            contrast = _check_contrast(contrast, input_ids.shape[0], trans_input_ids, adv, self.device)
+            if self._head_mask is not None:
+                raise RuntimeError("nbest_amd: contrast with a head mask set is not built (the contrastive term under a head mask, "
+                                   "trainable or not)")
+            if self.fp8_forward:
+                raise RuntimeError("nbest_amd: contrast on an fp8w model is not built (its CLS rows carry e4m3 noise of the size of "
+                                   "the cosine differences the term resolves)")
         if adv is not None:
             adv = _check_adv(adv, need_grad, distill, rdrop)
             if self._head_mask is not None:
@@ -785,15 +836,20 @@ class NBestSTCModel(nn.Module):
                 raise RuntimeError("nbest_amd: adv needs trainable embeddings (the perturbation is formed from the gradient w.r.t. "
                                    "the word embeddings, which a backward over frozen embeddings does not form)")
         ra, rt, (top, bott, fin, loss, dcls, _, _) = self._passes_and_heads(
-            input_ids, seg_ids, trans_input_ids if add_l2_loss else None, trans_seg_ids, self.training, labels_f=labels_f,
+            input_ids, seg_ids, trans_input_ids if (add_l2_loss or contrast is not None) else None, trans_seg_ids, self.training, labels_f=labels_f,
             need_grad=need_grad, accumulate=accumulate, perm=tok_perm, trans_perm=trans_tok_perm, plan=plan, distill=distill, rdrop=rdrop)
         B, H = ra.ps.B, self.cfg.hidden_size
-        dt = mse = None
+        dt = mse = con = None
         if rt is not None:
             dt = torch.empty(B, H, dtype=torch.float32, device=self.device) if need_grad else None
+        if rt is not None and add_l2_loss:
             mse = hb.cls_mse(ra.hidden, ra.ps.S * H, rt.hidden, rt.ps.S * H, B, H, dcls, dt, grad_scale=mse_grad_scale)
             if distill is None and rdrop is None:
                 loss[3:4].copy_(mse)
+        if contrast is not None:
+            ws = self._grow(vars(self), "_contrast_ws", hb.cls_contrast_ws_bytes(B, H))
+            con = hb.cls_contrast(ra.hidden, ra.ps.S * H, rt.hidden, rt.ps.S * H, B, H, contrast["weight"], contrast["temperature"],
+                                  keys=contrast["keys"], da=dcls if need_grad else None, dt=dt, accumulate_dt=mse is not None, ws=ws)
         if need_grad and encoder_grad_scale != 1.0:
             dcls.mul_(encoder_grad_scale)
             if dt is not None:
@@ -812,6 +868,8 @@ class NBestSTCModel(nn.Module):
         out = dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
         if adv_out is not None:
             out["adv_loss_parts"], out["adv_norm"] = adv_out
+        if con is not None:
+            out["contrast"] = con
         if (distill is not None or rdrop is not None) and mse is not None:
             out["mse"] = mse
         return out

@@ -345,7 +345,7 @@ def rdrop_batch(batch):
     indices sorted stably by word id, ties in ascending token index, nbest_embed_ln_bwd's contract - by hipabi.word_perm on the
     tensors' device (a sort on the current stream, no host synchronisation).  Everything else (``word_rows``) passes through."""
     out = dict(batch)
-    for k in ("ids", "seg", "labels", "tids", "tseg"):
+    for k in ("ids", "seg", "labels", "tids", "tseg", "tkey"):
         if batch.get(k) is not None:
             out[k] = torch.cat([batch[k], batch[k]], dim=0)
     for k, src in (("tok_perm", "ids"), ("ttok_perm", "tids")):
@@ -393,8 +393,42 @@ def adv_args(adv_epsilon, teacher, rdrop_alpha, world):
     return dict(epsilon=float(adv_epsilon))
 
 
+def transcript_keys(tids):
+    """int64 [B]: for every row of the transcript ids ``tids`` [B, S] the index of the FIRST row of the batch whose ids are
+    identical - the key under which the contrastive term (forward_backward's ``contrast``) leaves utterances with the same
+    transcript out of each other's denominators.  An exact comparison of the rows, not a hash; on the tensor's device (CPU or
+    GPU), no host synchronisation."""
+    B = tids.shape[0]
+    same = (tids.unsqueeze(1) == tids.unsqueeze(0)).all(dim=-1)                    # [B, B]
+    idx = torch.arange(B, dtype=torch.int64, device=tids.device)
+    return torch.where(same, idx.unsqueeze(0), torch.full_like(idx, B).unsqueeze(0)).min(dim=1).values
+
+
+def contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, world, check_only=False):
+    """forward_backward's ``contrast`` of one call under ``contrast_weight`` (None: none), for the batch the call runs on (under
+    R-Drop the doubled one: the twins share a key).  The keys are the batch's ``tkey`` or transcript_keys of its ``tids``.  The
+    negatives are the rows of one process's batch: not built under data parallelism, and not with FGM.  ``check_only``: the
+    refusals alone, nothing enqueued."""
+    if contrast_weight is None:
+        return None
+    if adv_epsilon is not None:
+        raise ValueError("nbest_amd: contrast_weight together with adv_epsilon is not built (the adversarial pass has the hard "
+                         "terms only)")
+    if world > 1:
+        raise RuntimeError("nbest_amd: contrast_weight under data parallelism is not built: the negatives would have to cross "
+                           "ranks (world size %d)" % world)
+    if batch.get("tids") is None:
+        raise ValueError("nbest_amd: contrast_weight needs the transcripts (batch['tids'])")
+    if check_only:
+        return None
+    keys = batch.get("tkey")
+    return dict(weight=float(contrast_weight), temperature=float(contrast_temperature),
+                keys=keys if keys is not None else transcript_keys(batch["tids"]))
+
+
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
-               distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None, adv_epsilon=None):
+               distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None, adv_epsilon=None, contrast_weight=None,
+               contrast_temperature=0.1):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
     ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
@@ -407,6 +441,11 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     second time on embeddings moved by epsilon along the normalised gradient and the optimizer steps ONCE on the sum of both passes'
     gradients; the returned scores and ``loss_parts`` are the clean pass's, ``adv_loss_parts`` / ``adv_norm`` come on top.  Not with a
     ``teacher`` or ``rdrop_alpha``; data parallelism is not built.
+    ``contrast_weight``: adds W x the in-batch contrastive loss between the ASR and the transcript CLS rows at
+    ``contrast_temperature`` (forward_backward's ``contrast``; the keys are the batch's ``tkey`` or transcript_keys of its ``tids``);
+    the outputs gain ``contrast``.  Under ``rdrop_alpha`` the term runs on the doubled batch with doubled keys, so the twins drop out
+    of each other's denominators.  Works with ``add_l2_loss``, a ``teacher`` and ``rdrop_alpha``; not with ``adv_epsilon``; data
+    parallelism is not built (negatives across ranks).
     A model under a trainable head mask (``set_head_mask(mask, trainable=True)``) steps as any other on one GPU; data parallelism is
     not built (refused before anything is enqueued).
     Returns the step outputs (device tensors; no host synchronisation)."""
@@ -415,7 +454,10 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
         raise RuntimeError("nbest_amd: training under a head mask under data parallelism is not built (world size %d)" % world)
     b_local = batch["ids"].shape[0]
     adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
+    if contrast_weight is not None:                              # refused before the teacher runs or the batch is doubled
+        contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, world, check_only=True)
     batch, distill, rdrop = soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids)
+    contrast = contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, world)
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
     # (FGM: the second pass adds to every gradient, so nothing is ready before the call returns - one world-size-1 exchange at the end)
     overlap = reducer is not None and adv is None
@@ -425,12 +467,13 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     mse_scale = b_local / float(global_batch) if global_batch else 1.0 / world
     sync_frozen(model, optimizer, reducer)
     if reducer is not None:
-        reducer.set_step_tokens(batch["ids"], batch.get("tids") if add_l2_loss else None, rows=batch.get("word_rows"))
+        reducer.set_step_tokens(batch["ids"], batch.get("tids") if (add_l2_loss or contrast is not None) else None,
+                                rows=batch.get("word_rows"))
     out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
                                  trans_seg_ids=batch.get("tseg"), add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale,
                                  chunks=chunks, on_chunk_done=reducer.layers_ready if overlap else None,
                                  tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop,
-                                 adv=adv)
+                                 adv=adv, **({} if contrast is None else dict(contrast=contrast)))
     if reducer is not None and not overlap:
         reducer.reduce_all()
         optimizer.step()
@@ -832,6 +875,9 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     temperature = getattr(opt, "distill_temperature", None)                                 # --distill_temperature
     rdrop_alpha = getattr(opt, "rdrop_alpha", None)                                         # --rdrop_alpha
     adv_epsilon = getattr(opt, "adv_epsilon", None)                                         # --adv_epsilon
+    contrast_weight = getattr(opt, "contrastive_weight", None)                              # --contrastive_weight
+    contrast_temperature = getattr(opt, "contrastive_temperature", None) or 0.1
+    contrast_sum = None                                              # fp32 [4] on the device: the epoch's sum of out["contrast"]
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -852,17 +898,20 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
         if n_accum == 1:
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
                              global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha,
-                             distill_temperature=temperature, rdrop_alpha=rdrop_alpha, adv_epsilon=adv_epsilon)
+                             distill_temperature=temperature, rdrop_alpha=rdrop_alpha, adv_epsilon=adv_epsilon,
+                             **({} if contrast_weight is None else dict(contrast_weight=contrast_weight,
+                                                                        contrast_temperature=contrast_temperature)))
             if sched is not None:
                 sched.step()
         else:
             adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
             b, distill, rdrop = soft_term_args(teacher, alpha, temperature, rdrop_alpha, b, world, opt.add_segment_ids)
+            contrast = contrast_args(contrast_weight, contrast_temperature, b, adv_epsilon, world)   # negatives: the micro-batch's
             seg = b.get("seg") if opt.add_segment_ids else None
             out = model.forward_backward(b["ids"], b["labels"], seg_ids=seg, trans_input_ids=b.get("tids"), trans_seg_ids=b.get("tseg"),
                                          add_l2_loss=opt.add_l2_loss, mse_grad_scale=len(mine) / float(len(lists[bi])),
                                          accumulate=not first, tok_perm=b.get("tok_perm"), trans_tok_perm=b.get("ttok_perm"),
-                                         distill=distill, rdrop=rdrop, adv=adv)
+                                         distill=distill, rdrop=rdrop, adv=adv, **({} if contrast is None else dict(contrast=contrast)))
             group_rows.append(b["word_rows"])
             if last:
                 sync_frozen(model, opt.optimizer, reducer)
@@ -872,6 +921,8 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                 opt.optimizer.step()
                 if sched is not None:
                     sched.step()
+        if contrast_weight is not None:
+            contrast_sum = out["contrast"].clone() if contrast_sum is None else contrast_sum.add_(out["contrast"])
         if rdrop_alpha is not None:
             # the record: half the hard parts of the 2 P rows; the metrics: the first copy of every utterance
             losses.append((rdrop_hard_loss_parts(out), len(mine), len(lists[bi])))
@@ -880,6 +931,8 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             losses.append((out["loss_parts"] if teacher is None else hard_loss_parts(out), len(mine), len(lists[bi])))
         pipe.push(out, [split.labels[j] for j in mine])
     counts, _ = pipe.finish()
+    if contrast_weight is not None:                                  # read by the CLI after the [Train] line: (sum L, hits, rows, 0)
+        opt.contrast_epoch = None if contrast_sum is None else contrast_sum.double().cpu().tolist()
     return _finish(losses, counts, model.device, len(lists))
 
 
