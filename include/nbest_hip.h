@@ -302,12 +302,32 @@ typedef struct nbest_gemm_fp8_args {
 } nbest_gemm_fp8_args;
 size_t nbest_gemm_fp8_ws_bytes(const nbest_gemm_fp8_args* a);
 int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t stream);
+/* DGELU writes the e4m3 copy only where it records: C8 without c8_amax_new is refused (NBEST_ERR_ARG, nothing enqueued), as
+ * nbest_layernorm_bwd_fp8 refuses out8 without amax_new.
+ * What nbest_gemm_fp8 would launch for an argument block (the fp8 counterpart of nbest_gemm_plan): computed from the block alone - no
+ * HIP call, nothing enqueued, no pointer dereferenced - and every refusal of nbest_gemm_fp8 with the same code and message.  The launch
+ * takes its decisions from this result, nbest_pack_bn_fp8 from the same tile rule.
+ *   bn, stages      256-row tiles of bn = 128 columns on a 3-stage ring or of bn = 256 columns on the 4-stage ping-pong ring
+ *   tiles_m/_n      the tile grid (tiles_m = ceil(M / 256))
+ *   group_cols      tile columns per L2 group: tiles run group by group, row-major inside a group of group_cols columns
+ *   packed_taken    1: the kernel reads B_packed instead of B (b_pack_bn == bn, ldb == K, 16-byte aligned)                          */
+typedef struct nbest_gemm_fp8_plan_info {
+  int32_t bn, stages;
+  int32_t tiles_m, tiles_n;
+  int32_t group_cols;
+  int32_t packed_taken;
+} nbest_gemm_fp8_plan_info;
+int nbest_gemm_fp8_plan(const nbest_gemm_fp8_args* a, nbest_gemm_fp8_plan_info* out);
 /* fp8 weight gradient: dW[M][N] (fp32) (+)= sum over K tokens of dY8[k][m] * X8[k][n] / s, both operands TOKEN-major e4m3
  * ([K][lda] / [K][ldb], as their producers wrote them: the reduction dimension is read through transposed LDS reads),
  * s = the gradient scale of dY8 (from the float bits at a_amax, NULL = 1) times the activation scale of X8 (x_amax, NULL = 1).
  * M, N multiples of 256; split-K over tokens into ws (>= nbest_wgrad_fp8_ws_bytes) + deterministic reduce.  Replaces the
  * weight-gradient half of the nn.Linear backward. */
 size_t nbest_wgrad_fp8_ws_bytes(int64_t M, int64_t N, int64_t K);
+/* the K-split the weight gradient (a pair: M = Ma + Mb, the virtual row count) runs with: split z covers the tokens
+ * [z k_per_split, min(K, (z + 1) k_per_split)); splits == 1: written directly, no workspace.  Host arithmetic only; refuses
+ * (NBEST_ERR_ARG / NBEST_ERR_SHAPE) the shapes nbest_wgrad_fp8 refuses.  The workspace queries and the launches use this result. */
+int nbest_wgrad_fp8_plan(int64_t M, int64_t N, int64_t K, int* splits, int64_t* k_per_split);
 int nbest_wgrad_fp8(const void* dY8, const void* X8, float* dW, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                     int64_t ldc, const uint32_t* a_amax, const uint32_t* x_amax, int accumulate, void* ws, size_t ws_bytes,
                     nbest_stream_t stream);

@@ -791,9 +791,18 @@ extern "C" int nbest_fp8_amax_fold(void* slots, void* out, int32_t n_tensors, vo
   return NBEST_OK;
 }
 
+// the K-split of a weight gradient with M x N outputs (a pair: M = Ma + Mb virtual rows) over K tokens: host arithmetic only.  The
+// workspace queries and the launch below all take it from here.
+extern "C" int nbest_wgrad_fp8_plan(int64_t M, int64_t N, int64_t K, int* splits, int64_t* k_per_split) {
+  NB_CHECK(splits && k_per_split && M > 0 && N > 0 && K > 0, NBEST_ERR_ARG, "wgrad_fp8: bad arguments");
+  NB_CHECK(M % 256 == 0 && N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_fp8: output %lld x %lld must be multiples of 256", (long long)M, (long long)N);
+  nb_splitk_plan((M / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, splits, k_per_split);
+  return NBEST_OK;
+}
+
 extern "C" size_t nbest_wgrad_fp8_ws_bytes(int64_t M, int64_t N, int64_t K) {
   int sp; int64_t kps;
-  nb_splitk_plan((M / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &sp, &kps);
+  if (nbest_wgrad_fp8_plan(M, N, K, &sp, &kps) != NBEST_OK) return 0;
   return sp > 1 ? (size_t)sp * M * N * sizeof(float) : 0;
 }
 
@@ -807,7 +816,7 @@ static int wgrad_fp8_impl(const void* dY8, const void* X8, float* dW, int64_t M,
   GemmP8T p;
   p.A = (const uint8_t*)dY8; p.B = (const uint8_t*)X8; p.C = dW; p.slab = (float*)ws;
   p.M = Mv; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  nb_splitk_plan((Mv / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &p.splits, &p.k_per_split);
+  if (const int rc = nbest_wgrad_fp8_plan(Mv, N, K, &p.splits, &p.k_per_split)) return rc;
   p.tiles_m = (int)(Mv / 256); p.tiles_n = (int)(N / 256);
   p.accumulate = accumulate;
   const int64_t ab = (K - 1) * lda + M, bb = (K - 1) * ldb + N;
@@ -834,8 +843,9 @@ static int wgrad_fp8_impl(const void* dY8, const void* X8, float* dW, int64_t M,
 extern "C" int nbest_wgrad_fp8(const void* dY8, const void* X8, float* dW, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                                int64_t ldc, const uint32_t* a_amax, const uint32_t* x_amax, int accumulate, void* ws, size_t ws_bytes,
                                nbest_stream_t stream) {
-  NB_CHECK(dY8 && X8 && dW && M > 0 && N > 0 && K > 0, NBEST_ERR_ARG, "wgrad_fp8: bad arguments");
-  NB_CHECK(M % 256 == 0 && N % 256 == 0, NBEST_ERR_SHAPE, "wgrad_fp8: output %lld x %lld must be multiples of 256", (long long)M, (long long)N);
+  NB_CHECK(dY8 && X8 && dW, NBEST_ERR_ARG, "wgrad_fp8: bad arguments");
+  int sp; int64_t kps;
+  if (const int rc = nbest_wgrad_fp8_plan(M, N, K, &sp, &kps)) return rc;
   NB_CHECK(lda % 16 == 0 && ldb % 16 == 0 && ldc % 8 == 0 && ((uintptr_t)dY8 & 15) == 0 && ((uintptr_t)X8 & 15) == 0 && ((uintptr_t)dW & 15) == 0,
            NBEST_ERR_ALIGN, "wgrad_fp8: alignment");
   return wgrad_fp8_impl(dY8, X8, dW, M, N, K, lda, ldb, ldc, a_amax, x_amax, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, accumulate, ws,
@@ -847,7 +857,7 @@ extern "C" int nbest_wgrad_fp8(const void* dY8, const void* X8, float* dW, int64
 extern "C" size_t nbest_wgrad_fp8_pair_ws_bytes(int64_t Ma, int64_t Mb, int64_t N, int64_t K) {
   if (Ma <= 0 || Mb <= 0 || Ma % 256 || Mb % 256 || N % 256) return 0;
   int sp; int64_t kps;
-  nb_splitk_plan(((Ma + Mb) / 256) * (N / 256), K, kSlots8T, kMinBlocks8T, &sp, &kps);
+  if (nbest_wgrad_fp8_plan(Ma + Mb, N, K, &sp, &kps) != NBEST_OK) return 0;
   return sp > 1 ? (size_t)sp * (Ma + Mb) * N * sizeof(float) : 0;
 }
 extern "C" int nbest_wgrad_fp8_pair(const void* dY8a, const void* X8a, float* dWa, int64_t Ma, int64_t lda_a, int64_t ldb_a, int64_t ldc_a,
@@ -864,9 +874,14 @@ extern "C" int nbest_wgrad_fp8_pair(const void* dY8a, const void* X8a, float* dW
 }
 
 // tile width gemm8_kernel uses for an [N][K] e4m3 weight at training-size token counts (its wn rule at M = 32 768)
+// THE tile rule of gemm8_kernel: 256x128 tiles, two workgroups per CU, where 256x256 tiles leave the last round half empty and the main
+// loop is short (N = K = 768: 384 big tiles on 256 CUs; 47 -> 41 us); the big ping-pong tile elsewhere (the two tie on the other shapes)
+static int gemm8_bn(int64_t M, int64_t N, int64_t K) {
+  return (N * ((M + 255) / 256) <= 3 * 128 * 256 && K <= 1024) ? 128 : 256;
+}
 extern "C" int nbest_pack_bn_fp8(int64_t N, int64_t K) {
   if (N % 256) return 0;
-  return (N <= 768 && K <= 1024) ? 128 : 256;
+  return gemm8_bn(32768, N, K);
 }
 extern "C" int nbest_pack_weights_fp8(const void* src, void* dst, const nbest_matrix_desc* descs, int n_matrices, int n_stages,
                                       nbest_stream_t stream) {
@@ -919,7 +934,9 @@ extern "C" size_t nbest_gemm_fp8_ws_bytes(const nbest_gemm_fp8_args* a) {
   return (a && a->colsum_out) ? (size_t)((a->M + 255) / 256) * 2 * a->N * sizeof(float) : 0;
 }
 
-extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t stream) {
+// what nbest_gemm_fp8 launches for an argument block, and every refusal it makes: host arithmetic on the block, no HIP call
+extern "C" int nbest_gemm_fp8_plan(const nbest_gemm_fp8_args* a, nbest_gemm_fp8_plan_info* out) {
+  NB_CHECK(out, NBEST_ERR_ARG, "gemm_fp8_plan: null output");
   NB_CHECK(a && a->A && a->B, NBEST_ERR_ARG, "gemm_fp8: null pointer");
   // the bf16 output may be dropped where the epilogue also writes the e4m3 copy its only readers take
   NB_CHECK(a->C || ((a->epilogue == NBEST_EPI_BIAS_GELU || a->epilogue == NBEST_EPI_DGELU) && a->C8), NBEST_ERR_ARG, "gemm_fp8: null output");
@@ -941,25 +958,40 @@ extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t strea
   if (epi == NBEST_EPI_DGELU) {
     NB_CHECK(a->U && a->ldu % 8 == 0 && ((uintptr_t)a->U & 7) == 0, NBEST_ERR_ARG, "gemm_fp8: DGELU needs U (8-bit gelu')");
     NB_CHECK(!a->C8 || (a->ldc8 % 8 == 0 && ((uintptr_t)a->C8 & 7) == 0), NBEST_ERR_ARG, "gemm_fp8: DGELU fp8 output alignment");
+    NB_CHECK(!a->C8 || a->c8_amax_new, NBEST_ERR_ARG, "gemm_fp8: DGELU writes C8 only where it records (c8_amax_new)");
     NB_CHECK(!a->colsum_out || (a->ws && a->ws_bytes >= nbest_gemm_fp8_ws_bytes(a)), NBEST_ERR_WORKSPACE, "gemm_fp8: column-sum workspace too small");
   }
+  const int64_t ab = (a->M - 1) * a->lda + a->K, bb = (a->N - 1) * a->ldb + a->K;
+  NB_CHECK(ab < ((int64_t)1 << 32) && bb < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm_fp8: operand larger than 4 GiB");
+  NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || make_drop(a->drop_p, a->seed, a->drop_stream).thr16 == 0, NBEST_ERR_SHAPE,
+           "gemm_fp8: dropout counter overflow");
+  out->bn = gemm8_bn(a->M, a->N, a->K);
+  out->stages = out->bn == 256 ? 4 : 3;
+  out->tiles_m = (int32_t)((a->M + 255) / 256);
+  out->tiles_n = (int32_t)(a->N / out->bn);
+  out->group_cols = nb_group_cols(out->tiles_n, (int64_t)out->bn * a->K, 1600);
+  out->packed_taken = (a->B_packed && a->b_pack_bn == out->bn && a->ldb == a->K && a->N * a->K < ((int64_t)1 << 32) &&
+                       ((uintptr_t)a->B_packed & 15) == 0) ? 1 : 0;
+  return NBEST_OK;
+}
+
+extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t stream) {
+  nbest_gemm_fp8_plan_info plan;
+  if (const int rc = nbest_gemm_fp8_plan(a, &plan)) return rc;
+  const int epi = a->epilogue;
   GemmP8 p;
   p.A = (const uint8_t*)a->A; p.B = (const uint8_t*)a->B; p.C = (bf16*)a->C; p.bias = a->bias; p.R = (const bf16*)a->R;
   p.U = (uint8_t*)a->U; p.C8 = (uint8_t*)a->C8;
   p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldu = a->ldu; p.ldc8 = a->ldc8;
-  // 256x128 tiles, two workgroups per CU, where 256x256 tiles leave the last round half empty and the main loop is short
-  // (N = K = 768: 384 big tiles on 256 CUs; 47 -> 41 us); the big ping-pong tile elsewhere (the two tie on the other shapes)
-  const int wn = (a->N * (int64_t)((a->M + 255) / 256) <= 3 * 128 * 256 && a->K <= 1024) ? 2 : 4;
-  p.tiles_m = (int)((a->M + 255) / 256);
-  p.tiles_n = (int)(a->N / (64 * wn));
+  const int wn = plan.bn / 64;
+  p.tiles_m = plan.tiles_m;
+  p.tiles_n = plan.tiles_n;
   p.Bp = nullptr; p.bp_bytes = 0;
-  if (a->B_packed && a->b_pack_bn == 64 * wn && a->ldb == a->K && a->N * a->K < ((int64_t)1 << 32) && ((uintptr_t)a->B_packed & 15) == 0) {
+  if (plan.packed_taken) {
     p.Bp = (const uint8_t*)a->B_packed;
     p.bp_bytes = (uint32_t)(a->N * a->K);
   }
-  const int64_t ab = (a->M - 1) * a->lda + a->K, bb = (a->N - 1) * a->ldb + a->K;
-  NB_CHECK(ab < ((int64_t)1 << 32) && bb < ((int64_t)1 << 32), NBEST_ERR_SHAPE, "gemm_fp8: operand larger than 4 GiB");
-  p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
+  p.a_bytes = (uint32_t)((a->M - 1) * a->lda + a->K); p.b_bytes = (uint32_t)((a->N - 1) * a->ldb + a->K);   // (< 4 GiB: checked by the plan)
   p.out_scale = a->out_scale;
   p.out_scale_dev = a->out_scale_dev;
   p.a_amax = a->a_amax;
@@ -968,8 +1000,7 @@ extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t strea
   p.colpart = (epi == NBEST_EPI_DGELU && a->colsum_out) ? (float*)a->ws : nullptr;
   p.drop = make_drop(a->drop_p, a->seed, a->drop_stream);
   p.stream_out = 1;   // every output is streamed (common.h st_stream)
-  p.gn = nb_group_cols(p.tiles_n, (int64_t)64 * wn * a->K, 1600);
-  NB_CHECK(a->M * a->N < ((int64_t)1 << 32) || p.drop.thr16 == 0, NBEST_ERR_SHAPE, "gemm_fp8: dropout counter overflow");
+  p.gn = plan.group_cols;
 
   const int grid = p.tiles_m * p.tiles_n;
   constexpr int lds4 = 4 * (256 + 256) * BK8, lds2 = 3 * (256 + 128) * BK8;

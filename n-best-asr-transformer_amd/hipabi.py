@@ -31,6 +31,7 @@ EXPORTS = [
     "nbest_head_gate_fwd", "nbest_head_gate_bwd",
     "nbest_embed_ln_fwd_adv", "nbest_embed_ln_bwd_adv", "nbest_embed_adv_ws_bytes", "nbest_embed_adv_delta",
     "nbest_layernorm_fwd_fp8", "nbest_layernorm_bwd_fp8", "nbest_attention_fwd_fp8", "nbest_attention_bwd_fp8", "nbest_cast_bf16_to_fp8_scaled", "nbest_amax_bf16",
+    "nbest_gemm_fp8_plan", "nbest_wgrad_fp8_plan",
 ]
 
 
@@ -60,6 +61,11 @@ class GemmFp8Args(C.Structure):
                 ("out_scale_dev", C.c_void_p), ("a_amax", C.c_void_p), ("c8_amax_prev", C.c_void_p), ("c8_amax_new", C.c_void_p),
                 ("colsum_out", C.c_void_p), ("colsum_accumulate", C.c_int32), ("pad", C.c_int32), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
                 ("B_packed", C.c_void_p), ("b_pack_bn", C.c_int32), ("pad3", C.c_int32)]
+
+
+class GemmFp8PlanInfo(C.Structure):
+    _fields_ = [("bn", C.c_int32), ("stages", C.c_int32), ("tiles_m", C.c_int32), ("tiles_n", C.c_int32), ("group_cols", C.c_int32),
+                ("packed_taken", C.c_int32)]
 
 
 class LabelSpaceC(C.Structure):
@@ -199,6 +205,8 @@ def lib():
         L.nbest_pack_bn_fp8.argtypes = [i64, i64]
         L.nbest_pack_weights_fp8.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nbest_gemm_fp8.argtypes = [C.POINTER(GemmFp8Args), vp]
+        L.nbest_gemm_fp8_plan.argtypes = [C.POINTER(GemmFp8Args), C.POINTER(GemmFp8PlanInfo)]
+        L.nbest_wgrad_fp8_plan.argtypes = [i64, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
         L.nbest_cast_bf16_to_fp8.argtypes = [vp, vp, i64, vp]
         L.nbest_wgrad_fp8_ws_bytes.restype = C.c_size_t
         L.nbest_wgrad_fp8_ws_bytes.argtypes = [i64, i64, i64]
@@ -503,26 +511,106 @@ def cast_fp8(x):
     return out
 
 
-def gemm_fp8(A8, W8, M, N, K, bias, out_scale=1.0, epilogue=EPI_BIAS, R=None, drop_p=0.0, seed=0, drop_stream=0, out=None, B_packed=None, b_pack_bn=0):
-    """C[M,N] (bf16) = epi((A8 . W8^T) * out_scale + bias), A8 / W8 e4m3 bytes; BIAS_GELU also returns (U 8-bit gelu', C8 fp8 copy)"""
+def _gemm_fp8_args(A8, W8, M, N, K, bias, out_scale, epilogue, R, drop_p, seed, drop_stream, out, B_packed, b_pack_bn, U, C8, colsum_out,
+                   colsum_accumulate, a_amax, c8_amax_prev, c8_amax_slots, out_scale_dev, want_c):
+    """the argument block of gemm_fp8 / gemm_fp8_plan: (GemmFp8Args, out, U, C8, workspace); every leading dimension is the tensor's
+    row stride"""
     dev = A8.device
-    if out is None:
+    if want_c and out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+    if not want_c:
+        out = None
+    if epilogue == EPI_BIAS_GELU:                                   # outputs; DGELU: U is the input, C8 an optional output of the caller's
+        if U is None:
+            U = torch.empty(M, N, dtype=torch.uint8, device=dev)
+        if C8 is None:
+            C8 = torch.empty(M, N, dtype=torch.uint8, device=dev)
     g = GemmFp8Args()
-    g.A, g.B, g.C, g.bias = A8.data_ptr(), W8.data_ptr(), out.data_ptr(), bias.data_ptr()
-    g.M, g.N, g.K, g.lda, g.ldb, g.ldc = M, N, K, A8.stride(0), W8.stride(0), out.stride(0)
+    g.A, g.B = A8.data_ptr(), W8.data_ptr()
+    g.C = out.data_ptr() if out is not None else None
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.M, g.N, g.K, g.lda, g.ldb = M, N, K, A8.stride(0), W8.stride(0)
+    g.ldc = out.stride(0) if out is not None else N
     g.epilogue, g.out_scale, g.drop_p, g.drop_stream, g.seed = epilogue, out_scale, drop_p, drop_stream, seed
-    U = C8 = None
-    if epilogue == EPI_BIAS_GELU:
-        U = torch.empty(M, N, dtype=torch.uint8, device=dev)
-        C8 = torch.empty(M, N, dtype=torch.uint8, device=dev)
-        g.U, g.C8, g.ldu, g.ldc8 = U.data_ptr(), C8.data_ptr(), N, N
+    if U is not None:
+        g.U, g.ldu = U.data_ptr(), U.stride(0)
+    if C8 is not None:
+        g.C8, g.ldc8 = C8.data_ptr(), C8.stride(0)
     if R is not None:
         g.R, g.ldr = R.data_ptr(), R.stride(0)
     if B_packed is not None:
         g.B_packed, g.b_pack_bn = B_packed.data_ptr(), b_pack_bn
+    if out_scale_dev is not None:
+        g.out_scale_dev = out_scale_dev.data_ptr()
+    if a_amax is not None:
+        g.a_amax = _amax_args(a_amax, None)[0]
+    g.c8_amax_prev, g.c8_amax_new = _amax_args(c8_amax_prev, c8_amax_slots)
+    ws = None
+    if colsum_out is not None:
+        g.colsum_out, g.colsum_accumulate = colsum_out.data_ptr(), int(colsum_accumulate)
+        ws = _ws(lib().nbest_gemm_fp8_ws_bytes(C.byref(g)), dev)
+        g.ws, g.ws_bytes = ws.data_ptr(), ws.numel()
+    return g, out, U, C8, ws
+
+
+def gemm_fp8(A8, W8, M, N, K, bias=None, out_scale=1.0, epilogue=EPI_BIAS, R=None, drop_p=0.0, seed=0, drop_stream=0, out=None, B_packed=None,
+             b_pack_bn=0, U=None, C8=None, colsum_out=None, colsum_accumulate=False, a_amax=None, c8_amax_prev=None, c8_amax_slots=None,
+             out_scale_dev=None, want_c=True):
+    """C[M,N] (bf16) = epi((A8 . W8^T) * out_scale + bias), A8 / W8 e4m3 bytes; BIAS_GELU also returns (U 8-bit gelu', C8 fp8 copy).
+    The whole of nbest_gemm_fp8_args: ``bias=None`` for NONE / RES / DGELU; ``U``: the GELU' rows DGELU reads (BIAS_GELU: where it writes
+    them); ``C8``: the e4m3 copy (DGELU: optional); ``colsum_out`` [N] fp32 (+)= the column sums of DGELU; ``a_amax`` / ``c8_amax_prev``:
+    1-element int32 tensors (float bits), ``c8_amax_slots``: a slot block, as _amax_args; ``out_scale_dev``: a device float that overrides
+    ``out_scale``; ``want_c=False``: C = NULL (None is returned in its place)."""
+    g, out, U, C8, ws = _gemm_fp8_args(A8, W8, M, N, K, bias, out_scale, epilogue, R, drop_p, seed, drop_stream, out, B_packed, b_pack_bn, U, C8,
+                                       colsum_out, colsum_accumulate, a_amax, c8_amax_prev, c8_amax_slots, out_scale_dev, want_c)
     check(lib().nbest_gemm_fp8(C.byref(g), stream_ptr()), "gemm_fp8")
     return (out, U, C8) if epilogue == EPI_BIAS_GELU else out
+
+
+def gemm_fp8_plan_args(g):
+    """nbest_gemm_fp8_plan on a filled GemmFp8Args, as a dict of the nbest_gemm_fp8_plan_info fields (host only, nothing enqueued); an
+    argument block nbest_gemm_fp8 refuses raises with the same code"""
+    info = GemmFp8PlanInfo()
+    check(lib().nbest_gemm_fp8_plan(C.byref(g), C.byref(info)), "gemm_fp8_plan")
+    return {name: int(getattr(info, name)) for name, _ in GemmFp8PlanInfo._fields_}
+
+
+def gemm_fp8_plan(A8, W8, M, N, K, bias=None, out_scale=1.0, epilogue=EPI_BIAS, R=None, drop_p=0.0, seed=0, drop_stream=0, out=None,
+                  B_packed=None, b_pack_bn=0, U=None, C8=None, colsum_out=None, colsum_accumulate=False, a_amax=None, c8_amax_prev=None,
+                  c8_amax_slots=None, out_scale_dev=None, want_c=True):
+    """the kernel ``gemm_fp8`` would launch for the same arguments (nbest_gemm_fp8_plan), as a dict; launches nothing"""
+    g = _gemm_fp8_args(A8, W8, M, N, K, bias, out_scale, epilogue, R, drop_p, seed, drop_stream, out, B_packed, b_pack_bn, U, C8, colsum_out,
+                       colsum_accumulate, a_amax, c8_amax_prev, c8_amax_slots, out_scale_dev, want_c)[0]
+    return gemm_fp8_plan_args(g)
+
+
+def gemm_fp8_plan_shape(M, N, K, epilogue=EPI_BIAS, lda=None, ldb=None, ldc=None, packed_bn=0, drop_p=0.0):
+    """gemm_fp8_plan from a shape alone (no torch, no GPU): stand-in addresses, every operand the epilogue reads present"""
+    g = GemmFp8Args()
+    fake = 1 << 20
+    g.A = g.B = g.C = fake
+    g.M, g.N, g.K = M, N, K
+    g.lda, g.ldb, g.ldc = (lda or K), (ldb or K), (ldc or N)
+    g.ldr = g.ldu = g.ldc8 = N
+    g.epilogue, g.out_scale, g.drop_p = epilogue, 1.0, drop_p
+    if epilogue in (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES):
+        g.bias = fake
+    if epilogue in (EPI_BIAS_DROP_RES, EPI_RES):
+        g.R = fake
+    if epilogue in (EPI_BIAS_GELU, EPI_DGELU):
+        g.U = fake
+    if epilogue == EPI_BIAS_GELU:
+        g.C8 = fake
+    if packed_bn:
+        g.B_packed, g.b_pack_bn = fake, packed_bn
+    return gemm_fp8_plan_args(g)
+
+
+def wgrad_fp8_plan(M, N, K):
+    """nbest_wgrad_fp8_plan -> (splits, k_per_split) of the fp8 weight gradient with M x N outputs (a pair: M = Ma + Mb) over K tokens"""
+    sp, kps = C.c_int(0), C.c_int64(0)
+    check(lib().nbest_wgrad_fp8_plan(M, N, K, C.byref(sp), C.byref(kps)), "wgrad_fp8_plan")
+    return int(sp.value), int(kps.value)
 
 
 def wgrad_fp8(dY8, X8, M, N, K, a_amax=None, out=None, accumulate=False, x_amax=None):
