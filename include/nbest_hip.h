@@ -416,6 +416,37 @@ int nbest_head_gate_fwd(const void* ctx_in, int64_t ld_in, void* ctx_out, int64_
 int nbest_head_gate_bwd(const void* ctx, void* dctx, const float* gate, float* dgate, int B, int S, int heads, int d, int dtype,
                         nbest_stream_t stream);
 
+/* Compact pruned heads (inference): a layer that keeps k of its heads, idx[0..k) ascending, is an ordinary layer with a [3 64k][H]
+ * QKV matrix, heads = k in the attention and an [H][64k] attention-output matrix.  The compact images of all layers, H = 64 heads:
+ *   weight image (compute dtype T), two sections - the Wqkv' of every layer, then the Wo' of every layer:
+ *     Wqkv' [3 64k][H]: row (t k + i) 64 + r is a bit copy of row (t heads + idx[i]) 64 + r of the layer's [3H][H] matrix, t in {Q, K, V}
+ *     Wo'   [H][64k]:   element [n][i 64 + r] = T(gate[l][idx[i]] * float(Wo[n][idx[i] 64 + r])) - the gate is folded into the output
+ *                       matrix (any float works); a gate of exactly 1 copies the bits
+ *   bias image (fp32): bqkv' [3 64k], the mapping of Wqkv' out of the fp32 arena.
+ * nbest_head_prune_layer: one layer's row of the table - element offsets of its three tensors in the arenas (src_*, as
+ *   nbest_layer_offsets) and in the images (dst_*), k and the indices.
+ * nbest_head_prune_plan (host arithmetic only, answers without a GPU): for the kept counts k[L] (1 <= k[l] <= heads <=
+ *   NBEST_HEAD_PRUNE_MAX_HEADS) fills layers[l].k and layers[l].dst_* - tensors packed back to back, every offset a multiple of 64
+ *   elements - and the byte sizes of the two weight sections and of the bias image (each pointer may be NULL).  Leaves src_* and idx
+ *   alone.  dst_wo counts from the start of the weight image: the Wo' section begins at byte *wqkv_bytes.
+ * nbest_head_prune_pack: ONE launch over all layers that gathers the images from wts (T) / prm (fp32) under gate [L][heads] fp32
+ *   (device).  table_host and table_dev hold the same L rows (the host copy is checked: 1 <= k <= heads, idx ascending and
+ *   < heads, every destination inside w_bytes / b_bytes, 16-byte alignment; the device copy is what the kernel reads).  A layer
+ *   with no kept head is packed by its caller as k = 1, idx = {0}: Wo' comes out all zeros through the gate.  16-byte accesses, no
+ *   atomics, bit-reproducible; writes exactly the planned bytes.  Reads and writes 4 H 64k (+ 3 64k biases) elements per layer.    */
+#define NBEST_HEAD_PRUNE_MAX_HEADS 32
+typedef struct nbest_head_prune_layer {
+  int64_t src_wqkv, src_bqkv, src_wo;
+  int64_t dst_wqkv, dst_bqkv, dst_wo;
+  int32_t k, pad;
+  int32_t idx[NBEST_HEAD_PRUNE_MAX_HEADS];
+} nbest_head_prune_layer;
+int nbest_head_prune_plan(const int32_t* k, int L, int heads, int dtype, nbest_head_prune_layer* layers, size_t* wqkv_bytes,
+                          size_t* wo_bytes, size_t* bqkv_bytes);
+int nbest_head_prune_pack(const void* wts, const float* prm, const float* gate, const nbest_head_prune_layer* table_host,
+                          const nbest_head_prune_layer* table_dev, int L, int heads, int dtype, void* w_out, size_t w_bytes,
+                          float* b_out, size_t b_bytes, nbest_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K5  LayerNorm over the hidden dimension (BertSelfOutput / BertOutput LayerNorm,
  * installed modeling_bert.py:282-293, 340-351).  stats[m] = {mean, rstd} fp32.                      */
@@ -958,6 +989,26 @@ int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const floa
 int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                              const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, float* cls_attn,
                              nbest_stream_t stream);
+/* nbest_encoder_infer on the compact images of nbest_head_prune_pack: layer l runs its QKV GEMM with N = 3 64k, K = H on Wqkv' and
+ * bqkv', the attention with heads = k on qkv [M][3 64k] -> ctx [M][64k], and the attention-output GEMM with N = H, K = 64k on Wo'
+ * (bias bo and the residual as always); LayerNorm and the FFN read the ordinary arena (and d->wpk).  The last layer keeps its
+ * CLS-row form: K|V over all rows out of rows 64k.. of Wqkv' (N = 2 64k), Q on the B CLS rows, the one-query attention with
+ * ldq = 64k, ldkv = 2 64k, heads = k.  No gate launch: the gate lives in Wo'.
+ *   images: w = the weight image, w_packed = its nbest_pack_weights image or NULL (bf16; read for layers 0 .. L-2 only), bqkv =
+ *   the bias image, layers_host = the table the images were packed by (k and dst_* are read).
+ * d->head_gate must be NULL (NBEST_ERR_ARG); there is no attention-map output (the maps are indexed by original head).  bf16: every k
+ * must be even (NBEST_ERR_SHAPE: the bf16 GEMM tiles need N = 64k to be a multiple of 128 - carry a head whose gate is 0).
+ * The other refusals and the workspace are those of nbest_encoder_infer: every compact tensor is no larger than its full-width
+ * counterpart.  Nothing is enqueued when a refusal is returned.                                                                   */
+typedef struct nbest_head_prune_images {
+  const void* w;
+  const void* w_packed;
+  const float* bqkv;
+  const nbest_head_prune_layer* layers_host;
+} nbest_head_prune_images;
+int nbest_encoder_infer_pruned(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                               const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                               const nbest_head_prune_images* images, nbest_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,11 @@ def parse_arguments(argv=None):
     g.add_argument("--head_mask", default=None, metavar="FILE",
                    help="gate the attention heads (HF's head_mask) for --testing, --predict and --head_importance: a JSON list of L rows "
                         "of `heads` numbers, 0 = head pruned, 1 = kept (any float scales the head's output).  Not for a training run")
+    g.add_argument("--compact_heads", action="store_true",
+                   help="with --predict FILE --head_mask FILE: run only the heads the mask keeps - per layer a [3 64k, H] QKV matrix, "
+                        "a k-head attention and an [H, 64k] output matrix with the gate folded in, rebuilt from the weights per "
+                        "batch - instead of gating full-width layers; same labels.  Not with --testing or --head_importance (they run "
+                        "the stash forward), --predict_attention or --predict_attribution")
     g.add_argument("--train_head_mask", default=None, metavar="FILE",
                    help="train under a head mask (the format of --head_mask; usually the pruned_mask of --head_importance --prune_heads, "
                         "with --init_checkpoint): the fine-tune that recovers what pruning lost (Michel et al., 2019).  Every step and "
@@ -326,6 +331,21 @@ def parse_arguments(argv=None):
             ap.error("--head_mask applies to --testing, --predict and --head_importance; training under a head mask is not built")
         if not os.path.isfile(opt.head_mask):
             ap.error("--head_mask %s: no such file" % opt.head_mask)
+    if opt.compact_heads:
+        if opt.testing or opt.head_importance is not None:
+            ap.error("--compact_heads applies to --predict only: %s runs the stash forward, and compacting the heads there is not "
+                     "built" % ("--testing" if opt.testing else "--head_importance"))
+        if opt.predict is None:
+            ap.error("--compact_heads is an inference flag: pass it with --predict FILE --head_mask FILE (training with compacted "
+                     "heads is not built)")
+        if opt.head_mask is None:
+            ap.error("--compact_heads compacts the heads a mask prunes: pass --head_mask FILE too")
+        if opt.predict_attention is not None:
+            ap.error("--compact_heads together with --predict_attention is not built (the CLS attention maps are indexed by "
+                     "original head)")
+        if opt.predict_attribution is not None:
+            ap.error("--compact_heads together with --predict_attribution is not built (the attribution runs the gated stash "
+                     "forward; drop --compact_heads)")
     if opt.train_head_mask is not None:
         for flag, on in (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None)):
             if on:
@@ -532,7 +552,8 @@ def main(argv=None):
 
     if opt.head_mask is not None:
         try:
-            model.set_head_mask(trainer.read_head_mask(opt.head_mask, cfg.num_hidden_layers, cfg.num_attention_heads))
+            model.set_head_mask(trainer.read_head_mask(opt.head_mask, cfg.num_hidden_layers, cfg.num_attention_heads),
+                                compact=opt.compact_heads)
         except ValueError as e:
             raise SystemExit("--head_mask: %s" % e)
 

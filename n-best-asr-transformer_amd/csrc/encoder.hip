@@ -434,6 +434,9 @@ struct GemmOp {   // fields after `bias` (a dgrad: after `epilogue`) are zero un
   const void* R; float drop_p; uint32_t drop_stream;     // BIAS_DROP_RES, RES: the residual rows; the dropout of BIAS_DROP_RES
   void* U; float* colsum;                                // BIAS_GELU (NULL: not kept), DGELU: the GELU' rows; DGELU: column sums of C
   uint8_t* C8; int c_idx;                                // fp8, BIAS_GELU and DGELU: the e4m3 copy of C and the index of its amax
+  // a matrix outside the pass's arena (the compact images of pruned heads): read instead of W.W(w_off), with its own packed image or
+  // NULL; bf16 / fp32 GEMMs only
+  const void* Wm; const void* Wm_packed;
 };
 
 static int layer_gemm(const GemmPass& c, const GemmOp& o) {
@@ -453,7 +456,7 @@ static int layer_gemm(const GemmPass& c, const GemmOp& o) {
     g.colsum_out = o.colsum; g.colsum_accumulate = c.accumulate; g.ws = c.colsum_ws; g.ws_bytes = c.colsum_ws_bytes;
     return nbest_gemm_fp8(&g, c.stream);
   }
-  nbest_gemm_args g = gemm_nt(c.dtype, o.A, c.W.W(o.w_off), o.C, c.M, o.N, o.K);
+  nbest_gemm_args g = gemm_nt(c.dtype, o.A, o.Wm ? o.Wm : c.W.W(o.w_off), o.C, c.M, o.N, o.K);
   if (c.b_kn) { g.trans_b = 1; g.ldb = o.N; }
   g.epilogue = o.epilogue; g.bias = o.bias;
   if (o.R) { g.R = o.R; g.ldr = o.N; }
@@ -462,7 +465,8 @@ static int layer_gemm(const GemmPass& c, const GemmOp& o) {
   if (o.epilogue == NBEST_EPI_DGELU) {
     g.colsum_out = o.colsum; g.colsum_accumulate = g.accumulate = c.accumulate; g.ws = c.colsum_ws; g.ws_bytes = c.colsum_ws_bytes;
   }
-  use_packed(g, c.packed, o.w_off);
+  if (o.Wm) use_packed(g, o.Wm_packed, 0);
+  else use_packed(g, c.packed, o.w_off);
   return nbest_gemm(&g, c.stream);
 }
 
@@ -539,8 +543,15 @@ static Fwd make_fwd(const nbest_encoder_desc* d, const void* wts, const float* p
 
 // Layer l over all M rows: xin -> xout through the buffers `b`.  x8_next: where the last LayerNorm leaves the e4m3 copy of xout for
 // the next layer's QKV GEMM (fp8 pass; NULL: no reader).  cls_probs != NULL: also the CLS rows' attention probabilities
-// [B][heads][S] fp32, launched right after the QKV projection.
-static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const LayerBufs& b, uint8_t* x8_next, float* cls_probs) {
+// [B][heads][S] fp32, launched right after the QKV projection.  pl != NULL (nbest_encoder_infer_pruned; bf16 / fp32, no cls_probs,
+// no head gate): the layer keeps pl->k heads - QKV and attention-out read the compact matrices, qkv is [M][3 64k], ctx [M][64k].
+struct PrunedLayer {
+  int k;
+  const void *wqkv, *wqkv_packed, *wo, *wo_packed;   // Wqkv' [3 64k][H], Wo' [H][64k] and their packed images (NULL: none)
+  const float* bqkv;                                 // bqkv' [3 64k]
+};
+static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const LayerBufs& b, uint8_t* x8_next, float* cls_probs,
+                         const PrunedLayer* pl = nullptr) {
   const nbest_encoder_desc* d = c.d;
   const nbest_layer_offsets& o = d->layers_host[l];
   const Ptrs& P = c.g.W;
@@ -548,27 +559,30 @@ static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const
   const int64_t M = c.g.M;
   const int H = d->H, F = d->F, dt = d->dtype, t = 4 * l;   // t + {0, 1, 2, 3}: the layer's matrices, and their A operands x, ctx, x1, gelu(u)
   const uint32_t s0 = d->drop_stream_base + 1 + 4 * l;
+  const int heads = pl ? pl->k : d->heads, Hk = 64 * heads;   // Hk = H unless the layer is pruned
   // QKV projection: [M,H] x [3H,H]^T + b
   if (c.g.fp8 && l == 0)   // later layers: written by the previous layer's LayerNorm
     RUN(nbest_internal_cast_bf16_to_fp8(xin, b.x8, M * H, c.AP(0), c.AN(0), (hipStream_t)stream));
-  const GemmOp wqkv = {xin, b.x8, t + 0, o.wqkv, t + 0, b.qkv, 3 * H, H, NBEST_EPI_BIAS, P.P(o.bqkv)};
+  GemmOp wqkv = {xin, b.x8, t + 0, o.wqkv, t + 0, b.qkv, 3 * Hk, H, NBEST_EPI_BIAS, pl ? pl->bqkv : P.P(o.bqkv)};
+  if (pl) { wqkv.Wm = pl->wqkv; wqkv.Wm_packed = pl->wqkv_packed; }
   RUN(layer_gemm(c.g, wqkv));
   if (cls_probs)   // q = row 0 of each utterance (ldq = S 3H), K | V = the second and third thirds of every row
     RUN(nbest_internal_attention_cls_probs(b.qkv, (int64_t)d->S * H * 3, (const char*)b.qkv + H * P.esz, 3 * H, c.key_mask, cls_probs, d->S,
                                            d->B, d->S, d->heads, 64, dt, stream));
   RUN(c.calib(xin, M * H, t + 0));
-  RUN(nbest_internal_attention_fwd8(b.qkv, c.key_mask, b.ctx, b.ctx8, b.lse, d->B, d->S, d->heads, 64, dt, d->attn_drop, d->seed, s0 + 0,
+  RUN(nbest_internal_attention_fwd8(b.qkv, c.key_mask, b.ctx, b.ctx8, b.lse, d->B, d->S, heads, 64, dt, d->attn_drop, d->seed, s0 + 0,
                                     stream, b.keep, c.AP(t + 1), c.AN(t + 1)));
-  RUN(c.calib(b.ctx, M * H, t + 1));
+  RUN(c.calib(b.ctx, M * Hk, t + 1));
   const void* ctx = b.ctx;   // what the attention-output GEMM reads: the context, or its gated copy
-  if (d->head_gate) {
+  if (d->head_gate && !pl) {   // (pruned: the gate is folded into Wo')
     void* gated = b.gctx ? b.gctx : b.ctx;
     RUN(nbest_head_gate_fwd(b.ctx, H, gated, H, d->head_gate + (int64_t)l * d->heads, M, d->heads, 64, dt, stream));
     ctx = gated;
   }
   // attention output projection + dropout + residual, then LayerNorm
-  GemmOp wo = {ctx, b.ctx8, t + 1, o.wo, t + 1, b.r1, H, H, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo)};
+  GemmOp wo = {ctx, b.ctx8, t + 1, o.wo, t + 1, b.r1, H, Hk, NBEST_EPI_BIAS_DROP_RES, P.P(o.bo)};
   wo.R = xin; wo.drop_p = d->hidden_drop; wo.drop_stream = s0 + 1;
+  if (pl) { wo.Wm = pl->wo; wo.Wm_packed = pl->wo_packed; }
   RUN(layer_gemm(c.g, wo));
   RUN(nbest_internal_layernorm_fwd8(b.r1, P.P(o.ln1_g), P.P(o.ln1_b), b.x1, b.x18, b.st1, M, H, d->ln_eps, dt, stream, c.AP(t + 2), c.AN(t + 2)));
   RUN(c.calib(b.x1, M * H, t + 2));
@@ -1156,6 +1170,8 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
 //   hact [M][F] T | lse [B heads S] f32 | st1 | st2 [M][2] f32.   Last layer: Q -> ctx, context -> r1, x1 -> x1, gelu -> hact,
 //   attention-out and FFN-down sums -> r2.  Independent of L.  Head gates (desc.head_gate) are applied in place, on ctx [M][H] of
 //   layers 0 .. L-2 and on the [B][H] CLS context of the last layer.
+//   Compact pruned heads (nbest_encoder_infer_pruned): layer l keeps k heads - qkv [M][3 64k], ctx [M][64k] (last layer: K|V [M][2 64k],
+//   Q and context [B][64k]) in the same buffers; no gate launch, the gate is in the compact attention-output matrix.
 namespace {
 struct InferLayout {
   size_t X0, X1, emb_stats, qkv, ctx, r1, x1, r2, hact, lse, st1, st2, total;
@@ -1183,10 +1199,12 @@ static LayerBufs infer_layer(const InferLayout& w, void* ws) {
 extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(sizes(d)).total : 0; }
 
 // cls_attn != NULL: also the CLS row's attention probabilities of every layer, [L][B][heads][S] fp32, each launched right after the
-// layer's QKV projection (last layer: after the CLS-row Q)
-extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
-                                        const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
-                                        float* cls_attn, nbest_stream_t stream) {
+// layer's QKV projection (last layer: after the CLS-row Q).
+// pr != NULL (nbest_encoder_infer_pruned): layer l keeps k = pr->layers_host[l].k heads and reads Wqkv', bqkv' and Wo' out of the compact
+// images (head_prune.hip) - every compact tensor fits the buffer of its full-width counterpart, so the workspace is the same.
+static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                      const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, float* cls_attn,
+                      const nbest_head_prune_images* pr, nbest_stream_t stream) {
   RUN(check_desc(d, false));
   NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
            "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
@@ -1198,6 +1216,20 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   const Sizes z = sizes(d);
   const InferLayout w = infer_layout(z);
   NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes, w.total);
+  if (pr) {
+    NB_CHECK(pr->w && pr->bqkv && pr->layers_host, NBEST_ERR_ARG, "encoder_infer_pruned: null image pointer");
+    NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder_infer_pruned: desc.head_gate must be NULL (the gate is folded into the compact Wo')");
+    NB_CHECK(((uintptr_t)pr->w & 15) == 0 && ((uintptr_t)pr->w_packed & 15) == 0 && ((uintptr_t)pr->bqkv & 15) == 0, NBEST_ERR_ALIGN,
+             "encoder_infer_pruned: the images must be 16-byte aligned");
+    for (int l = 0; l < d->L; ++l) {
+      const nbest_head_prune_layer& t = pr->layers_host[l];
+      NB_CHECK(t.k >= 1 && t.k <= d->heads, NBEST_ERR_ARG, "encoder_infer_pruned: layer %d keeps %d heads (1 .. %d)", l, t.k, d->heads);
+      NB_CHECK(d->dtype != NBEST_BF16 || t.k % 2 == 0, NBEST_ERR_SHAPE, "encoder_infer_pruned(bf16): layer %d keeps %d heads - the bf16 "
+               "GEMM tiles need an even count (N = 64 k a multiple of 128); carry a head whose gate is 0", l, t.k);
+      NB_CHECK(t.dst_wqkv >= 0 && t.dst_wo >= 0 && t.dst_bqkv >= 0 && t.dst_wqkv % 8 == 0 && t.dst_wo % 8 == 0 && t.dst_bqkv % 4 == 0,
+               NBEST_ERR_ALIGN, "encoder_infer_pruned: layer %d: image offsets must be non-negative multiples of 16 bytes", l);
+    }
+  }
   const Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
   const Ptrs& P = c.g.W;
   char* W = (char*)ws;
@@ -1210,22 +1242,39 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g), P.P(d->off_emb_ln_b),
                          X[0], (float*)(W + w.emb_stats), M, H, d->ln_eps, dt, d->hidden_drop, d->seed, d->drop_stream_base,
                          (hipStream_t)stream));
-  for (int l = 0; l + 1 < d->L; ++l) RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, probs(l)));
+  // the compact matrices of layer l (pr != NULL); the packed image serves the full-width GEMMs of layers 0 .. L-2 only
+  auto pruned = [&](int l) {
+    const nbest_head_prune_layer& t = pr->layers_host[l];
+    const char *wb = (const char*)pr->w, *pb = (const char*)pr->w_packed;
+    return PrunedLayer{t.k, wb + t.dst_wqkv * z.esz, pb ? pb + t.dst_wqkv * z.esz : nullptr, wb + t.dst_wo * z.esz,
+                       pb ? pb + t.dst_wo * z.esz : nullptr, pr->bqkv + t.dst_bqkv};
+  };
+  for (int l = 0; l + 1 < d->L; ++l) {
+    if (pr) {
+      const PrunedLayer pl = pruned(l);
+      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, nullptr, &pl));
+    } else {
+      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, probs(l)));
+    }
+  }
   // last layer, CLS rows only (weights read unpacked: the packed images are laid out for the full-width GEMMs)
   const int l = d->L - 1;
   const nbest_layer_offsets& o = d->layers_host[l];
   const void* xin = X[l & 1];
   void* kv = b.qkv; void* q = b.ctx; void* cctx = b.r1; void* cx1 = b.x1; void* ch = b.hact; void* cr = b.r2;
-  nbest_gemm_args g = gemm_nt(dt, xin, P.W(o.wqkv + (int64_t)H * H), kv, M, 2 * H, H);   // K | V, all rows
-  g.epilogue = NBEST_EPI_BIAS; g.bias = P.P(o.bqkv + H);
+  // pruned: Wqkv' [3 Hk][H] (Q rows, then K | V rows), bqkv', Wo' [H][Hk] and heads = k; Hk = H otherwise
+  const PrunedLayer pl = pr ? pruned(l) : PrunedLayer{d->heads, P.W(o.wqkv), nullptr, P.W(o.wo), nullptr, P.P(o.bqkv)};
+  const int heads = pl.k, Hk = 64 * heads;
+  nbest_gemm_args g = gemm_nt(dt, xin, (const char*)pl.wqkv + (size_t)Hk * H * z.esz, kv, M, 2 * Hk, H);   // K | V, all rows
+  g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv + Hk;
   RUN(nbest_gemm(&g, stream));
-  g = gemm_nt(dt, xin, P.W(o.wqkv), q, B, H, H);                                          // Q, CLS rows (lda = S H)
-  g.lda = SH; g.epilogue = NBEST_EPI_BIAS; g.bias = P.P(o.bqkv);
+  g = gemm_nt(dt, xin, pl.wqkv, q, B, Hk, H);                                             // Q, CLS rows (lda = S H)
+  g.lda = SH; g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv;
   RUN(nbest_gemm(&g, stream));
   if (cls_attn) RUN(nbest_internal_attention_cls_probs(q, H, kv, 2 * H, key_mask, probs(l), d->S, d->B, d->S, d->heads, 64, dt, stream));
-  RUN(nbest_attention_cls_fwd_internal(q, H, kv, 2 * H, key_mask, cctx, H, d->B, d->S, d->heads, 64, dt, stream, 0.f, 0, 0));
+  RUN(nbest_attention_cls_fwd_internal(q, Hk, kv, 2 * Hk, key_mask, cctx, Hk, d->B, d->S, heads, 64, dt, stream, 0.f, 0, 0));
   if (d->head_gate) RUN(nbest_head_gate_fwd(cctx, H, cctx, H, d->head_gate + (int64_t)l * d->heads, B, d->heads, 64, dt, stream));
-  g = gemm_nt(dt, cctx, P.W(o.wo), cr, B, H, H);
+  g = gemm_nt(dt, cctx, pl.wo, cr, B, H, Hk);
   g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.bias = P.P(o.bo); g.R = xin; g.ldr = SH;        // residual: the CLS rows
   RUN(nbest_gemm(&g, stream));
   RUN(nbest_internal_layernorm_fwd8(cr, P.P(o.ln1_g), P.P(o.ln1_b), cx1, nullptr, b.st1, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
@@ -1237,6 +1286,19 @@ extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void*
   RUN(nbest_gemm(&g, stream));
   RUN(nbest_internal_layernorm_fwd8(cr, P.P(o.ln2_g), P.P(o.ln2_b), cls_out, nullptr, b.st2, B, H, d->ln_eps, dt, stream, nullptr, nullptr));
   return NBEST_OK;
+}
+
+extern "C" int nbest_encoder_infer_attn(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                        const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                        float* cls_attn, nbest_stream_t stream) {
+  return infer_impl(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, cls_attn, nullptr, stream);
+}
+
+extern "C" int nbest_encoder_infer_pruned(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids,
+                                          const int64_t* seg, const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes,
+                                          void* cls_out, const nbest_head_prune_images* images, nbest_stream_t stream) {
+  NB_CHECK(images, NBEST_ERR_ARG, "encoder_infer_pruned: null images");
+  return infer_impl(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, images, stream);
 }
 
 extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,

@@ -29,6 +29,7 @@ EXPORTS = [
     "nbest_attention_probs", "nbest_attention_cls_probs", "nbest_encoder_act_view", "nbest_encoder_infer_attn",
     "nbest_embed_ln_fwd_interp", "nbest_embed_attrib",
     "nbest_head_gate_fwd", "nbest_head_gate_bwd",
+    "nbest_head_prune_plan", "nbest_head_prune_pack", "nbest_encoder_infer_pruned",
     "nbest_embed_ln_fwd_adv", "nbest_embed_ln_bwd_adv", "nbest_embed_adv_ws_bytes", "nbest_embed_adv_delta",
     "nbest_layernorm_fwd_fp8", "nbest_layernorm_bwd_fp8", "nbest_attention_fwd_fp8", "nbest_attention_bwd_fp8", "nbest_cast_bf16_to_fp8_scaled", "nbest_amax_bf16",
     "nbest_gemm_fp8_plan", "nbest_wgrad_fp8_plan",
@@ -80,6 +81,20 @@ class TensorDesc(C.Structure):
 
 class MatrixDesc(C.Structure):
     _fields_ = [("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("tile_start", C.c_int32), ("pad", C.c_int32)]
+
+
+HEAD_PRUNE_MAX_HEADS = 32      # include/nbest_hip.h NBEST_HEAD_PRUNE_MAX_HEADS
+
+
+class HeadPruneLayer(C.Structure):
+    """nbest_head_prune_layer: a layer's row of the compact-heads table (element offsets in the arenas / in the images, k, idx)"""
+    _fields_ = [("src_wqkv", C.c_int64), ("src_bqkv", C.c_int64), ("src_wo", C.c_int64),
+                ("dst_wqkv", C.c_int64), ("dst_bqkv", C.c_int64), ("dst_wo", C.c_int64),
+                ("k", C.c_int32), ("pad", C.c_int32), ("idx", C.c_int32 * HEAD_PRUNE_MAX_HEADS)]
+
+
+class HeadPruneImages(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("w_packed", C.c_void_p), ("bqkv", C.c_void_p), ("layers_host", C.POINTER(HeadPruneLayer))]
 
 
 class LayerOffsets(C.Structure):
@@ -195,6 +210,9 @@ def lib():
         L.nbest_encoder_infer.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp]
         L.nbest_attention_cls_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
         L.nbest_encoder_infer_attn.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp, vp]
+        L.nbest_head_prune_plan.argtypes = [C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(HeadPruneLayer)] + [C.POINTER(C.c_size_t)] * 3
+        L.nbest_head_prune_pack.argtypes = [vp, vp, vp, C.POINTER(HeadPruneLayer), vp, i32, i32, i32, vp, sz, vp, sz, vp]
+        L.nbest_encoder_infer_pruned.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, C.POINTER(HeadPruneImages), vp]
         L.nbest_encoder_act_view.argtypes = [C.POINTER(EncoderDesc), vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.nbest_attention_probs.argtypes = [vp] * 4 + [i32] * 5 + [vp]
         L.nbest_attention_cls_probs.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
@@ -741,6 +759,43 @@ def encoder_act_view(desc, act, layer):
     q, l = C.c_void_p(), C.c_void_p()
     check(lib().nbest_encoder_act_view(C.byref(desc), ptr(act), layer, C.byref(q), C.byref(l)), "encoder_act_view")
     return q.value, l.value
+
+
+def head_prune_plan(kept, heads, dtype, layer_offsets=None):
+    """nbest_head_prune_plan for the kept head indices ``kept`` (one ascending list per layer): the table (HeadPruneLayer array with
+    k, idx and the image offsets; the arena offsets too when ``layer_offsets`` - the arena's LayerOffsets - is given) and the byte
+    sizes (Wqkv' section, Wo' section, bias image).  Host arithmetic: no GPU needed."""
+    L = len(kept)
+    tab = (HeadPruneLayer * L)()
+    ks = (C.c_int32 * L)(*[len(ix) for ix in kept])
+    sizes = [C.c_size_t() for _ in range(3)]
+    check(lib().nbest_head_prune_plan(ks, L, heads, dtype_code(dtype), tab, *[C.byref(x) for x in sizes]), "head_prune_plan")
+    for l, ix in enumerate(kept):
+        for i, h in enumerate(ix):
+            tab[l].idx[i] = int(h)
+        if layer_offsets is not None:
+            o = layer_offsets[l]
+            tab[l].src_wqkv, tab[l].src_bqkv, tab[l].src_wo = o.wqkv, o.bqkv, o.wo
+    return tab, tuple(x.value for x in sizes)
+
+
+def head_prune_pack(wts, prm, gate, tab, heads, w_out, b_out, tab_dev=None):
+    """nbest_head_prune_pack: gather the compact images of table ``tab`` (head_prune_plan, arena offsets filled) out of ``wts`` /
+    ``prm`` under ``gate`` fp32 [L, heads] into ``w_out`` (the dtype of wts) and ``b_out`` (fp32), one launch.  ``tab_dev``: the
+    device copy of the table (uploaded here when None); returned."""
+    if tab_dev is None:
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(wts.device)
+    check(lib().nbest_head_prune_pack(ptr(wts), ptr(prm), ptr(gate), tab, ptr(tab_dev), len(tab), heads, dtype_code(wts.dtype),
+                                      ptr(w_out), w_out.numel() * w_out.element_size(), ptr(b_out),
+                                      b_out.numel() * b_out.element_size(), stream_ptr()), "head_prune_pack")
+    return tab_dev
+
+
+def encoder_infer_pruned(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, tab, w, w_packed, bqkv):
+    """nbest_encoder_infer_pruned -> cls_out [B, H] on the compact images ``w`` / ``w_packed`` (or None) / ``bqkv`` of table ``tab``"""
+    im = HeadPruneImages(w.data_ptr(), None if w_packed is None else w_packed.data_ptr(), bqkv.data_ptr(), tab)
+    check(lib().nbest_encoder_infer_pruned(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
+                                           ws.numel(), ptr(cls_out), C.byref(im), stream_ptr()), "encoder_infer_pruned")
 
 
 def encoder_infer(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, cls_attn=None):

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import hipabi as hb
+from . import prune
 from .arena import ParamArena
 from .config import EncoderConfig, LabelSpace, NAMED
 
@@ -283,6 +284,51 @@ def _check_contrast(contrast, B, trans_input_ids=None, adv=None, device=None):
     return dict(weight=vals["weight"], temperature=vals["temperature"], keys=keys)
 
 
+class _CompactHeads:
+    """What ``predict`` under ``set_head_mask(mask, compact=True)`` runs on: the kept head indices (host; one copy of the mask off
+    the device), the table of nbest_head_prune_plan on the host and the device, the image buffers, and - bf16 - the descriptors
+    nbest_pack_weights packs the Wqkv' and Wo' of layers 0 .. L-2 by (the last layer is read unpacked).  The images themselves are
+    rebuilt by every ``build``: there is no weights version to key a cache on."""
+
+    def __init__(self, model, mask):
+        cfg, dev = model.cfg, model.device
+        H, heads = cfg.hidden_size, cfg.num_attention_heads
+        bf16 = model.compute_dtype == torch.bfloat16
+        self.kept = prune.kept_heads(mask, even=bf16)
+        self.tab, (qb, ob, bb) = hb.head_prune_plan(self.kept, heads, model.compute_dtype, model.arena.layer_offsets)
+        self.tab_dev = torch.frombuffer(bytearray(bytes(self.tab)), dtype=torch.uint8).to(dev)
+        esz = 2 if bf16 else 4
+        self.w = torch.empty((qb + ob) // esz, dtype=model.compute_dtype, device=dev)
+        self.b = torch.empty(bb // 4, dtype=torch.float32, device=dev)
+        self.wp = self.pdescs = None
+        if bf16 and len(self.kept) > 1:
+            mats = []
+            for t in list(self.tab)[:-1]:
+                mats += [(t.dst_wqkv, 3 * 64 * t.k, H), (t.dst_wo, H, 64 * t.k)]
+            arr = (hb.MatrixDesc * len(mats))()
+            n_st = 0
+            for i, (off, n, k) in enumerate(mats):
+                bn = hb.lib().nbest_pack_bn(n)
+                if not (bn > 0 and k % 32 == 0 and n % bn == 0):      # all or nothing, as the arena's own packed copies
+                    arr = None
+                    break
+                arr[i].offset, arr[i].rows, arr[i].cols, arr[i].tile_start, arr[i].pad = off, n, k, n_st, bn
+                n_st += (n // bn) * (k // 32)
+            if arr is not None:
+                self.pdescs = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(mats), n_st)
+                self.wp = torch.empty_like(self.w)
+
+    def build(self, model, packed):
+        """gather the images from the model's current weights (and pack them: ``packed``, bf16); returns the packed image or None"""
+        a = model.arena
+        hb.head_prune_pack(a.weights, a.p, model.head_mask, self.tab, model.cfg.num_attention_heads, self.w, self.b, self.tab_dev)
+        if not (packed and self.pdescs is not None):
+            return None
+        pd, pn, pt = self.pdescs
+        hb.check(hb.lib().nbest_pack_weights(hb.ptr(self.w), hb.ptr(self.wp), hb.ptr(pd), pn, pt, hb.stream_ptr()), "pack_weights")
+        return self.wp
+
+
 def _require_trainable(plan):
     if plan is not None and not plan.trainable:
         raise RuntimeError("nbest_amd: no parameter requires grad: a backward has nothing to compute (every tensor of the model "
@@ -424,7 +470,14 @@ class NBestSTCModel(nn.Module):
         """True while the mask in force was installed with ``set_head_mask(mask, trainable=True)``"""
         return self._head_mask_trainable
 
-    def set_head_mask(self, mask, trainable=False):
+    _head_mask_compact = False             # set_head_mask(compact=True): predict runs only the kept heads (nbest_encoder_infer_pruned)
+    _prune = None                          # ... and what it runs them on: _CompactHeads (table, image buffers, pack descriptors)
+    @property
+    def head_mask_compact(self):
+        """True while the mask in force was installed with ``set_head_mask(mask, compact=True)``"""
+        return self._head_mask_compact
+
+    def set_head_mask(self, mask, trainable=False, compact=False):
         """Gate the attention heads, as ``BertModel.forward(head_mask=)``: ``mask`` [L, heads] of any floats (0 prunes head h of
         layer l, 1 is the identity) multiplies each head's attention context after dropout and P.V, before the attention-output
         projection; None removes it.  Held on the device, not part of ``state_dict``.  While set it applies to the eval / no_grad
@@ -441,18 +494,37 @@ class NBestSTCModel(nn.Module):
         (the transcript pass runs under the same mask), ``distill=`` and ``rdrop=`` (they change the heads call and the batch only)
         and the top layer on the CLS rows (``cls_top``) work as without a mask.  Still refused: the autograd-bridge forward, an
         fp8w model, ``adv=``, and data parallelism (``train_step``).  ``head_gate_grad``, ``attribute`` and ``predict`` run their own
-        descriptors as before."""
+        descriptors as before.
+        ``compact=True`` (needs a mask, refuses ``trainable=True``): ``predict`` runs only the heads the mask keeps (gate != 0) -
+        per layer a [3 64k, H] QKV matrix, a k-head attention and an [H, 64k] output matrix with the gate folded into its columns
+        (nbest_head_prune_pack, nbest_encoder_infer_pruned); no gate launch.  The kept indices are computed on the host here, at set
+        time: ONE device-to-host copy of the [L, heads] mask; nothing else synchronises.  The compact images are rebuilt from the
+        current weights at every ``predict`` call (one gather, plus one pack of the bf16 images).  In bf16 a layer with an odd
+        number of kept heads also runs its lowest-numbered pruned head, whose output columns are zeros (the bf16 GEMM tiles need
+        64 k to be a multiple of 128).  ``predict(return_attns=True)`` raises ValueError while it is set (the CLS maps are indexed by
+        original head).  Everything else that honours a mask - the eval ``forward``, ``forward_backward(need_grad=False)``,
+        ``attribute``, ``head_gate_grad`` - keeps running the gated full-width path under the same mask."""
         if mask is None:
             if trainable:
                 raise ValueError("nbest_amd set_head_mask: trainable=True needs a mask (got None)")
+            if compact:
+                raise ValueError("nbest_amd set_head_mask: compact=True needs a mask (got None)")
             self._head_mask, self._head_mask_trainable = None, False
+            self._head_mask_compact, self._prune = False, None
             return
+        if compact and trainable:
+            raise ValueError("nbest_amd set_head_mask: compact=True with trainable=True: training with compacted heads is not built")
         L, heads = self.cfg.num_hidden_layers, self.cfg.num_attention_heads
         m = torch.as_tensor(mask)
         if tuple(m.shape) != (L, heads):
             raise ValueError("nbest_amd set_head_mask: the mask must be [L=%d, heads=%d] (got %s)" % (L, heads, list(m.shape)))
-        self._head_mask = m.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        if compact and heads > hb.HEAD_PRUNE_MAX_HEADS:
+            raise ValueError("nbest_amd set_head_mask: compact=True supports at most %d heads (got %d)" % (hb.HEAD_PRUNE_MAX_HEADS, heads))
+        m = m.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        ch = _CompactHeads(self, m) if compact else None             # (raises before anything of the model changes)
+        self._head_mask = m
         self._head_mask_trainable = bool(trainable)
+        self._head_mask_compact, self._prune = bool(compact), ch
 
     def _refuse_training_under_mask(self, what, bridge=False):
         if self._head_mask is None:
@@ -914,8 +986,14 @@ class NBestSTCModel(nn.Module):
         classifier, then the softmax heads in head order), from nbest_stc_heads_logits on the same CLS rows: one launch after the
         heads call, which is unchanged; without the flag nothing new is enqueued.
         Touches no training state: stashes, gradients, optimizer moments, step_counter and the fp8 amax histories stay as they
-        are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it)."""
+        are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it).
+        Under ``set_head_mask(mask, compact=True)``: the compact images are gathered from the current weights (and packed, where
+        the packed bf16 copies are in use), then nbest_encoder_infer_pruned runs only the kept heads; ``return_attns`` raises
+        ValueError."""
         cfg = self.cfg
+        if return_attns and self._head_mask_compact:
+            raise ValueError("nbest_amd predict: return_attns under a compact head mask is not built (the CLS maps are indexed by "
+                             "original head); set the mask without compact=True")
         B, S = input_ids.shape
         H = cfg.hidden_size
         first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
@@ -932,7 +1010,12 @@ class NBestSTCModel(nn.Module):
         cls = torch.empty(B, H, dtype=self.compute_dtype, device=self.device)
         cls_attn = torch.empty(cfg.num_hidden_layers, B, cfg.num_attention_heads, S, dtype=torch.float32,
                                device=self.device) if return_attns else None
-        hb.encoder_infer(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, cls_attn)
+        if self._head_mask_compact:
+            d.head_gate = None                                # the gate lives in the compact Wo'
+            pk = self._prune.build(self, packed=d.wpk is not None)
+            hb.encoder_infer_pruned(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, self._prune.tab, self._prune.w, pk, self._prune.b)
+        else:
+            hb.encoder_infer(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, cls_attn)
         Wh, bh = a.heads_wb()
         labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
         top, bott, fin, _, _, _, _ = hb.stc_heads(cls, H, Wh, bh, self.dls, labels_f, B, H, need_grad=False, drop_p=0.0)
