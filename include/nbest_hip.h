@@ -158,7 +158,8 @@ enum {
   NBEST_EPI_BIAS_DROP_RES = 3, /* C = drop(acc + bias[n]) + R[m,n]                           */
   NBEST_EPI_DGELU = 4,         /* C = acc * U[m,n]   (U = gelu'(u) saved by BIAS_GELU, see U) */
   NBEST_EPI_RES = 5,           /* C = acc + R[m,n]                                           */
-  NBEST_EPI_F32_SPLITK = 6     /* Cf32[N x ...] = sum over K-splits (weight gradient), fp32  */
+  NBEST_EPI_F32_SPLITK = 6,    /* Cf32[N x ...] = sum over K-splits (weight gradient), fp32  */
+  NBEST_EPI_BIAS_GELU_Q8 = 7   /* nbest_gemm_fp8 only: C8 = e4m3(gelu_erf(acc + bias[n]) * s_c), nothing else (inference) */
 };
 typedef struct nbest_gemm_args {
   const void* A;
@@ -261,7 +262,11 @@ int nbest_wgrad_window(const nbest_gemm_args* problems, const int32_t* tile_firs
  * weight gradients have their own entry point (nbest_wgrad_fp8 below).  Forward epilogues: NBEST_EPI_BIAS, NBEST_EPI_BIAS_GELU
  * (writes C = gelu bf16, U = gelu' 8-bit, C8 = e4m3 copy of gelu for the next GEMM), NBEST_EPI_BIAS_DROP_RES; dgrad epilogues
  * (B = the TRANSPOSED e4m3 weight copy, A = e4m3 gradient copy): NBEST_EPI_NONE, NBEST_EPI_RES, NBEST_EPI_DGELU.
- * N % 256 == 0, K % 64 == 0.  C may be NULL for BIAS_GELU / DGELU when C8 is given (every reader takes the e4m3 copy).          */
+ * N % 256 == 0, K % 64 == 0.  C may be NULL for BIAS_GELU / DGELU when C8 is given (every reader takes the e4m3 copy).
+ * NBEST_EPI_BIAS_GELU_Q8 (forward without a backward: the inference FFN-up): C8[m][n] = e4m3(gelu(acc * out_scale / s_a + bias[n]) * s_c)
+ * and nothing else - no gelu' arithmetic, no U rows, no bf16 C, no amax record.  The value that is rounded is the fp32 gelu BIAS_GELU
+ * rounds, so the C8 bytes are those BIAS_GELU writes for the same inputs; same plan (nbest_gemm_fp8_plan) as BIAS_GELU for the same
+ * shape.  Refused (NBEST_ERR_ARG, nothing enqueued): C8 == NULL, bias == NULL, a non-NULL C, U or c8_amax_new.                   */
 typedef struct nbest_gemm_fp8_args {
   const void* A;      /* e4m3 [M][lda] */
   const void* B;      /* e4m3 [N][ldb] (the weight matrix as stored, [out][in]) */
@@ -703,6 +708,10 @@ typedef struct nbest_matrix_desc {
  * slots: uint32 [n_tensors][NBEST_AMAX_TENSOR_WORDS], zero-initialised by the caller once. */
 #define NBEST_AMAX_TENSOR_WORDS 1024
 int nbest_fp8_amax_fold(void* slots, void* out, int32_t n_tensors, nbest_stream_t stream);
+/* nbest_fp8_amax_fold that RAISES instead of overwriting: out[t] = max(out[t], max over the 16 slot words of tensor t), the slots
+ * zeroed.  Float bits are compared as unsigned integers (non-negative floats order like their bits).  What lets a calibration run
+ * over several batches: the history of the fp8 inference (nbest_encoder_infer_fp8) is folded with it.                         */
+int nbest_fp8_amax_fold_max(void* slots, void* out, int32_t n_tensors, nbest_stream_t stream);
 /* The fp8 PRODUCERS on their own: the kernels that write, next to their bf16 output, the e4m3 copy a later fp8 GEMM reads, and record
  * the amax the next pass scales by.  nbest_encoder_forward / _backward are their only other callers; these entries forward their
  * arguments to the same internal functions (no kernel and no dispatch of their own) so that the contract below can be tested
@@ -1009,6 +1018,25 @@ typedef struct nbest_head_prune_images {
 int nbest_encoder_infer_pruned(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                                const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
                                const nbest_head_prune_images* images, nbest_stream_t stream);
+
+/* nbest_encoder_infer for a model with the fp8 forward (desc.w8): same arguments, same cls_out [B][H] bf16.  The descriptor's fp8
+ * fields mean what they mean for nbest_encoder_forward, and two kinds of pass follow from them:
+ *   calibration pass (w8, w8_inv_scale, aamax_new set, fp8_act == 0): the launches of nbest_encoder_infer (cls_out has the same bits)
+ *     plus the nbest_amax_bf16 launches that record the GEMM inputs into their slot blocks of aamax_new: layers 0 .. L-2 record
+ *     x, ctx, x1, gelu(u) at index 4 l + {0, 1, 2, 3}, layer L-1 records x only, at 4 (L-1).  The caller folds the slots
+ *     (nbest_fp8_amax_fold_max over several batches) into the history the fp8 pass reads.
+ *   fp8 pass (fp8_act != 0, aamax_prev set): layers 0 .. L-2 run their four GEMMs on the block-scaled fp8 MFMA, on e4m3 copies in four
+ *     regions at the end of the workspace; FFN-up is NBEST_EPI_BIAS_GELU_Q8 (no bf16 gelu(u), no gelu' rows).  The scales are STATIC:
+ *     every producer scales by aamax_prev and records nothing (aamax_new is not read, no atomics).  Last layer: the K|V projection
+ *     over all M rows is an fp8 GEMM on the e4m3 copy of the layer input; the B CLS rows stay bf16.  L = 1 works.
+ *     A value beyond twice the calibrated amax saturates silently in the e4m3 cast (the scale is 2^floor(log2(224 / amax))).
+ * ws >= nbest_encoder_infer_fp8_ws_bytes(d) = nbest_encoder_infer_ws_bytes(d) + the four e4m3 regions (>= M (3 H + F) bytes;
+ * independent of L, the same for both passes).  Refuses, before the first launch: non-zero dropout, a dtype other than bf16, the shapes
+ * the fp8 forward refuses, no w8 / w8_inv_scale, fp8_act != 0 without aamax_prev, fp8_act == 0 without aamax_new, head_gate,
+ * base_ids / alpha, emb_delta (NBEST_ERR_ARG / _DTYPE / _SHAPE) and a short workspace (NBEST_ERR_WORKSPACE).                        */
+size_t nbest_encoder_infer_fp8_ws_bytes(const nbest_encoder_desc* d);
+int nbest_encoder_infer_fp8(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                            const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, nbest_stream_t stream);
 
 #ifdef __cplusplus
 }

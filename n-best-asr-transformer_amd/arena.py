@@ -111,6 +111,7 @@ class ParamArena:
         self.lazy_w16t = False      # set by the model while its backward runs in fp8: the bf16 transposed copy has no reader then
         self.w16t_stale = False
         self.w8 = self.w8t = self.w8_inv_scale = self._w8_ws = self.gamax = self.aamax = self.gamax_slots = self.aamax_slots = None
+        self.iamax = self.iamax_slots = None
         self._tdescs = None
         self.wpk = self.wpkt = None     # packed copies for the bf16 GEMMs (dropped when the fp8 mode is enabled: its GEMMs read w8 / w8t)
         self.w8p = self.w8tp = None
@@ -221,6 +222,10 @@ class ParamArena:
             # ... and the ACTIVATION amax history of the fp8 forward (x, ctx, x1, gelu(u) per layer), folded after every step
             self.aamax = torch.zeros(n, dtype=torch.int32, device=self.device)
             self.aamax_slots = torch.zeros(n * hb.AMAX_TENSOR_WORDS, dtype=torch.int32, device=self.device)
+            # ... and the history of the fp8 INFERENCE (predict(fp8=True)): recorded by an explicit calibration (fp8_calibrate, folded with
+            # nbest_fp8_amax_fold_max) and then held fixed; separate from aamax, which belongs to the training steps
+            self.iamax = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.iamax_slots = torch.zeros(n * hb.AMAX_TENSOR_WORDS, dtype=torch.int32, device=self.device)
             self.w8_inv_scale = torch.ones(n, dtype=torch.float32, device=self.device)
             self._w8_ws = torch.zeros(4 * n + 16, dtype=torch.uint8, device=self.device)
             # w8 / w8t packed for gemm8_kernel's tiles (nbest_pack_weights_fp8), as wpk / wpkt for the bf16 kernels

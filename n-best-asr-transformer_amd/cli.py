@@ -83,6 +83,13 @@ def parse_arguments(argv=None):
                         "token and each segment (cls, sys, h1, h2, ..)")
     g.add_argument("--attribution_steps", type=int, default=32, metavar="M",
                    help="--predict_attribution: path points of the integrated-gradients midpoint rule (>= 1)")
+    g.add_argument("--predict_fp8", action="store_true",
+                   help="with --predict FILE --dtype fp8w: label the file with the fp8 inference (model.predict(fp8=True)) - the "
+                        "full-width GEMMs on the fp8 MFMA with static activation scales calibrated on the first --fp8_calib_batches "
+                        "batches of FILE.  A value beyond twice the calibrated amax saturates silently.  Not with --head_mask, "
+                        "--compact_heads, --predict_attention or --predict_attribution")
+    g.add_argument("--fp8_calib_batches", type=int, default=8, metavar="N",
+                   help="--predict_fp8: batches of FILE the activation scales are calibrated on (>= 1; default 8)")
     g.add_argument("--head_mask", default=None, metavar="FILE",
                    help="gate the attention heads (HF's head_mask) for --testing, --predict and --head_importance: a JSON list of L rows "
                         "of `heads` numbers, 0 = head pruned, 1 = kept (any float scales the head's output).  Not for a training run")
@@ -312,6 +319,21 @@ def parse_arguments(argv=None):
         ap.error("--predict_attribution is an output of --predict: pass --predict FILE too")
     if opt.attribution_steps < 1:
         ap.error("--attribution_steps must be >= 1 (got %d)" % opt.attribution_steps)
+    if opt.fp8_calib_batches < 1:
+        ap.error("--fp8_calib_batches must be >= 1 (got %d)" % opt.fp8_calib_batches)
+    if opt.predict_fp8:
+        if opt.predict is None:
+            ap.error("--predict_fp8 is a mode of --predict: pass --predict FILE too")
+        if opt.dtype != "fp8w":
+            ap.error("--predict_fp8 needs a model with the fp8 forward: pass --dtype fp8w (got --dtype %s)" % opt.dtype)
+        if opt.compact_heads:
+            ap.error("--predict_fp8 together with --compact_heads is not built (compact heads in fp8)")
+        if opt.head_mask is not None:
+            ap.error("--predict_fp8 together with --head_mask is not built (the fp8 forward has no gated context)")
+        if opt.predict_attention is not None:
+            ap.error("--predict_fp8 together with --predict_attention is not built (the CLS attention maps in fp8)")
+        if opt.predict_attribution is not None:
+            ap.error("--predict_fp8 together with --predict_attribution is not built (the attribution runs the stash forward)")
     if opt.predict is not None:
         if not os.path.isfile(opt.predict):
             ap.error("--predict %s: no such file" % opt.predict)
@@ -586,7 +608,7 @@ def main(argv=None):
         attr_fp = open(opt.predict_attribution, "w") if opt.predict_attribution else None
         try:
             cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp, attr_fp=attr_fp,
-                                          attr_steps=opt.attribution_steps)
+                                          attr_steps=opt.attribution_steps, fp8=opt.predict_fp8, calib_batches=opt.fp8_calib_batches)
         finally:
             for fp in (attn_fp, attr_fp):
                 if fp is not None:

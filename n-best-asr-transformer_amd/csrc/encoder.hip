@@ -524,6 +524,7 @@ struct Fwd {
   GemmPass g;   // g.fp8: the four GEMMs of a layer on the block-scaled fp8 MFMA, their A operands the e4m3 copies x8 | ctx8 | x18 | h8
   const uint8_t* key_mask;
   bool arec;    // record the activation amax of this pass (fp8, or the calibration pass: fp8 mode without an activation history)
+  bool q8;      // fp8 inference (nbest_encoder_infer_fp8): no backward follows, so FFN-up writes the e4m3 copy of gelu(u) and nothing else
   // delayed scale of activation idx = 4 l + {x, ctx, x1, gelu} and the slot block its producer records this pass's amax in (fp8 pass)
   const uint32_t* AP(int idx) const { return g.fp8 ? d->aamax_prev + idx : nullptr; }
   uint32_t* AN(int idx) const { return (g.fp8 && arec) ? d->aamax_new + (int64_t)idx * NBEST_AMAX_TENSOR_WORDS : nullptr; }
@@ -538,7 +539,7 @@ static Fwd make_fwd(const nbest_encoder_desc* d, const void* wts, const float* p
                     nbest_stream_t stream) {
   const GemmPass g = {d->dtype, z.M, stream, d->seed, Ptrs{(const char*)wts, prm, z.esz}, d->wpk, false, fp8_forward_active(d),
                       d->w8, d->w8p, d->w8_inv_scale, d->aamax_prev, d->aamax_new, nullptr, 0, 0};
-  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16};
+  return Fwd{d, g, key_mask, d->w8 && d->aamax_new && d->dtype == NBEST_BF16, false};
 }
 
 // Layer l over all M rows: xin -> xout through the buffers `b`.  x8_next: where the last LayerNorm leaves the e4m3 copy of xout for
@@ -587,7 +588,8 @@ static int layer_forward(const Fwd& c, int l, const void* xin, void* xout, const
   RUN(nbest_internal_layernorm_fwd8(b.r1, P.P(o.ln1_g), P.P(o.ln1_b), b.x1, b.x18, b.st1, M, H, d->ln_eps, dt, stream, c.AP(t + 2), c.AN(t + 2)));
   RUN(c.calib(b.x1, M * H, t + 2));
   // FFN up + bias + GELU (GELU' of the pre-activation kept for the backward; fp8: also gelu(u) in e4m3, scaled by its own amax)
-  GemmOp w1 = {b.x1, b.x18, t + 2, o.w1, t + 2, b.hact, F, H, NBEST_EPI_BIAS_GELU, P.P(o.b1)};
+  // (fp8 inference: NBEST_EPI_BIAS_GELU_Q8, the e4m3 copy alone - no bf16 gelu(u); b.u is NULL there)
+  GemmOp w1 = {b.x1, b.x18, t + 2, o.w1, t + 2, c.q8 ? nullptr : b.hact, F, H, c.q8 ? NBEST_EPI_BIAS_GELU_Q8 : NBEST_EPI_BIAS_GELU, P.P(o.b1)};
   w1.U = b.u; w1.C8 = b.h8; w1.c_idx = t + 3;
   RUN(layer_gemm(c.g, w1));
   // FFN down + dropout + residual, then LayerNorm
@@ -1172,49 +1174,69 @@ extern "C" int nbest_encoder_backward(const nbest_encoder_desc* d, const void* w
 //   layers 0 .. L-2 and on the [B][H] CLS context of the last layer.
 //   Compact pruned heads (nbest_encoder_infer_pruned): layer l keeps k heads - qkv [M][3 64k], ctx [M][64k] (last layer: K|V [M][2 64k],
 //   Q and context [B][64k]) in the same buffers; no gate launch, the gate is in the compact attention-output matrix.
+//   fp8 (nbest_encoder_infer_fp8): four regions more, at the end - x8 | ctx8 | x18 [M][H] e4m3, h8 [M][F] e4m3, the copies of a layer's
+//   four GEMM inputs.  The fp8 pass uses [B][F] of hact only (the full-width FFN-up writes h8), the calibration pass none of the four
+//   regions: one size for both.  Last layer: K|V is an fp8 GEMM on x8; the B CLS rows are bf16 as above.
 namespace {
 struct InferLayout {
-  size_t X0, X1, emb_stats, qkv, ctx, r1, x1, r2, hact, lse, st1, st2, total;
+  size_t X0, X1, emb_stats, qkv, ctx, r1, x1, r2, hact, lse, st1, st2;
+  size_t x8, ctx8, x18, h8;   // fp8 only (else 0 bytes)
+  size_t total;
 };
-static InferLayout infer_layout(const Sizes& z) {
+static InferLayout infer_layout(const Sizes& z, bool fp8 = false) {
   InferLayout w;
   size_t o = 0;
   w.X0 = take(o, z.MH); w.X1 = take(o, z.MH); w.emb_stats = take(o, z.st);
   w.qkv = take(o, z.M3H); w.ctx = take(o, z.MH); w.r1 = take(o, z.MH); w.x1 = take(o, z.MH); w.r2 = take(o, z.MH);
   w.hact = take(o, z.MF); w.lse = take(o, z.lse); w.st1 = take(o, z.st); w.st2 = take(o, z.st);
+  w.x8 = take(o, fp8 ? z.MH8 : 0); w.ctx8 = take(o, fp8 ? z.MH8 : 0); w.x18 = take(o, fp8 ? z.MH8 : 0); w.h8 = take(o, fp8 ? z.MF8 : 0);
   w.total = o;
   return w;
 }
-// every layer runs on the same buffers; nothing is kept for a backward (no GELU' rows, no keep words, no e4m3 copies)
-static LayerBufs infer_layer(const InferLayout& w, void* ws) {
+// every layer runs on the same buffers; nothing is kept for a backward (no GELU' rows, no keep words).  fp8_pass: the GEMMs read the
+// e4m3 copies, and gelu(u) of the full-width layers exists in e4m3 only (hact serves the last layer's B CLS rows)
+static LayerBufs infer_layer(const InferLayout& w, void* ws, bool fp8_pass) {
   char* W = (char*)ws;
   LayerBufs b = {};
   b.qkv = W + w.qkv; b.ctx = W + w.ctx; b.lse = (float*)(W + w.lse);
   b.r1 = W + w.r1; b.st1 = (float*)(W + w.st1); b.x1 = W + w.x1;
   b.hact = W + w.hact; b.r2 = W + w.r2; b.st2 = (float*)(W + w.st2);
+  if (fp8_pass) { b.x8 = (uint8_t*)(W + w.x8); b.ctx8 = (uint8_t*)(W + w.ctx8); b.x18 = (uint8_t*)(W + w.x18); b.h8 = (uint8_t*)(W + w.h8); }
   return b;
 }
 }  // namespace
 
 extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(sizes(d)).total : 0; }
+extern "C" size_t nbest_encoder_infer_fp8_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(sizes(d), true).total : 0; }
 
 // cls_attn != NULL: also the CLS row's attention probabilities of every layer, [L][B][heads][S] fp32, each launched right after the
 // layer's QKV projection (last layer: after the CLS-row Q).
 // pr != NULL (nbest_encoder_infer_pruned): layer l keeps k = pr->layers_host[l].k heads and reads Wqkv', bqkv' and Wo' out of the compact
 // images (head_prune.hip) - every compact tensor fits the buffer of its full-width counterpart, so the workspace is the same.
+// f8 (nbest_encoder_infer_fp8 only; no cls_attn, no pr): the descriptor carries the fp8 forward.  Without an activation history
+// (fp8_act == 0) the pass is the bf16 one plus the amax records of the GEMM inputs (Fwd::calib); with one, the full-width GEMMs run in
+// fp8 on static scales: nothing is recorded.
 static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                       const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, float* cls_attn,
-                      const nbest_head_prune_images* pr, nbest_stream_t stream) {
+                      const nbest_head_prune_images* pr, nbest_stream_t stream, bool f8 = false) {
+  if (f8) {
+    NB_CHECK(d, NBEST_ERR_ARG, "encoder_infer_fp8: null descriptor");
+    NB_CHECK(d->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "encoder_infer_fp8: needs the bf16 path (dtype %d)", d->dtype);
+    NB_CHECK(d->w8 && d->w8_inv_scale, NBEST_ERR_ARG, "encoder_infer_fp8: needs the e4m3 weights and their inverse scales (desc.w8, w8_inv_scale)");
+    NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder_infer_fp8: head gates (desc.head_gate) are not supported");
+    if (d->fp8_act) NB_CHECK(d->aamax_prev, NBEST_ERR_ARG, "encoder_infer_fp8: fp8_act without an activation history (desc.aamax_prev); calibrate first");
+    else NB_CHECK(d->aamax_new, NBEST_ERR_ARG, "encoder_infer_fp8: the calibration pass (fp8_act == 0) needs the slot blocks it records in (desc.aamax_new)");
+  }
   RUN(check_desc(d, false));
   NB_CHECK(d->hidden_drop == 0.f && d->attn_drop == 0.f, NBEST_ERR_ARG,
            "encoder_infer: dropout must be 0 (hidden_drop=%g, attn_drop=%g): inference has no dropout", d->hidden_drop, d->attn_drop);
-  NB_CHECK(!d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");
+  NB_CHECK(f8 || !d->w8, NBEST_ERR_ARG, "encoder_infer: the fp8 forward (desc.w8) is not supported; pass the bf16 weights without w8");
   NB_CHECK(!d->base_ids && !d->alpha, NBEST_ERR_ARG, "encoder_infer: interpolated embeddings (desc.base_ids / alpha) are not supported; "
                                                      "run nbest_encoder_forward");
   NB_CHECK(!d->emb_delta, NBEST_ERR_ARG, "encoder_infer: perturbed embeddings (desc.emb_delta) are not supported; run nbest_encoder_forward");
   NB_CHECK(wts && prm && ids && pos && key_mask && ws && cls_out, NBEST_ERR_ARG, "encoder_infer: null pointer");
   const Sizes z = sizes(d);
-  const InferLayout w = infer_layout(z);
+  const InferLayout w = infer_layout(z, f8);
   NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes, w.total);
   if (pr) {
     NB_CHECK(pr->w && pr->bqkv && pr->layers_host, NBEST_ERR_ARG, "encoder_infer_pruned: null image pointer");
@@ -1230,13 +1252,15 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
                NBEST_ERR_ALIGN, "encoder_infer_pruned: layer %d: image offsets must be non-negative multiples of 16 bytes", l);
     }
   }
-  const Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
+  Fwd c = make_fwd(d, wts, prm, z, key_mask, stream);
+  const bool fp8_pass = c.g.fp8;   // (false unless f8: the other entry points refuse desc.w8)
+  if (fp8_pass) { c.q8 = true; c.arec = false; c.g.amax_new = nullptr; }   // static scales: no producer records
   const Ptrs& P = c.g.W;
   char* W = (char*)ws;
   const int64_t M = z.M, B = d->B, SH = (int64_t)d->S * d->H;
   const int H = d->H, F = d->F, dt = d->dtype;
   void* X[2] = {W + w.X0, W + w.X1};
-  const LayerBufs b = infer_layer(w, ws);
+  const LayerBufs b = infer_layer(w, ws, fp8_pass);
   auto probs = [&](int l) { return cls_attn ? cls_attn + (int64_t)l * B * d->heads * d->S : nullptr; };
 
   RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g), P.P(d->off_emb_ln_b),
@@ -1254,7 +1278,7 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
       const PrunedLayer pl = pruned(l);
       RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, nullptr, &pl));
     } else {
-      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, probs(l)));
+      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, b.x8, probs(l)));   // (fp8 pass: the next layer's x8 comes out of this LayerNorm)
     }
   }
   // last layer, CLS rows only (weights read unpacked: the packed images are laid out for the full-width GEMMs)
@@ -1265,9 +1289,20 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
   // pruned: Wqkv' [3 Hk][H] (Q rows, then K | V rows), bqkv', Wo' [H][Hk] and heads = k; Hk = H otherwise
   const PrunedLayer pl = pr ? pruned(l) : PrunedLayer{d->heads, P.W(o.wqkv), nullptr, P.W(o.wo), nullptr, P.P(o.bqkv)};
   const int heads = pl.k, Hk = 64 * heads;
-  nbest_gemm_args g = gemm_nt(dt, xin, (const char*)pl.wqkv + (size_t)Hk * H * z.esz, kv, M, 2 * Hk, H);   // K | V, all rows
-  g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv + Hk;
-  RUN(nbest_gemm(&g, stream));
+  nbest_gemm_args g;
+  if (fp8_pass) {   // K | V, all rows, in fp8: the e4m3 copy of the layer input against rows H .. 3H of the e4m3 QKV matrix (unpacked)
+    if (l == 0) RUN(nbest_internal_cast_bf16_to_fp8(xin, b.x8, M * H, c.AP(0), nullptr, (hipStream_t)stream));
+    nbest_gemm_fp8_args g8 = {};
+    g8.A = b.x8; g8.B = (const uint8_t*)d->w8 + o.wqkv + (int64_t)H * H; g8.C = kv; g8.bias = P.P(o.bqkv) + H;
+    g8.M = M; g8.N = 2 * H; g8.K = H; g8.lda = g8.ldb = H; g8.ldc = 2 * H;
+    g8.epilogue = NBEST_EPI_BIAS; g8.out_scale = 1.f; g8.out_scale_dev = d->w8_inv_scale + 4 * l; g8.a_amax = d->aamax_prev + 4 * l;
+    RUN(nbest_gemm_fp8(&g8, stream));
+  } else {
+    g = gemm_nt(dt, xin, (const char*)pl.wqkv + (size_t)Hk * H * z.esz, kv, M, 2 * Hk, H);   // K | V, all rows
+    g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv + Hk;
+    RUN(nbest_gemm(&g, stream));
+    RUN(c.calib(xin, M * H, 4 * l));   // (calibration pass of the fp8 inference: the one fp8 GEMM input of this layer)
+  }
   g = gemm_nt(dt, xin, pl.wqkv, q, B, Hk, H);                                             // Q, CLS rows (lda = S H)
   g.lda = SH; g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv;
   RUN(nbest_gemm(&g, stream));
@@ -1305,4 +1340,10 @@ extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts,
                                    const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
                                    nbest_stream_t stream) {
   return nbest_encoder_infer_attn(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, stream);
+}
+
+extern "C" int nbest_encoder_infer_fp8(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                       const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                       nbest_stream_t stream) {
+  return infer_impl(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, nullptr, stream, true);
 }

@@ -18,6 +18,8 @@
 // Epilogues: forward NBEST_EPI_BIAS, NBEST_EPI_BIAS_GELU (gelu' 8-bit + the e4m3 copy of gelu the next GEMM reads; bf16 gelu only on
 // request), NBEST_EPI_BIAS_DROP_RES; dgrad NBEST_EPI_NONE, NBEST_EPI_RES, NBEST_EPI_DGELU (x gelu', scaled e4m3 copy, amax, fused
 // column sums).  Other outputs are bf16: attention, LayerNorm and the heads are the bf16 path.
+// NBEST_EPI_BIAS_GELU_Q8 (inference): the BIAS_GELU instantiation without a backward's share - the e4m3 copy of gelu only; no gelu',
+// no U rows, no bf16 C, no amax.  Same fp32 gelu, same scale, same bytes.
 #include "common.h"
 
 namespace {
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
   const int nkt = (int)(p.K / BK8);
   constexpr int BNc = 64 * WN, B_BYTESc = BNc * BK8;
 
-  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES);
+  constexpr bool kHasBias = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES || EPI == NBEST_EPI_BIAS_GELU_Q8);
   constexpr bool kHasR = (EPI == NBEST_EPI_BIAS_DROP_RES || EPI == NBEST_EPI_RES);
   constexpr bool kHasUin = (EPI == NBEST_EPI_DGELU);
   const int64_t en8 = n0 + wn * WTN + (lane & 7) * 8;
@@ -109,9 +111,9 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
   if (kHasBias) { pb0 = *(const f32x4*)(p.bias + en8); pb1 = *(const f32x4*)(p.bias + en8 + 4); }
   float oscale = p.out_scale_dev ? *p.out_scale_dev : p.out_scale;
   // A8 = e4m3(a * s): a gradient (dgrad epilogues, scale target 56) or a forward activation (forward epilogues, target 224)
-  constexpr bool kFwdEpi = (EPI == NBEST_EPI_BIAS || EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_DROP_RES);
+  constexpr bool kFwdEpi = kHasBias;   // (the forward epilogues are the ones with a bias)
   if (p.a_amax) oscale /= kFwdEpi ? fp8_ascale_of(__uint_as_float(*p.a_amax)) : fp8_gscale_of(__uint_as_float(*p.a_amax));
-  const float c8s = (EPI == NBEST_EPI_BIAS_GELU) ? fp8_act_scale(p.c8g.amax_prev) : fp8_grad_scale(p.c8g.amax_prev);
+  const float c8s = (EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_BIAS_GELU_Q8) ? fp8_act_scale(p.c8g.amax_prev) : fp8_grad_scale(p.c8g.amax_prev);
   float amax8 = 0.f;
   auto load_pre = [&](int64_t m) -> i32x4 {   // residual rows: bf16, 16 bytes per lane; GELU' rows: 8-bit, 8 bytes per lane
     if constexpr (kHasR) {
@@ -292,6 +294,16 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
         for (int e = 0; e < 8; ++e) { q[e] = v[e] * c8s; amax8 = fmaxf(amax8, fabsf(v[e])); }
         st_stream((i32x2*)(p.C8 + oC8), i32x2{(int)fp8_pack4(q), (int)fp8_pack4(q + 4)}, p.stream_out);
       }
+      if (EPI == NBEST_EPI_BIAS_GELU_Q8) {   // the e4m3 copy alone: the same fp32 gelu (gelu_pair_fast's h; its g has no reader and is dropped)
+        float q[8];
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+          f32x2 h2, g2;
+          gelu_pair_fast(f32x2{v[e], v[e + 1]}, h2, g2);
+          q[e] = h2[0] * c8s; q[e + 1] = h2[1] * c8s;
+        }
+        st_stream((i32x2*)(p.C8 + oC8), i32x2{(int)fp8_pack4(q), (int)fp8_pack4(q + 4)}, p.stream_out);
+      }
       if (EPI == NBEST_EPI_BIAS_DROP_RES && p.drop.thr16) {
         const uint32_t k = nb_keep4(p.drop, dbase) | (nb_keep4(p.drop, dbase + 4) << 4);
 #pragma unroll
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm8_kernel(GemmP8 p) {
           }
         }
       }
-      if ((EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_DGELU) && !p.C) {   // only the e4m3 copy is wanted
+      if (EPI == NBEST_EPI_BIAS_GELU_Q8 || ((EPI == NBEST_EPI_BIAS_GELU || EPI == NBEST_EPI_DGELU) && !p.C)) {   // only the e4m3 copy is wanted
       } else {
         bf16x8 o;
 #pragma unroll
@@ -781,7 +793,25 @@ __global__ __launch_bounds__(64) void amax_fold_kernel(uint32_t* __restrict__ sl
   v = wave_max(v);
   if (lane == 0) out[t] = __float_as_uint(v);
 }
+// the same, raising: out[t] = max(out[t], ...) - a history gathered over several passes (the calibration of the fp8 inference)
+__global__ __launch_bounds__(64) void amax_fold_max_kernel(uint32_t* __restrict__ slots, uint32_t* __restrict__ out, int n) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  if (t >= n) return;
+  uint32_t* s = slots + (int64_t)t * NBEST_AMAX_TENSOR_WORDS + (lane & (kAmaxSlots - 1)) * kAmaxSlotStride;
+  float v = 0.f;
+  if (lane < kAmaxSlots) { v = __uint_as_float(*s); *s = 0u; }
+  const uint32_t b = __float_as_uint(wave_max(v));
+  if (lane == 0 && b > out[t]) out[t] = b;
+}
 }  // namespace
+
+extern "C" int nbest_fp8_amax_fold_max(void* slots, void* out, int32_t n_tensors, void* stream) {
+  NB_CHECK(slots && out && n_tensors >= 0, NBEST_ERR_ARG, "nbest_fp8_amax_fold_max: null argument");
+  if (n_tensors == 0) return NBEST_OK;
+  amax_fold_max_kernel<<<n_tensors, 64, 0, (hipStream_t)stream>>>((uint32_t*)slots, (uint32_t*)out, n_tensors);
+  NB_LAUNCH_CHECK();
+  return NBEST_OK;
+}
 
 extern "C" int nbest_fp8_amax_fold(void* slots, void* out, int32_t n_tensors, void* stream) {
   NB_CHECK(slots && out && n_tensors >= 0, NBEST_ERR_ARG, "nbest_fp8_amax_fold: null argument");
@@ -939,7 +969,8 @@ extern "C" int nbest_gemm_fp8_plan(const nbest_gemm_fp8_args* a, nbest_gemm_fp8_
   NB_CHECK(out, NBEST_ERR_ARG, "gemm_fp8_plan: null output");
   NB_CHECK(a && a->A && a->B, NBEST_ERR_ARG, "gemm_fp8: null pointer");
   // the bf16 output may be dropped where the epilogue also writes the e4m3 copy its only readers take
-  NB_CHECK(a->C || ((a->epilogue == NBEST_EPI_BIAS_GELU || a->epilogue == NBEST_EPI_DGELU) && a->C8), NBEST_ERR_ARG, "gemm_fp8: null output");
+  NB_CHECK(a->C || ((a->epilogue == NBEST_EPI_BIAS_GELU || a->epilogue == NBEST_EPI_DGELU || a->epilogue == NBEST_EPI_BIAS_GELU_Q8) && a->C8),
+           NBEST_ERR_ARG, "gemm_fp8: null output");
   NB_CHECK(a->M > 0 && a->N % 256 == 0 && a->K % BK8 == 0 && a->K >= BK8, NBEST_ERR_SHAPE,
            "gemm_fp8: needs N %% 256 == 0 and K %% 64 == 0 (M=%lld N=%lld K=%lld)", (long long)a->M, (long long)a->N, (long long)a->K);
   NB_CHECK(a->lda % 16 == 0 && a->ldb % 16 == 0 && a->ldc % 8 == 0, NBEST_ERR_ALIGN, "gemm_fp8: leading dimensions");
@@ -947,12 +978,15 @@ extern "C" int nbest_gemm_fp8_plan(const nbest_gemm_fp8_args* a, nbest_gemm_fp8_
            "gemm_fp8: pointers must be 16-byte aligned");
   const int epi = a->epilogue;
   NB_CHECK(epi == NBEST_EPI_NONE || epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES ||
-               epi == NBEST_EPI_DGELU || epi == NBEST_EPI_RES, NBEST_ERR_ARG, "gemm_fp8: epilogue %d is not built", epi);
-  if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES)
+               epi == NBEST_EPI_DGELU || epi == NBEST_EPI_RES || epi == NBEST_EPI_BIAS_GELU_Q8, NBEST_ERR_ARG, "gemm_fp8: epilogue %d is not built", epi);
+  if (epi == NBEST_EPI_BIAS || epi == NBEST_EPI_BIAS_GELU || epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_BIAS_GELU_Q8)
     NB_CHECK(a->bias, NBEST_ERR_ARG, "gemm_fp8: epilogue %d needs bias", epi);
   if (epi == NBEST_EPI_BIAS_GELU)
     NB_CHECK(a->U && a->C8 && a->ldu % 8 == 0 && a->ldc8 % 8 == 0 && ((uintptr_t)a->U & 7) == 0 && ((uintptr_t)a->C8 & 7) == 0,
              NBEST_ERR_ARG, "gemm_fp8: BIAS_GELU needs U (8-bit gelu') and C8 (fp8 copy of the output)");
+  if (epi == NBEST_EPI_BIAS_GELU_Q8)   // the inference form writes the e4m3 copy and nothing else: an output it would not write is an error
+    NB_CHECK(a->C8 && !a->C && !a->U && !a->c8_amax_new && a->ldc8 % 8 == 0 && ((uintptr_t)a->C8 & 7) == 0, NBEST_ERR_ARG,
+             "gemm_fp8: BIAS_GELU_Q8 writes C8 (fp8 copy of gelu) only: needs C8, and C, U and c8_amax_new must be NULL");
   if (epi == NBEST_EPI_BIAS_DROP_RES || epi == NBEST_EPI_RES)
     NB_CHECK(a->R && a->ldr % 8 == 0 && ((uintptr_t)a->R & 15) == 0, NBEST_ERR_ARG, "gemm_fp8: epilogue %d needs R", epi);
   if (epi == NBEST_EPI_DGELU) {
@@ -1017,6 +1051,7 @@ extern "C" int nbest_gemm_fp8(const nbest_gemm_fp8_args* a, nbest_stream_t strea
     break;
   switch (epi) {
     L8(NBEST_EPI_NONE) L8(NBEST_EPI_BIAS) L8(NBEST_EPI_BIAS_GELU) L8(NBEST_EPI_BIAS_DROP_RES) L8(NBEST_EPI_DGELU) L8(NBEST_EPI_RES)
+    L8(NBEST_EPI_BIAS_GELU_Q8)
     default: break;
   }
 #undef L8

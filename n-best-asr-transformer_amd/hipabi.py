@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("NBEST_LIB") or os.path.join(_HERE, "csrc", "libnbest_
 F32, BF16 = 0, 1
 ADAM_L2, ADAMW = 0, 1          # include/nbest_hip.h NBEST_ADAM_L2 / NBEST_ADAMW
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_DGELU, EPI_RES, EPI_F32_SPLITK = range(7)
+EPI_BIAS_GELU_Q8 = 7           # nbest_gemm_fp8 only: the e4m3 copy of gelu(u) and nothing else (the FFN-up of the fp8 inference)
 
 EXPORTS = [
     "nbest_version", "nbest_last_error", "nbest_embed_ln_fwd", "nbest_embed_ln_bwd", "nbest_embed_bwd_ws_bytes", "nbest_rows_gather", "nbest_rows_zero", "nbest_rows_add",
@@ -33,6 +34,7 @@ EXPORTS = [
     "nbest_embed_ln_fwd_adv", "nbest_embed_ln_bwd_adv", "nbest_embed_adv_ws_bytes", "nbest_embed_adv_delta",
     "nbest_layernorm_fwd_fp8", "nbest_layernorm_bwd_fp8", "nbest_attention_fwd_fp8", "nbest_attention_bwd_fp8", "nbest_cast_bf16_to_fp8_scaled", "nbest_amax_bf16",
     "nbest_gemm_fp8_plan", "nbest_wgrad_fp8_plan",
+    "nbest_fp8_amax_fold_max", "nbest_encoder_infer_fp8_ws_bytes", "nbest_encoder_infer_fp8",
 ]
 
 
@@ -137,7 +139,7 @@ def lib():
                 raise RuntimeError("nbest_amd: %s does not export %s" % (LIB_PATH, name))
         for name in ("nbest_embed_bwd_ws_bytes", "nbest_gemm_ws_bytes", "nbest_wgrad_pair_ws_bytes", "nbest_rowred_ws_bytes", "nbest_heads_ws_bytes",
                      "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_embed_adv_ws_bytes", "nbest_cls_contrast_ws_bytes",
-                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes"):
+                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer_fp8_ws_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.nbest_embed_bwd_ws_bytes.argtypes = [C.c_int64, C.c_int64]
         L.nbest_rows_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -195,6 +197,7 @@ def lib():
         L.nbest_stc_decode.argtypes = [vp, vp, C.POINTER(LabelSpaceC), vp, vp, i32, vp]
         L.nbest_stream_stamp.argtypes = [vp, i32, vp]
         L.nbest_fp8_amax_fold.argtypes = [vp, vp, i32, vp]
+        L.nbest_fp8_amax_fold_max.argtypes = [vp, vp, i32, vp]
         f64 = C.c_double                  # b1, b2 of every optimizer: the library forms (float)b and (float)(1 - b) itself
         L.nbest_bertadam_step.argtypes = [vp] * 6 + [i32, i32, f32, f64, f64, f32, f32, vp, sz, vp]
         L.nbest_bertadam_norms.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
@@ -208,6 +211,8 @@ def lib():
         L.nbest_encoder_forward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, sz, C.POINTER(C.c_void_p), vp]
         L.nbest_encoder_infer_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
         L.nbest_encoder_infer.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp]
+        L.nbest_encoder_infer_fp8_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
+        L.nbest_encoder_infer_fp8.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp]
         L.nbest_attention_cls_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
         L.nbest_encoder_infer_attn.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, vp, vp]
         L.nbest_head_prune_plan.argtypes = [C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(HeadPruneLayer)] + [C.POINTER(C.c_size_t)] * 3
@@ -543,6 +548,8 @@ def _gemm_fp8_args(A8, W8, M, N, K, bias, out_scale, epilogue, R, drop_p, seed, 
             U = torch.empty(M, N, dtype=torch.uint8, device=dev)
         if C8 is None:
             C8 = torch.empty(M, N, dtype=torch.uint8, device=dev)
+    if epilogue == EPI_BIAS_GELU_Q8 and C8 is None:                 # its one output (call with want_c=False: a C is refused)
+        C8 = torch.empty(M, N, dtype=torch.uint8, device=dev)
     g = GemmFp8Args()
     g.A, g.B = A8.data_ptr(), W8.data_ptr()
     g.C = out.data_ptr() if out is not None else None
@@ -578,10 +585,12 @@ def gemm_fp8(A8, W8, M, N, K, bias=None, out_scale=1.0, epilogue=EPI_BIAS, R=Non
     The whole of nbest_gemm_fp8_args: ``bias=None`` for NONE / RES / DGELU; ``U``: the GELU' rows DGELU reads (BIAS_GELU: where it writes
     them); ``C8``: the e4m3 copy (DGELU: optional); ``colsum_out`` [N] fp32 (+)= the column sums of DGELU; ``a_amax`` / ``c8_amax_prev``:
     1-element int32 tensors (float bits), ``c8_amax_slots``: a slot block, as _amax_args; ``out_scale_dev``: a device float that overrides
-    ``out_scale``; ``want_c=False``: C = NULL (None is returned in its place)."""
+    ``out_scale``; ``want_c=False``: C = NULL (None is returned in its place).  BIAS_GELU_Q8 (``want_c=False``, no ``U``, no slots) returns C8."""
     g, out, U, C8, ws = _gemm_fp8_args(A8, W8, M, N, K, bias, out_scale, epilogue, R, drop_p, seed, drop_stream, out, B_packed, b_pack_bn, U, C8,
                                        colsum_out, colsum_accumulate, a_amax, c8_amax_prev, c8_amax_slots, out_scale_dev, want_c)
     check(lib().nbest_gemm_fp8(C.byref(g), stream_ptr()), "gemm_fp8")
+    if epilogue == EPI_BIAS_GELU_Q8:
+        return C8
     return (out, U, C8) if epilogue == EPI_BIAS_GELU else out
 
 
@@ -611,14 +620,16 @@ def gemm_fp8_plan_shape(M, N, K, epilogue=EPI_BIAS, lda=None, ldb=None, ldc=None
     g.lda, g.ldb, g.ldc = (lda or K), (ldb or K), (ldc or N)
     g.ldr = g.ldu = g.ldc8 = N
     g.epilogue, g.out_scale, g.drop_p = epilogue, 1.0, drop_p
-    if epilogue in (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES):
+    if epilogue in (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES, EPI_BIAS_GELU_Q8):
         g.bias = fake
     if epilogue in (EPI_BIAS_DROP_RES, EPI_RES):
         g.R = fake
     if epilogue in (EPI_BIAS_GELU, EPI_DGELU):
         g.U = fake
-    if epilogue == EPI_BIAS_GELU:
+    if epilogue in (EPI_BIAS_GELU, EPI_BIAS_GELU_Q8):
         g.C8 = fake
+    if epilogue == EPI_BIAS_GELU_Q8:
+        g.C = None                                                  # it writes the e4m3 copy only
     if packed_bn:
         g.B_packed, g.b_pack_bn = fake, packed_bn
     return gemm_fp8_plan_args(g)
@@ -796,6 +807,12 @@ def encoder_infer_pruned(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, t
     im = HeadPruneImages(w.data_ptr(), None if w_packed is None else w_packed.data_ptr(), bqkv.data_ptr(), tab)
     check(lib().nbest_encoder_infer_pruned(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
                                            ws.numel(), ptr(cls_out), C.byref(im), stream_ptr()), "encoder_infer_pruned")
+
+
+def encoder_infer_fp8(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out):
+    """nbest_encoder_infer_fp8 -> cls_out [B, H]: the calibration pass or the fp8 pass, as the descriptor's fp8 fields say"""
+    check(lib().nbest_encoder_infer_fp8(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
+                                        ws.numel(), ptr(cls_out), stream_ptr()), "encoder_infer_fp8")
 
 
 def encoder_infer(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, cls_attn=None):
@@ -1183,6 +1200,12 @@ def stream_stamp(flag, value):
 
 
 AMAX_TENSOR_WORDS = 1024        # include/nbest_hip.h NBEST_AMAX_TENSOR_WORDS
+
+
+def fp8_amax_fold_max(slots, out):
+    """out[t] = max(out[t], max over the recording slots of tensor t); the slots are zeroed (nbest_fp8_amax_fold_max)"""
+    assert slots.numel() == out.numel() * AMAX_TENSOR_WORDS and slots.dtype == out.dtype == torch.int32
+    check(lib().nbest_fp8_amax_fold_max(ptr(slots), ptr(out), out.numel(), stream_ptr()), "fp8_amax_fold_max")
 
 
 def fp8_amax_fold(slots, out):

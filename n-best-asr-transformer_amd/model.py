@@ -362,6 +362,9 @@ class NBestSTCModel(nn.Module):
         # 2^floor(log2(224 / amax of the same tensor in the previous step)); the first step after (re)loading weights is a
         # calibration step: bf16 GEMMs, amax recorded (round 3 cast activations at unit scale and saturated silently beyond 448)
         self._aamax_valid = False
+        # batches folded into the inference history arena.iamax (fp8_calibrate; a loaded calibration counts as 1): predict(fp8=True)
+        # needs one, and new weights drop it
+        self.fp8_calibrated = 0
         if self.fp8_forward:
             if compute_dtype != torch.bfloat16:
                 raise RuntimeError("nbest_amd: fp8_forward rides on the bf16 path")
@@ -408,6 +411,18 @@ class NBestSTCModel(nn.Module):
             self._aamax_valid = False
             self.arena.aamax.zero_()
             self.arena.aamax_slots.zero_()
+        self._drop_fp8_calibration()
+
+    def _drop_fp8_calibration(self):
+        """new weights: the static scales of predict(fp8=True) belong to the old ones"""
+        if self.fp8_forward and self.fp8_calibrated:
+            self.fp8_calibrated = 0
+            self.arena.iamax.zero_()
+            self.arena.iamax_slots.zero_()
+
+    def load_state_dict(self, *args, **kwargs):
+        self._drop_fp8_calibration()
+        return super().load_state_dict(*args, **kwargs)
 
     def load_reference_state(self, sd, strict=True):
         self._drop_fp8_history()
@@ -977,7 +992,7 @@ class NBestSTCModel(nn.Module):
         return adv_loss, norm
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
-    def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False):
+    def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False, fp8=False):
         """Scores and decoded labels of one batch through nbest_encoder_infer: no activation stash, no dropout (in either
         mode), the heads on the compact CLS rows.  Returns dict(top, bott, final, cls [B, H] compute dtype, pred int32 [B, n_top]).
         ``return_attns``: also ``cls_attn``, fp32 [L, B, heads, S] - the CLS row's attention probabilities of every layer
@@ -989,8 +1004,25 @@ class NBestSTCModel(nn.Module):
         are.  An fp8w model runs its bf16 weight copy, unpacked (as its calibration pass reads it).
         Under ``set_head_mask(mask, compact=True)``: the compact images are gathered from the current weights (and packed, where
         the packed bf16 copies are in use), then nbest_encoder_infer_pruned runs only the kept heads; ``return_attns`` raises
-        ValueError."""
+        ValueError.
+        ``fp8=True`` (a model built with ``fp8_forward=True``, after ``fp8_calibrate``): nbest_encoder_infer_fp8 - the full-width GEMMs
+        of layers 0 .. L-2 and the last layer's K|V projection on the block-scaled fp8 MFMA, with the STATIC activation scales of the
+        calibration (2^floor(log2(224 / amax)): a value up to twice the calibrated amax is representable, beyond that the e4m3 cast
+        saturates silently); the B CLS rows of the last layer and the heads stay bf16.  RuntimeError on a model without the fp8
+        forward, before a calibration and under a head mask (compact or not); ValueError with ``return_attns``.  Without the
+        argument nothing changes: the bf16 path, bit for bit."""
         cfg = self.cfg
+        if fp8:
+            if not self.fp8_forward:
+                raise RuntimeError("nbest_amd predict(fp8=True): the model was not built with fp8_forward=True (--dtype fp8w)")
+            if return_attns:
+                raise ValueError("nbest_amd predict(fp8=True): return_attns is not built for the fp8 inference")
+            if self._head_mask is not None:
+                raise RuntimeError("nbest_amd predict(fp8=True): head masks (compact or not) are not supported in fp8; clear the mask")
+            if not self.fp8_calibrated:
+                raise RuntimeError("nbest_amd predict(fp8=True): no activation scales - run model.fp8_calibrate(batch) on representative "
+                                   "batches (or load_fp8_calibration) first")
+            return self._heads_out(self._infer_fp8(input_ids, seg_ids, calibrate=False), return_logits)
         if return_attns and self._head_mask_compact:
             raise ValueError("nbest_amd predict: return_attns under a compact head mask is not built (the CLS maps are indexed by "
                              "original head); set the mask without compact=True")
@@ -1016,15 +1048,83 @@ class NBestSTCModel(nn.Module):
             hb.encoder_infer_pruned(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, self._prune.tab, self._prune.w, pk, self._prune.b)
         else:
             hb.encoder_infer(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, cls_attn)
-        Wh, bh = a.heads_wb()
+        out = self._heads_out(cls, return_logits)
+        if return_attns:
+            out["cls_attn"] = cls_attn
+        return out
+
+    def _heads_out(self, cls, return_logits):
+        """the heads of an inference pass on its CLS rows [B, H]: the dict predict returns (without cls_attn)"""
+        B, H = cls.shape
+        Wh, bh = self.arena.heads_wb()
         labels_f = torch.zeros(B, self.labels.n_bottom, dtype=torch.float32, device=self.device)
         top, bott, fin, _, _, _, _ = hb.stc_heads(cls, H, Wh, bh, self.dls, labels_f, B, H, need_grad=False, drop_p=0.0)
         out = dict(top=top, bott=bott, final=fin, cls=cls, pred=self.decode(top, bott))
-        if return_attns:
-            out["cls_attn"] = cls_attn
         if return_logits:
             out["logits"] = hb.stc_heads_logits(cls, H, Wh, bh, self.dls, B, H)
         return out
+
+    # ---- fp8 inference: an explicit calibration, then static scales --------------------------------------------------------
+    def _infer_fp8(self, input_ids, seg_ids, calibrate):
+        """one nbest_encoder_infer_fp8 pass -> cls [B, H].  ``calibrate``: the bf16 launches of predict plus the amax records of the
+        GEMM inputs into arena.iamax_slots; else the fp8 pass on the history arena.iamax, which records nothing.  A descriptor of its
+        own ("infer8"): the fp8 fields are set per call, the training descriptors and histories are not touched."""
+        cfg, a = self.cfg, self.arena
+        B, S = input_ids.shape
+        first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
+        if S > 512 or S + first_pos > cfg.max_position_embeddings:
+            raise RuntimeError("nbest_amd predict: S=%d does not fit the position table (%d rows)" % (S, cfg.max_position_embeddings))
+        d = self._desc(B, S, "infer8").desc
+        ids, seg, pos, mask = self._inputs(input_ids, seg_ids)
+        d.hidden_drop = d.attn_drop = 0.0
+        d.seed = 0
+        d.head_gate = d.head_gate_grad = None
+        self._set_weights(d, "infer")
+        d.w8, d.w8_inv_scale = a.w8.data_ptr(), a.w8_inv_scale.data_ptr()
+        d.w8p = a.w8p.data_ptr() if a.w8p is not None else None
+        d.fp8_act = int(not calibrate)
+        d.aamax_prev = None if calibrate else a.iamax.data_ptr()
+        d.aamax_new = a.iamax_slots.data_ptr() if calibrate else None
+        ws = self._grow(vars(self), "_infer_ws", hb.lib().nbest_encoder_infer_fp8_ws_bytes(C.byref(d)))
+        cls = torch.empty(B, cfg.hidden_size, dtype=self.compute_dtype, device=self.device)
+        hb.encoder_infer_fp8(d, a.weights, a.p, ids, seg, pos, mask, ws, cls)
+        return cls
+
+    def fp8_calibrate(self, input_ids, seg_ids=None, reset=False):
+        """Record the activation scales predict(fp8=True) runs on, from one batch: the calibration pass of nbest_encoder_infer_fp8 (the
+        launches of the bf16 predict plus one amax launch per fp8 GEMM input) and the heads, then the recorded amax folded into the
+        inference history with a maximum (nbest_fp8_amax_fold_max), so several calls cover several batches; ``reset=True`` starts
+        over.  Returns what ``predict`` returns for the batch - the bits of the bf16 predict.  No host synchronisation; no training
+        state is touched.  The scale of a tensor is 2^floor(log2(224 / amax)): a value up to twice the calibrated amax is
+        representable, beyond that the e4m3 cast saturates silently - calibrate on data like the data to be labelled."""
+        if not self.fp8_forward:
+            raise RuntimeError("nbest_amd fp8_calibrate: the model was not built with fp8_forward=True (--dtype fp8w)")
+        if self._head_mask is not None:
+            raise RuntimeError("nbest_amd fp8_calibrate: head masks are not supported in fp8; clear the mask")
+        if reset:
+            self.arena.iamax.zero_()
+            self.fp8_calibrated = 0
+        cls = self._infer_fp8(input_ids, seg_ids, calibrate=True)
+        hb.fp8_amax_fold_max(self.arena.iamax_slots, self.arena.iamax)
+        self.fp8_calibrated += 1
+        return self._heads_out(cls, False)
+
+    def fp8_calibration(self):
+        """the inference history as fp32 [L, 4] (a copy): the calibrated amax of x, ctx, x1, gelu(u) per layer (the last layer: x only)"""
+        if not self.fp8_forward:
+            raise RuntimeError("nbest_amd fp8_calibration: the model was not built with fp8_forward=True")
+        return self.arena.iamax.view(torch.float32).view(self.cfg.num_hidden_layers, 4).clone()
+
+    def load_fp8_calibration(self, t):
+        """install a history ``fp8_calibration()`` returned (for these weights: a server keeps it next to model.pt); counts as one batch"""
+        if not self.fp8_forward:
+            raise RuntimeError("nbest_amd load_fp8_calibration: the model was not built with fp8_forward=True")
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if tuple(t.shape) != (self.cfg.num_hidden_layers, 4) or not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError("nbest_amd load_fp8_calibration: expected finite non-negative fp32 [L=%d, 4]" % self.cfg.num_hidden_layers)
+        self.arena.iamax.copy_(t.contiguous().view(torch.int32).view(-1).to(self.device))
+        self.arena.iamax_slots.zero_()
+        self.fp8_calibrated = 1
 
     # ---- integrated-gradients attribution (forward + input-gradient backward, no parameter gradient) ------------------------
     def default_baseline(self, input_ids):

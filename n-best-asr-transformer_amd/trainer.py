@@ -1013,13 +1013,15 @@ def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
 
 
 @torch.no_grad()
-def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32):
+def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32, fp8=False, calib_batches=8):
     """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
     [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
     ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only.
     ``attn_fp`` (--predict_attention): a text file that receives one attention_record JSON line per utterance, in split order
     ("line": 1-based index in the split).  ``attr_fp`` (--predict_attribution): one attribution_record JSON line per utterance, in
-    split order - integrated gradients (model.attribute, ``attr_steps`` path points) of every label the .pred line lists."""
+    split order - integrated gradients (model.attribute, ``attr_steps`` path points) of every label the .pred line lists.
+    ``fp8`` (--predict_fp8): ``model.fp8_calibrate`` on the first ``calib_batches`` batches of the split (from scratch), one line on
+    stdout about what was recorded, then every batch through ``model.predict(fp8=True)``."""
     _, world = dist_info()
     if world > 1:
         raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
@@ -1028,9 +1030,20 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     split = encoded(data, opt, memory)
     n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
     lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
+    if fp8:
+        if attn_fp is not None or attr_fp is not None:
+            raise RuntimeError("nbest_amd: the fp8 inference writes no attention maps and no attributions")
+        head = lists[:max(1, int(calib_batches))]
+        for k, (bi, mine, b) in enumerate(Prefetcher(split, head, model.device)):
+            model.fp8_calibrate(b["ids"], seg_ids=b["seg"] if opt.add_segment_ids else None, reset=k == 0)
+        cal = model.fp8_calibration().cpu()[:-1]          # layers 0 .. L-2 run all four fp8 GEMMs (the last layer: x only)
+        kinds = ["%s %.3g..%.3g" % (nm, cal[:, i].min().item(), cal[:, i].max().item()) for i, nm in enumerate(("x", "ctx", "x1", "gelu"))
+                 ] if len(cal) else ["x %.3g" % model.fp8_calibration()[-1, 0].item()]
+        print("fp8 calibration: %d batches, %d utterances; amax over the layers: %s"
+              % (len(head), sum(len(m) for m in head), ", ".join(kinds)), flush=True)
     for bi, mine, b in Prefetcher(split, lists, model.device):
         seg = b["seg"] if opt.add_segment_ids else None
-        out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None)
+        out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None, fp8=fp8)
         pipe.push(out, [split.labels[j] for j in mine], tag=mine)
         spans_of = {}
         for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None) else []):
