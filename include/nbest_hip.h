@@ -380,6 +380,19 @@ int nbest_attention_probs(const void* qkv, const uint8_t* key_mask, const float*
  * keys 0, a fully masked row all 0; unrounded in both dtypes.                                                                 */
 int nbest_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
                               int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
+/* One step of the attention rollout (Abnar & Zuidema, 2020): a row vector through residual I + (1 - residual) mean_h P_h, with P
+ * the probabilities of nbest_attention_probs (qkv, key_mask and lse as there: same scale, same mask rule, natural-log lse):
+ *   r_out[b][j] = residual r_in[b][j] + (1 - residual) / heads * sum_h sum_i r_in[b][i] P[b][h][i][j]
+ * r_in, r_out fp32 [B][S], different buffers.  No map is written: the probabilities are recomputed tile by tile (bf16: K Q^T on
+ * the 16x16x32 bf16 MFMA with fp32 accumulation; fp32: one sequential fma chain over d per score - the bits of
+ * nbest_attention_probs) and summed in fp32; traffic is the Q and K thirds of qkv, lse and the two vectors.  A query row with
+ * lse = -inf (no unmasked key) contributes 0.  Exact where nothing else contributes: r_out = residual r_in on masked keys, and
+ * r_out == r_in bit for bit at residual = 1.  Every r_out element is written exactly once; no atomics, bit-reproducible.
+ * d = 64, 1 <= S <= 512, fp32 or bf16, 0 <= residual <= 1; qkv 16-byte aligned.  Refused before anything is enqueued:
+ * NBEST_ERR_ARG (a null pointer, r_in == r_out, residual outside [0, 1] or not finite), NBEST_ERR_SHAPE, NBEST_ERR_DTYPE,
+ * NBEST_ERR_ALIGN.                                                                                                        */
+int nbest_attention_rollout_step(const void* qkv, const uint8_t* key_mask, const float* lse, const float* r_in, float* r_out,
+                                 float residual, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 /* dqkv [M][3H] receives dQ | dK | dV (overwritten, no accumulation).  dbias != NULL: dbias[3H] (+)= column
  * sums of dqkv (the Q|K|V bias gradient), fused into the kernel; ws >= nbest_attention_bwd_ws_bytes().   */
 size_t nbest_attention_bwd_ws_bytes(int B, int S, int heads);

@@ -83,6 +83,12 @@ def parse_arguments(argv=None):
                         "token and each segment (cls, sys, h1, h2, ..)")
     g.add_argument("--attribution_steps", type=int, default=32, metavar="M",
                    help="--predict_attribution: path points of the integrated-gradients midpoint rule (>= 1)")
+    g.add_argument("--predict_rollout", default=None, metavar="PATH",
+                   help="with --predict: also write one JSON line per input line, in input order - the attention rollout of the "
+                        "[CLS] row (Abnar & Zuidema, 2020: the product over the layers of R I + (1 - R) mean-over-heads attention), "
+                        "per token and per segment (cls, sys, h1, h2, ..).  Not with --predict_fp8, --head_mask or --compact_heads")
+    g.add_argument("--rollout_residual", type=float, default=None, metavar="R",
+                   help="--predict_rollout: the weight R of the residual connection in every layer, 0 <= R <= 1 (default 0.5)")
     g.add_argument("--predict_fp8", action="store_true",
                    help="with --predict FILE --dtype fp8w: label the file with the fp8 inference (model.predict(fp8=True)) - the "
                         "full-width GEMMs on the fp8 MFMA with static activation scales calibrated on the first --fp8_calib_batches "
@@ -317,6 +323,21 @@ def parse_arguments(argv=None):
         ap.error("--predict_attention is an output of --predict: pass --predict FILE too")
     if opt.predict_attribution is not None and opt.predict is None:
         ap.error("--predict_attribution is an output of --predict: pass --predict FILE too")
+    if opt.predict_rollout is not None:
+        if opt.predict is None:
+            ap.error("--predict_rollout is an output of --predict: pass --predict FILE too")
+        if opt.predict_fp8:
+            ap.error("--predict_rollout together with --predict_fp8 is not built (the rollout runs the stash forward)")
+        if opt.head_mask is not None or opt.compact_heads:
+            ap.error("--predict_rollout together with %s is not built (the mean over heads under a head mask is not defined here)"
+                     % ("--compact_heads" if opt.compact_heads else "--head_mask"))
+    if opt.rollout_residual is not None:
+        if opt.predict_rollout is None:
+            ap.error("--rollout_residual is a setting of --predict_rollout: pass --predict_rollout PATH too")
+        if not (0.0 <= opt.rollout_residual <= 1.0):
+            ap.error("--rollout_residual must be in [0, 1] (got %g)" % opt.rollout_residual)
+    else:
+        opt.rollout_residual = 0.5
     if opt.attribution_steps < 1:
         ap.error("--attribution_steps must be >= 1 (got %d)" % opt.attribution_steps)
     if opt.fp8_calib_batches < 1:
@@ -606,11 +627,13 @@ def main(argv=None):
         t0 = time.time()
         attn_fp = open(opt.predict_attention, "w") if opt.predict_attention else None
         attr_fp = open(opt.predict_attribution, "w") if opt.predict_attribution else None
+        roll_fp = open(opt.predict_rollout, "w") if opt.predict_rollout else None
         try:
             cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp, attr_fp=attr_fp,
-                                          attr_steps=opt.attribution_steps, fp8=opt.predict_fp8, calib_batches=opt.fp8_calib_batches)
+                                          attr_steps=opt.attribution_steps, fp8=opt.predict_fp8, calib_batches=opt.fp8_calib_batches,
+                                          rollout_fp=roll_fp, rollout_residual=opt.rollout_residual)
         finally:
-            for fp in (attn_fp, attr_fp):
+            for fp in (attn_fp, attr_fp, roll_fp):
                 if fp is not None:
                     fp.close()
         with open(out_path, "w") as fp:

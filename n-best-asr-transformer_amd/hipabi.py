@@ -35,6 +35,7 @@ EXPORTS = [
     "nbest_layernorm_fwd_fp8", "nbest_layernorm_bwd_fp8", "nbest_attention_fwd_fp8", "nbest_attention_bwd_fp8", "nbest_cast_bf16_to_fp8_scaled", "nbest_amax_bf16",
     "nbest_gemm_fp8_plan", "nbest_wgrad_fp8_plan",
     "nbest_fp8_amax_fold_max", "nbest_encoder_infer_fp8_ws_bytes", "nbest_encoder_infer_fp8",
+    "nbest_attention_rollout_step",
 ]
 
 
@@ -221,6 +222,7 @@ def lib():
         L.nbest_encoder_act_view.argtypes = [C.POINTER(EncoderDesc), vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.nbest_attention_probs.argtypes = [vp] * 4 + [i32] * 5 + [vp]
         L.nbest_attention_cls_probs.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
+        L.nbest_attention_rollout_step.argtypes = [vp] * 5 + [f32] + [i32] * 5 + [vp]
         L.nbest_encoder_backward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 9 + [sz, vp, vp, sz, i32, i32, i32, i32, vp]
         L.nbest_transpose_weights.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nbest_pack_bn.argtypes = [i64]
@@ -733,6 +735,15 @@ def attention_probs(qkv, key_mask, lse, B, S, heads, out=None):
     check(lib().nbest_attention_probs(ptr(qkv), ptr(key_mask), ptr(lse), ptr(probs), B, S, heads, 64, dtype_code(qkv.dtype),
                                       stream_ptr()), "attention_probs")
     return probs
+
+
+def attention_rollout_step(qkv, key_mask, lse, r_in, residual, B, S, heads, out=None):
+    """nbest_attention_rollout_step: fp32 [B, S] ``r_in`` through residual I + (1 - residual) mean_h P_h, P the probabilities
+    attention_probs gives for the same ``qkv`` / ``key_mask`` / ``lse`` (never written) -> fp32 [B, S] (``out``: another buffer)"""
+    r_out = torch.empty(B, S, dtype=torch.float32, device=qkv.device) if out is None else out
+    check(lib().nbest_attention_rollout_step(ptr(qkv), ptr(key_mask), ptr(lse), ptr(r_in), ptr(r_out), float(residual), B, S, heads, 64,
+                                             dtype_code(qkv.dtype), stream_ptr()), "attention_rollout_step")
+    return r_out
 
 
 def attention_cls_probs(q, ldq, kv, ldkv, key_mask, B, S, heads, out=None):

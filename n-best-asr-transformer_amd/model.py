@@ -844,6 +844,58 @@ class NBestSTCModel(nn.Module):
             out.append(hb.attention_probs(qkv, rec.inputs[3], lse, B, S, heads))
         return out
 
+    def _stash_attention_views(self, rec):
+        """per layer (qkv [B S, 3H] compute dtype, lse fp32 [B, heads, S]): views of what the pass ``rec`` left in its stash"""
+        ps = rec.ps
+        B, S, H, heads = ps.B, ps.S, self.cfg.hidden_size, self.cfg.num_attention_heads
+        act = self._stash[rec.slot]
+        base, esz = act.data_ptr(), (2 if self.compute_dtype == torch.bfloat16 else 4)
+        n_qkv, n_lse = B * S * 3 * H * esz, B * heads * S * 4
+        for l in range(self.cfg.num_hidden_layers):
+            qp, lp = hb.encoder_act_view(ps.desc, act, l)
+            yield (act[qp - base:qp - base + n_qkv].view(self.compute_dtype), act[lp - base:lp - base + n_lse].view(torch.float32))
+
+    # ---- attention rollout of the CLS row (Abnar & Zuidema, 2020) --------------------------------
+    @torch.no_grad()
+    def attention_rollout(self, input_ids, seg_ids=None, residual=0.5):
+        """The CLS row of A~_{L-1} ... A~_0, A~_l = residual I + (1 - residual) mean_h A_l: how much of the top [CLS] state rests on
+        each input token once the mixing of the layers below is accounted for.  One eval forward of the ASR pass with the full
+        stash (the pass of ``forward(return_attns=True)``, never with dropout, whatever ``model.training`` says), then L launches
+        of nbest_attention_rollout_step on the stashed qkv / lse, from the top layer down, on a one-hot [CLS] row: no attention
+        map is written, no host synchronisation.
+        Returns dict(top, bott, final, pred, rollout fp32 [B, S], layers fp32 [L, B, S]): the scores are the bits of the eval
+        forward and ``decode``; ``layers[l]`` is the CLS row of A~_{L-1} ... A~_l, so ``layers[0]`` is ``rollout`` and
+        ``layers[L-1]`` the last layer's head-mean CLS attention mixed with ``residual``.
+        Touches what an eval forward touches (the ASR stash; an fp8w model folds its activation amax as its ``return_attns``
+        forward does) and nothing else: no gradients, optimizer moments or ``step_counter``.
+        ValueError for a residual outside [0, 1] or not finite; RuntimeError while a head mask is set (not built: a head mean
+        under a gate is not defined here) and for an S the position table does not hold."""
+        rho = float(residual)
+        if not (0.0 <= rho <= 1.0):                                     # (NaN fails both comparisons)
+            raise ValueError("nbest_amd attention_rollout: residual must be a finite number in [0, 1] (got %r)" % (residual,))
+        if self._head_mask is not None:
+            raise RuntimeError("nbest_amd attention_rollout: rollout under a head mask (gated or compact) is not built (the mean "
+                               "over heads under a gate is not defined here); call set_head_mask(None) first")
+        cfg = self.cfg
+        B, S = input_ids.shape
+        first_pos = cfg.pad_token_id + 1 if cfg.family in ("roberta", "xlm-roberta") else 0
+        if S > 512 or S + first_pos > cfg.max_position_embeddings:     # refused before anything is enqueued
+            raise RuntimeError("nbest_amd attention_rollout: S=%d does not fit the position table (%d rows)"
+                               % (S, cfg.max_position_embeddings))
+        L, heads = cfg.num_hidden_layers, cfg.num_attention_heads
+        rows = torch.zeros(L + 1, B, S, dtype=torch.float32, device=self.device)
+        rows[L, :, 0] = 1.0                                             # e_CLS; rows[l] = the CLS row of A~_{L-1} ... A~_l
+
+        def after(rec):
+            self._check_stash(rec)
+            views = list(self._stash_attention_views(rec))
+            for l in range(L - 1, -1, -1):
+                hb.attention_rollout_step(views[l][0], rec.inputs[3], views[l][1], rows[l + 1], rho, B, S, heads, out=rows[l])
+
+        _, _, (top, bott, fin, _, _, _, _) = self._passes_and_heads(input_ids, seg_ids, None, None, False, after_asr=after, full_top=True)
+        self._end_of_step(False, advance=False)
+        return dict(top=top, bott=bott, final=fin, pred=self.decode(top, bott), rollout=rows[0], layers=rows[:L])
+
     # ---- one training forward + backward (n_best_asr_bert.py:249-264) ---------------------------
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,

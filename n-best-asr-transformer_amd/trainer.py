@@ -997,6 +997,36 @@ def attention_record(line, spans, cls_attn):
             "mass": [[round(x, 6) for x in row] for row in m.tolist()]}
 
 
+def rollout_reference(attns, residual):
+    """The arithmetic of ``model.attention_rollout`` restated with plain matrix products (Abnar & Zuidema, 2020).  ``attns``: the
+    tuple of L attention maps [B, heads, S, S] (``forward(return_attns=True)``).  With A~_l = residual I + (1 - residual) mean_h A_l,
+    returns fp64 [L, B, S]: row l is the CLS row (row 0) of A~_{L-1} ... A~_l - so row 0 is the rollout and row L-1 the last
+    layer's head-mean CLS attention mixed with the residual."""
+    rho = float(residual)
+    L = len(attns)
+    B, _, S, _ = attns[0].shape
+    r = torch.zeros(B, 1, S, dtype=torch.float64, device=attns[0].device)
+    r[:, 0, 0] = 1.0
+    eye = torch.eye(S, dtype=torch.float64, device=attns[0].device)
+    out = [None] * L
+    for l in range(L - 1, -1, -1):
+        r = r @ (rho * eye + (1.0 - rho) * attns[l].double().mean(dim=1))
+        out[l] = r[:, 0]
+    return torch.stack(out)
+
+
+def rollout_record(line, spans, row, residual):
+    """one --predict_rollout JSON record.  ``row``: fp32 [>= tokens], the CLS rollout of one utterance
+    (model.attention_rollout(...)["rollout"][b]); ``spans``: inputs.utterance_segments of it.  ``token_rollout`` is the row
+    normalised over the utterance's own tokens (as attention_record: under XLM-R the padding keys stay unmasked, quirk Q1, and
+    their share is left out), ``mass`` its per-span sums."""
+    ntok = spans[-1][2] if spans else 0
+    t = row.detach().double().cpu()[:ntok]
+    t = (t / sum(t[lo:hi].sum() for _, lo, hi in spans).clamp_min(1e-300)).tolist() if spans else []
+    return {"line": line, "segments": [n for n, _, _ in spans], "tokens": [hi - lo for _, lo, hi in spans], "residual": float(residual),
+            "mass": [round(sum(t[lo:hi]), 6) for _, lo, hi in spans], "token_rollout": [round(x, 6) for x in t]}
+
+
 def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
     """one --predict_attribution JSON record.  ``attr_row``: per label, fp32 [>= tokens] integrated-gradients attribution of one
     utterance (model.attribute); ``spans``: inputs.utterance_segments of it (as attention_record); ``labels`` / ``scores`` /
@@ -1013,7 +1043,8 @@ def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
 
 
 @torch.no_grad()
-def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32, fp8=False, calib_batches=8):
+def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32, fp8=False, calib_batches=8, rollout_fp=None,
+                  rollout_residual=0.5):
     """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
     [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
     ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only.
@@ -1021,7 +1052,9 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     ("line": 1-based index in the split).  ``attr_fp`` (--predict_attribution): one attribution_record JSON line per utterance, in
     split order - integrated gradients (model.attribute, ``attr_steps`` path points) of every label the .pred line lists.
     ``fp8`` (--predict_fp8): ``model.fp8_calibrate`` on the first ``calib_batches`` batches of the split (from scratch), one line on
-    stdout about what was recorded, then every batch through ``model.predict(fp8=True)``."""
+    stdout about what was recorded, then every batch through ``model.predict(fp8=True)``.
+    ``rollout_fp`` (--predict_rollout): one rollout_record JSON line per utterance, in split order - the CLS attention rollout
+    (model.attention_rollout with ``rollout_residual``); the labels still come from ``model.predict``."""
     _, world = dist_info()
     if world > 1:
         raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
@@ -1031,8 +1064,8 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
     lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
     if fp8:
-        if attn_fp is not None or attr_fp is not None:
-            raise RuntimeError("nbest_amd: the fp8 inference writes no attention maps and no attributions")
+        if attn_fp is not None or attr_fp is not None or rollout_fp is not None:
+            raise RuntimeError("nbest_amd: the fp8 inference writes no attention maps, no attributions and no rollout")
         head = lists[:max(1, int(calib_batches))]
         for k, (bi, mine, b) in enumerate(Prefetcher(split, head, model.device)):
             model.fp8_calibrate(b["ids"], seg_ids=b["seg"] if opt.add_segment_ids else None, reset=k == 0)
@@ -1046,7 +1079,7 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
         out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None, fp8=fp8)
         pipe.push(out, [split.labels[j] for j in mine], tag=mine)
         spans_of = {}
-        for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None) else []):
+        for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None or rollout_fp is not None) else []):
             spans = utterance_segments(split.asr[j], opt.tokenizer, opt, getattr(opt, "n_best", None), getattr(opt, "max_seq_len", None))
             if spans[-1][2] != len(split.rows[j][0]):
                 raise RuntimeError("nbest_amd: line %d: segment spans cover %d tokens, the encoded utterance has %d"
@@ -1056,6 +1089,10 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
             ca = out["cls_attn"].cpu()
             for k, j in enumerate(mine):
                 attn_fp.write(json.dumps(attention_record(j + 1, spans_of[j], ca[:, k])) + "\n")
+        if rollout_fp is not None:
+            ro = model.attention_rollout(b["ids"], seg_ids=seg, residual=rollout_residual)["rollout"].cpu()
+            for k, j in enumerate(mine):
+                rollout_fp.write(json.dumps(rollout_record(j + 1, spans_of[j], ro[k], rollout_residual)) + "\n")
         if attr_fp is not None:
             # the labels of the .pred line: decoded rows -> label strings (ontology filter as MetricsPipe) -> their bottom ids
             rows = out["pred"].cpu().tolist()
