@@ -1051,6 +1051,39 @@ size_t nbest_encoder_infer_fp8_ws_bytes(const nbest_encoder_desc* d);
 int nbest_encoder_infer_fp8(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                             const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, nbest_stream_t stream);
 
+/* ---- token elimination between layers (PoWER-BERT, Goyal et al., ICML 2020, at a fixed count per layer) -----------------------------
+ * nbest_token_select: per utterance, the k positions to keep out of S, by a score.  Position 0 is always kept; the other k - 1 are
+ * the first of the remaining positions in this total order: unmasked before masked, then a score that is a number before a NaN, then
+ * the higher score (-0 = +0, +inf highest), then the lower index.  score fp32 [B][S], key_mask u8 [B][S], 1 <= k <= S <= 512.
+ *   idx_out   int32 [B][k]  the kept positions, ascending (so idx_out[b][0] == 0)
+ *   mask_out  u8    [B][k]  key_mask of the kept positions (1 / 0); maskf_out fp32 [B][k] the same as 1.0 / 0.0
+ *   origin_out int32 [B][k] origin_in[b][idx_out[b][r]] - origin_in int32 [B][S], NULL: the identity; origin_out may be NULL
+ * One workgroup per utterance, ranks by counting over keys in LDS, slots by ballot and popcount: no atomics, bit-reproducible, every
+ * output element written once.  Refused before anything is enqueued: a null pointer, idx_out equal to an input, mask_out == key_mask,
+ * maskf_out == score or origin_out == origin_in (NBEST_ERR_ARG), a bad k or S (NBEST_ERR_SHAPE), NBEST_ERR_ALIGN.                    */
+int nbest_token_select(const float* score, const uint8_t* key_mask, const int32_t* origin_in, int k, int32_t* idx_out, uint8_t* mask_out,
+                       float* maskf_out, int32_t* origin_out, int B, int S, nbest_stream_t stream);
+/* dst[b][r][:] = src[b][idx[b][r]][:] for r < k: src [B][S][H], dst [B][k][H] of dtype (bf16 or fp32), idx int32 [B][k] in [0, S)
+ * (an index outside is clamped into it).  16-byte accesses: H a multiple of 8 (bf16) or 4 (fp32), src and dst 16-byte aligned and
+ * different buffers.  Every dst element is written once.  NBEST_ERR_ARG / _SHAPE / _DTYPE / _ALIGN before anything is enqueued.      */
+int nbest_rows_compact(const void* src, const int32_t* idx, void* dst, int B, int S, int k, int H, int dtype, nbest_stream_t stream);
+/* nbest_encoder_infer that drops tokens between layers.  keep_host: n_keep == L - 1 positive, non-increasing int32 on the host;
+ * keep_host[l] tokens per utterance leave layer l.  S_0 = S, S_{l+1} = min(keep_host[l], S_l).  Where S_{l+1} == S_l nothing is
+ * launched for the layer, so a schedule of entries >= S is nbest_encoder_infer launch for launch.  Otherwise, after layer l:
+ *   score[b][j] = (1 / heads) sum_h sum_{i unmasked} P_l[b][h][i][j]   (nbest_attention_rollout_step on the layer's qkv and lse, r_in
+ *                                                                       the current mask as 1.0 / 0.0, residual 0)
+ *   nbest_token_select keeps S_{l+1} positions; nbest_rows_compact gathers the layer's output rows; the key mask shrinks with them.
+ * Layer l + 1 then runs on B S_{l+1} rows with sequence length S_{l+1}; the last layer reads the CLS rows (row 0 stays row 0).
+ * token_kept: NULL or int32 [L-1][B][S] on the device; row l = the ORIGINAL positions of the tokens that leave layer l, ascending,
+ * then -1 (a layer that eliminated nothing repeats the row below it; layer 0: the identity).
+ * ws >= nbest_encoder_infer_tokens_ws_bytes(d) = nbest_encoder_infer_ws_bytes(d) + score, index, origin and mask rows (22 B S bytes,
+ * each region rounded up to 256).  Refuses, before the first launch, what nbest_encoder_infer refuses, and desc.head_gate, desc.w8, a null or
+ * wrong-length schedule, an entry < 1, an increasing schedule (NBEST_ERR_ARG).                                                       */
+size_t nbest_encoder_infer_tokens_ws_bytes(const nbest_encoder_desc* d);
+int nbest_encoder_infer_tokens(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                               const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                               const int32_t* keep_host, int n_keep, int32_t* token_kept, nbest_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,16 @@ def parse_arguments(argv=None):
                         "per token and per segment (cls, sys, h1, h2, ..).  Not with --predict_fp8, --head_mask or --compact_heads")
     g.add_argument("--rollout_residual", type=float, default=None, metavar="R",
                    help="--predict_rollout: the weight R of the residual connection in every layer, 0 <= R <= 1 (default 0.5)")
+    g.add_argument("--token_keep", default=None, metavar="SPEC",
+                   help="with --predict FILE: drop low-attention tokens between layers (PoWER-BERT at a fixed count per layer; "
+                        "model.predict(token_keep=...)).  SPEC: L - 1 comma-separated non-increasing counts, the tokens per utterance "
+                        "that leave each layer but the last, or FIRST:LAST, a geometric schedule between the two.  [CLS] is always "
+                        "kept; counts >= the sequence length change nothing.  Not with --predict_fp8, --head_mask, --compact_heads, "
+                        "--predict_attention, --predict_attribution, --predict_rollout, --testing or --head_importance")
+    g.add_argument("--predict_tokens", default=None, metavar="PATH",
+                   help="with --token_keep: also write one JSON line per input line, in input order - the segments of the utterance "
+                        "(cls, sys, h1, h2, ..), their token counts and, per eliminating layer boundary, how many tokens of each "
+                        "segment are still there")
     g.add_argument("--predict_fp8", action="store_true",
                    help="with --predict FILE --dtype fp8w: label the file with the fp8 inference (model.predict(fp8=True)) - the "
                         "full-width GEMMs on the fp8 MFMA with static activation scales calibrated on the first --fp8_calib_batches "
@@ -331,6 +341,25 @@ def parse_arguments(argv=None):
         if opt.head_mask is not None or opt.compact_heads:
             ap.error("--predict_rollout together with %s is not built (the mean over heads under a head mask is not defined here)"
                      % ("--compact_heads" if opt.compact_heads else "--head_mask"))
+    if opt.predict_tokens is not None and opt.token_keep is None:
+        ap.error("--predict_tokens is an output of --token_keep: pass --predict FILE --token_keep SPEC too")
+    if opt.token_keep is not None:
+        if opt.predict is None:
+            ap.error("--token_keep is an inference flag: pass it with --predict FILE (%s)"
+                     % ("--testing runs the stash forward, where dropping tokens is not built" if opt.testing else
+                        "--head_importance runs the stash forward, where dropping tokens is not built" if opt.head_importance is not None
+                        else "training under token elimination is not built"))
+        for flag, on in (("--predict_fp8", opt.predict_fp8), ("--head_mask", opt.head_mask is not None), ("--compact_heads", opt.compact_heads),
+                         ("--predict_attention", opt.predict_attention is not None),
+                         ("--predict_attribution", opt.predict_attribution is not None),
+                         ("--predict_rollout", opt.predict_rollout is not None), ("--testing", opt.testing),
+                         ("--head_importance", opt.head_importance is not None)):
+            if on:
+                ap.error("--token_keep together with %s is not built" % flag)
+        try:
+            trainer.parse_token_keep(opt.token_keep, None)
+        except ValueError as e:
+            ap.error("--token_keep %s: %s" % (opt.token_keep, e))
     if opt.rollout_residual is not None:
         if opt.predict_rollout is None:
             ap.error("--rollout_residual is a setting of --predict_rollout: pass --predict_rollout PATH too")
@@ -628,12 +657,20 @@ def main(argv=None):
         attn_fp = open(opt.predict_attention, "w") if opt.predict_attention else None
         attr_fp = open(opt.predict_attribution, "w") if opt.predict_attribution else None
         roll_fp = open(opt.predict_rollout, "w") if opt.predict_rollout else None
+        token_keep = None
+        if opt.token_keep is not None:
+            try:
+                token_keep = trainer.parse_token_keep(opt.token_keep, cfg.num_hidden_layers)
+            except ValueError as e:
+                raise SystemExit("--token_keep %s: %s" % (opt.token_keep, e))
+        tok_fp = open(opt.predict_tokens, "w") if opt.predict_tokens else None
         try:
             cases = trainer.predict_split(model, trainer.read_predict_data(opt.predict), opt, memory, attn_fp=attn_fp, attr_fp=attr_fp,
                                           attr_steps=opt.attribution_steps, fp8=opt.predict_fp8, calib_batches=opt.fp8_calib_batches,
-                                          rollout_fp=roll_fp, rollout_residual=opt.rollout_residual)
+                                          rollout_fp=roll_fp, rollout_residual=opt.rollout_residual,
+                                          **({} if token_keep is None else dict(token_keep=token_keep, tokens_fp=tok_fp)))
         finally:
-            for fp in (attn_fp, attr_fp, roll_fp):
+            for fp in (attn_fp, attr_fp, roll_fp, tok_fp):
                 if fp is not None:
                     fp.close()
         with open(out_path, "w") as fp:

@@ -1204,9 +1204,33 @@ static LayerBufs infer_layer(const InferLayout& w, void* ws, bool fp8_pass) {
   if (fp8_pass) { b.x8 = (uint8_t*)(W + w.x8); b.ctx8 = (uint8_t*)(W + w.ctx8); b.x18 = (uint8_t*)(W + w.x18); b.h8 = (uint8_t*)(W + w.h8); }
   return b;
 }
+
+// token elimination (nbest_encoder_infer_tokens): after infer_layout, the rows the selection works on - the score and the current mask
+// as floats [B][S] f32, the kept indices [B][S] i32, two origin rows [B][S] i32 and two masks [B][S] u8 (each pair: read one, write
+// the other; the first mask read is the caller's).  Every shrunken row fits its full-width region.
+struct TokenLayout {
+  size_t score, maskf, idx, org[2], mask[2], total;
+};
+static TokenLayout token_layout(const nbest_encoder_desc* d, size_t base) {
+  TokenLayout t;
+  const size_t n = (size_t)d->B * d->S;
+  size_t o = base;
+  t.score = take(o, al(4 * n)); t.maskf = take(o, al(4 * n)); t.idx = take(o, al(4 * n));
+  t.org[0] = take(o, al(4 * n)); t.org[1] = take(o, al(4 * n)); t.mask[0] = take(o, al(n)); t.mask[1] = take(o, al(n));
+  t.total = o;
+  return t;
+}
+// the schedule of nbest_encoder_infer_tokens and where the kept positions go (NULL: nowhere)
+struct TokenPrune {
+  const int32_t* keep;
+  int32_t* token_kept;
+};
 }  // namespace
 
 extern "C" size_t nbest_encoder_infer_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(sizes(d)).total : 0; }
+extern "C" size_t nbest_encoder_infer_tokens_ws_bytes(const nbest_encoder_desc* d) {
+  return d ? token_layout(d, infer_layout(sizes(d)).total).total : 0;
+}
 extern "C" size_t nbest_encoder_infer_fp8_ws_bytes(const nbest_encoder_desc* d) { return d ? infer_layout(sizes(d), true).total : 0; }
 
 // cls_attn != NULL: also the CLS row's attention probabilities of every layer, [L][B][heads][S] fp32, each launched right after the
@@ -1216,9 +1240,11 @@ extern "C" size_t nbest_encoder_infer_fp8_ws_bytes(const nbest_encoder_desc* d) 
 // f8 (nbest_encoder_infer_fp8 only; no cls_attn, no pr): the descriptor carries the fp8 forward.  Without an activation history
 // (fp8_act == 0) the pass is the bf16 one plus the amax records of the GEMM inputs (Fwd::calib); with one, the full-width GEMMs run in
 // fp8 on static scales: nothing is recorded.
+// tp != NULL (nbest_encoder_infer_tokens only; no cls_attn, no pr, no f8, no head gate): tokens are dropped between the layers by the
+// schedule tp->keep (token_prune.hip), and every layer runs on the rows that are left; the workspace grows by token_layout.
 static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
                       const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out, float* cls_attn,
-                      const nbest_head_prune_images* pr, nbest_stream_t stream, bool f8 = false) {
+                      const nbest_head_prune_images* pr, nbest_stream_t stream, bool f8 = false, const TokenPrune* tp = nullptr) {
   if (f8) {
     NB_CHECK(d, NBEST_ERR_ARG, "encoder_infer_fp8: null descriptor");
     NB_CHECK(d->dtype == NBEST_BF16, NBEST_ERR_DTYPE, "encoder_infer_fp8: needs the bf16 path (dtype %d)", d->dtype);
@@ -1237,7 +1263,17 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
   NB_CHECK(wts && prm && ids && pos && key_mask && ws && cls_out, NBEST_ERR_ARG, "encoder_infer: null pointer");
   const Sizes z = sizes(d);
   const InferLayout w = infer_layout(z, f8);
-  NB_CHECK(ws_bytes >= w.total, NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes, w.total);
+  const TokenLayout tw = token_layout(d, w.total);
+  NB_CHECK(ws_bytes >= (tp ? tw.total : w.total), NBEST_ERR_WORKSPACE, "encoder_infer: workspace too small (%zu < %zu)", ws_bytes,
+           tp ? tw.total : w.total);
+  if (tp) {
+    NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder_infer_tokens: head gates (desc.head_gate) are not supported (a head mean under a gate is not defined)");
+    for (int l = 0; l + 1 < d->L; ++l) {
+      NB_CHECK(tp->keep[l] >= 1, NBEST_ERR_ARG, "encoder_infer_tokens: keep[%d] = %d < 1", l, tp->keep[l]);
+      NB_CHECK(l == 0 || tp->keep[l] <= tp->keep[l - 1], NBEST_ERR_ARG, "encoder_infer_tokens: the schedule increases at layer %d (%d after %d)",
+               l, tp->keep[l], tp->keep[l - 1]);
+    }
+  }
   if (pr) {
     NB_CHECK(pr->w && pr->bqkv && pr->layers_host, NBEST_ERR_ARG, "encoder_infer_pruned: null image pointer");
     NB_CHECK(!d->head_gate, NBEST_ERR_ARG, "encoder_infer_pruned: desc.head_gate must be NULL (the gate is folded into the compact Wo')");
@@ -1257,14 +1293,14 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
   if (fp8_pass) { c.q8 = true; c.arec = false; c.g.amax_new = nullptr; }   // static scales: no producer records
   const Ptrs& P = c.g.W;
   char* W = (char*)ws;
-  const int64_t M = z.M, B = d->B, SH = (int64_t)d->S * d->H;
+  const int64_t B = d->B;
   const int H = d->H, F = d->F, dt = d->dtype;
-  void* X[2] = {W + w.X0, W + w.X1};
+  void *cur = W + w.X0, *nxt = W + w.X1;   // the layer's input and output; they change places after every layer
   const LayerBufs b = infer_layer(w, ws, fp8_pass);
   auto probs = [&](int l) { return cls_attn ? cls_attn + (int64_t)l * B * d->heads * d->S : nullptr; };
 
   RUN(nbest_embed_ln_fwd(ids, seg, pos, P.W(d->off_word), P.W(d->off_type), P.W(d->off_pos), P.P(d->off_emb_ln_g), P.P(d->off_emb_ln_b),
-                         X[0], (float*)(W + w.emb_stats), M, H, d->ln_eps, dt, d->hidden_drop, d->seed, d->drop_stream_base,
+                         cur, (float*)(W + w.emb_stats), z.M, H, d->ln_eps, dt, d->hidden_drop, d->seed, d->drop_stream_base,
                          (hipStream_t)stream));
   // the compact matrices of layer l (pr != NULL); the packed image serves the full-width GEMMs of layers 0 .. L-2 only
   auto pruned = [&](int l) {
@@ -1273,18 +1309,47 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
     return PrunedLayer{t.k, wb + t.dst_wqkv * z.esz, pb ? pb + t.dst_wqkv * z.esz : nullptr, wb + t.dst_wo * z.esz,
                        pb ? pb + t.dst_wo * z.esz : nullptr, pr->bqkv + t.dst_bqkv};
   };
+  // Token elimination (tp != NULL): layer l runs on dl, a copy of the descriptor with S = S_l, and on M = B S_l rows; without it S_l = S
+  // throughout and dl is the descriptor.  `mask`: the key mask of the S_l tokens; `org`: their original positions (NULL: the identity).
+  nbest_encoder_desc dl = *d;
+  c.d = &dl;
+  const uint8_t* mask = key_mask;
+  const int32_t* org = nullptr;
+  int side = 0;            // which of tw.org / tw.mask the next selection writes
+  bool have_maskf = false;   // tw.maskf holds `mask` as floats (written by the first scored layer, then by every selection)
   for (int l = 0; l + 1 < d->L; ++l) {
+    c.g.M = B * dl.S; c.key_mask = mask;
     if (pr) {
       const PrunedLayer pl = pruned(l);
-      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, nullptr, nullptr, &pl));
+      RUN(layer_forward(c, l, cur, nxt, b, nullptr, nullptr, &pl));
     } else {
-      RUN(layer_forward(c, l, X[l & 1], X[(l + 1) & 1], b, b.x8, probs(l)));   // (fp8 pass: the next layer's x8 comes out of this LayerNorm)
+      RUN(layer_forward(c, l, cur, nxt, b, b.x8, probs(l)));   // (fp8 pass: the next layer's x8 comes out of this LayerNorm)
     }
+    std::swap(cur, nxt);
+    if (!tp) continue;
+    const int Sl = dl.S, k = std::min((int)tp->keep[l], Sl);
+    if (k < Sl) {   // score from the layer's own attention (its qkv and lse are still in the workspace), select, gather into the free X
+      hipStream_t st = (hipStream_t)stream;
+      float *score = (float*)(W + tw.score), *maskf = (float*)(W + tw.maskf);
+      int32_t *idx = (int32_t*)(W + tw.idx), *org_out = (int32_t*)(W + tw.org[side]);
+      uint8_t* mask_out = (uint8_t*)(W + tw.mask[side]);
+      if (!have_maskf) RUN(nbest_internal_mask_to_f32(mask, maskf, B * Sl, st));
+      RUN(nbest_attention_rollout_step(b.qkv, mask, b.lse, maskf, score, 0.f, d->B, Sl, d->heads, 64, dt, stream));
+      RUN(nbest_token_select(score, mask, org, k, idx, mask_out, maskf, org_out, d->B, Sl, stream));
+      RUN(nbest_rows_compact(cur, idx, nxt, d->B, Sl, k, H, dt, stream));
+      std::swap(cur, nxt);
+      mask = mask_out; org = org_out; have_maskf = true; side ^= 1;
+      dl.S = k;
+    }
+    if (tp->token_kept)
+      RUN(nbest_internal_token_kept_row(org, tp->token_kept + (int64_t)l * B * d->S, d->B, d->S, dl.S, (hipStream_t)stream));
   }
+  const int64_t M = B * dl.S, SH = (int64_t)dl.S * H;   // what reaches the last layer
+  key_mask = mask;
   // last layer, CLS rows only (weights read unpacked: the packed images are laid out for the full-width GEMMs)
   const int l = d->L - 1;
   const nbest_layer_offsets& o = d->layers_host[l];
-  const void* xin = X[l & 1];
+  const void* xin = cur;
   void* kv = b.qkv; void* q = b.ctx; void* cctx = b.r1; void* cx1 = b.x1; void* ch = b.hact; void* cr = b.r2;
   // pruned: Wqkv' [3 Hk][H] (Q rows, then K | V rows), bqkv', Wo' [H][Hk] and heads = k; Hk = H otherwise
   const PrunedLayer pl = pr ? pruned(l) : PrunedLayer{d->heads, P.W(o.wqkv), nullptr, P.W(o.wo), nullptr, P.P(o.bqkv)};
@@ -1307,7 +1372,7 @@ static int infer_impl(const nbest_encoder_desc* d, const void* wts, const float*
   g.lda = SH; g.epilogue = NBEST_EPI_BIAS; g.bias = pl.bqkv;
   RUN(nbest_gemm(&g, stream));
   if (cls_attn) RUN(nbest_internal_attention_cls_probs(q, H, kv, 2 * H, key_mask, probs(l), d->S, d->B, d->S, d->heads, 64, dt, stream));
-  RUN(nbest_attention_cls_fwd_internal(q, Hk, kv, 2 * Hk, key_mask, cctx, Hk, d->B, d->S, heads, 64, dt, stream, 0.f, 0, 0));
+  RUN(nbest_attention_cls_fwd_internal(q, Hk, kv, 2 * Hk, key_mask, cctx, Hk, d->B, dl.S, heads, 64, dt, stream, 0.f, 0, 0));
   if (d->head_gate) RUN(nbest_head_gate_fwd(cctx, H, cctx, H, d->head_gate + (int64_t)l * d->heads, B, d->heads, 64, dt, stream));
   g = gemm_nt(dt, cctx, pl.wo, cr, B, H, Hk);
   g.epilogue = NBEST_EPI_BIAS_DROP_RES; g.bias = P.P(o.bo); g.R = xin; g.ldr = SH;        // residual: the CLS rows
@@ -1340,6 +1405,16 @@ extern "C" int nbest_encoder_infer(const nbest_encoder_desc* d, const void* wts,
                                    const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
                                    nbest_stream_t stream) {
   return nbest_encoder_infer_attn(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, stream);
+}
+
+extern "C" int nbest_encoder_infer_tokens(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,
+                                          const int64_t* pos, const uint8_t* key_mask, void* ws, size_t ws_bytes, void* cls_out,
+                                          const int32_t* keep_host, int n_keep, int32_t* token_kept, nbest_stream_t stream) {
+  NB_CHECK(d, NBEST_ERR_ARG, "encoder_infer_tokens: null descriptor");
+  NB_CHECK(n_keep == d->L - 1, NBEST_ERR_ARG, "encoder_infer_tokens: the schedule has %d entries, L - 1 = %d are needed", n_keep, d->L - 1);
+  NB_CHECK(keep_host || n_keep == 0, NBEST_ERR_ARG, "encoder_infer_tokens: null schedule");
+  const TokenPrune tp = {keep_host, token_kept};
+  return infer_impl(d, wts, prm, ids, seg, pos, key_mask, ws, ws_bytes, cls_out, nullptr, nullptr, stream, false, &tp);
 }
 
 extern "C" int nbest_encoder_infer_fp8(const nbest_encoder_desc* d, const void* wts, const float* prm, const int64_t* ids, const int64_t* seg,

@@ -46,6 +46,12 @@ int nbest_internal_attention_cls_bwd(const void* qkv, const uint8_t* key_mask, c
 int nbest_internal_attention_cls_probs(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const uint8_t* key_mask, float* probs,
                                        int64_t ldp, int B, int S, int heads, int d, int dtype, nbest_stream_t stream);
 
+// ---- token_prune.hip ----------------------------------------------------------------------------
+// out[i] = mask[i] ? 1 : 0 (the key mask as the first scored layer's r_in)
+int nbest_internal_mask_to_f32(const uint8_t* mask, float* out, int64_t n, hipStream_t stream);
+// out [B][S] = the k origins of each utterance (origin [B][k]; NULL: 0 .. k-1), then -1
+int nbest_internal_token_kept_row(const int32_t* origin, int32_t* out, int B, int S, int k, hipStream_t stream);
+
 // ---- gemm.hip: what the GEMM generations share ---------------------------------------------------
 // Split-K plan of a grid of `tiles` output tiles: the smallest split count whose grid fills whole rounds of the `slots`
 // workgroups resident at once (>= 93 %) with at least `min_blocks` workgroups, else the one with the fullest rounds; each

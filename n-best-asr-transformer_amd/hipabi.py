@@ -36,6 +36,7 @@ EXPORTS = [
     "nbest_gemm_fp8_plan", "nbest_wgrad_fp8_plan",
     "nbest_fp8_amax_fold_max", "nbest_encoder_infer_fp8_ws_bytes", "nbest_encoder_infer_fp8",
     "nbest_attention_rollout_step",
+    "nbest_token_select", "nbest_rows_compact", "nbest_encoder_infer_tokens_ws_bytes", "nbest_encoder_infer_tokens",
 ]
 
 
@@ -140,7 +141,8 @@ def lib():
                 raise RuntimeError("nbest_amd: %s does not export %s" % (LIB_PATH, name))
         for name in ("nbest_embed_bwd_ws_bytes", "nbest_gemm_ws_bytes", "nbest_wgrad_pair_ws_bytes", "nbest_rowred_ws_bytes", "nbest_heads_ws_bytes",
                      "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_embed_adv_ws_bytes", "nbest_cls_contrast_ws_bytes",
-                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer_fp8_ws_bytes"):
+                     "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer_fp8_ws_bytes",
+                     "nbest_encoder_infer_tokens_ws_bytes"):
             getattr(L, name).restype = C.c_size_t
         L.nbest_embed_bwd_ws_bytes.argtypes = [C.c_int64, C.c_int64]
         L.nbest_rows_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -223,6 +225,10 @@ def lib():
         L.nbest_attention_probs.argtypes = [vp] * 4 + [i32] * 5 + [vp]
         L.nbest_attention_cls_probs.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp]
         L.nbest_attention_rollout_step.argtypes = [vp] * 5 + [f32] + [i32] * 5 + [vp]
+        L.nbest_token_select.argtypes = [vp] * 3 + [i32] + [vp] * 4 + [i32, i32, vp]
+        L.nbest_rows_compact.argtypes = [vp] * 3 + [i32] * 5 + [vp]
+        L.nbest_encoder_infer_tokens_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]
+        L.nbest_encoder_infer_tokens.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, C.POINTER(C.c_int32), i32, vp, vp]
         L.nbest_encoder_backward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 9 + [sz, vp, vp, sz, i32, i32, i32, i32, vp]
         L.nbest_transpose_weights.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nbest_pack_bn.argtypes = [i64]
@@ -824,6 +830,40 @@ def encoder_infer_fp8(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out):
     """nbest_encoder_infer_fp8 -> cls_out [B, H]: the calibration pass or the fp8 pass, as the descriptor's fp8 fields say"""
     check(lib().nbest_encoder_infer_fp8(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
                                         ws.numel(), ptr(cls_out), stream_ptr()), "encoder_infer_fp8")
+
+
+def token_select(score, key_mask, k, origin=None, want_origin=True):
+    """nbest_token_select: per utterance the ``k`` positions to keep of fp32 [B, S] ``score`` under u8 [B, S] ``key_mask`` (position 0,
+    then unmasked before masked, numbers before NaN, higher score, lower index) -> (idx int32 [B, k] ascending, mask u8 [B, k],
+    maskf fp32 [B, k], origin int32 [B, k] or None); ``origin`` int32 [B, S]: what idx is translated through (None: the identity)"""
+    B, S = score.shape
+    dev = score.device
+    idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, k, dtype=torch.uint8, device=dev)
+    maskf = torch.empty(B, k, dtype=torch.float32, device=dev)
+    org = torch.empty(B, k, dtype=torch.int32, device=dev) if want_origin else None
+    check(lib().nbest_token_select(ptr(score), ptr(key_mask), ptr(origin), k, ptr(idx), ptr(mask), ptr(maskf), ptr(org), B, S, stream_ptr()),
+          "token_select")
+    return idx, mask, maskf, org
+
+
+def rows_compact(src, idx, out=None):
+    """nbest_rows_compact: ``src`` [B, S, H] (bf16 / fp32, contiguous) gathered by int32 [B, k] ``idx`` -> [B, k, H]"""
+    B, S, H = src.shape
+    k = idx.shape[1]
+    dst = torch.empty(B, k, H, dtype=src.dtype, device=src.device) if out is None else out
+    check(lib().nbest_rows_compact(ptr(src), ptr(idx), ptr(dst), B, S, k, H, dtype_code(src.dtype), stream_ptr()), "rows_compact")
+    return dst
+
+
+def encoder_infer_tokens(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, keep, token_kept=None):
+    """nbest_encoder_infer_tokens -> cls_out [B, H]: nbest_encoder_infer that keeps ``keep[l]`` tokens per utterance after layer l
+    (L - 1 host ints); ``token_kept`` (int32 [L - 1, B, S] or None) receives the original positions that leave every layer"""
+    n = len(keep)
+    arr = (C.c_int32 * max(n, 1))(*[int(x) for x in keep])
+    check(lib().nbest_encoder_infer_tokens(C.byref(desc), ptr(wts), ptr(prm), ptr(ids), ptr(seg), ptr(pos), ptr(key_mask), ptr(ws),
+                                           ws.numel(), ptr(cls_out), arr, n, ptr(token_kept), stream_ptr()), "encoder_infer_tokens")
+    return cls_out
 
 
 def encoder_infer(desc, wts, prm, ids, seg, pos, key_mask, ws, cls_out, cls_attn=None):

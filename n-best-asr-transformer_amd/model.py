@@ -1044,7 +1044,8 @@ class NBestSTCModel(nn.Module):
         return adv_loss, norm
 
     # ---- inference (forward only, CLS rows of the last layer) ------------------------------------
-    def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False, fp8=False):
+    def predict(self, input_ids, seg_ids=None, return_attns=False, return_logits=False, fp8=False, token_keep=None,
+                return_token_kept=False):
         """Scores and decoded labels of one batch through nbest_encoder_infer: no activation stash, no dropout (in either
         mode), the heads on the compact CLS rows.  Returns dict(top, bott, final, cls [B, H] compute dtype, pred int32 [B, n_top]).
         ``return_attns``: also ``cls_attn``, fp32 [L, B, heads, S] - the CLS row's attention probabilities of every layer
@@ -1062,8 +1063,33 @@ class NBestSTCModel(nn.Module):
         calibration (2^floor(log2(224 / amax)): a value up to twice the calibrated amax is representable, beyond that the e4m3 cast
         saturates silently); the B CLS rows of the last layer and the heads stay bf16.  RuntimeError on a model without the fp8
         forward, before a calibration and under a head mask (compact or not); ValueError with ``return_attns``.  Without the
-        argument nothing changes: the bf16 path, bit for bit."""
+        argument nothing changes: the bf16 path, bit for bit.
+        ``token_keep`` (L - 1 positive, non-increasing ints): nbest_encoder_infer_tokens - after layer l every utterance keeps
+        [CLS] plus the ``token_keep[l] - 1`` other tokens that received the most attention in that layer (head mean of the column
+        sums over the unmasked queries; unmasked before padding, ties to the lower index), and the layers above run on the shorter
+        sequence.  S_0 = S, S_{l+1} = min(token_keep[l], S_l); a layer that drops nothing launches nothing, so a schedule of entries
+        >= S gives the bits of the call without it.  ``return_token_kept``: also ``token_kept``, int32 [L - 1, B, S] (the original
+        positions that leave layer l, ascending, then -1) and ``token_counts``, the host list [S_0, ..., S_{L-1}].  ValueError for a
+        wrong length, an entry < 1, an increasing schedule, ``return_attns`` with it, or ``return_token_kept`` without it;
+        RuntimeError with ``fp8=True`` and under any head mask (not built).  ``None``: today's path, bit for bit."""
         cfg = self.cfg
+        if token_keep is not None:
+            keep = [int(x) for x in token_keep]
+            if len(keep) != cfg.num_hidden_layers - 1:
+                raise ValueError("nbest_amd predict: token_keep needs L - 1 = %d entries (got %d)" % (cfg.num_hidden_layers - 1, len(keep)))
+            if any(x < 1 for x in keep):
+                raise ValueError("nbest_amd predict: token_keep entries must be >= 1 (got %r)" % (keep,))
+            if any(y > x for x, y in zip(keep, keep[1:])):
+                raise ValueError("nbest_amd predict: token_keep must be non-increasing (got %r)" % (keep,))
+            if return_attns:
+                raise ValueError("nbest_amd predict: return_attns with token_keep is not built (cls_attn would change width per layer)")
+            if fp8:
+                raise RuntimeError("nbest_amd predict: token_keep with fp8=True is not built")
+            if self._head_mask is not None:
+                raise RuntimeError("nbest_amd predict: token_keep under a head mask (gated or compact) is not built (the mean over "
+                                   "heads under a gate is not defined here); call set_head_mask(None) first")
+        elif return_token_kept:
+            raise ValueError("nbest_amd predict: return_token_kept needs token_keep")
         if fp8:
             if not self.fp8_forward:
                 raise RuntimeError("nbest_amd predict(fp8=True): the model was not built with fp8_forward=True (--dtype fp8w)")
@@ -1089,9 +1115,20 @@ class NBestSTCModel(nn.Module):
         d.seed = 0
         self._set_head_gate(d)
         self._set_weights(d, "infer")
-        ws = self._grow(vars(self), "_infer_ws", hb.lib().nbest_encoder_infer_ws_bytes(C.byref(d)))
+        ws_bytes = hb.lib().nbest_encoder_infer_ws_bytes if token_keep is None else hb.lib().nbest_encoder_infer_tokens_ws_bytes
+        ws = self._grow(vars(self), "_infer_ws", ws_bytes(C.byref(d)))
         a = self.arena
         cls = torch.empty(B, H, dtype=self.compute_dtype, device=self.device)
+        if token_keep is not None:
+            kept = torch.empty(len(keep), B, S, dtype=torch.int32, device=self.device) if return_token_kept else None
+            hb.encoder_infer_tokens(d, a.weights, a.p, ids, seg, pos, mask, ws, cls, keep, kept)
+            out = self._heads_out(cls, return_logits)
+            if return_token_kept:
+                counts = [S]
+                for x in keep:
+                    counts.append(min(x, counts[-1]))
+                out["token_kept"], out["token_counts"] = kept, counts
+            return out
         cls_attn = torch.empty(cfg.num_hidden_layers, B, cfg.num_attention_heads, S, dtype=torch.float32,
                                device=self.device) if return_attns else None
         if self._head_mask_compact:

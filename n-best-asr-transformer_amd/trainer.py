@@ -1027,6 +1027,94 @@ def rollout_record(line, spans, row, residual):
             "mass": [round(sum(t[lo:hi]), 6) for _, lo, hi in spans], "token_rollout": [round(x, 6) for x in t]}
 
 
+def token_keep_schedule(L, first, last):
+    """A --token_keep schedule for an L-layer encoder: L - 1 non-increasing ints running geometrically from ``first`` (the tokens
+    that leave layer 0) to ``last`` (those that reach the last layer), entry i = round(first (last / first)^(i / (L - 2))).
+    L = 1 gives [], L = 2 gives [last] (the one boundary there is leads to the last layer).  ValueError unless
+    L >= 1 and first >= last >= 1."""
+    L, first, last = int(L), int(first), int(last)
+    if L < 1:
+        raise ValueError("token_keep_schedule: L must be >= 1 (got %d)" % L)
+    if not first >= last >= 1:
+        raise ValueError("token_keep_schedule: needs first >= last >= 1 (got %d, %d)" % (first, last))
+    n = L - 1
+    if n <= 1:
+        return [last] * n
+    out = [int(round(first * (last / float(first)) ** (i / float(n - 1)))) for i in range(n)]
+    out[0], out[-1] = first, last
+    for i in range(1, n):                                     # (rounding cannot raise a geometric sequence, but say so in code)
+        out[i] = max(last, min(out[i], out[i - 1]))
+    return out
+
+
+def parse_token_keep(spec, L):
+    """--token_keep SPEC -> the schedule for an L-layer encoder: ``a,b,c`` (L - 1 counts) or ``first:last``
+    (token_keep_schedule).  ``L`` None: check the syntax and what can be checked without the encoder's depth, return None.
+    ValueError names what is wrong."""
+    try:
+        if ":" in spec:
+            parts = [int(x) for x in spec.split(":")]
+            if len(parts) != 2:
+                raise ValueError
+            keep = token_keep_schedule(1 if L is None else L, parts[0], parts[1])   # (L None: its checks of first and last)
+            return None if L is None else keep
+        keep = [int(x) for x in spec.split(",")] if spec.strip() else []
+    except ValueError as e:
+        if str(e).startswith("token_keep_schedule"):
+            raise
+        raise ValueError("expected L - 1 comma-separated integers or FIRST:LAST")
+    if any(x < 1 for x in keep):
+        raise ValueError("every count must be >= 1")
+    if any(y > x for x, y in zip(keep, keep[1:])):
+        raise ValueError("the counts must not increase")
+    if L is not None and len(keep) != L - 1:
+        raise ValueError("%d counts for an encoder of %d layers (L - 1 = %d are needed)" % (len(keep), L, L - 1))
+    return None if L is None else keep
+
+
+def token_select_reference(score, mask, k):
+    """The selection of nbest_token_select restated with numpy.  ``score`` [B, S] (any float dtype; taken as fp64), ``mask`` [B, S]
+    (non-zero = a real token), 1 <= k <= S -> int64 [B, k]: position 0, then the k - 1 first of the other positions in the order
+    unmasked before masked, number before NaN, higher score first, lower index first - returned ascending."""
+    sc = np.asarray(score.detach().cpu().numpy() if torch.is_tensor(score) else score, dtype=np.float64)
+    mk = np.asarray(mask.detach().cpu().numpy() if torch.is_tensor(mask) else mask) != 0
+    B, S = sc.shape
+    if not 1 <= k <= S:
+        raise ValueError("token_select_reference: k=%d outside 1..S=%d" % (k, S))
+    out = np.zeros((B, k), dtype=np.int64)
+    for b in range(B):
+        nan = np.isnan(sc[b, 1:])
+        val = np.where(nan, 0.0, sc[b, 1:]) + 0.0
+        # lexsort: the LAST key is the primary one; it is stable, so equal keys stay in index order
+        order = np.lexsort((np.arange(S - 1), -val, nan, ~mk[b, 1:]))
+        out[b] = np.sort(np.concatenate(([0], 1 + order[:k - 1])))
+    return out
+
+
+def token_prune_reference(attn, mask, k):
+    """Score and selection of one eliminating layer of ``model.predict(token_keep=...)`` restated in fp64 (PoWER-BERT's
+    significance score).  ``attn``: the layer's attention map [B, heads, S, S] (``forward(return_attns=True)[l]``), ``mask``
+    [B, S] -> (score fp64 [B, S] = mean over heads of the column sums over the unmasked queries, idx int64 [B, k] =
+    token_select_reference of it)."""
+    a = np.asarray(attn.detach().double().cpu().numpy() if torch.is_tensor(attn) else attn, dtype=np.float64)
+    mk = (np.asarray(mask.detach().cpu().numpy() if torch.is_tensor(mask) else mask) != 0).astype(np.float64)
+    score = np.einsum("bi,bhij->bj", mk, a) / a.shape[1]
+    return score, token_select_reference(score, mk, k)
+
+
+def token_prune_record(line, spans, kept):
+    """one --predict_tokens JSON record.  ``kept``: int [L - 1, >= tokens] of one utterance (model.predict(...,
+    return_token_kept=True)["token_kept"][:, b]): per layer boundary the original positions still there, then -1; ``spans``:
+    inputs.utterance_segments of it (as attention_record).  ``kept[l][s]`` = how many tokens of segment s leave layer l
+    (kept padding positions belong to no segment)."""
+    rows = kept.tolist() if hasattr(kept, "tolist") else kept
+    out = []
+    for row in rows:
+        there = set(int(x) for x in row if x >= 0)
+        out.append([sum(1 for p in range(lo, hi) if p in there) for _, lo, hi in spans])
+    return {"line": line, "segments": [n for n, _, _ in spans], "tokens": [hi - lo for _, lo, hi in spans], "kept": out}
+
+
 def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
     """one --predict_attribution JSON record.  ``attr_row``: per label, fp32 [>= tokens] integrated-gradients attribution of one
     utterance (model.attribute); ``spans``: inputs.utterance_segments of it (as attention_record); ``labels`` / ``scores`` /
@@ -1044,7 +1132,7 @@ def attribution_record(line, spans, attr_row, labels, scores, baselines, steps):
 
 @torch.no_grad()
 def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_steps=32, fp8=False, calib_batches=8, rollout_fp=None,
-                  rollout_residual=0.5):
+                  rollout_residual=0.5, token_keep=None, tokens_fp=None):
     """Labels of every utterance of a split through ``model.predict`` (forward only, CLS rows of the last layer):
     [(asr words, predicted labels)] in split order.  Same batches, device decode and label strings as eval_epoch (the
     ontology filter too), so the labels equal eval_epoch's pred column for the same model and data.  One GPU only.
@@ -1054,7 +1142,9 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     ``fp8`` (--predict_fp8): ``model.fp8_calibrate`` on the first ``calib_batches`` batches of the split (from scratch), one line on
     stdout about what was recorded, then every batch through ``model.predict(fp8=True)``.
     ``rollout_fp`` (--predict_rollout): one rollout_record JSON line per utterance, in split order - the CLS attention rollout
-    (model.attention_rollout with ``rollout_residual``); the labels still come from ``model.predict``."""
+    (model.attention_rollout with ``rollout_residual``); the labels still come from ``model.predict``.
+    ``token_keep`` (--token_keep): every batch through ``model.predict(token_keep=...)``; ``tokens_fp`` (--predict_tokens): one
+    token_prune_record JSON line per utterance, in split order.  Not with ``fp8`` or any of the other outputs."""
     _, world = dist_info()
     if world > 1:
         raise RuntimeError("nbest_amd: predicting a file runs on one GPU (world size %d); start it without torchrun" % world)
@@ -1063,6 +1153,10 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
     split = encoded(data, opt, memory)
     n_accum = max(1, int(getattr(opt, "n_accum_steps", 1) or 1))
     lists = batch_indices(len(split), max(1, int(opt.batchSize / n_accum)))
+    if token_keep is None and tokens_fp is not None:
+        raise RuntimeError("nbest_amd: the token record is an output of token_keep")
+    if token_keep is not None and (fp8 or attn_fp is not None or attr_fp is not None or rollout_fp is not None):
+        raise RuntimeError("nbest_amd: token_keep together with fp8, attention maps, attributions or the rollout is not built")
     if fp8:
         if attn_fp is not None or attr_fp is not None or rollout_fp is not None:
             raise RuntimeError("nbest_amd: the fp8 inference writes no attention maps, no attributions and no rollout")
@@ -1076,15 +1170,22 @@ def predict_split(model, data, opt, memory, attn_fp=None, attr_fp=None, attr_ste
               % (len(head), sum(len(m) for m in head), ", ".join(kinds)), flush=True)
     for bi, mine, b in Prefetcher(split, lists, model.device):
         seg = b["seg"] if opt.add_segment_ids else None
-        out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None, fp8=fp8)
+        if token_keep is None:
+            out = model.predict(b["ids"], seg_ids=seg, return_attns=attn_fp is not None, fp8=fp8)
+        else:
+            out = model.predict(b["ids"], seg_ids=seg, token_keep=token_keep, return_token_kept=tokens_fp is not None)
         pipe.push(out, [split.labels[j] for j in mine], tag=mine)
         spans_of = {}
-        for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None or rollout_fp is not None) else []):
+        for k, j in enumerate(mine if (attn_fp is not None or attr_fp is not None or rollout_fp is not None or tokens_fp is not None) else []):
             spans = utterance_segments(split.asr[j], opt.tokenizer, opt, getattr(opt, "n_best", None), getattr(opt, "max_seq_len", None))
             if spans[-1][2] != len(split.rows[j][0]):
                 raise RuntimeError("nbest_amd: line %d: segment spans cover %d tokens, the encoded utterance has %d"
                                    % (j + 1, spans[-1][2], len(split.rows[j][0])))
             spans_of[j] = spans
+        if tokens_fp is not None:
+            tk = out["token_kept"].cpu()
+            for k, j in enumerate(mine):
+                tokens_fp.write(json.dumps(token_prune_record(j + 1, spans_of[j], tk[:, k])) + "\n")
         if attn_fp is not None:
             ca = out["cls_attn"].cpu()
             for k, j in enumerate(mine):
