@@ -704,6 +704,41 @@ int nbest_ema_update(float* ema, const float* p, const nbest_tensor_desc* descs,
                      float one_minus_decay, nbest_stream_t stream);
 int nbest_ema_exchange(float* p, float* ema, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
                        nbest_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
+ * K9l  LoRA on merged weights (--lora_rank; new functionality, the reference has none).  The encoder keeps reading the merged
+ * matrix W = W0 + s B A (s = alpha / r) from the arenas; the factors live in an adapter arena `ab` (fp32) and never appear inside
+ * a layer.  One table of nbest_lora_desc, ordered by tile_start, has one entry per adapted BLOCK: a contiguous row range of one
+ * arena matrix (so query / key / value, the row thirds of the fused [3H, H] matrix, are blocks of their own).  A [rank, cols] and
+ * B [rows, rank] are row-major at a_off / b_off of `ab`; `base` holds a packed [rows, cols] copy of W0's block at base_off.
+ * The table is passed twice: descs_host (checked on the host before anything is enqueued) and descs_dev, the same bytes in device
+ * memory (what the kernels read).  nbest_lora_plan fills tile_start and ws_off of a host table (tiles of 64 rows x 256 columns)
+ * and returns the tile total and the workspace of nbest_lora_grad (== nbest_lora_grad_ws_bytes).
+ * nbest_lora_merge: p[i, j] = base[i, j] + scale * sum_{k < rank} B[i, k] A[k, j] for every element of every block, in fp32, k
+ *   ascending; p_lowp != NULL: also the bf16 (round to nearest even) of that value at the same element offset.  One writer per
+ *   element, nothing outside the blocks is written; a result that compares equal to base keeps base's bits (B = 0: p == base).
+ *   8 B per element (+ 2), one launch.
+ * nbest_lora_grad: g_ab[a_off + k cols + j] = scale * sum_i B[i, k] g[i, j] and g_ab[b_off + i rank + k] = scale * sum_j g[i, j] A[k, j],
+ *   g the dense gradient at the offsets of p.  g is read once (4 B per element); tile partials go to ws and a second launch adds
+ *   them in tile order: no atomics, bit-identical run to run whatever ws held before.  Two launches.
+ * Refused before the first launch: a NULL pointer, rank outside 1 .. NBEST_LORA_MAX_RANK, a tile_start / ws_off that is not
+ * nbest_lora_plan's (NBEST_ERR_ARG); cols % 4 != 0, stride != cols (NBEST_ERR_SHAPE); an offset that is no multiple of 4 elements
+ * or a buffer that is not 16-byte aligned (NBEST_ERR_ALIGN); a short ws (NBEST_ERR_WORKSPACE).                                     */
+#define NBEST_LORA_MAX_RANK 64
+typedef struct nbest_lora_desc {
+  int64_t p_off;       /* first element of the block in p / p_lowp / g */
+  int64_t base_off;    /* ... of its packed copy in base */
+  int64_t a_off, b_off;/* A [rank, cols], B [rows, rank] in ab / g_ab */
+  int64_t ws_off;      /* nbest_lora_plan: the block's partials in ws (elements) */
+  int32_t rows, cols, stride, rank;   /* stride: row stride in p (== cols) */
+  float scale;         /* alpha / rank */
+  int32_t tile_start;  /* nbest_lora_plan: sum of the earlier blocks' ceil(rows / 64) * ceil(cols / 256) */
+} nbest_lora_desc;
+int nbest_lora_plan(nbest_lora_desc* descs_host, int n, int* n_tiles, size_t* ws_bytes);
+size_t nbest_lora_grad_ws_bytes(const nbest_lora_desc* descs_host, int n);
+int nbest_lora_merge(float* p, void* p_lowp /* may be NULL */, const float* base, const float* ab, const nbest_lora_desc* descs_host,
+                     const nbest_lora_desc* descs_dev, int n, nbest_stream_t stream);
+int nbest_lora_grad(const float* g, const float* ab, float* g_ab, const nbest_lora_desc* descs_host, const nbest_lora_desc* descs_dev,
+                    int n, void* ws, size_t ws_bytes, nbest_stream_t stream);
 /* Transposed bf16 copy of the weight matrices (same element offsets in `dst` as in `src`): matrix t is
  * [rows][cols] in src and [cols][rows] in dst.  The backward's dgrad GEMMs read this copy so that both of
  * their operands are k-contiguous (no transposed LDS reads).  descs: DEVICE array ordered by tile_start,

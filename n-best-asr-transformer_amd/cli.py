@@ -229,7 +229,74 @@ def parse_arguments(argv=None):
                         "GPU; not with --adv_epsilon, --dtype fp8w or --train_head_mask")
     g.add_argument("--contrastive_temperature", type=float, default=None, metavar="T",
                    help="with --contrastive_weight: the temperature the cosines are divided by; finite and > 0 (default 0.1)")
+    g.add_argument("--lora_rank", type=int, default=None, metavar="R",
+                   help="LoRA (Hu et al., 2022): freeze the encoder and train a rank-R update W0 + (A / R) B A on the --lora_targets "
+                        "matrices of every layer, plus the STC heads; 1 <= R <= 64.  The arenas keep the merged weights (the encoder "
+                        "kernels are untouched: nbest_lora_grad projects the dense weight gradient onto the factors, nbest_lora_merge "
+                        "rewrites the adapted blocks after the update), so model.pt holds merged weights in the reference's keys and "
+                        "every scoring flag works on it; lora.pt (factors + heads + base digest, a few MB) is written next to it; "
+                        "exp_dir gains __lora_r<R>_a<A>_<targets joined by '+'>.  A training flag, one GPU, --optim_choice bertadam; "
+                        "not with --dtype fp8w, --shard_optimizer on, --ema_decay, --freeze_embeddings / --freeze_layers, "
+                        "--train_head_mask or --adv_epsilon.  Adapter dropout is not built (it cannot act on merged weights)")
+    g.add_argument("--lora_alpha", type=float, default=None, metavar="A", help="with --lora_rank: the update is scaled by A / R (default 2 R)")
+    g.add_argument("--lora_targets", default=None, metavar="t0,t1,...",
+                   help="with --lora_rank: the adapted matrices, from query, key, value, attn_out, ffn_up, ffn_down (default query,value)")
+    g.add_argument("--lora_lr", type=float, default=None, metavar="LR", help="with --lora_rank: learning rate of the factors (default --lr)")
+    g.add_argument("--lora_adapter", default=None, metavar="FILE",
+                   help="with --testing, --predict or --head_importance: after <exp_dir>/model.pt (the BASE weights) is loaded, apply "
+                        "the lora.pt of a --lora_rank run (factors and heads) and merge.  The file carries a digest of the base blocks "
+                        "it was trained on: a model.pt that differs there (an already merged one, say) exits naming both digests")
     opt = ap.parse_args(argv)
+    scoring = (("--testing", opt.testing), ("--predict", opt.predict is not None), ("--head_importance", opt.head_importance is not None))
+    if opt.lora_rank is None:
+        for flag, v in (("--lora_alpha", opt.lora_alpha), ("--lora_targets", opt.lora_targets), ("--lora_lr", opt.lora_lr)):
+            if v is not None:
+                ap.error("%s is a setting of --lora_rank: pass --lora_rank R too" % flag)
+    else:
+        from . import lora as _lora
+        for flag, on in scoring:
+            if on:
+                ap.error("--lora_rank is a training flag: %s reads model.pt from the directory named without it (apply an adapter "
+                         "file to a base model with --lora_adapter FILE)" % flag)
+        if opt.lora_alpha is None:
+            opt.lora_alpha = 2.0 * opt.lora_rank
+        try:
+            opt.lora_rank, opt.lora_alpha, _ = _lora.check_config(opt.lora_rank, opt.lora_alpha, 1)
+            opt.lora_targets = ",".join(_lora.parse_targets("query,value" if opt.lora_targets is None else opt.lora_targets))
+        except ValueError as e:
+            ap.error("--lora_rank / --lora_alpha / --lora_targets: %s" % e)
+        if opt.lora_lr is None:
+            opt.lora_lr = opt.lr
+        if not (opt.lora_lr > 0.0 and math.isfinite(opt.lora_lr)):
+            ap.error("--lora_lr %s: must be a finite number > 0" % opt.lora_lr)
+        if opt.dtype == "fp8w":
+            ap.error("--lora_rank together with --dtype fp8w is not built (the e4m3 weight copies are quantised from the full master "
+                     "after every step; LoRA under fp8 has not been measured)")
+        if opt.optim_choice != "bertadam":
+            ap.error("--lora_rank together with --optim_choice %s is not built (its global-norm clip would have to span the main and "
+                     "the adapter arena); use --optim_choice bertadam" % opt.optim_choice)
+        if opt.shard_optimizer == "on":
+            ap.error("--lora_rank together with --shard_optimizer on is not built (the adapter arena is not sharded)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--lora_rank runs on one GPU: LoRA under data parallelism is not built (world size %s)" % os.environ["WORLD_SIZE"])
+        if opt.ema_decay is not None:
+            ap.error("--lora_rank together with --ema_decay is not built (the average would have to follow the factors, not the "
+                     "merged weights)")
+        if opt.freeze_embeddings or opt.freeze_layers > 0:
+            ap.error("--lora_rank freezes the whole encoder itself: not with --freeze_embeddings or --freeze_layers (adapting only "
+                     "some layers from the command line is not built)")
+        if opt.train_head_mask is not None:
+            ap.error("--lora_rank together with --train_head_mask is not built (LoRA under a head mask)")
+        if opt.adv_epsilon is not None:
+            ap.error("--lora_rank together with --adv_epsilon is not built (FGM needs trainable embeddings, LoRA freezes them)")
+    if opt.lora_adapter is not None:
+        if not any(on for _, on in scoring):
+            ap.error("--lora_adapter applies to --testing, --predict and --head_importance: a training run writes lora.pt itself "
+                     "(--lora_rank)")
+        if opt.dtype == "fp8w":
+            ap.error("--lora_adapter together with --dtype fp8w is not built (LoRA on an fp8w model)")
+        if not os.path.isfile(opt.lora_adapter):
+            ap.error("--lora_adapter %s: no such file" % opt.lora_adapter)
     if opt.contrastive_weight is None:
         if opt.contrastive_temperature is not None:
             ap.error("--contrastive_temperature applies to --contrastive_weight only")
@@ -466,6 +533,9 @@ def exp_dir(opt):
         parts.append("fgm_%s" % opt.adv_epsilon)
     if getattr(opt, "contrastive_weight", None) is not None:
         parts.append("cl_%s_%s" % (opt.contrastive_weight, opt.contrastive_temperature))
+    if getattr(opt, "lora_rank", None) is not None:
+        from . import lora as _lora
+        parts.append(_lora.exp_dir_part(opt.lora_rank, opt.lora_alpha, opt.lora_targets))
     if getattr(opt, "train_head_mask", None) is not None:                                # last: the mask's digest, not the file's name
         parts.append("hm_%s" % trainer.head_mask_file_digest(opt.train_head_mask))
     return os.path.join(opt.experiment, "data_%s" % opt.dataset, "__".join(parts))
@@ -509,6 +579,22 @@ def load_teacher(opt, family, cfg, labels, dev):
     for p in teacher.parameters():
         p.requires_grad_(False)
     return teacher, sd
+
+
+def _lora_checkpoint(model):
+    from . import lora as _lora
+    return _lora.checkpoint_entry(model)
+
+
+def apply_lora_adapter(model, path):
+    """--lora_adapter: the adapter file on top of the base weights the model holds; the model is left plain (merged weights, LoRA
+    off), so everything that scores a model.pt runs as on a merged one"""
+    from . import lora as _lora
+    try:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        _lora.load(model, sd, keep=False)
+    except (ValueError, KeyError, RuntimeError) as e:
+        raise SystemExit("--lora_adapter %s: %s" % (path, e))
 
 
 def predict_output_path(opt):
@@ -599,6 +685,12 @@ def main(argv=None):
     frozen = freeze_parameters(model, opt.freeze_embeddings, opt.freeze_layers)
     n_params = sum(s.numel for s in model.arena.slots if s.name not in frozen)
     n_bert = sum(s.numel for s in model.arena.slots if "bert_encoder" in s.name and s.name not in frozen)
+    lora_cfg = None
+    if opt.lora_rank is not None:                          # after the weights are in place: they become the base
+        lora_cfg = dict(rank=opt.lora_rank, alpha=opt.lora_alpha, targets=opt.lora_targets.split(","), seed=opt.random_seed)
+        st = model.enable_lora(**lora_cfg)
+        n_bert = st.n_trainable
+        n_params = n_bert + sum(s.numel for s in model.arena.slots if s.name.startswith("clf."))
     # (the weights are in place: --init_checkpoint is the usual companion; a mask of the wrong shape exits before a directory is made)
     train_mask = None
     if opt.train_head_mask is not None:                    # after the weights are in place (--init_checkpoint is the usual companion)
@@ -631,6 +723,8 @@ def main(argv=None):
 
     if opt.head_importance is not None:
         model.load_model(os.path.join(opt.exp_dir, "model.pt"))
+        if opt.lora_adapter is not None:
+            apply_lora_adapter(model, opt.lora_adapter)
         data = load(opt.valid_file)
         if data is None:
             raise SystemExit("--head_importance: no split at %s" % os.path.join(opt.dataroot, opt.valid_file))
@@ -652,6 +746,8 @@ def main(argv=None):
 
     if opt.predict is not None:
         model.load_model(os.path.join(opt.exp_dir, "model.pt"))
+        if opt.lora_adapter is not None:
+            apply_lora_adapter(model, opt.lora_adapter)
         out_path = predict_output_path(opt)
         t0 = time.time()
         attn_fp = open(opt.predict_attention, "w") if opt.predict_attention else None
@@ -682,6 +778,8 @@ def main(argv=None):
     valid, test = load(opt.valid_file), load(opt.test_file)
     if opt.testing:
         model.load_model(os.path.join(opt.exp_dir, "model.pt"))
+        if opt.lora_adapter is not None:
+            apply_lora_adapter(model, opt.lora_adapter)
         log = _Log(os.path.join(opt.exp_dir, "log.test"), rank)
         for name, data in (("Train", load(opt.train_file)), ("Valid", valid), ("Test", test)):
             if data is None:
@@ -699,7 +797,7 @@ def main(argv=None):
     t_total = (len(train) // opt.batchSize + 1) * opt.max_epoch            # n_best_asr_bert.py:556
     if opt.optim_choice == "bertadam":
         opt.optimizer = HipBertAdam(model, lr=opt.lr, bert_lr=opt.bert_lr, warmup=opt.warmup_proportion, t_total=t_total,
-                                    shard=opt.shard_optimizer == "on", ema_decay=opt.ema_decay)
+                                    shard=opt.shard_optimizer == "on", ema_decay=opt.ema_decay, lora_lr=opt.lora_lr)
     else:                                                                   # n_best_asr_bert.py:551-569
         opt.optimizer = HipAdam(model, kind=opt.optim_choice, lr=opt.lr, bert_lr=opt.bert_lr, l2=opt.l2, warmup=opt.warmup_proportion,
                                 t_total=t_total, max_grad_norm=opt.max_norm, shard=opt.shard_optimizer == "on", ema_decay=opt.ema_decay)
@@ -728,6 +826,10 @@ def main(argv=None):
                  "head's weights get a zero gradient, model.pt keeps the full tensors (evaluate with --testing --head_mask)"
                  % (opt.train_head_mask, trainer.head_mask_digest(train_mask), [sum(1 for x in r if x != 0.0) for r in train_mask],
                     cfg.num_attention_heads))
+    if lora_cfg is not None:
+        log.info("LoRA: rank %d, alpha %g, targets %s, lr %s; %d trainable parameters (%d in the factors of %d blocks + the STC heads), "
+                 "the encoder's own tensors are frozen; model.pt holds the merged weights, lora.pt the factors and heads"
+                 % (opt.lora_rank, opt.lora_alpha, opt.lora_targets, opt.lora_lr, n_params, model.lora.n_trainable, len(model.lora.blocks)))
     if opt.ema_decay is not None:
         log.info("Weight EMA: decay %s (warm-up min(D, (1 + t) / (10 + t))); evaluation and model.pt use the averaged weights" % opt.ema_decay)
     best = dict(epoch=0, vf=0.0, tef=0.0, v_acc=0.0, te_acc=0.0)
@@ -738,7 +840,19 @@ def main(argv=None):
             said = lambda m: "without a head mask" if m is None else "under the head mask %s" % trainer.head_mask_digest(m)
             raise SystemExit("--resume from %s: the checkpoint was trained %s, this run trains %s; resume with the --train_head_mask "
                              "it was started with" % (last, said(ck.get("head_mask")), said(train_mask)))
+        from . import lora as _lora
+        have = ck.get("lora")
+        want = None if lora_cfg is None else model.lora.config()
+        if (None if have is None else have["config"]) != want:
+            said = lambda c: "without LoRA" if c is None else "with LoRA %s" % (c,)
+            raise SystemExit("--resume from %s: the checkpoint was trained %s, this run trains %s; resume with the --lora_* flags it "
+                             "was started with" % (last, said(None if have is None else have["config"]), said(want)))
+        if lora_cfg is not None:
+            model.disable_lora()
         model.load_reference_state(ck["model"])
+        if lora_cfg is not None:                                               # the merged weights are in: put base and factors back
+            model.enable_lora(**lora_cfg)
+            _lora.restore_checkpoint(model, have)
         try:
             opt.optimizer.load_state_dict(ck["optimizer"])
         except ValueError as e:
@@ -780,13 +894,16 @@ def main(argv=None):
                 opt.optimizer.gather_master(moments=False)
                 if rank == 0:
                     model.save_model(os.path.join(opt.exp_dir, "model.pt"))
+                    if model.lora is not None:
+                        torch.save(model.lora_state_dict(), os.path.join(opt.exp_dir, "lora.pt"))
                 log.info("NEW BEST:\tEpoch: %02d\tvalid F1/Acc: %.2f/%.2f\ttest F1/Acc: %.2f/%.2f" % (ep, vf, v_acc, tef, te_acc))
         if opt.resume:
             opt.optimizer.gather_master()           # all ranks (collectives); master and moments are whole everywhere afterwards
             if rank == 0:                           # ... so the state dicts are built AFTER the gather, on rank 0 only
                 torch.save(dict(model={k: v.detach().cpu() for k, v in model.state_dict().items()},
                                 optimizer=opt.optimizer.state_dict(gather=False), best=best, epoch=ep, dropout_step=model.step_counter,
-                                **({} if train_mask is None else dict(head_mask=train_mask))),
+                                **({} if train_mask is None else dict(head_mask=train_mask)),
+                                **({} if model.lora is None else dict(lora=_lora_checkpoint(model)))),
                            last + ".tmp")
                 os.replace(last + ".tmp", last)
         if opt.stop_after_epoch is not None and ep >= opt.stop_after_epoch:

@@ -37,6 +37,7 @@ EXPORTS = [
     "nbest_fp8_amax_fold_max", "nbest_encoder_infer_fp8_ws_bytes", "nbest_encoder_infer_fp8",
     "nbest_attention_rollout_step",
     "nbest_token_select", "nbest_rows_compact", "nbest_encoder_infer_tokens_ws_bytes", "nbest_encoder_infer_tokens",
+    "nbest_lora_plan", "nbest_lora_grad_ws_bytes", "nbest_lora_merge", "nbest_lora_grad",
 ]
 
 
@@ -85,6 +86,16 @@ class TensorDesc(C.Structure):
 
 class MatrixDesc(C.Structure):
     _fields_ = [("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("tile_start", C.c_int32), ("pad", C.c_int32)]
+
+
+LORA_MAX_RANK = 64             # include/nbest_hip.h NBEST_LORA_MAX_RANK
+
+
+class LoraDesc(C.Structure):
+    """nbest_lora_desc: one adapted block (a contiguous row range of one arena matrix); tile_start / ws_off are nbest_lora_plan's"""
+    _fields_ = [("p_off", C.c_int64), ("base_off", C.c_int64), ("a_off", C.c_int64), ("b_off", C.c_int64), ("ws_off", C.c_int64),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int32), ("rank", C.c_int32),
+                ("scale", C.c_float), ("tile_start", C.c_int32)]
 
 
 HEAD_PRUNE_MAX_HEADS = 32      # include/nbest_hip.h NBEST_HEAD_PRUNE_MAX_HEADS
@@ -248,6 +259,11 @@ def lib():
         L.nbest_quantize_weights_fp8.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
         L.nbest_gemm_fp8_ws_bytes.restype = C.c_size_t
         L.nbest_gemm_fp8_ws_bytes.argtypes = [C.POINTER(GemmFp8Args)]
+        L.nbest_lora_plan.argtypes = [C.POINTER(LoraDesc), i32, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+        L.nbest_lora_grad_ws_bytes.restype = C.c_size_t
+        L.nbest_lora_grad_ws_bytes.argtypes = [C.POINTER(LoraDesc), i32]
+        L.nbest_lora_merge.argtypes = [vp, vp, vp, vp, C.POINTER(LoraDesc), vp, i32, vp]
+        L.nbest_lora_grad.argtypes = [vp, vp, vp, C.POINTER(LoraDesc), vp, i32, vp, sz, vp]
         L.nbest_last_error.argtypes = [C.c_char_p, sz]
         _lib = L
     return _lib
@@ -1309,3 +1325,42 @@ def cls_grad_scatter(dcls, B, S, H, dtype, out=None):
 
 def cast_bf16(src, dst):
     check(lib().nbest_cast_f32_to_bf16(ptr(src), ptr(dst), src.numel(), stream_ptr()), "cast_f32_to_bf16")
+
+
+class LoraTable:
+    """an nbest_lora_desc table: ``host`` (ctypes array, tile_start / ws_off filled by nbest_lora_plan), ``dev`` (the same bytes on
+    ``device``; None on the CPU), ``n``, ``n_tiles``, ``ws_bytes``.  ``blocks``: dicts with the descriptor's fields (stride defaults
+    to cols)."""
+
+    def __init__(self, blocks, device=None, plan=True):
+        self.n = len(blocks)
+        self.host = (LoraDesc * max(self.n, 1))()
+        for d, b in zip(self.host, blocks):
+            d.p_off, d.base_off, d.a_off, d.b_off = b["p_off"], b["base_off"], b["a_off"], b["b_off"]
+            d.rows, d.cols, d.rank, d.scale = b["rows"], b["cols"], b["rank"], b["scale"]
+            d.stride = b.get("stride", b["cols"])
+        self.n_tiles, self.ws_bytes = 0, 0
+        if plan:
+            self.plan()
+        self.dev = None
+        if device is not None and torch.device(device).type == "cuda":
+            self.upload(device)
+
+    def plan(self):
+        nt, wb = C.c_int(0), C.c_size_t(0)
+        check(lib().nbest_lora_plan(self.host, self.n, C.byref(nt), C.byref(wb)), "lora_plan")
+        self.n_tiles, self.ws_bytes = int(nt.value), int(wb.value)
+
+    def upload(self, device):
+        self.dev = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(device)
+
+
+def lora_merge(p, p_lowp, base, ab, table):
+    """every block of ``table``: p = base + scale B A (+ its bf16 copy in ``p_lowp``, or None) - nbest_lora_merge"""
+    check(lib().nbest_lora_merge(ptr(p), ptr(p_lowp), ptr(base), ptr(ab), table.host, ptr(table.dev), table.n, stream_ptr()), "lora_merge")
+
+
+def lora_grad(g, ab, g_ab, table, ws):
+    """dA / dB of every block from the dense gradient ``g`` into ``g_ab`` - nbest_lora_grad (``ws``: uint8, >= table.ws_bytes)"""
+    check(lib().nbest_lora_grad(ptr(g), ptr(ab), ptr(g_ab), table.host, ptr(table.dev), table.n, ptr(ws), ws.numel(), stream_ptr()),
+          "lora_grad")

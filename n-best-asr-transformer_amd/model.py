@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import hipabi as hb
+from . import lora as _lora
 from . import prune
 from .arena import ParamArena
 from .config import EncoderConfig, LabelSpace, NAMED
@@ -66,22 +67,27 @@ class FreezePlan(collections.namedtuple("FreezePlan", "key trainable first_train
 def freeze_plan(model):
     """the FreezePlan of the model's current ``requires_grad`` flags (cached per flag pattern)"""
     flags = tuple(p.requires_grad and "pooler" not in n for n, p in model._params)
-    plan = model._plans.get(flags)
+    lora = getattr(model, "lora", None)
+    ckey = flags if lora is None else (flags, id(lora))
+    plan = model._plans.get(ckey)
     if plan is not None:
         return plan
     trainable = frozenset(n for (n, _), f in zip(model._params, flags) if f)
+    # LoRA: a matrix with an adapted block needs its dense gradient (nbest_lora_grad projects it onto the factors), so for the
+    # backward it counts as trainable; it is not in ``trainable``, which the optimizer and the .grad views read
+    live = trainable if lora is None else trainable | lora.adapted
     L = model.cfg.num_hidden_layers
-    emb = any(n.startswith("bert_encoder.embeddings.") for n in trainable)
-    layer = [any(n.startswith("bert_encoder.encoder.layer.%d." % l) for n in trainable) for l in range(L)]
+    emb = any(n.startswith("bert_encoder.embeddings.") for n in live)
+    layer = [any(n.startswith("bert_encoder.encoder.layer.%d." % l) for n in live) for l in range(L)]
     first = 0 if emb else next((l for l in range(L) if layer[l]), L)
     pre = "bert_encoder.encoder.layer.%d."
     mats = (["attention.self.%s.weight" % q for q in ("query", "key", "value")], ["attention.output.dense.weight"],
             ["intermediate.dense.weight"], ["output.dense.weight"])
-    skip = [int(not any((pre % l) + m in trainable for m in ms)) for l in range(L) for ms in mats]
+    skip = [int(not any((pre % l) + m in live for m in ms)) for l in range(L) for ms in mats]
     plan = FreezePlan(flags, trainable, first, int(not emb), emb, (C.c_uint8 * len(skip))(*skip) if any(skip) else None)
     if len(model._plans) >= 64:
         model._plans.clear()
-    model._plans[flags] = plan
+    model._plans[ckey] = plan
     return plan
 
 
@@ -420,11 +426,18 @@ class NBestSTCModel(nn.Module):
             self.arena.iamax.zero_()
             self.arena.iamax_slots.zero_()
 
+    def _refuse_load_under_lora(self, what):
+        if self.lora is not None:
+            raise RuntimeError("nbest_amd: %s with LoRA enabled: the base copy of the adapted blocks would go stale; load the "
+                               "weights first, then enable_lora / load_lora" % what)
+
     def load_state_dict(self, *args, **kwargs):
+        self._refuse_load_under_lora("load_state_dict")
         self._drop_fp8_calibration()
         return super().load_state_dict(*args, **kwargs)
 
     def load_reference_state(self, sd, strict=True):
+        self._refuse_load_under_lora("load_reference_state")
         self._drop_fp8_history()
         return self.arena.load_state(sd, strict)
 
@@ -432,6 +445,7 @@ class NBestSTCModel(nn.Module):
         torch.save({k: v.detach().cpu() for k, v in self.state_dict().items()}, path)
 
     def load_model(self, path):
+        self._refuse_load_under_lora("load_model")
         self._drop_fp8_history()
         self.arena.load_state(torch.load(path, map_location="cpu", weights_only=True))
 
@@ -450,6 +464,7 @@ class NBestSTCModel(nn.Module):
             if not found:
                 raise FileNotFoundError("no model.safetensors / pytorch_model.bin under %s" % path)
             path = found[0]
+        self._refuse_load_under_lora("load_pretrained_encoder")
         self._drop_fp8_history()
         if path.endswith(".safetensors"):
             from safetensors.torch import load_file
@@ -472,6 +487,40 @@ class NBestSTCModel(nn.Module):
             raise RuntimeError("checkpoint lacks encoder tensors: %s" % hard[:5])
         self.arena.load_state(sd, strict=False)
         return missing
+
+    # ---- LoRA (nbest_amd/lora.py) ------------------------------------------------------------------
+    lora = None                            # the LoraState while LoRA is enabled
+
+    def enable_lora(self, rank, alpha, targets=("query", "value"), layers=None, seed=0):
+        """Parameter-efficient fine-tuning (Hu et al., 2022): freeze every tensor but the STC heads (``clf.*``) and train a rank-r
+        update W = W0 + (alpha / rank) B A on the ``targets`` (from query, key, value, attn_out, ffn_up, ffn_down) of ``layers``
+        (None: all).  A ~ U(-1/sqrt(in), 1/sqrt(in)) from ``seed``, B = 0: a forward gives the bits it gave before.  The arenas
+        keep the MERGED weights, so every forward, ``predict`` and ``state_dict`` run unchanged; ``forward_backward`` leaves the
+        dense gradient of the adapted matrices in ``arena.g`` (the layers below the lowest adapted one run without a stash or a
+        backward, the base tensors' ``.grad`` is None) and ``HipBertAdam.step`` projects it onto the factors, updates them and the
+        heads, and merges.  ``self.lora`` (lora.LoraState) holds the factors as ``params``.  Refused: an fp8w model, a head mask in
+        force, a second call.  Adapter dropout is not built (it cannot act on merged weights)."""
+        return _lora.enable(self, rank, alpha, targets, layers, seed)
+
+    def disable_lora(self, restore_base=False):
+        """leave LoRA: the ``requires_grad`` flags return to what they were; the weights stay merged, or with ``restore_base``
+        the adapted blocks get the base bits back"""
+        _lora.disable(self, restore_base)
+
+    def lora_merge(self):
+        """rewrite the adapted blocks from base + (alpha / rank) B A (after changing ``self.lora.params`` by hand)"""
+        _lora.merge(self)
+
+    def lora_state_dict(self):
+        """what a task ships: format tag, rank, alpha, targets, layers, ``base_digest`` (SHA-1 of the fp32 little-endian bytes of
+        the base blocks in table order), ``<tensor name>.lora_A`` / ``.lora_B`` and the ``clf.*`` tensors (the heads train too)"""
+        return _lora.state_dict(self)
+
+    def load_lora(self, sd):
+        """apply a ``lora_state_dict`` to this model, which must hold the base weights it was trained on (ValueError names both
+        digests otherwise): installs the factors and heads, merges"""
+        self._drop_fp8_calibration()
+        _lora.load(self, sd)
 
     # ---- head mask (HF's head_mask) ---------------------------------------------------------------
     _head_mask_trainable = False           # set_head_mask(trainable=True): forward_backward(need_grad=True) runs under the mask

@@ -58,7 +58,12 @@ class HipBertAdam:
     ``shard`` together with ``ema_decay`` raises."""
 
     def __init__(self, model, lr, bert_lr=None, warmup=-1, t_total=-1, b1=0.9, b2=0.999, e=1e-6, max_grad_norm=1.0, shard=False,
-                 ema_decay=None):
+                 ema_decay=None, lora_lr=None):
+        self.lora_lr = lr if lora_lr is None else lora_lr
+        self._lora = None           # the model.lora the adapter descriptors below were built for
+        self._lora_part = None      # (descs, n_tensors, n_blocks, workspace) of the adapter arena
+        if getattr(model, "lora", None) is not None:
+            self._refuse_with_lora(shard, ema_decay)
         if ema_decay is not None:
             ema_decay = float(ema_decay)
             if not 0.0 <= ema_decay < 1.0:
@@ -205,6 +210,67 @@ class HipBertAdam:
         self.owner_ranges = [[self.elem_ranges[p_][r] for p_ in range(len(self.parts)) if self.elem_ranges[p_][r][1] > self.elem_ranges[p_][r][0]]
                              for r in range(W)]
 
+    # ---- LoRA (model.enable_lora): the adapter arena next to the main one ------------------------------------------------------
+    def _refuse_with_lora(self, shard, ema_decay):
+        if type(self) is not HipBertAdam:
+            raise RuntimeError("nbest_amd: %s on a model with LoRA enabled is not built (its global-norm clip would have to span "
+                               "the main and the adapter arena); use HipBertAdam" % type(self).__name__)
+        if shard:
+            raise RuntimeError("nbest_amd: the sharded optimizer on a model with LoRA enabled is not built")
+        if ema_decay is not None:
+            raise RuntimeError("nbest_amd: ema_decay on a model with LoRA enabled is not built (the average would have to follow "
+                               "the factors, not the merged weights)")
+
+    def _sync_lora(self):
+        """the adapter descriptors, moments and workspace of the model's current LoraState (None: LoRA is off)"""
+        st = getattr(self.model, "lora", None)
+        if st is self._lora:
+            return st
+        if st is not None:
+            self._refuse_with_lora(self.sharded, self.ema_decay)
+            if st.m is None:
+                st.m, st.v = torch.zeros_like(st.p), torch.zeros_like(st.p)
+            descs, n_t, n_b = st.build_descs(self.lora_lr)
+            self._lora_part = (descs, n_t, n_b, torch.empty((n_b + n_t + 16) * 4, dtype=torch.uint8, device=st.device))
+        else:
+            self._lora_part = None
+        self._lora = st
+        return st
+
+    def _step_lora(self, st):
+        """step_main with LoRA on: project the dense gradient onto the factors, BertAdam on the main arena (only the heads are
+        active) and on the adapter arena (same schedule position, lora_lr, decay 0.01, per-tensor clip), merge"""
+        st.project_grad(self.arena)
+        self._launch(0)
+        descs, n_t, n_b, ws = self._lora_part
+        hb.check(hb.lib().nbest_bertadam_step(hb.ptr(st.p), hb.ptr(st.g), hb.ptr(st.m), hb.ptr(st.v), None, hb.ptr(descs), n_t, n_b,
+                                              self.get_lr_mult(), self.b1, self.b2, self.e, self.max_grad_norm, hb.ptr(ws), ws.numel(),
+                                              hb.stream_ptr()), "bertadam_step (adapter arena)")
+        st.merge(self.arena)
+        self.arena.refresh_transposed()
+
+    def _lora_state(self):
+        st = self._sync_lora()
+        if st is None:
+            return {}
+        return dict(lora={n: dict(next_m=st.view(st.m, n).detach().cpu().clone(), next_v=st.view(st.v, n).detach().cpu().clone())
+                          for n, _, _ in st.slots})
+
+    def _load_lora_state(self, sd):
+        st = self._sync_lora()
+        has = sd.get("lora") is not None
+        if has != (st is not None):
+            raise ValueError("optimizer state %s adapter moments cannot be loaded into an optimizer of a model %s LoRA"
+                             % ("with" if has else "without", "without" if has else "with"))
+        if has:
+            for n, _, shape in st.slots:
+                m = sd["lora"].get(n)
+                if m is None or tuple(m["next_m"].shape) != tuple(shape):
+                    raise ValueError("optimizer state: adapter moments of %s are missing or of another shape (--lora_* must match "
+                                     "the run that wrote it)" % n)
+                st.view(st.m, n).copy_(m["next_m"])
+                st.view(st.v, n).copy_(m["next_v"])
+
     def _build_descs(self, select):
         return self.arena.build_descs(self.lr, self.bert_lr, select=select, active=self._active())
 
@@ -305,6 +371,9 @@ class HipBertAdam:
         """every tensor except the embedding tables (+ the k-contiguous weight copy the next forward / dgrad reads)"""
         self._refuse_step_in_ema()
         self.sync_frozen()
+        st = self._sync_lora()
+        if st is not None:
+            return self._step_lora(st)
         self._launch(0)
         self._ema_update(0)
         self.arena.refresh_transposed()
@@ -329,13 +398,15 @@ class HipBertAdam:
         a = self.arena
         return dict(step=self.step_count, t_total=self.t_total, warmup=self.warmup,
                     state={s.name: dict(next_m=a.view(a.m, s.name).detach().cpu().clone(),
-                                        next_v=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots}, **self._ema_state())
+                                        next_v=a.view(a.v, s.name).detach().cpu().clone()) for s in a.slots}, **self._ema_state(),
+                    **self._lora_state())
 
     def load_state_dict(self, sd):
         if sd.get("kind", "bertadam") != "bertadam":
             raise ValueError("optimizer state of kind %r cannot be loaded into BertAdam (--optim_choice must match the run that "
                              "wrote it)" % sd["kind"])
         self._load_ema_state(sd, "BertAdam")
+        self._load_lora_state(sd)
         a = self.arena
         self.step_count = int(sd["step"])
         for s in a.slots:
@@ -427,6 +498,8 @@ class HipAdam(HipBertAdam):
     def step_main(self):
         """the block norms of every tensor but the embedding tables: nothing is updated before their gradients are in"""
         self._refuse_step_in_ema()
+        if getattr(self.model, "lora", None) is not None:
+            self._refuse_with_lora(self.sharded, self.ema_decay)
         self.sync_frozen()
         if self.sharded and self.max_grad_norm > 0:
             self.partial.zero_()
