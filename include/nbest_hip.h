@@ -705,6 +705,32 @@ int nbest_ema_update(float* ema, const float* p, const nbest_tensor_desc* descs,
 int nbest_ema_exchange(float* p, float* ema, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
                        nbest_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
+ * K9s  sharpness-aware minimization (--sam_rho; new functionality, the reference has none): the weight-space half of a SAM step
+ * (Foret et al., 2021: the gradient is taken at w + e, e = rho g / ||g||, and applied at w) and of its scale-invariant variant
+ * ASAM (Kwon et al., 2021: e = rho T^2 g / ||T g||, T = diag(|w| + eta)), over the same arenas and descriptor tables, one launch
+ * per table, n_blocks workgroups, no workspace, bit-reproducible.  Inactive tensors and the elements between tensors are never
+ * read or written; g is read, never written.
+ * nbest_sam_norms: the adaptive norm stage, partial[blk] = sum over block blk of (t g)^2, t = |p| + eta, in the summation shape
+ *   of nbest_bertadam_norms (0 for the blocks of inactive tensors).  Plain SAM uses nbest_bertadam_norms itself.  Either way the
+ *   caller lays the partials of all tables back to back and nbest_adam_clip_coef(partial, n, 0, clip) leaves the norm in clip[1],
+ *   on the device: no other reduce kernel, no host synchronisation.  8 B per parameter.  eta finite and > 0.
+ * nbest_sam_perturb: s = rho / (norm[0] + 1e-12f) (norm: device fp32[1]); for every element of every active tensor backup = p,
+ *   then p = fma(s, g, p) (eta < 0: plain) or t = |p| + eta, p = fma(s, (t t) g, p) (eta > 0: adaptive), the fma explicit;
+ *   p_lowp != NULL: also the bf16 (round to nearest even) of the new p at the same element offsets.  rho == 0, or a norm that is 0
+ *   or not finite: s = 0 - no arithmetic on g (which may hold inf or NaN), p keeps its bits (it is not rewritten), backup and
+ *   p_lowp are written all the same.  18 B per parameter (8 read, 10 written: backup, p and the bf16 copy).
+ * nbest_sam_restore: p = backup and p_lowp = its bf16, for every active tensor.  A pure move: after perturb + restore every bit of
+ *   p and (a p_lowp that was the bf16 of p) is what it was.  10 B per parameter.
+ * Refused before any launch (NBEST_ERR_ARG): a NULL p / g / backup / descs / norm / partial, n_tensors <= 0 or n_blocks <= 0, a
+ * negative or non-finite rho, eta == 0 or a non-finite eta (nbest_sam_norms: eta <= 0).                                          */
+int nbest_sam_norms(const float* p, const float* g, const nbest_tensor_desc* descs, int n_tensors, int n_blocks, float eta,
+                    float* partial, nbest_stream_t stream);
+int nbest_sam_perturb(float* p, const float* g, float* backup, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors,
+                      int n_blocks, const float* norm /* device fp32[1] */, float rho, float eta /* < 0: plain */,
+                      nbest_stream_t stream);
+int nbest_sam_restore(float* p, const float* backup, void* p_lowp, const nbest_tensor_desc* descs, int n_tensors, int n_blocks,
+                      nbest_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
  * K9l  LoRA on merged weights (--lora_rank; new functionality, the reference has none).  The encoder keeps reading the merged
  * matrix W = W0 + s B A (s = alpha / r) from the arenas; the factors live in an adapter arena `ab` (fp32) and never appear inside
  * a layer.  One table of nbest_lora_desc, ordered by tile_start, has one entry per adapted BLOCK: a contiguous row range of one

@@ -218,6 +218,21 @@ def parse_arguments(argv=None):
                         "the sum of both passes' gradients; E finite and > 0.  The [Train] line's Loss and F1 are the clean pass's; exp_dir "
                         "gains __fgm_<E>.  A training flag, one GPU; not with --distill_from, --rdrop_alpha, --dtype fp8w, "
                         "--freeze_embeddings or --freeze_layers K > 0")
+    g.add_argument("--sam_rho", type=float, default=None, metavar="R",
+                   help="sharpness-aware minimization (Foret et al., 2021): every training step takes the gradient at w + e, e = R g / "
+                        "||g|| (one norm over every trainable tensor, nbest_sam_perturb), under the same dropout bits as the pass that "
+                        "produced g, and applies it at w (nbest_sam_restore); R finite and > 0.  About twice the step.  The [Train] "
+                        "line's Loss and F1 are the first pass's (at w); one more line per epoch carries the mean loss rise at w + e and "
+                        "the mean gradient norm; exp_dir gains __sam_<R>.  A training flag, one GPU; works with the three optimizers, "
+                        "--add_l2_loss, --rdrop_alpha, --distill_from, --contrastive_weight, --ema_decay, --freeze_* and --resume; not "
+                        "with --adv_epsilon, --lora_rank, --dtype fp8w, --train_head_mask, --shard_optimizer on or --n_layers 12 "
+                        "(gradient accumulation)")
+    g.add_argument("--sam_adaptive", action="store_true",
+                   help="with --sam_rho: ASAM (Kwon et al., 2021), the scale-invariant variant: e = R T^2 g / ||T g||, T = |w| + "
+                        "--sam_eta element by element (nbest_sam_norms); exp_dir gains __asam_<R>_<eta> instead")
+    g.add_argument("--sam_eta", type=float, default=None, metavar="ETA",
+                   help="with --sam_rho --sam_adaptive: the floor added to |w|; finite and > 0 (default 0.01).  Plain SAM does not read "
+                        "it: given without --sam_adaptive it is refused")
     g.add_argument("--contrastive_weight", type=float, default=None, metavar="W",
                    help="in-batch contrastive alignment of the n-best list with its transcript (Chang & Chen, 2022; the loss of SimCSE / "
                         "CLIP): every step runs the transcript pass and adds W x the symmetric InfoNCE between the ASR and the "
@@ -504,6 +519,38 @@ def parse_arguments(argv=None):
             trainer.head_mask_file_digest(opt.train_head_mask)
         except ValueError as e:
             ap.error("--train_head_mask: %s" % e)
+    if opt.sam_rho is None:
+        if opt.sam_adaptive or opt.sam_eta is not None:
+            ap.error("--sam_adaptive / --sam_eta are settings of --sam_rho: pass --sam_rho R too")
+    else:
+        if not (opt.sam_rho > 0.0 and math.isfinite(opt.sam_rho)):
+            ap.error("--sam_rho %s: must be a finite number > 0" % opt.sam_rho)
+        if opt.sam_eta is not None and not opt.sam_adaptive:
+            ap.error("--sam_eta is a setting of --sam_adaptive: pass --sam_adaptive too")
+        if opt.sam_eta is None:
+            opt.sam_eta = 0.01
+        if not (opt.sam_eta > 0.0 and math.isfinite(opt.sam_eta)):
+            ap.error("--sam_eta %s: must be a finite number > 0" % opt.sam_eta)
+        for flag, on in scoring:
+            if on:
+                ap.error("--sam_rho is a training flag: %s reads model.pt from the directory named without it" % flag)
+        if opt.adv_epsilon is not None:
+            ap.error("--sam_rho together with --adv_epsilon is not built (two two-pass schemes in one step)")
+        if opt.lora_rank is not None:
+            ap.error("--sam_rho together with --lora_rank is not built (the perturbation would have to follow the factors, not the "
+                     "merged weights)")
+        if opt.dtype == "fp8w":
+            ap.error("--sam_rho together with --dtype fp8w is not built (the amax histories would record twice per step and the e4m3 "
+                     "images would be cut from perturbed weights)")
+        if opt.train_head_mask is not None:
+            ap.error("--sam_rho together with --train_head_mask is not built (SAM under a head mask)")
+        if opt.shard_optimizer == "on":
+            ap.error("--sam_rho together with --shard_optimizer on is not built (the fp32 master is current only on each range's owner)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--sam_rho runs on one GPU: SAM under data parallelism is not built (world size %s)" % os.environ["WORLD_SIZE"])
+        if opt.n_layers == 12:
+            ap.error("--sam_rho together with --n_layers 12 is not built (that flag turns gradient accumulation on; the perturbation "
+                     "is formed from one batch's gradient)")
     opt.gpu_index = 0 if opt.deviceId == 0 else opt.deviceId - 1            # n_best_asr_bert.py:116-126 (0: auto -> first GPU)
     # gradient accumulation exactly as the reference derives it (n_best_asr_bert.py:522): 4 micro-batches of batchSize / 4
     # per optimizer step when --n_layers 12 is passed (the shipped script never passes it -> 1)
@@ -533,6 +580,8 @@ def exp_dir(opt):
         parts.append("fgm_%s" % opt.adv_epsilon)
     if getattr(opt, "contrastive_weight", None) is not None:
         parts.append("cl_%s_%s" % (opt.contrastive_weight, opt.contrastive_temperature))
+    if getattr(opt, "sam_rho", None) is not None:
+        parts.append("asam_%s_%s" % (opt.sam_rho, opt.sam_eta) if getattr(opt, "sam_adaptive", False) else "sam_%s" % opt.sam_rho)
     if getattr(opt, "lora_rank", None) is not None:
         from . import lora as _lora
         parts.append(_lora.exp_dir_part(opt.lora_rank, opt.lora_alpha, opt.lora_targets))
@@ -821,6 +870,10 @@ def main(argv=None):
         log.info("Contrastive: weight %s, temperature %s; every step runs the transcript pass and adds weight x the in-batch symmetric "
                  "InfoNCE between the ASR and the transcript CLS rows (identical transcripts are no negatives), Loss below stays the hard "
                  "loss (+ MSE)" % (opt.contrastive_weight, opt.contrastive_temperature))
+    if opt.sam_rho is not None:
+        log.info("%s: rho %s%s; every step takes the gradient at w + e (e along the first pass's gradient, same dropout bits) and "
+                 "applies it at w, Loss and F1 below are the first pass's"
+                 % ("ASAM" if opt.sam_adaptive else "SAM", opt.sam_rho, ", eta %s" % opt.sam_eta if opt.sam_adaptive else ""))
     if train_mask is not None:
         log.info("Head mask: %s (digest %s), heads kept per layer %s of %d; every step and every evaluation run under it, a pruned "
                  "head's weights get a zero gradient, model.pt keeps the full tensors (evaluate with --testing --head_mask)"
@@ -867,6 +920,9 @@ def main(argv=None):
         if opt.contrastive_weight is not None and getattr(opt, "contrast_epoch", None):
             csum, chits, crows = opt.contrast_epoch[:3]
             log.info("[Contrast]\tEpoch: %02d\tLoss: %.4f\tAlign: %.2f" % (ep, csum / max(crows, 1.0), 100.0 * chits / max(crows, 1.0)))
+        if opt.sam_rho is not None and getattr(opt, "sam_epoch", None):
+            ssum, snorm, sutts, ssteps = opt.sam_epoch[:4]
+            log.info("[SAM]\tEpoch: %02d\tSharpness: %.4f\tGradNorm: %.4f" % (ep, ssum / max(sutts, 1.0), snorm / max(ssteps, 1.0)))
         # --ema_decay: the evaluations and the model.pt write run on the averaged weights; the raw ones are back afterwards
         with (opt.optimizer.ema_weights() if opt.ema_decay is not None else contextlib.nullcontext()):
             res = {}

@@ -23,7 +23,7 @@ EXPORTS = [
     "nbest_gemm_ws_bytes", "nbest_gemm", "nbest_gemm_plan", "nbest_wgrad_pair_ws_bytes", "nbest_wgrad_pair", "nbest_wgrad_group", "nbest_wgrad_window", "nbest_pack_bn", "nbest_pack_weights", "nbest_pack_bn_fp8", "nbest_pack_weights_fp8", "nbest_attention_fwd", "nbest_attention_bwd", "nbest_attention_bwd_ws_bytes", "nbest_attention_keep_bytes", "nbest_attention_fwd_keep", "nbest_attention_bwd_keep", "nbest_layernorm_fwd",
     "nbest_layernorm_bwd", "nbest_rowred_ws_bytes", "nbest_colsum", "nbest_heads_ws_bytes", "nbest_stc_heads", "nbest_stc_heads_kd", "nbest_stc_heads_kd_t", "nbest_stc_heads_logits", "nbest_stc_heads_rdrop",
     "nbest_stc_heads_vjp", "nbest_cls_mse", "nbest_cls_contrast_ws_bytes", "nbest_cls_contrast", "nbest_cls_grad_scatter", "nbest_stc_decode", "nbest_stream_stamp", "nbest_fp8_amax_fold", "nbest_bertadam_chunk", "nbest_bertadam_step", "nbest_bertadam_norms", "nbest_bertadam_update",
-    "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange",
+    "nbest_adam_clip_coef", "nbest_adam_update", "nbest_adam_step", "nbest_ema_update", "nbest_ema_exchange", "nbest_sam_norms", "nbest_sam_perturb", "nbest_sam_restore",
     "nbest_cast_f32_to_bf16", "nbest_transpose_weights", "nbest_encoder_act_bytes", "nbest_encoder_ws_bytes", "nbest_encoder_wgrad_launches_per_layer", "nbest_encoder_wgrad_plan", "nbest_encoder_forward",
     "nbest_encoder_backward", "nbest_gemm_fp8", "nbest_gemm_fp8_ws_bytes", "nbest_wgrad_fp8", "nbest_wgrad_fp8_ws_bytes", "nbest_wgrad_fp8_pair", "nbest_wgrad_fp8_pair_ws_bytes", "nbest_cast_bf16_to_fp8", "nbest_quantize_weights_fp8",
     "nbest_attention_cls_fwd", "nbest_encoder_infer_ws_bytes", "nbest_encoder_infer",
@@ -221,6 +221,9 @@ def lib():
         L.nbest_adam_step.argtypes = [i32] + [vp] * 6 + [i32, i32, f32, f32, f32, f64, f64, f32, f32, vp, sz, vp]
         L.nbest_ema_update.argtypes = [vp, vp, vp, i32, i32, f32, vp]
         L.nbest_ema_exchange.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+        L.nbest_sam_norms.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp]
+        L.nbest_sam_perturb.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, f32, f32, vp]
+        L.nbest_sam_restore.argtypes = [vp, vp, vp, vp, i32, i32, vp]
         L.nbest_cast_f32_to_bf16.argtypes = [vp, vp, i64, vp]
         L.nbest_encoder_forward.argtypes = [C.POINTER(EncoderDesc)] + [vp] * 7 + [sz, vp, sz, C.POINTER(C.c_void_p), vp]
         L.nbest_encoder_infer_ws_bytes.argtypes = [C.POINTER(EncoderDesc)]

@@ -949,7 +949,7 @@ class NBestSTCModel(nn.Module):
     def forward_backward(self, input_ids, labels_f, seg_ids=None, trans_input_ids=None, trans_seg_ids=None,
                          add_l2_loss=False, mse_grad_scale=1.0, chunks=None, on_chunk_done=None, need_grad=True,
                          accumulate=False, encoder_grad_scale=1.0, tok_perm=None, trans_tok_perm=None, distill=None, rdrop=None,
-                         adv=None, contrast=None):
+                         adv=None, contrast=None, advance=True):
         """Returns dict(top, bott, final, loss_parts[4] (device), asr_cls, trans_cls).  Gradients of the sum
         BCE(final) + BCE(top) + mean-CE (+ MSE) are left in ``arena.g``.  The transcript pass runs only
         when its output is used (--add_l2_loss); the reference computes and discards it otherwise (Q4).
@@ -996,7 +996,10 @@ class NBestSTCModel(nn.Module):
         unweighted, the number of rows whose own transcript is their nearest kept one, B, 0.  ``loss_parts`` is untouched.  The
         negatives are the rows of THIS call: under gradient accumulation those of the micro-batch.  ``need_grad=False``: the loss
         only.  weight finite and >= 0, temperature finite and > 0; needs ``trans_input_ids``; not with ``adv``, not on an fp8w model
-        and not under a head mask (not built).  Four launches more than the same step without it, no host synchronisation."""
+        and not under a head mask (not built).  Four launches more than the same step without it, no host synchronisation.
+        ``advance=False``: ``step_counter`` stays where it is, so the NEXT call runs under the same dropout bits (encoder and heads) -
+        the first pass of a SAM step (trainer.train_step(sam_rho=)), whose second pass must see the network instance that produced
+        the gradient.  Everything else is as without it."""
         if contrast is not None:
             contrast = _check_contrast(contrast, input_ids.shape[0], trans_input_ids, adv, self.device)
             if self._head_mask is not None:
@@ -1052,7 +1055,7 @@ class NBestSTCModel(nn.Module):
         adv_out = None
         if adv is not None:
             adv_out = self._adversarial_pass(ra, labels_f, adv["epsilon"], plan, chunks, on_chunk_done, encoder_grad_scale)
-        self._end_of_step(need_grad)
+        self._end_of_step(need_grad, advance=advance)
         out = dict(top=top, bott=bott, final=fin, loss_parts=loss, asr_cls=ra.cls, trans_cls=None if rt is None else rt.cls)
         if adv_out is not None:
             out["adv_loss_parts"], out["adv_norm"] = adv_out

@@ -55,7 +55,14 @@ class HipBertAdam:
     embedding exchange, like its update; the replicas compute the same bits).  A frozen tensor is skipped: its average is its
     value.  ``ema_weights()`` swaps the average in for an evaluation or a checkpoint.  Not built for the sharded optimizer (the
     master is current only on each range's owner: the kernel would need an owner-range form and every evaluation a gather):
-    ``shard`` together with ``ema_decay`` raises."""
+    ``shard`` together with ``ema_decay`` raises.
+
+    ``sam_perturb`` / ``sam_restore`` (new functionality: sharpness-aware minimization, trainer.train_step(sam_rho=)): the weight-
+    space half of a SAM / ASAM step through the K9s kernels.  ``sam_perturb(rho)`` moves every trainable tensor to w + e,
+    e = rho g / ||g|| with ONE norm over both descriptor tables (adaptive: e = rho T^2 g / ||T g||, T = |w| + eta), keeps w in
+    ``sam_backup`` (fp32, the size of ``p``; None until the first call) and refreshes the bf16 copy and the derived weight images;
+    the next ``step_main()`` (or ``sam_restore()``) moves w back, to the bit, before it steps.  Frozen tensors are neither moved nor
+    in the norm.  Not built for the sharded optimizer or with LoRA; refused while the EMA weights are swapped in."""
 
     def __init__(self, model, lr, bert_lr=None, warmup=-1, t_total=-1, b1=0.9, b2=0.999, e=1e-6, max_grad_norm=1.0, shard=False,
                  ema_decay=None, lora_lr=None):
@@ -77,6 +84,8 @@ class HipBertAdam:
         self.warmup, self.t_total = max(warmup, 0.0), t_total
         self.b1, self.b2, self.e, self.max_grad_norm = b1, b2, e, max_grad_norm
         self.step_count = 0
+        self.sam_backup, self.sam_norm, self.sam_pending = None, None, False   # sam_perturb: w, the device [1] norm, w + e is in p
+        self._sam_partial = self._sam_clip = None
         a = self.arena
         self._frozen_key = None     # requires_grad pattern the descriptors were built for (model.FreezePlan.key)
         self._trainable = None      # its trainable tensor names (None: every tensor but the pooler)
@@ -142,6 +151,8 @@ class HipBertAdam:
             raise RuntimeError("ema_weights: the optimizer was built without ema_decay")
         if self._in_ema:
             raise RuntimeError("ema_weights() is already entered: it does not nest")
+        if self.sam_pending:
+            raise RuntimeError("ema_weights() while a SAM perturbation is pending: the model holds w + e (step or sam_restore() first)")
         self._ema_exchange()
         self._in_ema = True
         try:
@@ -175,6 +186,70 @@ class HipBertAdam:
             a = self.arena
             for s in a.slots:
                 a.view(a.ema, s.name).copy_(sd["ema"][s.name])
+
+    # ---- sharpness-aware minimization (K9s) -------------------------------------------------------------------------------------
+    def sam_perturb(self, rho, adaptive=False, eta=0.01):
+        """p += e over the trainable tensors, e = rho g / ||g|| (``adaptive``: rho T^2 g / ||T g||, T = |p| + eta), g = ``arena.g``:
+        the norms of both descriptor tables back to back, nbest_adam_clip_coef's fixed-order total into ``sam_norm`` (device [1]),
+        one nbest_sam_perturb per table (which also saves p into ``sam_backup`` and rewrites the bf16 copy), then the derived weight
+        images.  rho finite and >= 0 (0: nothing moves), eta finite and > 0.  No host synchronisation.  Raises before anything is
+        enqueued when a perturbation is pending, the optimizer is sharded, LoRA is on or the EMA weights are swapped in."""
+        rho, eta = float(rho), float(eta)
+        if not (rho >= 0.0 and rho != float("inf")):
+            raise ValueError("sam_perturb: rho must be finite and >= 0, not %r" % (rho,))
+        if adaptive and not (eta > 0.0 and eta != float("inf")):
+            raise ValueError("sam_perturb: eta must be finite and > 0, not %r" % (eta,))
+        if self.sam_pending:
+            raise RuntimeError("sam_perturb: a perturbation is pending (step or sam_restore() first)")
+        if self.sharded:
+            raise RuntimeError("nbest_amd: SAM with the sharded optimizer is not built (the fp32 master is current only on each "
+                               "range's owner)")
+        if getattr(self.model, "lora", None) is not None:
+            raise RuntimeError("nbest_amd: SAM on a model with LoRA enabled is not built (the perturbation would have to follow "
+                               "the factors, not the merged weights)")
+        if self._in_ema:
+            raise RuntimeError("sam_perturb inside ema_weights(): the model holds the averaged weights")
+        self.sync_frozen()
+        a, L, P, st = self.arena, hb.lib(), hb.ptr, hb.stream_ptr()
+        if self.sam_backup is None:
+            self.sam_backup = torch.zeros_like(a.p)
+            self._sam_partial = torch.zeros(max(self.parts[0][2] + self.parts[1][2], 1), dtype=torch.float32, device=a.device)
+            self._sam_clip = torch.zeros(2, dtype=torch.float32, device=a.device)         # [unused coefficient, total norm]
+            self.sam_norm = self._sam_clip[1:2]
+        base = 0
+        for descs, n_t, n_b, _ in self.parts:
+            if n_t:
+                if adaptive:
+                    hb.check(L.nbest_sam_norms(P(a.p), P(a.g), P(descs), n_t, n_b, eta, P(self._sam_partial[base:]), st), "sam_norms")
+                else:
+                    hb.check(L.nbest_bertadam_norms(P(a.g), P(descs), n_t, n_b, 0, n_b, P(self._sam_partial[base:]), st), "bertadam_norms")
+            base += n_b
+        hb.check(L.nbest_adam_clip_coef(P(self._sam_partial), self._sam_partial.numel(), 0.0, P(self._sam_clip), st), "adam_clip_coef")
+        for descs, n_t, n_b, _ in self.parts:
+            if n_t:
+                hb.check(L.nbest_sam_perturb(P(a.p), P(a.g), P(self.sam_backup), P(a.w16), P(descs), n_t, n_b, P(self.sam_norm), rho,
+                                             eta if adaptive else -1.0, st), "sam_perturb")
+        self.sam_pending = True
+        a.refresh_transposed()
+
+    def _sam_restore_launch(self):
+        """p = sam_backup (+ the bf16 copy) over the tables the pending perturbation used; the caller refreshes the derived images"""
+        a = self.arena
+        for descs, n_t, n_b, _ in self.parts:
+            if n_t:
+                hb.check(hb.lib().nbest_sam_restore(hb.ptr(a.p), hb.ptr(self.sam_backup), hb.ptr(a.w16), hb.ptr(descs), n_t, n_b,
+                                                    hb.stream_ptr()), "sam_restore")
+        self.sam_pending = False
+
+    def sam_restore(self):
+        """undo a pending sam_perturb without stepping: every bit of p, the bf16 copy and the derived images is what it was.
+        ``ema_weights()`` refuses to be entered while a perturbation is pending, and this call inside it"""
+        if not self.sam_pending:
+            raise RuntimeError("sam_restore: no perturbation is pending")
+        if self._in_ema:
+            raise RuntimeError("sam_restore inside ema_weights(): the arenas are exchanged")
+        self._sam_restore_launch()
+        self.arena.refresh_transposed()
 
     # ---- sharding plan (identical on every rank: pure geometry) -------------------------------------------------------------
     def _plan_shards(self):
@@ -370,6 +445,8 @@ class HipBertAdam:
     def step_main(self):
         """every tensor except the embedding tables (+ the k-contiguous weight copy the next forward / dgrad reads)"""
         self._refuse_step_in_ema()
+        if self.sam_pending:            # back to w before anything steps (before the descriptors can change); the refresh below covers it
+            self._sam_restore_launch()
         self.sync_frozen()
         st = self._sync_lora()
         if st is not None:
@@ -500,6 +577,8 @@ class HipAdam(HipBertAdam):
         self._refuse_step_in_ema()
         if getattr(self.model, "lora", None) is not None:
             self._refuse_with_lora(self.sharded, self.ema_decay)
+        if self.sam_pending:            # back to w before anything steps; step_embeddings' refresh covers it
+            self._sam_restore_launch()
         self.sync_frozen()
         if self.sharded and self.max_grad_norm > 0:
             self.partial.zero_()

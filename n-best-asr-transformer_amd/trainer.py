@@ -393,6 +393,40 @@ def adv_args(adv_epsilon, teacher, rdrop_alpha, world):
     return dict(epsilon=float(adv_epsilon))
 
 
+def sam_args(sam_rho, sam_adaptive, sam_eta, model, optimizer, adv_epsilon, world, n_accum=1):
+    """optimizer.sam_perturb's arguments of one step under ``sam_rho`` (None: none): dict(rho, adaptive, eta).  Every combination
+    that is not built is refused here, before anything is enqueued: FGM (two two-pass schemes in one step), LoRA, the fp8w mode
+    (its amax histories would record twice per step and the e4m3 images would be cut from perturbed weights), a trainable head
+    mask, the sharded optimizer, data parallelism and gradient accumulation (the perturbation is formed from ONE batch's
+    gradient)."""
+    if sam_rho is None:
+        return None
+    rho, eta = float(sam_rho), float(sam_eta)
+    if not (rho >= 0.0 and rho != float("inf")):
+        raise ValueError("nbest_amd: sam_rho must be finite and >= 0, not %r" % (sam_rho,))
+    if sam_adaptive and not (eta > 0.0 and eta != float("inf")):
+        raise ValueError("nbest_amd: sam_eta must be finite and > 0, not %r" % (sam_eta,))
+    if adv_epsilon is not None:
+        raise ValueError("nbest_amd: sam_rho together with adv_epsilon is not built (two two-pass schemes in one step)")
+    if getattr(model, "lora", None) is not None:
+        raise RuntimeError("nbest_amd: sam_rho on a model with LoRA enabled is not built (the perturbation would have to follow the "
+                           "factors, not the merged weights)")
+    if getattr(model, "fp8_forward", False):
+        raise RuntimeError("nbest_amd: sam_rho on an fp8w model is not built (the amax histories would record twice per step and "
+                           "the e4m3 images would be cut from perturbed weights)")
+    if getattr(model, "head_mask_trainable", False):
+        raise RuntimeError("nbest_amd: sam_rho under a trainable head mask is not built")
+    if getattr(optimizer, "sharded", False):
+        raise RuntimeError("nbest_amd: sam_rho with the sharded optimizer is not built (the fp32 master is current only on each "
+                           "range's owner)")
+    if world > 1:
+        raise RuntimeError("nbest_amd: sam_rho under data parallelism is not built (world size %d)" % world)
+    if n_accum > 1:
+        raise RuntimeError("nbest_amd: sam_rho under gradient accumulation is not built (n_accum_steps %d: the perturbation is "
+                           "formed from one batch's gradient)" % n_accum)
+    return dict(rho=rho, adaptive=bool(sam_adaptive), eta=eta)
+
+
 def transcript_keys(tids):
     """int64 [B]: for every row of the transcript ids ``tids`` [B, S] the index of the FIRST row of the batch whose ids are
     identical - the key under which the contrastive term (forward_backward's ``contrast``) leaves utterances with the same
@@ -428,7 +462,7 @@ def contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, wor
 
 def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True, reducer=None, global_batch=None, teacher=None,
                distill_alpha=0.5, distill_temperature=None, rdrop_alpha=None, adv_epsilon=None, contrast_weight=None,
-               contrast_temperature=0.1):
+               contrast_temperature=0.1, sam_rho=None, sam_adaptive=False, sam_eta=0.01):
     """One optimisation step on this rank's shard.  batch: dict(ids, seg, labels[, tids, tseg]) device tensors.
     ``global_batch`` = utterances of the whole minibatch over all ranks (default: world x this shard).
     ``teacher``: a second NBestSTCModel (knowledge distillation) - its ``predict`` scores of the batch become the soft targets of
@@ -448,19 +482,33 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     parallelism is not built (negatives across ranks).
     A model under a trainable head mask (``set_head_mask(mask, trainable=True)``) steps as any other on one GPU; data parallelism is
     not built (refused before anything is enqueued).
+    ``sam_rho``: sharpness-aware minimization (Foret et al., 2021; ``sam_adaptive``: ASAM, Kwon et al., 2021, with ``sam_eta``).  The
+    step runs forward_backward twice under the SAME dropout bits (``advance=False`` on the first): the first pass's gradient g
+    moves the trainable weights to w + e (optimizer.sam_perturb: e = rho g / ||g||, one norm over every trainable tensor), the
+    second pass overwrites ``arena.g`` with the gradient there, and ``optimizer.step()`` moves the weights back to w, to the bit,
+    and applies that gradient.  The soft-term arguments are computed once (one teacher ``predict``, one doubled batch, one set of
+    contrast keys).  The returned dict is the FIRST pass's (scores and ``loss_parts`` at w, so the [Train] record compares with a
+    run without the flag; ``asr_cls`` / ``trans_cls`` are views of the stash and show the second pass) plus ``sam_loss_parts``
+    (the second pass's ``loss_parts``, at w + e) and ``sam_norm`` (fp32 [1]: ||g||, adaptive: ||T g||).  Works with the three
+    optimizers, ``add_l2_loss``, a ``teacher``, ``rdrop_alpha``, ``contrast_weight``, ema_decay and frozen tensors (neither moved
+    nor in the norm); sam_args lists what is refused.  About twice the step plus two streaming passes over the arenas.
     Returns the step outputs (device tensors; no host synchronisation)."""
     _, world = dist_info()
     if world > 1 and getattr(model, "head_mask_trainable", False):
         raise RuntimeError("nbest_amd: training under a head mask under data parallelism is not built (world size %d)" % world)
     b_local = batch["ids"].shape[0]
     adv = adv_args(adv_epsilon, teacher, rdrop_alpha, world)
+    sam = sam_args(sam_rho, sam_adaptive, sam_eta, model, optimizer, adv_epsilon, world)
+    if sam is not None and getattr(optimizer, "sam_pending", False):
+        raise RuntimeError("nbest_amd: a SAM perturbation is pending on the optimizer (step or sam_restore() first)")
     if contrast_weight is not None:                              # refused before the teacher runs or the batch is doubled
         contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, world, check_only=True)
     batch, distill, rdrop = soft_term_args(teacher, distill_alpha, distill_temperature, rdrop_alpha, batch, world, add_segment_ids)
     contrast = contrast_args(contrast_weight, contrast_temperature, batch, adv_epsilon, world)
     seg = batch.get("seg") if add_segment_ids else None          # n_best_asr_bert.py:252
-    # (FGM: the second pass adds to every gradient, so nothing is ready before the call returns - one world-size-1 exchange at the end)
-    overlap = reducer is not None and adv is None
+    # (FGM: the second pass adds to every gradient, so nothing is ready before the call returns - one world-size-1 exchange at the end;
+    # SAM: the first pass's gradient is never exchanged, the second pass's is - the same single exchange)
+    overlap = reducer is not None and adv is None and sam is None
     chunks = reducer.chunks if overlap else None
     # MSE is a MEAN over B_global x H (n_best_asr_bert.py:574): the local kernel differentiates the mean over its own
     # B_local rows, so after the SUM all-reduce the term needs the weight B_local / B_global (= 1/world for equal shards)
@@ -469,11 +517,18 @@ def train_step(model, optimizer, batch, add_l2_loss=False, add_segment_ids=True,
     if reducer is not None:
         reducer.set_step_tokens(batch["ids"], batch.get("tids") if (add_l2_loss or contrast is not None) else None,
                                 rows=batch.get("word_rows"))
-    out = model.forward_backward(batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"),
-                                 trans_seg_ids=batch.get("tseg"), add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale,
-                                 chunks=chunks, on_chunk_done=reducer.layers_ready if overlap else None,
-                                 tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop,
-                                 adv=adv, **({} if contrast is None else dict(contrast=contrast)))
+    passes = lambda **kw: model.forward_backward(
+        batch["ids"], batch["labels"], seg_ids=seg, trans_input_ids=batch.get("tids"), trans_seg_ids=batch.get("tseg"),
+        add_l2_loss=add_l2_loss, mse_grad_scale=mse_scale, chunks=chunks, on_chunk_done=reducer.layers_ready if overlap else None,
+        tok_perm=batch.get("tok_perm"), trans_tok_perm=batch.get("ttok_perm"), distill=distill, rdrop=rdrop, adv=adv,
+        **({} if contrast is None else dict(contrast=contrast)), **kw)
+    if sam is None:
+        out = passes()
+    else:
+        out = passes(advance=False)                              # the gradient at w; step_counter stays: the same dropout bits below
+        optimizer.sam_perturb(sam["rho"], adaptive=sam["adaptive"], eta=sam["eta"])
+        at_e = passes(accumulate=False, advance=True)            # the gradient at w + e replaces it; optimizer.step() restores w
+        out["sam_loss_parts"], out["sam_norm"] = at_e["loss_parts"], optimizer.sam_norm.clone()
     if reducer is not None and not overlap:
         reducer.reduce_all()
         optimizer.step()
@@ -878,6 +933,10 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     contrast_weight = getattr(opt, "contrastive_weight", None)                              # --contrastive_weight
     contrast_temperature = getattr(opt, "contrastive_temperature", None) or 0.1
     contrast_sum = None                                              # fp32 [4] on the device: the epoch's sum of out["contrast"]
+    sam = dict(sam_rho=getattr(opt, "sam_rho", None), sam_adaptive=bool(getattr(opt, "sam_adaptive", False)),   # --sam_rho
+               sam_eta=getattr(opt, "sam_eta", None) or 0.01)
+    sam_args(sam["sam_rho"], sam["sam_adaptive"], sam["sam_eta"], model, opt.optimizer, adv_epsilon, world, n_accum)
+    sam_sum, sam_utts = None, 0                                      # fp32 [2] on the device: sum of (hard loss at w + e - at w), of sam_norm
     for bi, mine, b in Prefetcher(split, lists, model.device, rank, world):
         first, last = (bi % n_accum == 0), ((bi + 1) % n_accum == 0)
         if first:
@@ -899,6 +958,7 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
             out = train_step(model, opt.optimizer, b, add_l2_loss=opt.add_l2_loss, add_segment_ids=opt.add_segment_ids, reducer=reducer,
                              global_batch=len(lists[bi]), teacher=teacher, distill_alpha=alpha,
                              distill_temperature=temperature, rdrop_alpha=rdrop_alpha, adv_epsilon=adv_epsilon,
+                             **({} if sam["sam_rho"] is None else sam),
                              **({} if contrast_weight is None else dict(contrast_weight=contrast_weight,
                                                                         contrast_temperature=contrast_temperature)))
             if sched is not None:
@@ -923,6 +983,11 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
                     sched.step()
         if contrast_weight is not None:
             contrast_sum = out["contrast"].clone() if contrast_sum is None else contrast_sum.add_(out["contrast"])
+        if sam["sam_rho"] is not None:
+            step = torch.cat([(out["sam_loss_parts"][:3].sum() - out["loss_parts"][:3].sum()).reshape(1), out["sam_norm"]])
+            if rdrop_alpha is not None:
+                step[:1].mul_(0.5)                                   # 2 P rows: per utterance, as the [Train] record
+            sam_sum, sam_utts = (step if sam_sum is None else sam_sum.add_(step)), sam_utts + len(mine)
         if rdrop_alpha is not None:
             # the record: half the hard parts of the 2 P rows; the metrics: the first copy of every utterance
             losses.append((rdrop_hard_loss_parts(out), len(mine), len(lists[bi])))
@@ -933,6 +998,8 @@ def train_epoch(model, data, opt, memory, epoch=0, shuffle=True):
     counts, _ = pipe.finish()
     if contrast_weight is not None:                                  # read by the CLI after the [Train] line: (sum L, hits, rows, 0)
         opt.contrast_epoch = None if contrast_sum is None else contrast_sum.double().cpu().tolist()
+    if sam["sam_rho"] is not None:                  # read by the CLI after the [Train] line: (sum of differences, sum of norms, utterances, steps)
+        opt.sam_epoch = None if sam_sum is None else sam_sum.double().cpu().tolist() + [sam_utts, len(lists)]
     return _finish(losses, counts, model.device, len(lists))
 
 
